@@ -10,8 +10,10 @@ A "step" is one full Lloyd iteration over the (row-sharded) synthetic batch: cen
 MFMA filter + exact refinement (bit-identical assignments), move-delta reduction, the fused
 all-reduce (N > 1), the stop test (on the device, read by the host one step late) and the centroid update.  Inputs are resident in HBM before timing starts.
 STRONG scaling: the 8M rows are split over the N ranks.  Rank 0 prints ONE JSON line.
-After the timed region (never inside it) rank 0 checks >= 1M rows of the state it has just timed
-against the CPU oracle ("verify" in the line; --no-verify skips it).
+A plain run sets up, warms up, times the steps and prints the line.  --full adds, after the timed region (never
+inside it): rank 0 checks >= 1M rows of the state it has just timed against the CPU oracle ("verify"; --no-verify
+skips it), the other filter's roofline on the same state, one whole kmeans_cuda() call and the CPU baselines.
+--dump-outputs DIR writes what the last timed step computed (centroids, assignments) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -24,6 +26,23 @@ sys.path.insert(0, ROOT)
 
 PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 PMC_TRAFFIC_SOURCE = None   # the profiles/ file `roofline.traffic` was read from (reported in the line)
+DUMP_BYTES = 64 << 20       # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, arrays, total_bytes):
+    """Writes every array as path/<name>.npy.  total_bytes: what all ranks' arrays hold together; past DUMP_BYTES each
+    array keeps its share as a fixed, seeded sample of its rows, whose indices go to path/<name>_rows.npy."""
+    import numpy
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES - (1 << 16)   # room for the .npy headers
+    for name, a in arrays.items():
+        if total_bytes > cap:
+            m = int(cap * a.nbytes / total_bytes) // (a.nbytes // a.shape[0] + 8)
+            if m < a.shape[0]:
+                rows = numpy.sort(numpy.random.RandomState(0).choice(a.shape[0], m, replace=False))
+                numpy.save(os.path.join(path, name + "_rows.npy"), rows.astype(numpy.float64))
+                a = a[rows]
+        numpy.save(os.path.join(path, name + ".npy"), a)
 
 
 def pmc_traffic(rows_per_launch, filt="f32"):
@@ -206,6 +225,9 @@ def api_bench(args):
         runs.append({"wall_s": wall, "loop_s": loop_s.value, "setup_s": setup_s.value, "iterations": it.value,
                      "shards": shards.value, "rccl_ranks": rccl.value, "collective_ms": cms.value,
                      "collectives": cn.value})
+    if args.dump_outputs:   # what the last timed call returned
+        dump_outputs(args.dump_outputs, {"centroids": cen.cpu().numpy(), "assignments": asg.cpu().numpy().astype("float32")},
+                     K * D * 4 + N * 4)
     timed = runs[1:] if len(runs) > 1 else runs
     iters = sum(r["iterations"] for r in timed)
     loop = sum(r["loop_s"] for r in timed)
@@ -244,7 +266,13 @@ def main():
     ap.add_argument("--samples", type=int, default=8000000)
     ap.add_argument("--features", type=int, default=256)
     ap.add_argument("--clusters", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run what the headline figure does not need: the oracle check of "
+                         "the timed state, the other filter's roofline, a whole kmeans_cuda() call, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (centroids; assignments as float32) as DIR/<name>.npy, "
+                         "at most 64 MB in all (a fixed, seeded sample of the rows beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-row-cache", action="store_true",
                     help="convert the coarse stage's operands from the rows on every pass instead of streaming the "
                          "engine's centred half copy (kmamd_set_row_cache); assignments are identical")
@@ -253,10 +281,11 @@ def main():
                          "hi.hi pass, then the contenders of the undecided rows in fp32; default), f32 = "
                          "v_mfma_f32_32x32x2_f32.  Assignments are bit-identical")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the oracle check of the timed state (outside the timed region)")
+                    help="--full: skip the oracle check of the timed state (outside the timed region)")
     ap.add_argument("--verify-rows", type=int, default=1000000)
     ap.add_argument("--no-api-leg", action="store_true",
-                    help="skip the whole kmeans_cuda() call that is timed beside the step loop (outside the timed region)")
+                    help="--full: skip the whole kmeans_cuda() call that is timed beside the step loop (outside the timed "
+                         "region)")
     ap.add_argument("--api", action="store_true",
                     help="time whole kmeans_cuda() calls through the drop-in C ABI (device mask = the first --gpus "
                          "GPUs, ONE process, device-resident input) instead of the one-process-per-GPU step loop")
@@ -360,29 +389,36 @@ def main():
     tail = loop.buf[K * D + K:K * D + K + 4].cpu().tolist()
     flagged = int(tail[1])
     pair_rows = int(tail[3])
-    # outside the timed region, and BEFORE anything else touches the state: the pass that follows the last timed
-    # update (it reassigns what a 21st step would: its change counter is checked on real moves)
+    backend.engine.profile(False)
+    if args.dump_outputs:   # what a caller of the loop receives after the last timed step, before anything else runs
+        arrays = {"centroids": backend.centroids.cpu().numpy()} if rank == 0 else {}   # (replicated on every rank)
+        name = "assignments" if world == 1 else "assignments_rank%d" % rank               # this rank's rows
+        arrays[name] = backend.assignments.cpu().numpy().astype("float32")
+        dump_outputs(args.dump_outputs, arrays, K * D * 4 + N * 4)
+    # --full, outside the timed region, and BEFORE anything else touches the state: the pass that follows the last
+    # timed update (it reassigns what a 21st step would: its change counter is checked on real moves)
     verify = None
-    if rank == 0 and not args.no_verify:
+    if args.full and rank == 0 and not args.no_verify:
         verify = verify_state(backend, args.verify_rows)
     # then the OTHER filter on the same state, for the side-by-side roofline entry
     other = "f32" if args.filter != "f32" else "f16"
-    backend.engine.set_filter(other)
-    backend.assign()
-    backend.engine.profile(True)
-    for _ in range(2):
+    if args.full:
+        backend.engine.set_filter(other)
         backend.assign()
-    torch.cuda.synchronize(dev)
-    prof_other = backend.engine.profile_read()
-    backend.engine.set_filter(args.filter)
-    backend.engine.profile(False)
+        backend.engine.profile(True)
+        for _ in range(2):
+            backend.assign()
+        torch.cuda.synchronize(dev)
+        prof_other = backend.engine.profile_read()
+        backend.engine.set_filter(args.filter)
+        backend.engine.profile(False)
     changed_last = loop.changed_last()
     # The drop-in entry point on the same rows, outside the timed region (`value` times the
     # one-process-per-GPU step loop; what a caller of kmeans_cuda() gets had no driver-run record): one whole call
     # through the C ABI -- device-resident rows, init=random, tolerance 0.01, yinyang_t=0 -- timed by the library's own
     # clock around its iteration loop (kmamd_last_run_stats).
     api_leg = None
-    if rank == 0 and world == 1 and not args.no_api_leg and args.dtype == "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_api_leg and args.dtype == "f32":
         try:
             import ctypes
             from kmcuda_amd import _lib
@@ -436,8 +472,6 @@ def main():
             ach = flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
             return pk, ach
         peak, achieved = roof(args.filter, dom_ms)
-        other_ms = prof_other["filter_ms"] / max(prof_other["filter_launches"], 1)
-        opeak, oach = roof(other, other_ms)
         hr = "true" if f16 else "false"
         kname = {"f16": "lloyd_coarse2_kernel<256,%s,true,%s>" % (("false", "true") if cached else (hr, "false")),
                  "f32": "lloyd_filter_kernel<256,true>"}
@@ -478,9 +512,6 @@ def main():
                                       "scripts/mfma_probe.hip, profiles/r6b_*)",
                          "kernel": kname[args.filter],
                          "kernel_ms": dom_ms, "filter_stage_ms": filter_ms, "rows_per_launch": n_local},
-            "roofline_other_filter": {"filter": other, "kernel": kname[other], "kernel_ms": other_ms, "achieved": oach,
-                                      "peak": opeak, "unit": "TFLOP/s", "frac": oach / opeak,
-                                      "note": "same rows and centroids, timed outside the timed region"},
             "breakdown_ms_per_step": {"filter": filter_ms, "filter_coarse_kernel": coarse_ms,
                                       "exact_refine": prof["exact_ms"] / launches,
                                       "update": prof["update_ms"] / launches},
@@ -493,11 +524,17 @@ def main():
                                              "all-reduce)"},
             "rows_full_exact_scan_last_step": flagged, "rows_pair_refined_last_step": pair_rows, "reassigned_last_step": changed_last,
         }
+        if args.full:
+            other_ms = prof_other["filter_ms"] / max(prof_other["filter_launches"], 1)
+            opeak, oach = roof(other, other_ms)
+            out["roofline_other_filter"] = {"filter": other, "kernel": kname[other], "kernel_ms": other_ms,
+                                            "achieved": oach, "peak": opeak, "unit": "TFLOP/s", "frac": oach / opeak,
+                                            "note": "same rows and centroids, timed outside the timed region"}
         if verify is not None:
             out["verify"] = verify
         if api_leg is not None:
             out["api_kmeans_cuda"] = api_leg
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(D, K)
             out["cpu_baseline_sklearn"] = sklearn_baseline(D, K)
         print(json.dumps(out))

@@ -5,7 +5,7 @@
 # Steps (arguments after the first ':' -- use ',' for spaces inside them):
 #   smoke                     __graft_entry__.smoke()
 #   test:<pytest args>        python -m pytest <args> -m gpu -q            e.g. test:tests/test_gpu_lloyd.py,-x
-#   bench[:<bench.py args>]   the bench line (default flags) + a one-line digest
+#   bench[:<bench.py args>]   the bench line with --full (verify, other filter, API leg, CPU baselines) + a one-line digest
 #   shard                     the 1M-row shard of the headline config (what one of 8 GPUs sees)
 #   api[:<args>]              bench.py --api (whole kmeans_cuda() calls)
 #   stats[:<bench.py args>]   rocprofv3 --kernel-trace --stats of the bench command -> kernel_stats_<tag>.csv
@@ -44,8 +44,8 @@ for step in "$@"; do
     env) export "$args" ;;
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ;;
     test) timeout 3000 python -m pytest $args -m gpu -q > $OUT/pytest_$TAG.log 2>&1; echo "pytest rc=$?"; tail -15 $OUT/pytest_$TAG.log | cut -c1-300 ;;
-    bench) timeout 900 python bench.py $args > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench rc=$?"; digest $OUT/bench_$TAG.json ;;
-    shard) timeout 600 python bench.py --samples 1000000 --steps 40 --warmup 10 --no-cpu-baseline --verify-rows 200000 > $OUT/bench1m_$TAG.json 2> $OUT/bench1m_$TAG.err; echo "rc=$?"; digest $OUT/bench1m_$TAG.json ;;
+    bench) timeout 900 python bench.py --full $args > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench rc=$?"; digest $OUT/bench_$TAG.json ;;
+    shard) timeout 600 python bench.py --full --samples 1000000 --steps 40 --warmup 10 --no-cpu-baseline --verify-rows 200000 > $OUT/bench1m_$TAG.json 2> $OUT/bench1m_$TAG.err; echo "rc=$?"; digest $OUT/bench1m_$TAG.json ;;
     api) timeout 900 python bench.py --api --steps 20 $args > $OUT/bench_api_$TAG.json 2> $OUT/bench_api_$TAG.err; echo "rc=$?"
          python -c "import json;d=json.loads(open('$OUT/bench_api_$TAG.json').read().strip().splitlines()[-1]);print('api', d['ms_per_step'], [(c['iterations'],round(c['loop_s'],4),round(c['wall_s'],3)) for c in d['calls']])" ;;
     stats) rm -rf $OUT/prof_$TAG

@@ -47,7 +47,7 @@ PY
 }
 # 1. one process per GPU
 if [ $ONE = 1 ]; then envs="KMCUDA_AMD_BENCH_SINGLE_DEVICE=1 KMCUDA_AMD_BENCH_BACKEND=gloo"; else envs=""; fi
-env $envs timeout 1800 python bench.py --gpus $N --samples $ROWS --steps $STEPS --warmup 5 --no-cpu-baseline --verify-rows 200000 \
+env $envs timeout 1800 python bench.py --gpus $N --samples $ROWS --steps $STEPS --warmup 5 --full --no-cpu-baseline --verify-rows 200000 \
   > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { echo "FAIL bench.py --gpus $N: rc $? (tail of $OUT/${TAG}_bench.err:)"; tail -5 $OUT/${TAG}_bench.err; fail=1; }
 check $OUT/${TAG}_bench.json $N "bench.py --gpus $N (one process per GPU)" || fail=1
 # 2. the library's own sharding

@@ -1,7 +1,7 @@
 """Parity at the sizes that are benchmarked ("What's weak" 1): the oracle judges whole passes
 over 1M x 256 rows against K = 1024 centroids on a state several iterations into a run -- the regime
 bench.py times -- instead of the few-thousand-row cases of the other files.  The assignment pass of the
-8M-row bench state itself is checked by `bench.py` (its "verify" entry: >= 1M rows of the timed state
+8M-row bench state itself is checked by `bench.py --full` (its "verify" entry: >= 1M rows of the timed state
 against the oracle, outside the timed region); here the same check runs inside the test suite."""
 import numpy
 import pytest

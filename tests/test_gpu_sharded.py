@@ -188,7 +188,7 @@ def test_bench_two_ranks_on_one_gpu_reports_its_communicator_and_collective():
     import subprocess
     env = dict(os.environ, KMCUDA_AMD_BENCH_SINGLE_DEVICE="1", KMCUDA_AMD_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--samples", "200000", "--clusters",
-                          "256", "--steps", "4", "--warmup", "3", "--no-cpu-baseline", "--verify-rows", "20000"],
+                          "256", "--steps", "4", "--warmup", "3", "--full", "--no-cpu-baseline", "--verify-rows", "20000"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
