@@ -395,8 +395,10 @@ struct KnnArgs {
                                // be if an operand set without a visiting query were not scored
 };
 constexpr int KNN_STATS = 5;
+// mu (the f16 filter's centre, else null): stats[1] = 1 if a finite row of a cluster leaves the half range once centred
 hipError_t launch_knn_gather(const float *samples, uint32_t N, uint32_t D, uint32_t DP, const uint32_t *inv,
-                             float *xs, float *n2s, uint32_t *stats, hipStream_t st);
+                             float *xs, float *n2s, uint32_t *stats, const float *mu, const uint32_t *offsets, uint32_t K,
+                             hipStream_t st);
 hipError_t launch_knn_prep(int metric, const float *xs, uint32_t N, uint32_t D, uint32_t DP, const uint32_t *offsets,
                            uint32_t K, const float *centroids, float *mydist, float *rdist, float *R, float *C,
                            bool strict_h2, hipStream_t st);

@@ -1616,7 +1616,7 @@ class KnnJob {
     if (!dp_filter) INFO("k-NN: every candidate is evaluated with the exact arithmetic (no matrix-core filter)\n");
     // which matrix-core instruction filters the candidates: f16 on centred hi/lo-split rows (default,
     // needs DP >= 16) or f32 (KMCUDA_AMD_FILTER=f32)
-    const bool use_f16 = dp_filter >= 16 && !want_f32;
+    bool use_f16 = dp_filter >= 16 && !want_f32;
     // mu = mean of the finite centroid rows (any vector works: distances are translation invariant)
     std::vector<float> mu_host(DP, 0.f);
     float mu2 = 0.f;
@@ -1704,7 +1704,8 @@ class KnnJob {
       if (launch_inverse_assignments(s->assignments, N, K, s->keys_tmp, s->vals_tmp, s->keys_sorted, s->inv,
                                      s->offsets, s->sort_temp, sort_bytes, s->stream) != hipSuccess)
         return kmcudaRuntimeError;
-      if (launch_knn_gather(s->samples, N, D, DP, s->inv, s->xs, s->n2s, s->stats, s->stream) != hipSuccess)
+      if (launch_knn_gather(s->samples, N, D, DP, s->inv, s->xs, s->n2s, s->stats, use_f16 ? s->mu : nullptr, s->offsets,
+                            K, s->stream) != hipSuccess)
         return kmcudaRuntimeError;
     }
     INFO("calculating the cluster radiuses...\n");
@@ -1723,6 +1724,17 @@ class KnnJob {
       if (hipStreamSynchronize(f.stream) != hipSuccess) return kmcudaRuntimeError;
       if (hipMemcpy(offsets.data(), f.offsets, (K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return kmcudaMemoryCopyError;
+      // the half range: a finite row of a cluster whose centred value is no finite half would be
+      // scored NaN by the f16 filter -- the whole call takes the f32 filter (D <= 256) or the exact search instead
+      uint32_t overflow = 0;
+      if (use_f16 && hipMemcpy(&overflow, f.stats + 1, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return kmcudaMemoryCopyError;
+      if (overflow) {
+        use_f16 = false;
+        if (D > 256) dp_filter = 0;
+        INFO("k-NN: a centred row leaves the half range, %s\n",
+             dp_filter ? "the f32 matrix-core filter instead of the f16 one" : "every candidate is evaluated with the exact arithmetic");
+      }
     }
     std::vector<uint32_t> blocks;  // (cluster, first position) pairs
     const uint32_t qpb = use_f16 ? knn_qpb_f16(DP) : KNN_QPB_F32;
@@ -1847,12 +1859,10 @@ class KnnJob {
       if (e != hipSuccess) return kmcudaRuntimeError;
     }
     // ---- outputs: rows back in sample order ----
-    if (device_ptrs >= 0 && dp_filter && assigned < N) {
-      // rows without a cluster (NaN samples) get no neighbours: 0xFFFFFFFF, as the host branch writes
-      // (the scatter below only covers the assigned positions)
-      (void)hipSetDevice(device_ptrs);
-      if (hipMemset(neighbors, 0xFF, (size_t)N * k * sizeof(uint32_t)) != hipSuccess) return kmcudaRuntimeError;
-    }
+    // rows without a cluster (NaN samples) get no neighbours: 0xFFFFFFFF.  The filters' blocks cover the assigned
+    // positions only; the rows behind them are written here, by the call that runs the last share of the plan (with
+    // KMCUDA_AMD_KNN_SHARD, a call that does not leaves them untouched like every row of the other shares)
+    const bool fill_unassigned = dp_filter && assigned < N && plan_first + shards.size() == plan_shards;
     unsigned long long dists_calced = 0;
     std::vector<uint32_t> host_inv, host_out;
     if (device_ptrs < 0) {
@@ -1910,11 +1920,28 @@ class KnnJob {
         if (e != hipSuccess) return kmcudaRuntimeError;
       }
     }
-    if (dp_filter && assigned < N) {  // rows without a cluster: no neighbours (the reference reads out of bounds)
-      if (device_ptrs < 0) {
-        for (uint32_t p = assigned; p < N; p++)
-          for (uint32_t i = 0; i < k; i++) neighbors[(size_t)host_inv[p] * k + i] = UINT32_MAX;
+    if (fill_unassigned && device_ptrs < 0) {  // (the reference reads out of bounds for these rows)
+      for (uint32_t p = assigned; p < N; p++)
+        for (uint32_t i = 0; i < k; i++) neighbors[(size_t)host_inv[p] * k + i] = UINT32_MAX;
+    } else if (fill_unassigned) {
+      KnnShard &l = *shards.back();
+      uint32_t *none = nullptr, *tmp_inv = nullptr;
+      struct TmpFree { uint32_t **a, **b; ~TmpFree() { if (*a) (void)hipFree(*a); if (*b) (void)hipFree(*b); } }
+          tmp_guard{&none, &tmp_inv};
+      (void)hipSetDevice(device_ptrs);
+      const uint32_t *src_inv = l.inv;
+      if (l.dev != device_ptrs) {
+        if (hipMalloc((void **)&tmp_inv, (size_t)N * sizeof(uint32_t)) != hipSuccess) return kmcudaMemoryAllocationFailure;
+        if (hipMemcpyPeer(tmp_inv, device_ptrs, l.inv, l.dev, (size_t)N * sizeof(uint32_t)) != hipSuccess)
+          return kmcudaMemoryCopyError;
+        src_inv = tmp_inv;
       }
+      if (hipMalloc((void **)&none, (size_t)(N - assigned) * k * sizeof(uint32_t)) != hipSuccess)
+        return kmcudaMemoryAllocationFailure;
+      hipError_t e = hipMemset(none, 0xFF, (size_t)(N - assigned) * k * sizeof(uint32_t));
+      if (e == hipSuccess) e = launch_knn_scatter(none, src_inv, assigned, N, k, neighbors, nullptr);
+      if (e == hipSuccess) e = hipDeviceSynchronize();
+      if (e != hipSuccess) return kmcudaRuntimeError;
     }
     INFO("calculated %f of all the distances\n", (dists_calced + .0) / ((double)N * N));  // knn.cu:529-530
     return 0;

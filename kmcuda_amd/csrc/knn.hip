@@ -39,30 +39,42 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------
-// prep 1: cluster-sorted padded copy, plain squared norms (filter only), max norm
+// prep 1: cluster-sorted padded copy, plain squared norms (filter only), max norm; with mu (the f16 filter's
+// centre): stats[1] = 1 if a finite row of a cluster has a centred value that is no finite half (|x - mu| >= 65520,
+// the half range).  The f16 filter would store it as +-inf and score NaN; the host then takes another search
+// (DESIGN.md 4.2).  Rows with a NaN or inf feature, and rows without a cluster, do not count.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void knn_gather_kernel(const float *__restrict__ samples, uint32_t N, uint32_t D,
                                                          uint32_t DP, const uint32_t *__restrict__ inv,
                                                          float *__restrict__ xs, float *__restrict__ n2s,
-                                                         uint32_t *__restrict__ stats) {
+                                                         uint32_t *__restrict__ stats, const float *__restrict__ mu,
+                                                         const uint32_t *__restrict__ offsets, uint32_t K) {
   const uint32_t lane = threadIdx.x & 63;
+  const uint32_t assigned = mu ? offsets[K] : 0;
   for (uint32_t p = blockIdx.x * 4 + (threadIdx.x >> 6); p < N; p += gridDim.x * 4) {   // (kernels.hpp: wave_row_grid)
     const float *src = samples + (size_t)inv[p] * D;
     float *dst = xs + (size_t)p * DP;
     float a = 0.f;
+    bool nonfinite = false, over = false;
     for (uint32_t f = lane; f < DP; f += 64) {
       const float v = f < D ? src[f] : 0.f;
       dst[f] = v;
       a = fmaf(v, v, a);
+      if (p < assigned && f < D) {
+        nonfinite |= !((v - v) == 0.f);
+        over |= !(fabsf(v - mu[f]) < 65520.f);
+      }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
+    const bool trip = __any(over) && !__any(nonfinite);
     if (lane == 0) {
       n2s[p] = a;
       // finite, non-negative: bits order like values.  Look before the atomic: N of them on one address serialise
       // in L2 (8M rows: 90 ms for a kernel that moves 16 GB), and the running maximum rarely moves
       if ((a - a) == 0.f && __float_as_uint(a) > *reinterpret_cast<volatile uint32_t *>(&stats[0]))
         atomicMax(&stats[0], __float_as_uint(a));
+      if (trip && *reinterpret_cast<volatile uint32_t *>(&stats[1]) == 0u) atomicOr(&stats[1], 1u);
     }
   }
 }
@@ -605,10 +617,12 @@ __global__ void knn_scatter_kernel(const uint32_t *__restrict__ sorted_out, cons
 // launchers
 // ---------------------------------------------------------------------------------------
 hipError_t launch_knn_gather(const float *samples, uint32_t N, uint32_t D, uint32_t DP, const uint32_t *inv,
-                             float *xs, float *n2s, uint32_t *stats, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(stats, 0, sizeof(uint32_t), st);
+                             float *xs, float *n2s, uint32_t *stats, const float *mu, const uint32_t *offsets, uint32_t K,
+                             hipStream_t st) {
+  hipError_t e = hipMemsetAsync(stats, 0, 2 * sizeof(uint32_t), st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(knn_gather_kernel, dim3(wave_row_grid(N)), dim3(256), 0, st, samples, N, D, DP, inv, xs, n2s, stats);
+  hipLaunchKernelGGL(knn_gather_kernel, dim3(wave_row_grid(N)), dim3(256), 0, st, samples, N, D, DP, inv, xs, n2s, stats,
+                     mu, offsets, K);
   return hipGetLastError();
 }
 

@@ -1188,9 +1188,13 @@ int kmo_knn(uint32_t k, int metric, uint32_t N, uint32_t D, uint32_t K, const fl
   uint64_t calced = 0;
 #pragma omp parallel for schedule(dynamic, 16) reduction(+ : calced)
   for (uint32_t s = 0; s < N; s++) {
+    const uint32_t mycls = assignments[s];
+    if (mycls >= K) {   /* no cluster (NaN sample): no neighbours, as the product defines it; never a candidate either */
+      for (uint32_t i = 0; i < k; i++) neighbors[(size_t)s * k + i] = UINT32_MAX;
+      continue;
+    }
     float *heap = (float *)malloc(sizeof(float) * 2 * k);
     const float *x = samples + (size_t)s * D;
-    const uint32_t mycls = assignments[s];
     const float mydist = kmo_distance(metric, x, centroids + (size_t)mycls * D, D);
     float mndist = FLT_MAX;
     for (uint32_t i = 0; i < k; i++) { heap[2 * i] = FLT_MAX; ((uint32_t *)heap)[2 * i + 1] = 0; }

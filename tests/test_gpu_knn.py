@@ -7,6 +7,7 @@ import numpy
 import pytest
 
 import oracle
+from _angular import assert_knn_only_acos_matters
 from test_gpu_kmeans import StdoutListener
 
 pytestmark = pytest.mark.gpu
@@ -166,3 +167,4 @@ def test_cosine():
     nb = knn_cuda(10, x, c, a, metric="cos", device=1)
     ref, _ = oracle.knn(10, x, c, a, metric="cos")
     assert (nb != ref).mean() < 0.02
+    assert_knn_only_acos_matters(x, nb, ref, "test_cosine")   # and every difference is a last-place matter of acos
