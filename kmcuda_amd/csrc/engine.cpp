@@ -123,6 +123,7 @@ int Engine::init(int device, uint32_t n_rows, uint32_t D, uint32_t K, int metric
   if (const char *c = getenv("KMCUDA_AMD_CARRY_PAIRS")) carry_pairs_ = atoi(c) != 0;
   if (const char *c = getenv("KMCUDA_AMD_SETTLE")) settle_ = atoi(c) != 0;
   if (const char *c = getenv("KMCUDA_AMD_DUO")) { duo_on_ = atoi(c) != 0; duo_always_ = atoi(c) == 2; }
+  if (const char *c = getenv("KMCUDA_AMD_COARSE_MFMA")) coarse_mfma_ = atoi(c) == 32 ? 32u : 16u;
   if (const char *c = getenv("KMCUDA_AMD_WIDE")) wide_ok_ = atoi(c) != 0;
   if (const char *c = getenv("KMCUDA_AMD_GEMM")) wide_ok_ = atoi(c) != 0;   // (the switch's name while stage 1 was a library GEMM)
   if (const char *u = getenv("KMCUDA_AMD_UPDATE"))
@@ -546,6 +547,7 @@ int Engine::lloyd_assign(const float *samples, const float *centroids, uint32_t 
   a.eps = eps_; a.tie_slack = tie_slack_;
   a.assignments = assignments; a.assignments_prev = assignments_prev;
   a.flagged = flagged_; a.pairs = pairs_; a.counters = counters_;
+  a.coarse_mfma = coarse_mfma_;
   if (N_ == 0) return kSuccess;
   if (wide_sel) {
     const int rc = lloyd_assign_wide(a, centroids, wide_steady, rows_on_side, carry_was_valid);

@@ -185,6 +185,7 @@ class Engine {
   uint32_t *duo_ = nullptr;       // 4 N: stage 1's rows with two contenders known by index (counters_[kDuoCount] of them)
   bool duo_on_ = true;            // KMCUDA_AMD_DUO=0: every undecided row takes stage 2's sweep (the A/B)
   bool duo_always_ = false;       // KMCUDA_AMD_DUO=2: the duo list whatever the lists' lengths (the tests); default: when it pays
+  uint32_t coarse_mfma_ = 16;     // KMCUDA_AMD_COARSE_MFMA=32: stage 1 on 32x32x16 everywhere (the A/B; lloyd_coarse.hpp, SHAPE)
   // 0: two-stage f16 matrix-core filter (hi.hi, then the contenders in fp32; default),
   // 1: f32 matrix-core filter (KMCUDA_AMD_FILTER=f32; cross-check)
   int filter_mode_ = 0;

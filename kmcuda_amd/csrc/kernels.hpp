@@ -25,6 +25,7 @@ struct LloydArgs {
   uint32_t *pairs;           // 3N: (row, i1, i2) rows with exactly two contenders
   uint32_t *counters;        // [0] changed, [1] flagged, [2] passed (yinyang), [3] pairs, [4] undecided by stage 1,
                              // [kStopFlag] the device-side stop flag
+  uint32_t coarse_mfma = 16; // stage 1's MFMA (lloyd_coarse.hpp, SHAPE): 16 = 16x16x32 where it applies, 32 = 32x32x16
 };
 // counters[kStopFlag] != 0: the stop rule fired ON THE DEVICE (apply_delta_kernel with a threshold): the kernels
 // that assign every row return at once, so iterations enqueued past the stop leave the state untouched

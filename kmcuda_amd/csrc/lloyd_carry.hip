@@ -228,10 +228,19 @@ static hipError_t launch_coarse_carry_dp(const LloydArgs &a, const void *rows, b
   const uint32_t rows_per_block = 128u * NSET;
   uint32_t grid = (a.N + rows_per_block - 1) / rows_per_block;
   const bool fast = a.D == (uint32_t)DP;
-#define KMX_CARRY_LAUNCH(H, F, C, MODE, SRC)                                                                          \
-  hipLaunchKernelGGL((lloyd_coarse2_kernel<DP, H, F, C, NSET, MODE>), dim3(grid), dim3(256), lds_bytes, st, SRC,      \
-                     xmeta, a.N, a.D, reinterpret_cast<const float *>(panelhi), a.bias, a.mu, a.K_pad, a.K, a.stats,   \
+  // (the shapes as in lloyd_f16.hip, launch_coarse2_dp; the listed pass at 256 features keeps 32x32x16: with the
+  //  gathered rows' conversion 16x16x32 spills there)
+  constexpr bool kS16 = NSET == 2 && DP >= 32;
+  const bool s16 = kS16 && a.coarse_mfma != 32;
+#define KMX_CARRY_LAUNCH_S(H, F, C, MODE, SRC, SHAPE)                                                                       \
+  hipLaunchKernelGGL((lloyd_coarse2_kernel<DP, H, F, C, NSET, MODE, SHAPE>), dim3(grid), dim3(256), lds_bytes, st, SRC,     \
+                     xmeta, a.N, a.D, reinterpret_cast<const float *>(panelhi), a.bias, a.mu, a.K_pad, a.K, a.stats,        \
                      a.eps, a.tie_slack, a.assignments, a.assignments_prev, undecided, und_thr, a.counters, cy, duo)
+#define KMX_CARRY_LAUNCH(H, F, C, MODE, SRC)                           \
+  do {                                                                 \
+    if (s16) KMX_CARRY_LAUNCH_S(H, F, C, MODE, SRC, (kS16 && !(MODE == 2 && DP >= 256)) ? 16 : 32); \
+    else KMX_CARRY_LAUNCH_S(H, F, C, MODE, SRC, 32);                   \
+  } while (0)
   if (!cy.row_list) {   // every row, streamed from the row cache
     KMX_CARRY_LAUNCH(false, true, true, 1, xcache);
     return hipGetLastError();
@@ -254,6 +263,7 @@ static hipError_t launch_coarse_carry_dp(const LloydArgs &a, const void *rows, b
     if (fast) KMX_CARRY_LAUNCH(false, true, false, 2, rows); else KMX_CARRY_LAUNCH(false, false, false, 2, rows);
   }
 #undef KMX_CARRY_LAUNCH
+#undef KMX_CARRY_LAUNCH_S
   return hipGetLastError();
 }
 

@@ -40,9 +40,32 @@ __device__ __forceinline__ f16x8 lds_frag_issue(uint32_t addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(f) : "v"(addr) : "memory");
   return f;
 }
+template <int OFF>
+__device__ __forceinline__ f16x8 lds_frag_issue_off(uint32_t addr) {   // (a constant byte offset in the instruction)
+  f16x8 f;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f) : "v"(addr), "n"(OFF) : "memory");
+  return f;
+}
 template <int N>
 __device__ __forceinline__ void lds_frag_wait(f16x8 &f) {
   asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "n"(N));
+}
+// Two 32x32x16 B fragments of a 32-row set, pieces j and j' (lane (col, h): row col, chunk (h, j)), into two 16x16x32
+// ones: lanes 16-31 of the first trade places with lanes 0-15 of the second, lanes 48-63 with lanes 32-47
+// (v_permlane16_swap_b32: the odd 16-lane rows of its first operand with the even rows of its second).  Afterwards the
+// first holds rows 0-15, the second rows 16-31, lane (n, g) of either the k-chunk (h0, j), (h0, j'), (h1, j), (h1, j')
+// for g = 0, 1, 2, 3.
+__device__ __forceinline__ void frag_swap16(f16x8 &p, f16x8 &q) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 a = __builtin_bit_cast(u32x4, p), b = __builtin_bit_cast(u32x4, q);
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    const auto r = __builtin_amdgcn_permlane16_swap(a[d], b[d], false, false);
+    a[d] = r[0];
+    b[d] = r[1];
+  }
+  p = __builtin_bit_cast(f16x8, a);
+  q = __builtin_bit_cast(f16x8, b);
 }
 
 // 4 waves x 64 rows per block, 2 independent blocks per CU (2 x 67 KB of LDS).  (Tried and dropped:
@@ -51,12 +74,18 @@ __device__ __forceinline__ void lds_frag_wait(f16x8 &f) {
 // CACHED: the B operands come from the engine's row cache (row_cache_kernel below) instead of the rows.
 // NSET: 32-row operand sets per wave -- 2 up to 256 features; 1 for 512 (the halves of 64 rows x 512
 // features would be the whole register file), with each A fragment feeding one MFMA again.
+// SHAPE: the MFMA.  32 = v_mfma_f32_32x32x16_f16 -- a k-step is 16 features, one A fragment (32 centroids) feeds NSET
+// products of 32 x 32.  16 = v_mfma_f32_16x16x32_f16 at the same wave tile (NSET 2 only: 64 rows x 32 centroids) -- a
+// k-step is 32 features, two A fragments (centroids 0-15, 16-31 of the tile) feed four products of 16 x 16 each: the
+// same fragment read per 64 MFMA cycles and the same 32 accumulator registers, but on random halves the chip holds a
+// higher clock under its power limit with the smaller shape.  The row cache keeps the 32x32x16 operand
+// order (the Yinyang sweeps read it too): the operands are rearranged in registers once per block (frag_swap16).
 // CARRY (lloyd_carry.hip; 0 = the plain pass, nothing below exists in it): 1 = every row, and the pass leaves per-row
 // distance bounds behind -- an upper bound of the distance to the row's centroid, a lower bound of the distance to
 // every other finite centroid, both read off the best and second-best coarse scores it has anyway; 2 = the same over
 // the rows of cy.row_list only (the rows whose bounds, moved by the centroids' drifts, no longer certify their
 // assignment: carry_skip_kernel), gathered from the rows like stage 2 does, with the row cache's measured norms.
-template <int DP, bool HALF_ROWS, bool FAST, bool CACHED, int NSET, int CARRY = 0>
+template <int DP, bool HALF_ROWS, bool FAST, bool CACHED, int NSET, int CARRY = 0, int SHAPE = 32>
 __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
     const void *__restrict__ rows, const float *__restrict__ xmeta, uint32_t N, uint32_t D, const float *__restrict__ panelhi,
     const float *__restrict__ bias, const float *__restrict__ mu, uint32_t K_pad, uint32_t K,
@@ -65,6 +94,8 @@ __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
     uint32_t *__restrict__ counters, CarryArgs cy, uint32_t *__restrict__ duo = nullptr) {
   static_assert(CARRY == 0 || CARRY == 1 || CARRY == 2, "CARRY");
   static_assert(CARRY != 2 || !CACHED, "listed rows are gathered from the rows, not streamed from the row cache");
+  static_assert(SHAPE == 32 || (SHAPE == 16 && NSET == 2 && DP >= 32), "16x16x32: two row sets, 32 features per k-step");
+  constexpr bool S16 = SHAPE == 16;
   constexpr int NKH = DP / 2;
   constexpr int KS = NKH / 8;               // k-steps = 16-byte chunks per half row
   constexpr int ROWB = DP * 2;              // bytes of one LDS row (DP hi halves)
@@ -242,6 +273,13 @@ __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
   }
   stage_issue(0, 0, WV, wave);
   load_rows();   // waits for the DMA above and closes with a barrier after its first batch
+  if constexpr (S16) {   // 16x16x32: xa[2 p + R] / xb[2 p + R] = rows 16 R .. 16 R + 15 of set A / B at k-step p
+#pragma unroll
+    for (int p = 0; p < KS / 2; p++) {
+      frag_swap16(xa[2 * p], xa[2 * p + 1]);
+      frag_swap16(xb[2 * p], xb[2 * p + 1]);
+    }
+  }
 
   // FOUR top-2 trackers per row, not two: a lane keeps one for the even tiles and one for the odd tiles (the two
   // halves of the wave see different centroids of a tile anyway).  Same work per score -- a tile's scores go into
@@ -249,8 +287,19 @@ __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
   // contenders sit in different quarters (3 cases of 4), stage 2 need not sweep the centroids again to find them.
   float v1a[2] = {-INFINITY, -INFINITY}, v2a[2] = {-INFINITY, -INFINITY}, v1b[2] = {-INFINITY, -INFINITY}, v2b[2] = {-INFINITY, -INFINITY};
   uint32_t tba[2] = {0, 0}, tbb[2] = {0, 0};
-  // fragment address of k-step j: rowbase ^ swizzle ^ (16 j); (row, half) part fixed per lane
-  const uint32_t fragbase = lds0 + (uint32_t)col * ROWB + (uint32_t)h * (KS * 16) + (uint32_t)((col & SWM) * 16);
+  // 16x16x32: ONE tracker per row, four rows per lane -- lane (n, g) = (lane & 15, lane >> 4) holds row n of the wave's
+  // 16-row blocks q = 0..3 (set A: 0, 1; set B: 2, 3) and sees centroids 4g..4g+3 and 16+4g..16+4g+3 of every tile, so
+  // the four lane groups are the four quarters
+  float w1[4], w2[4];   // (unused by 32x32x16)
+  uint32_t wt[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) { w1[q] = w2[q] = -INFINITY; wt[q] = 0; }
+  // fragment address of k-step j: rowbase ^ swizzle ^ (16 j); (row, half) part fixed per lane.  16x16x32: lane (m, g)
+  // reads centroid m (of the half tile) at the chunk its lane group holds in B -- half g >> 1, chunk 2 p + (g & 1) of
+  // k-step p: rowbase ^ swizzle ^ (32 p); sixteen lanes read one chunk of 16 rows, 16 distinct 16-byte slots
+  const uint32_t fragbase =
+      S16 ? lds0 + (uint32_t)(lane & 15) * ROWB + (uint32_t)h * (KS * 16) + (uint32_t)(((((lane >> 4) & 1) ^ (lane & 15)) & SWM) * 16)
+          : lds0 + (uint32_t)col * ROWB + (uint32_t)h * (KS * 16) + (uint32_t)((col & SWM) * 16);
   // max(v1, pk) as med3(v1, pk, +inf): fmaxf() costs a canonicalising v_max per operand on top
   float pinf = INFINITY;
   asm volatile("" : "+s"(pinf));
@@ -281,8 +330,91 @@ __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
   // block, one per SIMD), so they are not in step: one's bookkeeping runs under the other's MFMAs.
   // (Double-buffered accumulators with the bookkeeping interleaved in-wave need ~230 registers: the
   // B operands spill, measured slower.)
+  // Fragment reads are issued by hand, PD k-steps ahead, with counted waits: while an LDS-DMA is in
+  // flight hipcc turns every wait on a fragment into lgkmcnt(0), i.e. it waits for the read it
+  // has just issued.  (LDS returns in order: lgkmcnt(n) = all but the youngest n reads landed.)
+  constexpr int PD = KS <= 3 ? KS - 1 : 3;   // (every other depth spills the B operands at D = 256)
+  auto frag_wait = [&](int j, f16x8 &f) {
+    constexpr int kMaxBehind = PD;
+    const int behind = (KS - 1 - j) < kMaxBehind ? (KS - 1 - j) : kMaxBehind;  // younger reads in flight
+    if (behind == 7) lds_frag_wait<7>(f);
+    else if (behind == 6) lds_frag_wait<6>(f);
+    else if (behind == 5) lds_frag_wait<5>(f);
+    else if (behind == 4) lds_frag_wait<4>(f);
+    else if (behind == 3) lds_frag_wait<3>(f);
+    else if (behind == 2) lds_frag_wait<2>(f);
+    else if (behind == 1) lds_frag_wait<1>(f);
+    else lds_frag_wait<0>(f);
+  };
+  // the next super-tile's LDS-DMA pieces, one at a time in the shadow of the MFMAs: issued
+  // back to back the four waves' 32 pieces queue up in the texture path and hold up the wave
+  // (all of them during the super-tile's FIRST tile: the second one's 32 MFMAs cover the flight.  Issued from
+  // the bookkeeping phase instead -- the other block's MFMAs would cover the issue -- the kernel is 2 % slower:
+  // 3.51 against 3.44 ms on the same box, profiles/r3d_*)
+  auto stage_after = [&](int j, bool stage, uint32_t sp_next, int buf_next) {
+    constexpr int SPREAD = KS >= 8 ? KS / 8 : 1;            // a piece every SPREAD k-steps
+    if (!(KMX_ABL & 1) && stage && (j % SPREAD) == SPREAD / 2 && j / SPREAD < 8) {
+      const int slot = j / SPREAD;                           // 0..7
+      for (int p = slot * 4 + wave; p < NP; p += 32) stage_piece(sp_next, buf_next, p);
+      if (slot == 0 && wave == 0) stage_bias(sp_next, buf_next);
+    }
+  };
+  // 16x16x32: the same LDS reads (KS per tile, read j = half tile j & 1 of k-step j >> 1), each feeding four products
+  // of 16 cycles (the wave's four 16-row blocks) instead of two of 32; accumulator i of half tile b in lane group g is
+  // centroid 16 b + 4 g + i, packed as index 4 b + i
+  auto tile_pass16 = [&](uint32_t ldsbase, uint32_t biasaddr, uint32_t t, bool stage, uint32_t sp_next, int buf_next) {
+    const int g = lane >> 4;
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int b = 0; b < 2; b++) {
+      const f32x4 b4 = lds_f4(biasaddr + (16 * b + 4 * g) * 4);
+#pragma unroll
+      for (int q = 0; q < 4; q++) acc[b][q] = b4;
+    }
+    uint32_t fb = fragbase + ldsbase;
+    asm volatile("" : "+v"(fb));
+    auto issue = [&](int j) {   // (half tile 1 sits 16 rows further: the instruction's offset)
+      const uint32_t a = fb ^ (uint32_t)((j >> 1) * 32);
+      return (j & 1) ? lds_frag_issue_off<16 * ROWB>(a) : lds_frag_issue(a);
+    };
+    f16x8 fr[PD + 1];
+#pragma unroll
+    for (int j = 0; j < PD; j++) fr[j] = issue(j);
+#pragma unroll
+    for (int j = 0; j < KS; j++) {
+      if (j + PD < KS) fr[(j + PD) % (PD + 1)] = issue(j + PD);
+      f16x8 &f = fr[j % (PD + 1)];
+      frag_wait(j, f);
+      const int b = j & 1, p = j >> 1;
+      acc[b][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, xa[2 * p], acc[b][0], 0, 0, 0);
+      acc[b][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, xa[2 * p + 1], acc[b][1], 0, 0, 0);
+      acc[b][2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, xb[2 * p], acc[b][2], 0, 0, 0);
+      acc[b][3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, xb[2 * p + 1], acc[b][3], 0, 0, 0);
+      stage_after(j, stage, sp_next, buf_next);
+    }
+    float w1_in[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) w1_in[q] = w1[q];
+    if (KMX_ABL & 4) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) { w1[q] = fmaxf(w1[q], acc[0][q][0]); w2[q] = fmaxf(w2[q], acc[1][q][3]); }
+    } else {
+#pragma unroll
+      for (int b = 0; b < 2; b++)
+#pragma unroll
+        for (int i = 0; i < 4; i += 2)
+#pragma unroll
+          for (int q = 0; q < 4; q++) book2(acc[b][q][i], acc[b][q][i + 1], 4 * b + i, w1[q], w2[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) wt[q] = (w1[q] != w1_in[q]) ? t : wt[q];
+  };
   auto tile_pass = [&](uint32_t ldsbase, uint32_t biasaddr, uint32_t t, bool stage, uint32_t sp_next, int buf_next, auto parity) {
     constexpr int PAR = decltype(parity)::value;
+    if constexpr (S16) {
+      tile_pass16(ldsbase, biasaddr, t, stage, sp_next, buf_next);
+      return;
+    }
     f32x16 accA, accB;
     load_bias(biasaddr, accA);
     accB = accA;
@@ -290,40 +422,17 @@ __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
     // visible, the KS addresses are hoisted out of the tile loop and the B operands spill instead
     uint32_t fb = fragbase + ldsbase;
     asm volatile("" : "+v"(fb));
-    // Fragment reads are issued by hand, PD k-steps ahead, with counted waits: while an LDS-DMA is in
-    // flight hipcc turns every wait on a fragment into lgkmcnt(0), i.e. it waits for the read it
-    // has just issued.  (LDS returns in order: lgkmcnt(n) = all but the youngest n reads landed.)
-    constexpr int PD = KS <= 3 ? KS - 1 : 3;   // (every other depth spills the B operands at D = 256)
     f16x8 fr[PD + 1];
 #pragma unroll
     for (int j = 0; j < PD; j++) fr[j] = lds_frag_issue(fb ^ (uint32_t)(j * 16));
 #pragma unroll
     for (int j = 0; j < KS; j++) {
       if (j + PD < KS) fr[(j + PD) % (PD + 1)] = lds_frag_issue(fb ^ (uint32_t)((j + PD) * 16));
-      constexpr int kMaxBehind = PD;
-      const int behind = (KS - 1 - j) < kMaxBehind ? (KS - 1 - j) : kMaxBehind;  // younger reads in flight
       f16x8 &f = fr[j % (PD + 1)];
-      if (behind == 7) lds_frag_wait<7>(f);
-      else if (behind == 6) lds_frag_wait<6>(f);
-      else if (behind == 5) lds_frag_wait<5>(f);
-      else if (behind == 4) lds_frag_wait<4>(f);
-      else if (behind == 3) lds_frag_wait<3>(f);
-      else if (behind == 2) lds_frag_wait<2>(f);
-      else if (behind == 1) lds_frag_wait<1>(f);
-      else lds_frag_wait<0>(f);
+      frag_wait(j, f);
       accA = __builtin_amdgcn_mfma_f32_32x32x16_f16(f, xa[j], accA, 0, 0, 0);
       if constexpr (TWO) accB = __builtin_amdgcn_mfma_f32_32x32x16_f16(f, xb[j], accB, 0, 0, 0);
-      // the next super-tile's LDS-DMA pieces, one at a time in the shadow of the MFMAs: issued
-      // back to back the four waves' 32 pieces queue up in the texture path and hold up the wave
-      // (all of them during the super-tile's FIRST tile: the second one's 32 MFMAs cover the flight.  Issued from
-      // the bookkeeping phase instead -- the other block's MFMAs would cover the issue -- the kernel is 2 % slower:
-      // 3.51 against 3.44 ms on the same box, profiles/r3d_*)
-      constexpr int SPREAD = KS >= 8 ? KS / 8 : 1;            // a piece every SPREAD k-steps
-      if (!(KMX_ABL & 1) && stage && (j % SPREAD) == SPREAD / 2 && j / SPREAD < 8) {
-        const int slot = j / SPREAD;                           // 0..7
-        for (int p = slot * 4 + wave; p < NP; p += 32) stage_piece(sp_next, buf_next, p);
-        if (slot == 0 && wave == 0) stage_bias(sp_next, buf_next);
-      }
+      stage_after(j, stage, sp_next, buf_next);
     }
     const float v1a_in = v1a[PAR], v1b_in = v1b[PAR];
     if (KMX_ABL & 4) {
@@ -350,7 +459,11 @@ __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
     if (!(KMX_ABL & 16)) __syncthreads();
   }
   if (KMX_ABL & 8) {   // (keep the sweep alive, skip the epilogue)
-    if (v1a[0] + v2a[0] + v1b[0] + v2b[0] + v1a[1] + v2a[1] + v1b[1] + v2b[1] == 1.2345f) assignments[0] = tba[0] + tbb[0] + tba[1] + tbb[1];
+    float keep = 0.f;
+    uint32_t keept = 0;
+#pragma unroll
+    for (int q = 0; q < (S16 ? 4 : 1); q++) { keep += w1[q] + w2[q]; keept += wt[q]; }
+    if (v1a[0] + v2a[0] + v1b[0] + v2b[0] + v1a[1] + v2a[1] + v1b[1] + v2b[1] + keep == 1.2345f) assignments[0] = tba[0] + tbb[0] + tba[1] + tbb[1] + keept;
     return;
   }
 
@@ -376,21 +489,50 @@ __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
   const bool want_duo = duo != nullptr;
   const bool angular = tie_slack > 0.f;   // (engine.cpp: the angular metric's plateau slack; 0 under L2)
   // xdm = x.mu, xab >= sum |x_f mu_f| (< 0: not summed here -- the row cache's record: ||x|| ||mu|| bounds it)
-  auto finish = [&](uint32_t s, bool live, const float (&q1)[2], const float (&q2)[2], const uint32_t (&qt)[2], float xn2,
-                    float x0, float dx2, float xdm, float xab, bool &und, unsigned long long &um, float &cut, bool &is_duo,
-                    unsigned long long &dm, uint32_t &dc1, uint32_t &dc2, float &drest) {
-    const bool insane = (x0 != x0);  // kmeans.cu:312
-    // the four quarters' bests with their centroids (mine: even / odd tiles; the other half-wave's), sorted; everything
-    // else the row has seen scored at most `others`
+  // the four quarters' bests of a row with their centroids; everything else the row has seen scored at most `others`.
+  // 32x32x16: the quarters are (even / odd tiles) x (half-wave), the row's two lanes col and col + 32
+  auto quarters32 = [&](const float (&q1)[2], const float (&q2)[2], const uint32_t (&qt)[2], float (&kq)[4],
+                        uint32_t (&jq)[4], float &others) {
     auto index_of = [&](float v, uint32_t tb, uint32_t hh) {
       const uint32_t r = __float_as_uint(v) & 15u;
       return tb * 32u + (r & 3u) + 8u * (r >> 2) + 4u * hh;
     };
-    float k0 = q1[0], k1 = q1[1], k2 = __shfl_xor(q1[0], 32), k3 = __shfl_xor(q1[1], 32);
-    uint32_t j0 = index_of(k0, qt[0], h), j1 = index_of(k1, qt[1], h);
-    uint32_t j2 = __shfl_xor(j0, 32), j3 = __shfl_xor(j1, 32);
+    kq[0] = q1[0]; kq[1] = q1[1]; kq[2] = __shfl_xor(q1[0], 32); kq[3] = __shfl_xor(q1[1], 32);
+    jq[0] = index_of(kq[0], qt[0], h); jq[1] = index_of(kq[1], qt[1], h);
+    jq[2] = __shfl_xor(jq[0], 32); jq[3] = __shfl_xor(jq[1], 32);
     const float mine2 = fmaxf(q2[0], q2[1]);
-    const float others = fmaxf(mine2, __shfl_xor(mine2, 32));
+    others = fmaxf(mine2, __shfl_xor(mine2, 32));
+  };
+  // 16x16x32: the quarters are the four lane groups.  Transposed so that every lane finishes ONE row: lane (n, g) takes
+  // row block g (wave row 16 g + n = set h, row col -- its own lane in the 32x32x16 layout of the row state), and round
+  // r brings in quarter g ^ r: every lane sends the tracker of block (its g) ^ r to lane xor 16 r
+  auto quarters16 = [&](float (&kq)[4], uint32_t (&jq)[4], float &others) {
+    const int g = lane >> 4;
+    float o[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int gq = g ^ r;
+      auto pick = [&](const auto (&a)[4]) {
+        const auto lo = (gq & 1) ? a[1] : a[0], hi = (gq & 1) ? a[3] : a[2];
+        return (gq & 2) ? hi : lo;
+      };
+      float v = pick(w1), v2 = pick(w2);
+      uint32_t tb = pick(wt);
+      if (r) { v = __shfl_xor(v, 16 * r); v2 = __shfl_xor(v2, 16 * r); tb = __shfl_xor(tb, 16 * r); }
+      const uint32_t ri = __float_as_uint(v) & 15u;   // 4 b + i
+      kq[r] = v;
+      o[r] = v2;
+      jq[r] = tb * 32u + 16u * (ri >> 2) + 4u * (uint32_t)gq + (ri & 3u);
+    }
+    others = fmaxf(fmaxf(o[0], o[1]), fmaxf(o[2], o[3]));
+  };
+  auto finish = [&](uint32_t s, bool mine, const float (&kq)[4], const uint32_t (&jq)[4], float others, float xn2,
+                    float x0, float dx2, float xdm, float xab, bool &und, unsigned long long &um, float &cut, bool &is_duo,
+                    unsigned long long &dm, uint32_t &dc1, uint32_t &dc2, float &drest) {
+    const bool insane = (x0 != x0);  // kmeans.cu:312
+    // the four quarters' bests, sorted
+    float k0 = kq[0], k1 = kq[1], k2 = kq[2], k3 = kq[3];
+    uint32_t j0 = jq[0], j1 = jq[1], j2 = jq[2], j3 = jq[3];
     auto order = [](float &a, uint32_t &ia, float &b, uint32_t &ib) {   // a >= b afterwards (a stays in front on ties)
       const bool g = b > a;
       const float ta = g ? b : a, tb2 = g ? a : b;
@@ -416,7 +558,6 @@ __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
     // angular: no centroid but the best may reach the clamp at product 1, the best not the one at -1 (filter_common.hpp)
     const ClampLimits lim = clamp_limits(angular, xdm, dot_error(DP, xab >= 0.f ? xab : xo * mu_norm), 0.5f * thr);
     const bool certain = insane || (in_range && ((v1 - v2) > thr) && (v2 < lim.hi) && (v1 > lim.lo));  // NaN anywhere => not certain
-    const bool mine = (h == 0) && live;
     bool changed = false;
     if (mine && certain) changed = commit_row(s, insane ? K : i1, assignments, assignments_prev);
     und = mine && !certain;
@@ -503,10 +644,23 @@ __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
     xdma += __shfl_xor(xdma, 32); xaba += __shfl_xor(xaba, 32);
     xdmb += __shfl_xor(xdmb, 32); xabb += __shfl_xor(xabb, 32);
   }
-  float cuta, cutb;
-  finish(sA, liveA, v1a, v2a, tba, xn2a, x0a, dx2a, xdma, xaba, unda, uma, cuta, duoa, dma, d1a, d2a, dra);
-  cutb = 0.f;
-  if constexpr (TWO) finish(sB, liveB, v1b, v2b, tbb, xn2b, x0b, dx2b, xdmb, xabb, undb, umb, cutb, duob, dmb, d1b, d2b, drb);
+  float cuta, cutb = 0.f;
+  float kq[4], oth;
+  uint32_t jq[4];
+  if constexpr (S16) {   // one row per lane: set h, row col; it goes on the lists as "A"
+    quarters16(kq, jq, oth);
+    const bool mine = h ? liveB : liveA;
+    sA = h ? sB : sA;
+    finish(sA, mine, kq, jq, oth, h ? xn2b : xn2a, h ? x0b : x0a, h ? dx2b : dx2a, h ? xdmb : xdma, h ? xabb : xaba, unda, uma,
+           cuta, duoa, dma, d1a, d2a, dra);
+  } else {   // the lanes of half 0 finish both sets' rows
+    quarters32(v1a, v2a, tba, kq, jq, oth);
+    finish(sA, h == 0 && liveA, kq, jq, oth, xn2a, x0a, dx2a, xdma, xaba, unda, uma, cuta, duoa, dma, d1a, d2a, dra);
+    if constexpr (TWO) {
+      quarters32(v1b, v2b, tbb, kq, jq, oth);
+      finish(sB, h == 0 && liveB, kq, jq, oth, xn2b, x0b, dx2b, xdmb, xabb, undb, umb, cutb, duob, dmb, d1b, d2b, drb);
+    }
+  }
   // ONE pair of global atomics per block, not three per wave: the counters share a cache line, same-address
   // atomics are served one at a time by L2 (measured round 2: 11 ns each in a kernel that did nothing else), and
   // 125 K waves per launch all arrive with theirs at the end of the same scheduling round

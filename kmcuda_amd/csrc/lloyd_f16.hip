@@ -261,10 +261,18 @@ static hipError_t launch_coarse2_dp(const LloydArgs &a, const void *rows, bool h
   const uint32_t rows_per_block = 128u * NSET;
   const uint32_t grid = (a.N + rows_per_block - 1) / rows_per_block;
   const bool fast = a.D == (uint32_t)DP;
-#define KMX_CRS2_LAUNCH(H, F, C, SRC)                                                                              \
-  hipLaunchKernelGGL((lloyd_coarse2_kernel<DP, H, F, C, NSET>), dim3(grid), dim3(256), lds_bytes, st, SRC, xmeta,   \
-                     a.N, a.D, reinterpret_cast<const float *>(panelhi), a.bias, a.mu, a.K_pad, a.K, a.stats,       \
+  // 16x16x32 with two row sets (DP 32..256); DP 16 (one k-step of 32 features does not fit) and 512 keep 32x32x16
+  constexpr bool kS16 = NSET == 2 && DP >= 32;
+  const bool s16 = kS16 && a.coarse_mfma != 32;
+#define KMX_CRS2_LAUNCH_S(H, F, C, SRC, SHAPE)                                                                            \
+  hipLaunchKernelGGL((lloyd_coarse2_kernel<DP, H, F, C, NSET, 0, SHAPE>), dim3(grid), dim3(256), lds_bytes, st, SRC, xmeta, \
+                     a.N, a.D, reinterpret_cast<const float *>(panelhi), a.bias, a.mu, a.K_pad, a.K, a.stats,             \
                      a.eps, a.tie_slack, a.assignments, a.assignments_prev, undecided, und_thr, a.counters, CarryArgs(), duo)
+#define KMX_CRS2_LAUNCH(H, F, C, SRC)                       \
+  do {                                                      \
+    if (s16) KMX_CRS2_LAUNCH_S(H, F, C, SRC, kS16 ? 16 : 32); \
+    else KMX_CRS2_LAUNCH_S(H, F, C, SRC, 32);               \
+  } while (0)
   if (xcache) {
     KMX_CRS2_LAUNCH(false, true, true, xcache);
   } else if (half_rows) {
@@ -273,6 +281,7 @@ static hipError_t launch_coarse2_dp(const LloydArgs &a, const void *rows, bool h
     if (fast) KMX_CRS2_LAUNCH(false, true, false, rows); else KMX_CRS2_LAUNCH(false, false, false, rows);
   }
 #undef KMX_CRS2_LAUNCH
+#undef KMX_CRS2_LAUNCH_S
   return hipGetLastError();
 }
 

@@ -2,7 +2,8 @@
 // synthetic operands of the headline shape: N x 256 centred halves in the row cache's layout, a 1024 x 256 half panel.
 // Built several times with -DKMX_ABL=<mask> (lloyd_coarse.hpp: timing-only ablations) it prices the kernel's parts
 // on ONE box; -DHARNESS_KERNEL=3 runs lloyd_coarse3_kernel (lloyd_coarse3.hpp) on the same inputs and checks that its
-// assignments / undecided lists equal the stage it replaces.
+// assignments / undecided lists equal the stage it replaces.  -DHARNESS_SHAPE=32 builds the kernel on
+// v_mfma_f32_32x32x16_f16 (KMCUDA_AMD_COARSE_MFMA=32), the default 16 on v_mfma_f32_16x16x32_f16.
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -Ikmcuda_amd/csrc -Iinclude scripts/coarse_harness.hip -o h && ./h [rows] [reps]
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,6 +19,9 @@
 #endif
 
 using namespace kmx;
+#ifndef HARNESS_SHAPE
+#define HARNESS_SHAPE 16
+#endif
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 
@@ -102,9 +106,9 @@ int main(int argc, char **argv) {
   CHECK(hipEventCreate(&e1));
   auto launch2 = [&]() {
     const size_t lds_bytes = 2 * 64 * (size_t)(DP * 2) + 512 + 64 + (size_t)DP * 4;
-    CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&lloyd_coarse2_kernel<DP, false, true, true, 2, 0>),
+    CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&lloyd_coarse2_kernel<DP, false, true, true, 2, 0, HARNESS_SHAPE>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL((lloyd_coarse2_kernel<DP, false, true, true, 2, 0>), dim3((N + 255) / 256), dim3(256), lds_bytes, 0,
+    hipLaunchKernelGGL((lloyd_coarse2_kernel<DP, false, true, true, 2, 0, HARNESS_SHAPE>), dim3((N + 255) / 256), dim3(256), lds_bytes, 0,
                        (const void *)xcache, xmeta, N, (uint32_t)DP, reinterpret_cast<const float *>(panel), biasf, mu, K_pad, K, stats, eps, 0.f,
                        asg, prev, und, und_thr, counters, CarryArgs());
   };

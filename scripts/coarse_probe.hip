@@ -9,6 +9,10 @@
 //   BOOK  0 none, 1 = 2.5 VALU per score (pack + med3 + med3 + max3 per pair), 2 = 1.5 (no index bits: value-only)
 //   SYNC  a block barrier every second tile (the super-tile hand-over of the real kernel); 2: every fourth
 //   BW    waves per block: 4 (two blocks per CU at WPS 2) or 8 (one block: both waves of a SIMD meet at its barriers)
+//   SHAPE 32 = v_mfma_f32_32x32x16_f16 (one fragment read per k-step of 16 features feeds NSET products), 16 =
+//         v_mfma_f32_16x16x32_f16 at the same output tile per wave (64 rows x 32 centroids at NSET 2): a k-step of 32
+//         features reads two A fragments (centroids 0-15, 16-31 of the tile) and feeds each to 2 NSET products of 16
+//         cycles -- the same LDS bytes per FLOP, the same 32 scores per lane per tile for the bookkeeping (PIPE 0 only)
 // Prints TFLOP/s, the fraction of 2500 and the clock implied if the matrix pipe never idled.
 //   hipcc -O3 --offload-arch=gfx950 scripts/coarse_probe.hip -o scratch/bin/coarse_probe && scratch/bin/coarse_probe [tiles]
 #include <hip/hip_runtime.h>
@@ -21,6 +25,7 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include <type_traits>
 
 __device__ __forceinline__ f16x8 lds_frag_issue(uint32_t addr) {
   f16x8 f;
@@ -34,7 +39,7 @@ __device__ __forceinline__ void lds_frag_wait(f16x8 &f) {
 
 constexpr int KS = 16, ROWB = 512, TILEB = 32 * ROWB;
 
-template <int WPS, int NSET, int PIPE, int BOOK, int SYNC, int BW = 4>
+template <int WPS, int NSET, int PIPE, int BOOK, int SYNC, int BW = 4, int SHAPE = 32>
 __global__ __launch_bounds__(BW * 64, BW == 8 ? 1 : WPS) void probe(const f16x8 *__restrict__ ops, const f16x8 *__restrict__ panel, int tiles,
                                                   float *__restrict__ out) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
@@ -72,10 +77,65 @@ __global__ __launch_bounds__(BW * 64, BW == 8 ? 1 : WPS) void probe(const f16x8 
       b1 = __builtin_amdgcn_fmed3f(__builtin_amdgcn_fmed3f(b1, a, pinf), b, pinf);   // (max3 through the compiler's eyes)
     }
   };
+  constexpr int PD = 3;
+  if constexpr (SHAPE == 16) {
+    static_assert(PIPE == 0, "SHAPE 16: PIPE 0 only");
+    // lane (m, g) = (lane & 15, lane >> 4) reads centroid 16 b + m of the tile at the chunk its lane group holds in B:
+    // half g >> 1, chunk 2 p + (g & 1) of k-step p (x[s][2 p + R] = rows 16 R .. 16 R + 15 of set s at k-step p)
+    const int m = lane & 15, g = lane >> 4;
+    const uint32_t fb16 = lds0 + (uint32_t)m * ROWB + (uint32_t)(g >> 1) * (KS * 16) + (uint32_t)((((g & 1) ^ m) & 15) * 16);
+    float w1[2 * NSET], w2[2 * NSET];
+#pragma unroll
+    for (int q = 0; q < 2 * NSET; q++) w1[q] = w2[q] = -INFINITY;
+    for (int t = 0; t < tiles; t++) {
+      uint32_t fb = fb16 + (uint32_t)(t & 3) * TILEB;
+      asm volatile("" : "+v"(fb));
+      f32x4 acc[2][2 * NSET];
+#pragma unroll
+      for (int b = 0; b < 2; b++)
+#pragma unroll
+        for (int q = 0; q < 2 * NSET; q++) acc[b][q] = f32x4{(float)t};
+      f16x8 fr[PD + 1];
+      auto addr = [&](int j) { return (fb ^ (uint32_t)((j >> 1) * 32)) + (uint32_t)((j & 1) * 16 * ROWB); };
+#pragma unroll
+      for (int j = 0; j < PD; j++) fr[j] = lds_frag_issue(addr(j));
+#pragma unroll
+      for (int j = 0; j < KS; j++) {   // read j: half tile b = j & 1 of k-step p = j >> 1
+        if (j + PD < KS) fr[(j + PD) % (PD + 1)] = lds_frag_issue(addr(j + PD));
+        const int behind = (KS - 1 - j) < PD ? (KS - 1 - j) : PD;
+        f16x8 &f = fr[j % (PD + 1)];
+        if (behind == 3) lds_frag_wait<3>(f);
+        else if (behind == 2) lds_frag_wait<2>(f);
+        else if (behind == 1) lds_frag_wait<1>(f);
+        else lds_frag_wait<0>(f);
+        const int b = j & 1, p = j >> 1;
+#pragma unroll
+        for (int q = 0; q < 2 * NSET; q++)
+          acc[b][q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, x[q >> 1][2 * p + (q & 1)], acc[b][q], 0, 0, 0);
+      }
+      if (BOOK) {
+#pragma unroll
+        for (int q = 0; q < 2 * NSET; q++)
+#pragma unroll
+          for (int b = 0; b < 2; b++) {
+            book2(acc[b][q][0], acc[b][q][1], 4 * b, w1[q], w2[q]);
+            book2(acc[b][q][2], acc[b][q][3], 4 * b + 2, w1[q], w2[q]);
+          }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 2 * NSET; q++) w1[q] += acc[0][q][0] + acc[1][q][3];
+      }
+      if (SYNC == 1 ? (t & 1) : (SYNC == 2 && (t & 3) == 3)) __syncthreads();
+    }
+    float sum = 0;
+#pragma unroll
+    for (int q = 0; q < 2 * NSET; q++) sum += w1[q] + w2[q];
+    if (sum == 1.2345f) out[0] = sum;
+    return;
+  }
   f32x16 acc[2][NSET];
 #pragma unroll
   for (int s = 0; s < NSET; s++) acc[0][s] = acc[1][s] = f32x16{0};
-  constexpr int PD = 3;
 
   // one tile: products into acc[cur]; PIPE: the bookkeeping of acc[cur ^ 1] between them
   auto tile = [&](int t, auto curc, bool have_prev) {
@@ -137,6 +197,13 @@ __global__ __launch_bounds__(BW * 64, BW == 8 ? 1 : WPS) void probe(const f16x8 
   if (sum == 1.2345f) out[0] = sum;
 }
 
+__global__ void permlane_check(unsigned *o) {
+  const unsigned l = threadIdx.x;
+  const auto r = __builtin_amdgcn_permlane16_swap(l, 1000u + l, false, false);
+  o[l] = r[0];
+  o[64 + l] = r[1];
+}
+
 static uint16_t f2h(float f) {
   _Float16 hh = (_Float16)f;
   uint16_t u;
@@ -144,21 +211,21 @@ static uint16_t f2h(float f) {
   return u;
 }
 
-template <int WPS, int NSET, int PIPE, int BOOK, int SYNC, int BW = 4>
+template <int WPS, int NSET, int PIPE, int BOOK, int SYNC, int BW = 4, int SHAPE = 32>
 static void run(const char *what, int cus, const f16x8 *ops, const f16x8 *panel, int tiles, float *out) {
   const int blocks = cus * WPS * 4 / BW;
   const size_t ldsb = WPS == 1 ? 96 * 1024 : 4 * TILEB;   // (one block per CU when a wave is to have its SIMD to itself)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&probe<WPS, NSET, PIPE, BOOK, SYNC, BW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&probe<WPS, NSET, PIPE, BOOK, SYNC, BW, SHAPE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
-  hipLaunchKernelGGL((probe<WPS, NSET, PIPE, BOOK, SYNC, BW>), dim3(blocks), dim3(BW * 64), ldsb, 0, ops, panel, tiles / 4, out);
+  hipLaunchKernelGGL((probe<WPS, NSET, PIPE, BOOK, SYNC, BW, SHAPE>), dim3(blocks), dim3(BW * 64), ldsb, 0, ops, panel, tiles / 4, out);
   hipDeviceSynchronize();
   float sum = 0, best = 1e30f;
   const int reps = 3;
   for (int r = 0; r < reps; r++) {
     hipEventRecord(e0, 0);
-    hipLaunchKernelGGL((probe<WPS, NSET, PIPE, BOOK, SYNC, BW>), dim3(blocks), dim3(BW * 64), ldsb, 0, ops, panel, tiles, out);
+    hipLaunchKernelGGL((probe<WPS, NSET, PIPE, BOOK, SYNC, BW, SHAPE>), dim3(blocks), dim3(BW * 64), ldsb, 0, ops, panel, tiles, out);
     hipEventRecord(e1, 0);
     hipEventSynchronize(e1);
     float ms;
@@ -171,8 +238,8 @@ static void run(const char *what, int cus, const f16x8 *ops, const f16x8 *panel,
   const double flop = mfmas_per_wave * blocks * BW * 32768.0;
   const double ms = sum / reps;
   const double cyc = mfmas_per_wave * WPS * 32.0;
-  printf("%-46s wps %d nset %d pipe %d book %d sync %d : %8.3f ms  %7.1f TFLOP/s  (%.3f of 2500)  pipe-saturated clock >= %.2f GHz %s\n", what,
-         WPS, NSET, PIPE, BOOK, SYNC, ms, flop / (ms * 1e-3) / 1e12, flop / (ms * 1e-3) / 1e12 / 2500.0, cyc / (ms * 1e-3) / 1e9,
+  printf("%-46s shape %d wps %d nset %d pipe %d book %d sync %d : %8.3f ms  %7.1f TFLOP/s  (%.3f of 2500)  pipe-saturated clock >= %.2f GHz %s\n", what,
+         SHAPE, WPS, NSET, PIPE, BOOK, SYNC, ms, flop / (ms * 1e-3) / 1e12, flop / (ms * 1e-3) / 1e12 / 2500.0, cyc / (ms * 1e-3) / 1e9,
          err == hipSuccess ? "" : hipGetErrorString(err));
   fflush(stdout);
 }
@@ -195,6 +262,35 @@ int main(int argc, char **argv) {
   hipMalloc(&out, 4);
   hipMemcpy(ops, host.data(), nops * 16, hipMemcpyHostToDevice);
   hipMemcpy(panel, hpanel.data(), 4 * TILEB, hipMemcpyHostToDevice);
+  // v_permlane16_swap_b32 (lloyd_coarse.hpp uses it to turn 32x32x16 B operands into 16x16x32 ones): which lanes go where
+  {
+    unsigned *pl;
+    hipMalloc(&pl, 128 * 4);
+    hipLaunchKernelGGL(permlane_check, dim3(1), dim3(64), 0, 0, pl);
+    unsigned h[128];
+    hipMemcpy(h, pl, sizeof(h), hipMemcpyDeviceToHost);
+    bool ok = true;   // first: lanes 16-31 <- second's 0-15, 48-63 <- 32-47; second: lanes 0-15 <- first's 16-31, 32-47 <- 48-63
+    for (int l = 0; l < 64; l++) {
+      const int r = l >> 4;
+      const unsigned want0 = (r & 1) ? 1000u + (unsigned)(l - 16) : (unsigned)l;
+      const unsigned want1 = (r & 1) ? 1000u + (unsigned)l : (unsigned)(l + 16);
+      ok = ok && h[l] == want0 && h[64 + l] == want1;
+    }
+    printf("permlane16_swap lane map: %s (lane 16 of the first <- %u, lane 0 of the second <- %u)\n", ok ? "as expected" : "DIFFERENT", h[16], h[64]);
+    hipFree(pl);
+  }
+  const char *only = getenv("COARSE_PROBE_SHAPES");
+  if (only) {   // the two shapes interleaved, three rounds: today's structure and the products alone
+    for (int rep = 0; rep < 3; rep++) {
+      run<2, 2, 0, 1, 1, 4, 32>("today's structure", cus, ops, panel, tiles, out);
+      run<2, 2, 0, 1, 1, 4, 16>("today's structure", cus, ops, panel, tiles, out);
+      run<2, 2, 0, 0, 0, 4, 32>("products + fragment reads only", cus, ops, panel, tiles, out);
+      run<2, 2, 0, 0, 0, 4, 16>("products + fragment reads only", cus, ops, panel, tiles, out);
+      run<2, 2, 0, 1, 0, 4, 32>("bookkeeping, no barrier", cus, ops, panel, tiles, out);
+      run<2, 2, 0, 1, 0, 4, 16>("bookkeeping, no barrier", cus, ops, panel, tiles, out);
+    }
+    return 0;
+  }
   //   WPS NSET PIPE BOOK SYNC
   run<2, 2, 0, 0, 0>("2 waves/SIMD, products + fragment reads only", cus, ops, panel, tiles, out);
   run<2, 2, 0, 1, 0>("  + bookkeeping (today's mix), no barrier", cus, ops, panel, tiles, out);

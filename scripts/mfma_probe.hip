@@ -6,7 +6,9 @@
 //   random  uniform(-1, 1) halves, a fresh pair of fragments per MFMA (what a real filter feeds it)
 // at 1 and 2 waves per SIMD, optionally with VALU filler ops per MFMA (the bookkeeping load of
 // lloyd_coarse2_kernel: 3 per score = 1.5 VALU per ... see DESIGN.md 4.6).  Prints TFLOP/s and the
-// effective clock implied by the instruction count.  Built by scripts/gpu_round2.sh into scratch/bin.
+// effective clock implied by the instruction count.  SHAPE 16: the same loop on v_mfma_f32_16x16x32_f16 at the same
+// output tile per wave (16 accumulators of 16 x 16 for the four of 32 x 32, eight products per step for four: equal
+// FLOP and equal MFMA cycles per step).  Built by scripts/gpu_round2.sh into scratch/bin.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -16,8 +18,9 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int FILL>
+template <int FILL, int SHAPE = 32>
 __global__ __launch_bounds__(256) void probe(const f16x8 *__restrict__ ops, int iters, float *__restrict__ out) {
   constexpr int NF = 8;
   f16x8 a[NF], b[NF];
@@ -25,6 +28,34 @@ __global__ __launch_bounds__(256) void probe(const f16x8 *__restrict__ ops, int 
   const size_t base = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (2 * NF) * 64 + lane;
 #pragma unroll
   for (int i = 0; i < NF; i++) { a[i] = ops[base + (2 * i) * 64]; b[i] = ops[base + (2 * i + 1) * 64]; }
+  if constexpr (SHAPE == 16) {
+    f32x4 c[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) c[k] = f32x4{0};
+    float v1 = -1e30f, v2 = -1e30f;
+    for (int it = 0; it < iters; it++) {
+#pragma unroll
+      for (int i = 0; i < NF; i++) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {   // accumulators 8 (i & 1) .. + 7: each is reused every 16 products
+          const int ci = 8 * (i & 1) + k;
+          c[ci] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[(i + (k >> 1)) % NF], b[(i + (k & 1)) % NF], c[ci], 0, 0, 0);
+          if (FILL && (k & 1)) {
+#pragma unroll
+            for (int q = 0; q < 4 * FILL; q++) {
+              v2 = __builtin_amdgcn_fmed3f(v1, v2, (float)(it + q));
+              v1 = __builtin_amdgcn_fmed3f(v1, v2, 1e30f);
+            }
+          }
+        }
+      }
+    }
+    float s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) s += c[k][0] + c[k][1] + c[k][2] + c[k][3];
+    if (s == 1.2345f || v1 + v2 == 3.3f) out[0] = s;
+    return;
+  }
   f32x16 acc0 = {0}, acc1 = {0}, acc2 = {0}, acc3 = {0};
   float v1 = -1e30f, v2 = -1e30f;
   for (int it = 0; it < iters; it++) {
@@ -73,18 +104,26 @@ int main(int argc, char **argv) {
   hipEventCreate(&e0);
   hipEventCreate(&e1);
   const char *names[3] = {"zero", "const", "random"};
+  const int shapes = getenv("MFMA_PROBE_SHAPES") ? 2 : 1;   // set: both shapes, interleaved per line
   for (int data = 0; data < 3; data++) {
     srand(1);
     for (size_t i = 0; i < host.size(); i++)
       host[i] = data == 0 ? 0 : (data == 1 ? f2h(0.5f) : f2h((rand() / (float)RAND_MAX) * 2.f - 1.f));
     hipMemcpy(dev, host.data(), n * 16, hipMemcpyHostToDevice);
     for (int wps = 1; wps <= 2; wps++) {
-      for (int fill = 0; fill <= 2; fill++) {
+      for (int fill = 0; fill <= 2; fill++)
+      for (int sh = 0; sh < shapes; sh++) {
         const int blocks = cus * wps;
         auto launch = [&](int its) {
-          if (fill == 0) hipLaunchKernelGGL(probe<0>, dim3(blocks), dim3(256), 0, 0, dev, its, out);
-          else if (fill == 1) hipLaunchKernelGGL(probe<1>, dim3(blocks), dim3(256), 0, 0, dev, its, out);
-          else hipLaunchKernelGGL(probe<2>, dim3(blocks), dim3(256), 0, 0, dev, its, out);
+          if (sh == 0) {
+            if (fill == 0) hipLaunchKernelGGL(probe<0>, dim3(blocks), dim3(256), 0, 0, dev, its, out);
+            else if (fill == 1) hipLaunchKernelGGL(probe<1>, dim3(blocks), dim3(256), 0, 0, dev, its, out);
+            else hipLaunchKernelGGL(probe<2>, dim3(blocks), dim3(256), 0, 0, dev, its, out);
+          } else {
+            if (fill == 0) hipLaunchKernelGGL((probe<0, 16>), dim3(blocks), dim3(256), 0, 0, dev, its, out);
+            else if (fill == 1) hipLaunchKernelGGL((probe<1, 16>), dim3(blocks), dim3(256), 0, 0, dev, its, out);
+            else hipLaunchKernelGGL((probe<2, 16>), dim3(blocks), dim3(256), 0, 0, dev, its, out);
+          }
         };
         launch(iters / 4);   // warm up / ramp the clocks
         hipDeviceSynchronize();
@@ -105,8 +144,8 @@ int main(int argc, char **argv) {
         const double ms = sum / reps;
         // one SIMD issues an MFMA every 32 cycles at best: implied clock if the pipe were saturated
         const double cycles_per_simd = mfmas_per_wave * wps * 32.0;
-        printf("%-6s waves/SIMD %d  VALU per MFMA %d : %8.3f ms  %7.1f TFLOP/s  (%.3f of 2500)  pipe-saturated clock >= %.2f GHz\n",
-               names[data], wps, 4 * fill * 2 / 4, ms, flop / (ms * 1e-3) / 1e12, flop / (ms * 1e-3) / 1e12 / 2500.0,
+        printf("%-6s shape %d waves/SIMD %d  VALU per MFMA %d : %8.3f ms  %7.1f TFLOP/s  (%.3f of 2500)  pipe-saturated clock >= %.2f GHz\n",
+               names[data], sh ? 16 : 32, wps, 4 * fill * 2 / 4, ms, flop / (ms * 1e-3) / 1e12, flop / (ms * 1e-3) / 1e12 / 2500.0,
                cycles_per_simd / (ms * 1e-3) / 1e9);
       }
     }
