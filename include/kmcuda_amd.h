@@ -229,6 +229,36 @@ int kmamd_last_run_stats(uint32_t *iterations, double *loop_seconds, double *set
  * shard's move sums is inside: that is what an iteration pays), and their number.  0 / 0 otherwise. */
 int kmamd_last_run_collective(double *milliseconds, uint32_t *count);
 
+/* k nearest neighbours of NEW rows (queries) among a clustered corpus (no counterpart in the reference, whose knn_cuda
+ * -- kmcuda.h, kmcuda.cc:572-730 -- is the self-join of the corpus).  An index owns one GPU's prepared corpus: the
+ * cluster-sorted fp32 copy, its f16 split, the radii, the K x K centroid distances, mu and the stats, built once as
+ * knn_cuda() builds them and reused by every query.
+ *   create   samples n_rows x features, centroids clusters x features (fp32, or IEEE halves when fp16x2 != 0 --
+ *            `features` counts halves then and must be even; fp32 arithmetic on the half values as knn_cuda()),
+ *            assignments n_rows (>= clusters: the row has no cluster and is never returned).  device_ptrs: -1 host
+ *            buffers, else the index's device.  The index keeps copies: the caller's buffers may change afterwards.
+ *   query    k in [1, min(n_rows, 65535)]; n_queries x features rows in the corpus's dtype.  query_assignments
+ *            (optional, in): each query's cluster c_q in [0, clusters) with a finite centroid (else InvalidArguments); NULL: its nearest
+ *            centroid in kmamd_lloyd_assign's arithmetic and tie rule, written to query_assignments_out if that is
+ *            given (the passed-in ones otherwise).  Outputs n_queries x k: neighbors (corpus row indices), distances
+ *            (optional, float32: the exact distance the heap compared -- L2 distance or the angular metric's acos
+ *            value).  A query's list is the reference's procedure for it as one more row of cluster c_q WITHOUT the
+ *            self-skip: own cluster in ascending corpus order, then the others in ascending id under the triangle
+ *            prune, push iff distance <= kth, output in the heap's sorted order.  Any c_q gives the same lists (the
+ *            prune is rigorous); only the speed changes.  A query with a NaN or inf feature: indices 0xFFFFFFFF,
+ *            distances NaN.  device_ptrs: -1 host buffers, else the index's device (all of the call's buffers).
+ *            Synchronous: the outputs are complete on return.  Env KMCUDA_AMD_KNN_QUERY_CHUNK=<n> (tests): at most n
+ *            queries per chunk (default: lb and heaps of a chunk within 4 GiB).
+ * KMCUDA_AMD_KNN_EXACT, KMCUDA_AMD_FILTER=f32 and KMCUDA_AMD_FP16_STRICT select the search as for knn_cuda(). */
+typedef struct kmamd_knn_index kmamd_knn_index;
+int kmamd_knn_index_create(kmamd_knn_index **out, int device, int metric, int fp16x2, uint32_t n_rows,
+                           uint32_t features, uint32_t clusters, const void *samples, const void *centroids,
+                           const uint32_t *assignments, int32_t device_ptrs, int verbosity);
+int kmamd_knn_index_query(kmamd_knn_index *ix, uint32_t k, uint32_t n_queries, const void *queries,
+                          const uint32_t *query_assignments, uint32_t *neighbors, float *distances,
+                          uint32_t *query_assignments_out, int32_t device_ptrs);
+void kmamd_knn_index_destroy(kmamd_knn_index *ix);
+
 /* host -> raw device pointer copy on `device` (what python.cc:330-345 does with cudaMemcpy for imported
  * centroids in device-pointer mode; lets a binding without a HIP runtime of its own fill caller-owned memory). */
 int kmamd_copy_to_device(int device, void *dst, const void *host_src, size_t bytes);

@@ -394,6 +394,16 @@ struct KnnArgs {
                                // scored on the matrix cores (32 x 32 per wave, operand set and sub-tile), [2] of those:
                                // live, unpruned query x real candidate, [3] exact chains evaluated, [4] what [1] would
                                // be if an operand set without a visiting query were not scored
+  // The query side (kmamd_knn_index_query: the search kernels' SELF = false instantiations).  knn_cuda's self-join
+  // reads its queries from the candidate side above (SELF = true) and leaves these unread; a query batch has its own
+  // cluster-sorted rows (qxs: DP-padded fp32, the exact chains; qxs16: centred halves, the f16 filter's B operand),
+  // norms (qn2s: plain for the f32 filter, centred for the f16 one), mu.(x - mu) (qmux), distances to their own
+  // centroid (qmydist) and CSR offsets (qoffsets, K + 1: own_end, the exact kernel's cluster_of).  Block plan, qperm,
+  // lb, heaps and out are indexed by QUERY positions; offsets / xs / xs16 / kbias / inv stay the corpus's.
+  const float *qxs = nullptr, *qn2s = nullptr, *qmux = nullptr, *qmydist = nullptr;
+  const void *qxs16 = nullptr;
+  const uint32_t *qoffsets = nullptr;
+  float *outd = nullptr;       // query mode, optional: (p_end - p_base) x k distances beside `out`
 };
 constexpr int KNN_STATS = 5;
 // mu (the f16 filter's centre, else null): stats[1] = 1 if a finite row of a cluster leaves the half range once centred
@@ -403,7 +413,17 @@ hipError_t launch_knn_gather(const float *samples, uint32_t N, uint32_t D, uint3
 hipError_t launch_knn_prep(int metric, const float *xs, uint32_t N, uint32_t D, uint32_t DP, const uint32_t *offsets,
                            uint32_t K, const float *centroids, float *mydist, float *rdist, float *R, float *C,
                            bool strict_h2, hipStream_t st);
-hipError_t launch_knn_filter(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st);
+// self = false (the search kernels' query mode, KnnArgs::q*): the candidate distances of the member kernel without the
+// radius reduction -- mydist of every sorted row of a query batch (rdist: scratch of N floats)
+hipError_t launch_knn_member(int metric, const float *xs, uint32_t N, uint32_t D, uint32_t DP, const uint32_t *offsets,
+                             uint32_t K, const float *centroids, float *mydist, float *rdist, bool strict_h2,
+                             hipStream_t st);
+// query preparation: eff[q] = assignments[q] for a row of finite features, K ("no cluster") for a row with a NaN or
+// inf feature; a finite row whose assignment is >= K or names a non-finite centroid raises flags[0] (an invalid
+// caller-supplied assignment)
+hipError_t launch_knn_query_clusters(const float *rows, uint32_t Q, uint32_t D, const uint32_t *assignments, uint32_t K,
+                                     const float *centroids, uint32_t *eff, uint32_t *flags, hipStream_t st);
+hipError_t launch_knn_filter(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self = true);
 // lb[c * stride + (p - p_base)] for the sorted positions [p_base, p_end) and all K centroids (L2, D <= 1024)
 hipError_t launch_knn_centroid_bounds(const float *xs, uint32_t D, uint32_t DP, uint32_t p_base, uint32_t p_end,
                                       const float *centroids, uint32_t K, const float *R, float *lb, size_t stride,
@@ -413,10 +433,10 @@ bool launch_knn_query_order(const float *lb, size_t stride, const uint32_t *offs
                             uint32_t *qperm, void *temp, size_t temp_bytes, hipStream_t st, int mode,
                             const float *mydist, const float *R);
 // strict_h2 (both): the reference's half2 arithmetic on rows that hold half values (KMCUDA_AMD_FP16_STRICT)
-hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st);
+hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st, bool self = true);
 hipError_t launch_knn_split(int metric, const float *xs, uint32_t N, uint32_t D, uint32_t DP, const float *mu,
                             void *xs16, float *n2c, float *mux, float *kbias, uint32_t *stats, hipStream_t st);
-hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st);
+hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self = true);
 hipError_t launch_knn_scatter(const uint32_t *sorted_out, const uint32_t *inv, uint32_t p_base, uint32_t p_end,
                               uint32_t k, uint32_t *neighbors, hipStream_t st);
 

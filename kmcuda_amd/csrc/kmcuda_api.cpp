@@ -28,6 +28,7 @@
 #include "../../include/kmcuda.h"
 #include "../../include/kmcuda_amd.h"
 #include "engine.hpp"
+#include "knn_host.hpp"
 
 using namespace kmx;
 
@@ -1512,71 +1513,6 @@ class Job {
 // data-path collective.  The small replicated pieces (radii, K x K centroid distances) are
 // recomputed on every GPU instead of exchanged.
 // ---------------------------------------------------------------------------------------
-struct KnnShard {
-  int dev = 0;
-  hipStream_t stream = nullptr;
-  const float *samples = nullptr, *centroids = nullptr;
-  const uint32_t *assignments = nullptr;
-  float *xs = nullptr, *n2s = nullptr, *mydist = nullptr, *rdist = nullptr, *R = nullptr, *C = nullptr, *heaps = nullptr;
-  float *mu = nullptr, *mux = nullptr, *kbias = nullptr;
-  uint16_t *xs16 = nullptr;
-  uint32_t *inv = nullptr, *offsets = nullptr, *keys_tmp = nullptr, *vals_tmp = nullptr, *keys_sorted = nullptr,
-           *stats = nullptr, *blocks = nullptr, *out = nullptr;
-  unsigned long long *calced = nullptr;
-  void *sort_temp = nullptr;
-  uint32_t first_block = 0, nblocks = 0, p_base = 0, p_end = 0;
-  std::vector<void *> owned;
-  ~KnnShard() {
-    (void)hipSetDevice(dev);
-    for (void *p : owned) (void)hipFree(p);
-    pooled_stream_release(dev, stream);
-  }
-  template <typename T>
-  int alloc(T **p, size_t count) {
-    void *q = nullptr;
-    if (hipMalloc(&q, count ? count * sizeof(T) : sizeof(T)) != hipSuccess) return kmcudaMemoryAllocationFailure;
-    owned.push_back(q);
-    *p = static_cast<T *>(q);
-    return 0;
-  }
-  // brings `count` elements of a caller buffer onto this device (or uses it in place)
-  template <typename T>
-  int stage_in(const T *src, size_t count, int32_t device_ptrs, const T **dst) {
-    if (device_ptrs >= 0 && device_ptrs == dev) {
-      *dst = src;
-      return 0;
-    }
-    T *buf = nullptr;
-    int rc = alloc(&buf, count);
-    if (rc) return rc;
-    hipError_t e = device_ptrs < 0
-                       ? hipMemcpyAsync(buf, src, count * sizeof(T), hipMemcpyHostToDevice, stream)
-                       : hipMemcpyPeerAsync(buf, dev, src, device_ptrs, count * sizeof(T), stream);
-    if (e != hipSuccess) return kmcudaMemoryCopyError;
-    *dst = buf;
-    return 0;
-  }
-};
-
-// brings `count` halves of a caller buffer onto the shard's device and widens them to fp32
-static int stage_in_half(KnnShard &sh, const void *src, size_t count, int32_t device_ptrs, const float **dst) {
-  float *buf = nullptr;
-  int rc = sh.alloc(&buf, count);
-  if (rc) return rc;
-  const uint16_t *dev_half = reinterpret_cast<const uint16_t *>(src);
-  uint16_t *tmp = nullptr;
-  if (!(device_ptrs >= 0 && device_ptrs == sh.dev)) {
-    if ((rc = sh.alloc(&tmp, count))) return rc;
-    hipError_t e = device_ptrs < 0 ? hipMemcpyAsync(tmp, src, count * sizeof(uint16_t), hipMemcpyHostToDevice, sh.stream)
-                                   : hipMemcpyPeerAsync(tmp, sh.dev, src, device_ptrs, count * sizeof(uint16_t), sh.stream);
-    if (e != hipSuccess) return kmcudaMemoryCopyError;
-    dev_half = tmp;
-  }
-  if (launch_half_to_float(dev_half, count, buf, sh.stream) != hipSuccess) return kmcudaRuntimeError;
-  *dst = buf;
-  return 0;
-}
-
 class KnnJob {
  public:
   std::vector<std::unique_ptr<KnnShard>> shards;
@@ -1598,63 +1534,15 @@ class KnnJob {
         shard_devs.assign(1, devs[0]);
       }
     }
-    const char *force_exact = getenv("KMCUDA_AMD_KNN_EXACT");
-    // KMCUDA_AMD_FP16_STRICT (fp16x2 only): radii, centroid distances and every candidate distance in the reference's
-    // half2 arithmetic (knn.hip, half2_ops.hpp) -- the verification mode of half2_strict.hip for this entry point;
-    // no matrix-core filter (its bound is stated against the fp32 arithmetic)
-    const char *strict_env = getenv("KMCUDA_AMD_FP16_STRICT");
-    const bool strict_h2 = fp16 && strict_env && atoi(strict_env) != 0;
-    if (strict_h2) INFO("k-NN: the reference's half2 arithmetic (KMCUDA_AMD_FP16_STRICT)\n");
-    const char *fenv = getenv("KMCUDA_AMD_FILTER");
-    const bool want_f32 = fenv && strcmp(fenv, "f32") == 0;
-    uint32_t dp_filter = ((force_exact && atoi(force_exact)) || strict_h2) ? 0 : filter_dp_for(D);
-    // 256 < D <= 1024: the f16 filter's one-operand-set instantiations (knn_f16.hip: 512 with two blocks per CU;
-    // 768 / 1024 with one -- the queries' operands alone are 192 / 256 registers; the f32 filter stops at 256)
-    if (!dp_filter && !(force_exact && atoi(force_exact)) && !strict_h2 && !want_f32 && D > 256 && D <= 1024)
-      dp_filter = D <= 512 ? 512u : (D <= 768 ? 768u : 1024u);
-    const uint32_t DP = dp_filter ? dp_filter : D;
-    if (!dp_filter) INFO("k-NN: every candidate is evaluated with the exact arithmetic (no matrix-core filter)\n");
-    // which matrix-core instruction filters the candidates: f16 on centred hi/lo-split rows (default,
-    // needs DP >= 16) or f32 (KMCUDA_AMD_FILTER=f32)
-    bool use_f16 = dp_filter >= 16 && !want_f32;
+    const KnnPath path = knn_choose_path(D, fp16, verbosity);
+    const bool strict_h2 = path.strict_h2;
+    uint32_t dp_filter = path.dp_filter;
+    const uint32_t DP = path.DP;
+    bool use_f16 = path.use_f16;
     // mu = mean of the finite centroid rows (any vector works: distances are translation invariant)
     std::vector<float> mu_host(DP, 0.f);
     float mu2 = 0.f;
-    if (use_f16) {
-      std::vector<float> cen((size_t)K * D);
-      if (fp16) {
-        std::vector<uint16_t> raw((size_t)K * D);
-        if (device_ptrs < 0) memcpy(raw.data(), centroids, raw.size() * sizeof(uint16_t));
-        else if (hipMemcpy(raw.data(), centroids, raw.size() * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess)
-          return kmcudaMemoryCopyError;
-        for (size_t i = 0; i < raw.size(); i++) {  // half -> float on the host
-          const uint32_t hbits = raw[i], sign = (hbits & 0x8000u) << 16, ex = (hbits >> 10) & 0x1Fu, man = hbits & 0x3FFu;
-          float v;
-          if (ex == 0) v = ldexpf((float)man, -24);
-          else if (ex == 31) v = man ? NAN : INFINITY;
-          else v = ldexpf((float)(man | 0x400u), (int)ex - 25);
-          cen[i] = sign ? -v : v;
-        }
-      } else if (device_ptrs < 0) {
-        memcpy(cen.data(), centroids, cen.size() * sizeof(float));
-      } else if (hipMemcpy(cen.data(), centroids, cen.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-        return kmcudaMemoryCopyError;
-      }
-      std::vector<double> acc(D, 0.0);
-      uint32_t nfin = 0;
-      for (uint32_t c = 0; c < K; c++) {
-        bool fin = true;
-        for (uint32_t f = 0; f < D && fin; f++) fin = std::isfinite(cen[(size_t)c * D + f]);
-        if (!fin) continue;
-        for (uint32_t f = 0; f < D; f++) acc[f] += cen[(size_t)c * D + f];
-        nfin++;
-      }
-      for (uint32_t f = 0; f < D; f++) {
-        mu_host[f] = nfin ? (float)(acc[f] / nfin) : 0.f;
-        mu2 += mu_host[f] * mu_host[f];
-      }
-      mu2 *= 1.0001f;
-    }
+    if (use_f16) RETERR(knn_centroid_mean(centroids, K, D, fp16, device_ptrs, mu_host, &mu2));
     const size_t sort_bytes = sort_temp_bytes(N, K);
     for (int dev : shard_devs) {
       auto sh = std::make_unique<KnnShard>();
@@ -1700,13 +1588,7 @@ class KnnJob {
     INFO("initializing the inverse assignments...\n");
     for (auto &s : shards) {
       (void)hipSetDevice(s->dev);
-      if (hipMemsetAsync(s->calced, 0, KNN_STATS * sizeof(unsigned long long), s->stream) != hipSuccess) return kmcudaRuntimeError;
-      if (launch_inverse_assignments(s->assignments, N, K, s->keys_tmp, s->vals_tmp, s->keys_sorted, s->inv,
-                                     s->offsets, s->sort_temp, sort_bytes, s->stream) != hipSuccess)
-        return kmcudaRuntimeError;
-      if (launch_knn_gather(s->samples, N, D, DP, s->inv, s->xs, s->n2s, s->stats, use_f16 ? s->mu : nullptr, s->offsets,
-                            K, s->stream) != hipSuccess)
-        return kmcudaRuntimeError;
+      RETERR(knn_sort_and_gather(*s, N, D, DP, K, use_f16, sort_bytes));
     }
     INFO("calculating the cluster radiuses...\n");
     INFO("calculating the centroid distance matrix...\n");

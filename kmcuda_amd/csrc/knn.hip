@@ -250,7 +250,9 @@ __global__ void knn_cdist_kernel(const float *__restrict__ centroids, uint32_t K
 // MFMA orientation as in lloyd.hip: A = candidate rows (32), B = queries (32 columns); lane l
 // holds, for query l&31, the scores of rows (r&3) + 8*(r>>2) + 4*(l>>5), r = 0..15; the lower
 // half-wave contracts features [0, DP/2), the upper half [DP/2, DP).
-template <int DP, int METRIC>
+// SELF: knn_cuda's self-join (queries = the corpus rows, the row itself skipped); else a query batch read from the
+// KnnArgs::q* buffers, nothing skipped (kmamd_knn_index_query).  The candidate side is the same either way.
+template <int DP, int METRIC, bool SELF>
 __global__ __launch_bounds__(256, 2) void knn_filter_kernel(KnnArgs a) {
   constexpr int NK = DP / 2;
   constexpr int LDW = DP + 4;
@@ -268,14 +270,19 @@ __global__ __launch_bounds__(256, 2) void knn_filter_kernel(KnnArgs a) {
   const int h = lane >> 5;
   const uint32_t K = a.K, k = a.k, D = a.D;
 
+  // the query side (SELF: the candidate side itself)
+  const float *const q_xs = SELF ? a.xs : a.qxs, *const q_n2s = SELF ? a.n2s : a.qn2s;
+  const float *const q_mydist = SELF ? a.mydist : a.qmydist;
+  const uint32_t *const q_offsets = SELF ? a.offsets : a.qoffsets;
+
   const uint32_t cls0 = a.blocks[2 * (size_t)blockIdx.x], p0 = a.blocks[2 * (size_t)blockIdx.x + 1];
-  const uint32_t own_end = a.offsets[cls0 + 1];
+  const uint32_t own_end = q_offsets[cls0 + 1];
   const uint32_t qp = p0 + wave * 32 + col;
   const bool live = qp < own_end;
 
   float xb[NK];
   {
-    const f32x4 *src = reinterpret_cast<const f32x4 *>(a.xs + (size_t)(live ? qp : p0) * DP + h * NK);
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(q_xs + (size_t)(live ? qp : p0) * DP + h * NK);
 #pragma unroll
     for (int j = 0; j < NK / 4; j++) {
       const f32x4 v = src[j];
@@ -286,8 +293,8 @@ __global__ __launch_bounds__(256, 2) void knn_filter_kernel(KnnArgs a) {
     }
   }
   const int nvalid = (int)D - h * NK < 0 ? 0 : ((int)D - h * NK > NK ? NK : (int)D - h * NK);  // real features here
-  const float qn2 = live ? a.n2s[qp] : 0.f;
-  const float md = live ? a.mydist[qp] : 0.f;
+  const float qn2 = live ? q_n2s[qp] : 0.f;
+  const float md = live ? q_mydist[qp] : 0.f;
   float *heap = a.heaps + (size_t)((live ? qp : p0) - a.p_base) * 2 * k;
   if (live && h == 0) {
     for (uint32_t i = 0; i < k; i++) {
@@ -415,7 +422,7 @@ __global__ __launch_bounds__(256, 2) void knn_filter_kernel(KnnArgs a) {
             const uint32_t rho = active ? (uint32_t)__ffs((int)rowmask) - 1u : 0u;
             rowmask &= rowmask - 1u;
             const uint32_t cp = tile_base + rho;
-            if (step == 0 && cp == qp) active = false;  // knn.cu:204-206: not its own neighbour
+            if (SELF && step == 0 && cp == qp) active = false;  // knn.cu:204-206: not its own neighbour
             if (cp >= end) active = false;  // tile padding (-inf score) passes while the heap is not full (amin = -inf)
             const float *crow = tile_ptr(buf) + rho * LDW + h * NK;
             // one serial Kahan chain over the D features: the lower half-wave runs features
@@ -459,8 +466,11 @@ __global__ __launch_bounds__(256, 2) void knn_filter_kernel(KnnArgs a) {
   }
   if (live && h == 0) {  // knn.cu:239-242
     uint32_t *out = a.out + (size_t)(qp - a.p_base) * k;
+    float *outd = SELF ? nullptr : a.outd;
+    if (outd) outd += (size_t)(qp - a.p_base) * k;
     for (int i = (int)k - 1; i >= 0; i--) {
       out[i] = reinterpret_cast<uint32_t *>(heap)[1];
+      if (!SELF && outd) outd[i] = heap[0];   // the exact distance the heap compared
       knn_push_sample(k, -1.f, 0xFFFFFFFFu, heap);
     }
   }
@@ -470,19 +480,24 @@ __global__ __launch_bounds__(256, 2) void knn_filter_kernel(KnnArgs a) {
 // ---------------------------------------------------------------------------------------
 // the unfiltered search: one thread per sorted position, every candidate evaluated exactly
 // ---------------------------------------------------------------------------------------
-template <int METRIC, bool H2>
+// SELF as in knn_filter_kernel: the self-join, or a query batch from the KnnArgs::q* buffers (nothing skipped)
+template <int METRIC, bool H2, bool SELF>
 __global__ __launch_bounds__(64) void knn_exact_kernel(KnnArgs a) {
   const uint32_t qp = a.p_base + blockIdx.x * blockDim.x + threadIdx.x;
   if (qp >= a.p_end) return;
   const uint32_t K = a.K, k = a.k, D = a.D, DP = a.DP;
-  const uint32_t mycls = cluster_of(a.offsets, K, qp);
+  const uint32_t mycls = cluster_of(SELF ? a.offsets : a.qoffsets, K, qp);
   uint32_t *out = a.out + (size_t)(qp - a.p_base) * k;
+  float *outd = SELF ? nullptr : a.outd;
+  if (outd) outd += (size_t)(qp - a.p_base) * k;
   if (mycls >= K) {  // a row without a cluster (NaN sample): the reference reads out of bounds here
     for (uint32_t i = 0; i < k; i++) out[i] = 0xFFFFFFFFu;
+    if (!SELF && outd)
+      for (uint32_t i = 0; i < k; i++) outd[i] = NAN;
     return;
   }
-  const float *x = a.xs + (size_t)qp * DP;
-  const float md = a.mydist[qp];
+  const float *x = (SELF ? a.xs : a.qxs) + (size_t)qp * DP;
+  const float md = (SELF ? a.mydist : a.qmydist)[qp];
   float *heap = a.heaps + (size_t)(qp - a.p_base) * 2 * k;
   for (uint32_t i = 0; i < k; i++) {
     heap[2 * i] = 3.402823466e+38f;
@@ -501,7 +516,7 @@ __global__ __launch_bounds__(64) void knn_exact_kernel(KnnArgs a) {
     const uint32_t beg = a.offsets[cls], end = a.offsets[cls + 1];
     calced += end - beg;
     for (uint32_t cp = beg; cp < end; cp++) {
-      if (cp == qp) continue;
+      if (SELF && cp == qp) continue;
       const float dist = H2 ? h2_distance<METRIC>(x, a.xs + (size_t)cp * DP, D)   // distance_tt, F = half2
                             : finalize<METRIC>(partial_vv<METRIC>(x, a.xs + (size_t)cp * DP, D));
       if (dist <= mndist) {
@@ -512,6 +527,7 @@ __global__ __launch_bounds__(64) void knn_exact_kernel(KnnArgs a) {
   }
   for (int i = (int)k - 1; i >= 0; i--) {
     out[i] = reinterpret_cast<uint32_t *>(heap)[1];
+    if (!SELF && outd) outd[i] = heap[0];
     knn_push_sample(k, -1.f, 0xFFFFFFFFu, heap);
   }
   atomicAdd(a.calced, calced);
@@ -626,13 +642,14 @@ hipError_t launch_knn_gather(const float *samples, uint32_t N, uint32_t D, uint3
   return hipGetLastError();
 }
 
-hipError_t launch_knn_prep(int metric, const float *xs, uint32_t N, uint32_t D, uint32_t DP, const uint32_t *offsets,
-                           uint32_t K, const float *centroids, float *mydist, float *rdist, float *R, float *C,
-                           bool strict_h2, hipStream_t st) {
+hipError_t launch_knn_member(int metric, const float *xs, uint32_t N, uint32_t D, uint32_t DP, const uint32_t *offsets,
+                             uint32_t K, const float *centroids, float *mydist, float *rdist, bool strict_h2,
+                             hipStream_t st) {
+  if (N == 0) return hipSuccess;
   // (the tiled member kernel: whole 32-feature chunks, 16-byte aligned rows and centroids; else, and for the half2
   //  arithmetic, a thread per row)
   const bool tiled = !strict_h2 && D >= 32 && (D & 31u) == 0 && (DP & 3u) == 0 && (((uintptr_t)xs | (uintptr_t)centroids) & 15u) == 0;
-#define KMX_KNN_PREP(M, H)                                                                                          \
+#define KMX_KNN_MEMBER(M, H)                                                                                        \
   do {                                                                                                              \
     if (tiled)                                                                                                      \
       hipLaunchKernelGGL((knn_member_tiled_kernel<M>), dim3((N + kMemberBlock - 1) / kMemberBlock), dim3(kMemberBlock), 0, \
@@ -640,30 +657,78 @@ hipError_t launch_knn_prep(int metric, const float *xs, uint32_t N, uint32_t D, 
     else                                                                                                            \
       hipLaunchKernelGGL((knn_member_kernel<M, H>), dim3((N + 127) / 128), dim3(128), 0, st, xs, N, D, DP, offsets, K, \
                          centroids, mydist, rdist);                                                                 \
-    hipLaunchKernelGGL((knn_cdist_kernel<M, H>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C); \
   } while (0)
   if (metric == 0) {
-    if (strict_h2) KMX_KNN_PREP(0, true); else KMX_KNN_PREP(0, false);
+    if (strict_h2) KMX_KNN_MEMBER(0, true); else KMX_KNN_MEMBER(0, false);
   } else {
-    if (strict_h2) KMX_KNN_PREP(1, true); else KMX_KNN_PREP(1, false);
+    if (strict_h2) KMX_KNN_MEMBER(1, true); else KMX_KNN_MEMBER(1, false);
   }
-#undef KMX_KNN_PREP
+#undef KMX_KNN_MEMBER
+  return hipGetLastError();
+}
+
+hipError_t launch_knn_prep(int metric, const float *xs, uint32_t N, uint32_t D, uint32_t DP, const uint32_t *offsets,
+                           uint32_t K, const float *centroids, float *mydist, float *rdist, float *R, float *C,
+                           bool strict_h2, hipStream_t st) {
+  hipError_t e = launch_knn_member(metric, xs, N, D, DP, offsets, K, centroids, mydist, rdist, strict_h2, st);
+  if (e != hipSuccess) return e;
+  if (metric == 0) {
+    if (strict_h2) hipLaunchKernelGGL((knn_cdist_kernel<0, true>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
+    else hipLaunchKernelGGL((knn_cdist_kernel<0, false>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
+  } else {
+    if (strict_h2) hipLaunchKernelGGL((knn_cdist_kernel<1, true>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
+    else hipLaunchKernelGGL((knn_cdist_kernel<1, false>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
+  }
   hipLaunchKernelGGL(knn_radii_kernel, dim3(K), dim3(64), 0, st, rdist, offsets, K, R);
   return hipGetLastError();
 }
 
-template <int DP, int METRIC>
-static hipError_t launch_knn_filter_t(const KnnArgs &a, uint32_t nblocks, hipStream_t st) {
-  const size_t lds_bytes = (2 * 32 * (DP + 4) + 64 + 8) * sizeof(float);
-  hipLaunchKernelGGL((knn_filter_kernel<DP, METRIC>), dim3(nblocks), dim3(256), lds_bytes, st, a);
+// query preparation (kmamd_knn_index_query): a query with a NaN or inf feature has no cluster (K: it sorts behind
+// every cluster and gets no neighbours, as a corpus row without one); one wave per row.  A finite query whose cluster id
+// is >= K or names a centroid with a NaN / inf value raises flags[0]: the reference's search skips every cluster whose
+// centroid distance to the own one is NaN (knn.cu:219-221), so such a cluster would find nothing
+__global__ __launch_bounds__(256) void knn_query_clusters_kernel(const float *__restrict__ rows, uint32_t Q, uint32_t D,
+                                                                 const uint32_t *__restrict__ assignments, uint32_t K,
+                                                                 const float *__restrict__ centroids,
+                                                                 uint32_t *__restrict__ eff, uint32_t *__restrict__ flags) {
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6); q < Q; q += gridDim.x * 4) {   // (kernels.hpp: wave_row_grid)
+    const float *src = rows + (size_t)q * D;
+    const uint32_t c = assignments[q];
+    bool nonfinite = false, cbad = c >= K;
+    for (uint32_t f = lane; f < D; f += 64) {
+      nonfinite |= !((src[f] - src[f]) == 0.f);
+      if (c < K) cbad |= !((centroids[(size_t)c * D + f] - centroids[(size_t)c * D + f]) == 0.f);
+    }
+    const bool bad = __any(nonfinite), invalid = __any(cbad);
+    if (lane == 0) {
+      eff[q] = bad || invalid ? K : c;
+      if (!bad && invalid) atomicOr(&flags[0], 1u);
+    }
+  }
+}
+
+hipError_t launch_knn_query_clusters(const float *rows, uint32_t Q, uint32_t D, const uint32_t *assignments, uint32_t K,
+                                     const float *centroids, uint32_t *eff, uint32_t *flags, hipStream_t st) {
+  if (Q == 0) return hipSuccess;
+  hipLaunchKernelGGL(knn_query_clusters_kernel, dim3(wave_row_grid(Q)), dim3(256), 0, st, rows, Q, D, assignments, K,
+                     centroids, eff, flags);
   return hipGetLastError();
 }
 
-hipError_t launch_knn_filter(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st) {
+template <int DP, int METRIC>
+static hipError_t launch_knn_filter_t(const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self) {
+  const size_t lds_bytes = (2 * 32 * (DP + 4) + 64 + 8) * sizeof(float);
+  if (self) hipLaunchKernelGGL((knn_filter_kernel<DP, METRIC, true>), dim3(nblocks), dim3(256), lds_bytes, st, a);
+  else hipLaunchKernelGGL((knn_filter_kernel<DP, METRIC, false>), dim3(nblocks), dim3(256), lds_bytes, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_knn_filter(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self) {
   if (nblocks == 0) return hipSuccess;
 #define KMX_KNN_CASE(dp)                                                             \
   case dp:                                                                           \
-    return metric == 0 ? launch_knn_filter_t<dp, 0>(a, nblocks, st) : launch_knn_filter_t<dp, 1>(a, nblocks, st)
+    return metric == 0 ? launch_knn_filter_t<dp, 0>(a, nblocks, st, self) : launch_knn_filter_t<dp, 1>(a, nblocks, st, self)
   switch (a.DP) {
     KMX_KNN_CASE(8);
     KMX_KNN_CASE(16);
@@ -676,16 +741,22 @@ hipError_t launch_knn_filter(int metric, const KnnArgs &a, uint32_t nblocks, hip
 #undef KMX_KNN_CASE
 }
 
-hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st) {
+template <bool SELF>
+static void launch_knn_exact_t(int metric, const KnnArgs &a, bool strict_h2, uint32_t grid, hipStream_t st) {
+  if (metric == 0) {
+    if (strict_h2) hipLaunchKernelGGL((knn_exact_kernel<0, true, SELF>), dim3(grid), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((knn_exact_kernel<0, false, SELF>), dim3(grid), dim3(64), 0, st, a);
+  } else {
+    if (strict_h2) hipLaunchKernelGGL((knn_exact_kernel<1, true, SELF>), dim3(grid), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((knn_exact_kernel<1, false, SELF>), dim3(grid), dim3(64), 0, st, a);
+  }
+}
+
+hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st, bool self) {
   if (a.p_end <= a.p_base) return hipSuccess;
   const uint32_t grid = (a.p_end - a.p_base + 63) / 64;
-  if (metric == 0) {
-    if (strict_h2) hipLaunchKernelGGL((knn_exact_kernel<0, true>), dim3(grid), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((knn_exact_kernel<0, false>), dim3(grid), dim3(64), 0, st, a);
-  } else {
-    if (strict_h2) hipLaunchKernelGGL((knn_exact_kernel<1, true>), dim3(grid), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((knn_exact_kernel<1, false>), dim3(grid), dim3(64), 0, st, a);
-  }
+  if (self) launch_knn_exact_t<true>(metric, a, strict_h2, grid, st);
+  else launch_knn_exact_t<false>(metric, a, strict_h2, grid, st);
   return hipGetLastError();
 }
 

@@ -103,7 +103,11 @@ __global__ __launch_bounds__(256) void knn_split_kernel(const float *__restrict_
 //     holds are not in step, so one's mask phases and barriers run under the other's products.
 // Instrumented builds of the one-set kernel (per-phase s_memtime counters, per-wave timeline of one block):
 // profiles/r2e_knn_filter_phase_counters.log, r2e_knn_filter_block_timeline.log.
-template <int DP, int METRIC, bool FASTX>
+// SELF: knn_cuda's self-join (the queries are the corpus rows, the row itself is skipped); else a query batch from the
+// KnnArgs::q* buffers and nothing is skipped (kmamd_knn_index_query).  The candidate side is the same either way, and
+// so is the bound: it is stated for x = the query (its own centred norm, mu.x') against any candidate y (stats[0], the
+// corpus maximum) and never assumes that x is a corpus row.
+template <int DP, int METRIC, bool FASTX, bool SELF>
 __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void knn_filter_f16_kernel(KnnArgs a) {
   constexpr int WV = knn16_waves(DP), NSET = knn16_nset(DP);
   constexpr int NKH = DP / 2;   // features per half-wave
@@ -125,9 +129,14 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 31, h = lane >> 5;
   const uint32_t K = a.K, k = a.k, D = a.D;
 
+  // the query side (SELF: the candidate side itself)
+  const void *const q_xs16 = SELF ? a.xs16 : a.qxs16;
+  const float *const q_xs = SELF ? a.xs : a.qxs, *const q_n2s = SELF ? a.n2s : a.qn2s;
+  const float *const q_mydist = SELF ? a.mydist : a.qmydist, *const q_mux = SELF ? a.mux : a.qmux;
+
   const uint32_t cls0 = a.blocks[2 * (size_t)blockIdx.x], p0 = a.blocks[2 * (size_t)blockIdx.x + 1];
   if (cls0 == 0xFFFFFFFFu) return;   // an empty slot of the dispatch plan (kmcuda_api.cpp: one cluster's blocks per XCD)
-  const uint32_t own_end = a.offsets[cls0 + 1];
+  const uint32_t own_end = (SELF ? a.offsets : a.qoffsets)[cls0 + 1];
   uint32_t qp[NSET];
   bool live[NSET];
   // B operands: my half of my queries' rows (centred halves)
@@ -151,7 +160,7 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
     live[e] = qp[e] < own_end;
     if (a.qperm && live[e]) qp[e] = a.qperm[qp[e] - a.p_base];     // ... and the query of this cluster it stands for
     const uint32_t qq = live[e] ? qp[e] : p0;
-    const _Float16 *src = reinterpret_cast<const _Float16 *>(a.xs16) + (size_t)qq * DP + h * NKH;
+    const _Float16 *src = reinterpret_cast<const _Float16 *>(q_xs16) + (size_t)qq * DP + h * NKH;
 #pragma unroll
     for (int j = 0; j < KS; j++) {
       xhi[e][j] = reinterpret_cast<const f16x8 *>(src)[j];
@@ -160,8 +169,8 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
         for (int q = 0; q < 8; q++) xhi[e][j][q] = (_Float16)0.f;
       }
     }
-    qn2[e] = live[e] ? a.n2s[qp[e]] : 0.f;      // centred squared norm
-    md[e] = live[e] ? a.mydist[qp[e]] : 0.f;
+    qn2[e] = live[e] ? q_n2s[qp[e]] : 0.f;      // centred squared norm
+    md[e] = live[e] ? q_mydist[qp[e]] : 0.f;
     float *heap = a.heaps + (size_t)(qq - a.p_base) * 2 * k;
     if (live[e] && h == 0) {
       for (uint32_t i = 0; i < k; i++) {
@@ -178,7 +187,7 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
       E[e] = 4.04f * (3.0f * a.eps + 16.0f * u) * (qn2[e] + nmax2) + 6e-8f * sqrtf((float)DP) * (qn + nmx) + 2.0f * e_round;
     } else {
       const float mun = sqrtf(a.mu2) * 1.0001f;
-      kq[e] = (live[e] ? a.mux[qp[e]] : 0.f) + a.mu2;      // x.y = acc + mu.x' + ||mu||^2
+      kq[e] = (live[e] ? q_mux[qp[e]] : 0.f) + a.mu2;      // x.y = acc + mu.x' + ||mu||^2
       E[e] = 2.02f * (3.0f * a.eps + 16.0f * u) * (qn * nmx + mun * nmx) + 3e-8f * sqrtf((float)DP) * (qn + nmx) +
              a.eps * (mun * qn + a.mu2) + 1e-6f + e_round;
     }
@@ -249,7 +258,7 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
   uint32_t chains = 0;   // exact chains this lane's queries have paid for (statistics)
   auto flush = [&](int e) {  // wave-uniform call
     const uint32_t qq = live[e] ? qp[e] : p0;
-    const float *xrow = a.xs + (size_t)qq * DP;   // original values (exact chains)
+    const float *xrow = q_xs + (size_t)qq * DP;   // original values (exact chains)
     float *heap = a.heaps + (size_t)(qq - a.p_base) * 2 * k;
     const float *crow[4];
 #pragma unroll
@@ -416,7 +425,7 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
           const uint32_t rho = active ? (uint32_t)__ffs((int)rowmask) - 1u : 0u;
           rowmask &= rowmask - 1u;
           const uint32_t cp = tile_base + rho;
-          if (step == 0 && cp == qp[e]) active = false;  // knn.cu:204-206: not its own neighbour
+          if (SELF && step == 0 && cp == qp[e]) active = false;  // knn.cu:204-206: not its own neighbour
           if (cp >= end) active = false;                 // tile padding passes while the heap is not full
           if (active) {
 #pragma unroll
@@ -470,8 +479,11 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
     if (live[e] && h == 0) {  // knn.cu:239-242
       float *heap = a.heaps + (size_t)(qp[e] - a.p_base) * 2 * k;
       uint32_t *out = a.out + (size_t)(qp[e] - a.p_base) * k;
+      float *outd = SELF ? nullptr : a.outd;
+      if (outd) outd += (size_t)(qp[e] - a.p_base) * k;
       for (int i = (int)k - 1; i >= 0; i--) {
         out[i] = reinterpret_cast<uint32_t *>(heap)[1];
+        if (!SELF && outd) outd[i] = heap[0];   // the exact distance the heap compared
         knn_push_sample(k, -1.f, 0xFFFFFFFFu, heap);
       }
     }
@@ -505,29 +517,30 @@ hipError_t launch_knn_split(int metric, const float *xs, uint32_t N, uint32_t D,
   return hipGetLastError();
 }
 
-template <int DP, int METRIC>
+template <int DP, int METRIC, bool SELF>
 static hipError_t launch_knn_f16_t(const KnnArgs &a, uint32_t nblocks, hipStream_t st) {
   const size_t lds_bytes = (size_t)knn16_nbuf(DP) * (32 * knn16_sub(DP) * DP * 2) + knn16_nbuf(DP) * 256 + 2 * knn16_waves(DP) * 4;
   if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, true>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, true, SELF>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, false>),
+      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, false, SELF>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
   }
   if (a.D == (uint32_t)DP)
-    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, true>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
+    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, true, SELF>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
   else
-    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, false>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
+    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, false, SELF>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
   return hipGetLastError();
 }
 
-hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st) {
+hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self) {
   if (nblocks == 0) return hipSuccess;
-#define KMX_KNN16_CASE(dp)                                                           \
-  case dp:                                                                           \
-    return metric == 0 ? launch_knn_f16_t<dp, 0>(a, nblocks, st) : launch_knn_f16_t<dp, 1>(a, nblocks, st)
+#define KMX_KNN16_CASE(dp)                                                                                 \
+  case dp:                                                                                                 \
+    return self ? (metric == 0 ? launch_knn_f16_t<dp, 0, true>(a, nblocks, st) : launch_knn_f16_t<dp, 1, true>(a, nblocks, st)) \
+                : (metric == 0 ? launch_knn_f16_t<dp, 0, false>(a, nblocks, st) : launch_knn_f16_t<dp, 1, false>(a, nblocks, st))
   switch (a.DP) {
     KMX_KNN16_CASE(16);
     KMX_KNN16_CASE(32);

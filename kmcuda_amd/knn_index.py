@@ -1,0 +1,202 @@
+"""k nearest neighbours of NEW rows (queries) among a clustered corpus (C ABI: kmamd_knn_index_*, include/kmcuda_amd.h).
+
+knn_cuda() is the self-join of the corpus: every row's neighbours among the OTHER rows.  A KnnIndex prepares the
+corpus once -- the same cluster-sorted copies, radii and centroid distances knn_cuda() builds -- and answers query
+batches against it on the same search kernels:
+
+    index = KnnIndex(samples, centroids, assignments, metric="L2", device=0)
+    neighbors, distances = index.query(queries, k)
+    index.close()
+
+or, once, knn_query(k, samples, centroids, assignments, queries).  A query's list is what the reference's procedure
+gives for it as one more row of its cluster (its nearest centroid unless `query_assignments` says otherwise), WITHOUT
+skipping anything: own cluster first, then the others in ascending id under the triangle prune.
+
+numpy in, numpy out (neighbors uint32, distances float32, assignments uint32).  torch tensors on the index's device
+in, torch tensors on that device out (neighbors / assignments int32: 0xFFFFFFFF reads -1), with no host round trip;
+the call orders with torch's work on the device (it waits for the device first and its outputs are complete when
+it returns).  float16 inputs select fp16x2: fp32 arithmetic on the half values, as knn_cuda().
+"""
+import ctypes
+
+import numpy
+
+from . import _lib
+from .api import _get_metric, _raise_for
+
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _rows(x, name, device=None):
+    """(array-or-tensor, fp16, rows, features, on_device) for a 2-D float32 / float16 operand."""
+    if _is_torch(x):
+        import torch
+        if x.dtype not in (torch.float32, torch.float16):
+            raise TypeError("\"%s\" must be a 2D float32 or float16 tensor" % name)
+        if x.dim() != 2:
+            raise ValueError("\"%s\" must be a 2D tensor" % name)
+        if not x.is_cuda:
+            raise ValueError("\"%s\" must be on a GPU (or be a numpy array)" % name)
+        if device is not None and x.device.index != device:
+            raise ValueError("\"%s\" must be on device %d" % (name, device))
+        return x.contiguous(), x.dtype == torch.float16, int(x.shape[0]), int(x.shape[1]), True
+    if isinstance(x, numpy.ndarray) and x.dtype == numpy.float16:
+        arr, fp16 = numpy.ascontiguousarray(x), True
+    else:
+        if isinstance(x, numpy.ndarray) and x.dtype != numpy.float32:
+            raise TypeError("\"%s\" must be a 2D float32 or float16 numpy array" % name)
+        try:
+            arr = numpy.ascontiguousarray(x, dtype=numpy.float32)
+        except (TypeError, ValueError):
+            raise TypeError("\"%s\" must be a 2D float32 or float16 numpy array" % name)
+        fp16 = False
+    if arr.ndim != 2:
+        raise ValueError("\"%s\" must be a 2D numpy array" % name)
+    return arr, fp16, int(arr.shape[0]), int(arr.shape[1]), False
+
+
+def _labels(x, n, name, clusters=None, device=None):
+    """1-D cluster ids of length n (uint32 numpy / int32 tensor); with `clusters`: every id must be below it."""
+    if _is_torch(x):
+        import torch
+        if x.dtype.is_floating_point or x.dtype == torch.bool:
+            raise TypeError("\"%s\" must be a 1D integer tensor" % name)
+        if x.dim() != 1:
+            raise ValueError("\"%s\" must be a 1D tensor" % name)
+        if x.shape[0] != n:
+            raise ValueError("\"%s\" must have one entry per row (%d)" % (name, n))
+        if not x.is_cuda or (device is not None and x.device.index != device):
+            raise ValueError("\"%s\" must be on the index's device" % name)
+        if clusters is not None and n and bool(((x < 0) | (x >= clusters)).any()):
+            raise ValueError("\"%s\" must hold cluster ids in [0, %d)" % (name, clusters))
+        return x.to(torch.int32).contiguous(), True
+    if isinstance(x, numpy.ndarray) and x.dtype.kind not in "iu":
+        raise TypeError("\"%s\" must be a 1D integer numpy array" % name)
+    arr = numpy.asarray(x)
+    if arr.ndim != 1:
+        raise ValueError("\"%s\" must be a 1D numpy array" % name)
+    if arr.shape[0] != n:
+        raise ValueError("\"%s\" must have one entry per row (%d)" % (name, n))
+    if clusters is not None and n and (arr.min() < 0 or arr.max() >= clusters):
+        raise ValueError("\"%s\" must hold cluster ids in [0, %d)" % (name, clusters))
+    return numpy.ascontiguousarray(arr, dtype=numpy.uint32), False
+
+
+def _check_corpus(samples, centroids, assignments, device):
+    s, fp16, n, d, on_dev = _rows(samples, "samples", device)
+    c, cfp16, clusters, cd, c_dev = _rows(centroids, "centroids", device)
+    if cfp16 != fp16 or c_dev != on_dev:
+        raise TypeError("\"centroids\" must be of the same kind and dtype as \"samples\"")
+    if cd != d:
+        raise ValueError("\"centroids\" must have same number of features as \"samples\" (shape[-1])")
+    if n == 0 or d == 0:
+        raise ValueError("\"samples\" must not be empty")
+    if clusters < 1:
+        raise ValueError("\"centroids\" must not be empty")
+    if fp16 and d % 2:
+        raise ValueError("the number of features must be even in fp16 mode")
+    if _is_torch(assignments) != on_dev:
+        raise TypeError("\"assignments\" must be of the same kind as \"samples\" (numpy array or torch tensor)")
+    a, _ = _labels(assignments, n, "assignments", None, device)
+    return s, c, a, fp16, n, d, clusters, on_dev
+
+
+def _check_k(k, n):
+    if isinstance(k, bool) or not isinstance(k, (int, numpy.integer)):
+        raise TypeError("\"k\" must be an integer")
+    k = int(k)
+    if k < 1 or k > min(n, 0xFFFF):
+        raise ValueError("\"k\" must be in [1, min(number of samples, 65535)] = [1, %d]" % min(n, 0xFFFF))
+    return k
+
+
+def _check_queries(queries, fp16, d, clusters, query_assignments, device):
+    q, qfp16, nq, qd, q_dev = _rows(queries, "queries", device)
+    if qfp16 != fp16:
+        raise TypeError("\"queries\" must have the dtype of \"samples\"")
+    if qd != d:
+        raise ValueError("\"queries\" must have same number of features as \"samples\" (shape[-1])")
+    qa = None
+    if query_assignments is not None:
+        if _is_torch(query_assignments) != q_dev:
+            raise TypeError("\"query_assignments\" must be of the same kind as \"queries\"")
+        qa, _ = _labels(query_assignments, nq, "query_assignments", clusters, device)
+    return q, nq, q_dev, qa
+
+
+def _ptr(x):
+    return ctypes.c_void_p(x.data_ptr() if _is_torch(x) else x.ctypes.data)
+
+
+class KnnIndex:
+    """A corpus prepared for k-NN queries on one GPU (kmamd_knn_index_create)."""
+
+    def __init__(self, samples, centroids, assignments, metric="L2", device=0, verbosity=0):
+        metric_id = _get_metric(metric)
+        s, c, a, fp16, n, d, clusters, on_dev = _check_corpus(samples, centroids, assignments, device)
+        self.n_rows, self.features, self.clusters, self.fp16 = n, d, clusters, fp16
+        self.metric, self.device = metric, int(device)
+        self.lib = _lib.lib()
+        h = ctypes.c_void_p()
+        rc = self.lib.kmamd_knn_index_create(ctypes.byref(h), self.device, metric_id, int(fp16), n, d, clusters,
+                                             _ptr(s), _ptr(c), _ptr(a), self.device if on_dev else -1, int(verbosity))
+        _raise_for(rc, "kmamd_knn_index_create")
+        self.h = h
+
+    def query(self, queries, k, query_assignments=None, return_distances=True, return_assignments=False):
+        """The k nearest corpus rows of every query row: neighbors (Q x k corpus row indices), then, as asked,
+        distances (Q x k float32, the exact distances the search compared) and the queries' clusters (Q)."""
+        if not getattr(self, "h", None):
+            raise ValueError("the index is closed")
+        k = _check_k(k, self.n_rows)
+        q, nq, q_dev, qa = _check_queries(queries, self.fp16, self.features, self.clusters, query_assignments,
+                                          self.device)
+        if q_dev:
+            import torch
+            dev = torch.device("cuda", self.device)
+            nb = torch.empty((nq, k), dtype=torch.int32, device=dev)
+            dist = torch.empty((nq, k), dtype=torch.float32, device=dev) if return_distances else None
+            asg = torch.empty((nq,), dtype=torch.int32, device=dev) if return_assignments else None
+        else:
+            nb = numpy.empty((nq, k), numpy.uint32)
+            dist = numpy.empty((nq, k), numpy.float32) if return_distances else None
+            asg = numpy.empty((nq,), numpy.uint32) if return_assignments else None
+        if nq:
+            rc = self.lib.kmamd_knn_index_query(self.h, k, nq, _ptr(q), _ptr(qa) if qa is not None else None, _ptr(nb),
+                                                _ptr(dist) if dist is not None else None,
+                                                _ptr(asg) if asg is not None else None, self.device if q_dev else -1)
+            _raise_for(rc, "kmamd_knn_index_query")
+        out = (nb,) + ((dist,) if return_distances else ()) + ((asg,) if return_assignments else ())
+        return out[0] if len(out) == 1 else out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.kmamd_knn_index_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def knn_query(k, samples, centroids, assignments, queries, metric="L2", device=0, query_assignments=None,
+              return_distances=True, return_assignments=False, verbosity=0):
+    """One-shot KnnIndex(samples, centroids, assignments, metric, device).query(queries, k, ...): every argument is
+    checked before the device is touched."""
+    _get_metric(metric)
+    _, _, _, fp16, n, d, clusters, _ = _check_corpus(samples, centroids, assignments, device)
+    _check_k(k, n)
+    _check_queries(queries, fp16, d, clusters, query_assignments, device)
+    with KnnIndex(samples, centroids, assignments, metric=metric, device=device, verbosity=verbosity) as ix:
+        return ix.query(queries, k, query_assignments=query_assignments, return_distances=return_distances,
+                        return_assignments=return_assignments)
