@@ -1,4 +1,5 @@
-// kmcuda_api.cpp -- the drop-in C ABI: kmeans_cuda() and knn_cuda() of include/kmcuda.h.
+// kmcuda_api.cpp -- the drop-in C ABI: kmeans_cuda() and knn_cuda() of include/kmcuda.h (knn_cuda()'s argument checks;
+// its host job is knn_job.cpp).
 //
 // Host orchestration mirroring the reference's contract (src/kmcuda.cc:402-531 kmeans_cuda,
 // src/kmeans.cu:934-1026 kmeans_cuda_lloyd, :1028-1263 kmeans_cuda_yy): same argument
@@ -1506,330 +1507,6 @@ class Job {
 };
 
 
-// ---------------------------------------------------------------------------------------
-// k-NN host side (reference: knn_cuda, kmcuda.cc:572-730 + knn_cuda_calc, knn.cu:381-532).
-// Every GPU of the mask holds the whole corpus (as in the reference, kmcuda.cc:593-598) in
-// CLUSTER-SORTED order and searches a contiguous slice of the sorted positions; there is no
-// data-path collective.  The small replicated pieces (radii, K x K centroid distances) are
-// recomputed on every GPU instead of exchanged.
-// ---------------------------------------------------------------------------------------
-class KnnJob {
- public:
-  std::vector<std::unique_ptr<KnnShard>> shards;
-
-  int run(const std::vector<int> &devs, int nvirtual, uint32_t k, int metric, uint32_t N, uint32_t D, uint32_t K,
-          int32_t device_ptrs, int verbosity, bool fp16, const float *samples, const float *centroids,
-          const uint32_t *assignments, uint32_t *neighbors) {
-    std::vector<int> shard_devs = devs;
-    if (nvirtual > 1 && devs.size() == 1) shard_devs.assign(nvirtual, devs[0]);  // test hook
-    // measurement hook KMCUDA_AMD_KNN_SHARD="i/n": plan the queries for n GPUs but run ONLY share i, on the
-    // first GPU of the mask (what one rank of an n-GPU search does: whole corpus resident, 1/n of the
-    // queries); the other rows of `neighbors` are left untouched
-    size_t plan_shards = shard_devs.size(), plan_first = 0;
-    if (const char *only = getenv("KMCUDA_AMD_KNN_SHARD")) {
-      unsigned i = 0, n = 0;
-      if (sscanf(only, "%u/%u", &i, &n) == 2 && n >= 1 && i < n) {
-        plan_shards = n;
-        plan_first = i;
-        shard_devs.assign(1, devs[0]);
-      }
-    }
-    const KnnPath path = knn_choose_path(D, fp16, verbosity);
-    const bool strict_h2 = path.strict_h2;
-    uint32_t dp_filter = path.dp_filter;
-    const uint32_t DP = path.DP;
-    bool use_f16 = path.use_f16;
-    // mu = mean of the finite centroid rows (any vector works: distances are translation invariant)
-    std::vector<float> mu_host(DP, 0.f);
-    float mu2 = 0.f;
-    if (use_f16) RETERR(knn_centroid_mean(centroids, K, D, fp16, device_ptrs, mu_host, &mu2));
-    const size_t sort_bytes = sort_temp_bytes(N, K);
-    for (int dev : shard_devs) {
-      auto sh = std::make_unique<KnnShard>();
-      sh->dev = dev;
-      if (hipSetDevice(dev) != hipSuccess) return kmcudaNoSuchDevice;
-      if (!(sh->stream = pooled_stream_acquire(dev))) return kmcudaRuntimeError;
-      if (fp16) {  // half buffers -> fp32 working copies (fp32 arithmetic on the half values)
-        RETERR(stage_in_half(*sh, samples, (size_t)N * D, device_ptrs, &sh->samples));
-        RETERR(stage_in_half(*sh, centroids, (size_t)K * D, device_ptrs, &sh->centroids));
-      } else {
-        RETERR(sh->stage_in(samples, (size_t)N * D, device_ptrs, &sh->samples));
-        RETERR(sh->stage_in(centroids, (size_t)K * D, device_ptrs, &sh->centroids));
-      }
-      RETERR(sh->stage_in(assignments, (size_t)N, device_ptrs, &sh->assignments));
-      int rc;
-      if ((rc = sh->alloc(&sh->xs, (size_t)N * DP))) return rc;
-      if ((rc = sh->alloc(&sh->n2s, N))) return rc;
-      if ((rc = sh->alloc(&sh->mydist, N))) return rc;
-      if ((rc = sh->alloc(&sh->rdist, N))) return rc;
-      if ((rc = sh->alloc(&sh->R, K))) return rc;
-      if ((rc = sh->alloc(&sh->C, (size_t)K * K))) return rc;
-      if ((rc = sh->alloc(&sh->inv, N))) return rc;
-      if ((rc = sh->alloc(&sh->offsets, (size_t)K + 2))) return rc;
-      if ((rc = sh->alloc(&sh->keys_tmp, N))) return rc;
-      if ((rc = sh->alloc(&sh->vals_tmp, N))) return rc;
-      if ((rc = sh->alloc(&sh->keys_sorted, N))) return rc;
-      if ((rc = sh->alloc(&sh->stats, 4))) return rc;
-      if ((rc = sh->alloc(&sh->calced, KNN_STATS))) return rc;
-      if (use_f16) {
-        if ((rc = sh->alloc(&sh->xs16, ((size_t)N + KNN16_PAD_ROWS) * DP))) return rc;
-        if ((rc = sh->alloc(&sh->kbias, (size_t)N + KNN16_PAD_ROWS))) return rc;
-        if ((rc = sh->alloc(&sh->mu, DP))) return rc;
-        if ((rc = sh->alloc(&sh->mux, N))) return rc;
-        if (hipMemcpyAsync(sh->mu, mu_host.data(), DP * sizeof(float), hipMemcpyHostToDevice, sh->stream) != hipSuccess)
-          return kmcudaMemoryCopyError;
-      }
-      char *t = nullptr;
-      if ((rc = sh->alloc(&t, sort_bytes + 16))) return rc;
-      sh->sort_temp = t;
-      shards.push_back(std::move(sh));
-    }
-    // ---- per GPU: inverse assignments, sorted copy, radii, centroid distances ----
-    INFO("initializing the inverse assignments...\n");
-    for (auto &s : shards) {
-      (void)hipSetDevice(s->dev);
-      RETERR(knn_sort_and_gather(*s, N, D, DP, K, use_f16, sort_bytes));
-    }
-    INFO("calculating the cluster radiuses...\n");
-    INFO("calculating the centroid distance matrix...\n");
-    for (auto &s : shards) {
-      (void)hipSetDevice(s->dev);
-      if (launch_knn_prep(metric, s->xs, N, D, DP, s->offsets, K, s->centroids, s->mydist, s->rdist, s->R, s->C,
-                          strict_h2, s->stream) != hipSuccess)
-        return kmcudaRuntimeError;
-    }
-    // ---- the block list: KNN_QPB_* consecutive sorted positions of one cluster per block ----
-    std::vector<uint32_t> offsets(K + 1);
-    {
-      KnnShard &f = *shards[0];
-      (void)hipSetDevice(f.dev);
-      if (hipStreamSynchronize(f.stream) != hipSuccess) return kmcudaRuntimeError;
-      if (hipMemcpy(offsets.data(), f.offsets, (K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return kmcudaMemoryCopyError;
-      // the half range: a finite row of a cluster whose centred value is no finite half would be
-      // scored NaN by the f16 filter -- the whole call takes the f32 filter (D <= 256) or the exact search instead
-      uint32_t overflow = 0;
-      if (use_f16 && hipMemcpy(&overflow, f.stats + 1, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return kmcudaMemoryCopyError;
-      if (overflow) {
-        use_f16 = false;
-        if (D > 256) dp_filter = 0;
-        INFO("k-NN: a centred row leaves the half range, %s\n",
-             dp_filter ? "the f32 matrix-core filter instead of the f16 one" : "every candidate is evaluated with the exact arithmetic");
-      }
-    }
-    std::vector<uint32_t> blocks;  // (cluster, first position) pairs
-    const uint32_t qpb = use_f16 ? knn_qpb_f16(DP) : KNN_QPB_F32;
-    for (uint32_t c = 0; c < K; c++)
-      for (uint32_t p = offsets[c]; p < offsets[c + 1]; p += qpb) {
-        blocks.push_back(c);
-        blocks.push_back(p);
-      }
-    const uint32_t total_blocks = (uint32_t)(blocks.size() / 2);
-    const uint32_t assigned = offsets[K];  // positions >= assigned belong to no cluster (NaN samples)
-    for (size_t si = 0; si < shards.size(); si++) {
-      KnnShard &s = *shards[si];
-      const size_t i = plan_first + si;
-      s.first_block = (uint32_t)((uint64_t)total_blocks * i / plan_shards);
-      const uint32_t next = (uint32_t)((uint64_t)total_blocks * (i + 1) / plan_shards);
-      s.nblocks = next - s.first_block;
-      s.p_base = s.nblocks ? blocks[2 * (size_t)s.first_block + 1] : assigned;
-      s.p_end = next < total_blocks ? blocks[2 * (size_t)next + 1] : assigned;
-      if (!s.nblocks) s.p_end = s.p_base;
-      if (i + 1 == plan_shards && !dp_filter) s.p_end = N;  // the exact kernel also fills the unassigned rows
-    }
-    if (use_f16) {  // after the radii / member distances, which read the plain norms' buffer no more
-      for (auto &s : shards) {
-        (void)hipSetDevice(s->dev);
-        if (launch_knn_split(metric, s->xs, N, D, DP, s->mu, s->xs16, s->n2s, s->mux, s->kbias, s->stats, s->stream) != hipSuccess)
-          return kmcudaRuntimeError;
-      }
-    }
-    INFO("searching for the nearest neighbors...\n");
-    for (auto &sp : shards) {
-      KnnShard &s = *sp;
-      (void)hipSetDevice(s.dev);
-      const uint32_t len = s.p_end - s.p_base;
-      int rc;
-      if ((rc = s.alloc(&s.heaps, (size_t)len * 2 * k))) return rc;
-      if ((rc = s.alloc(&s.out, (size_t)len * k))) return rc;
-      // KMCUDA_AMD_KNN_XCD=1 (an experiment of round 5, off by default): the blocks of one query cluster -- which visit
-      // the same candidate clusters in the same order, 512 bytes per candidate and block: 4.3 TB of fetches for config
-      // D's share -- dispatched to ONE XCD (workgroup indices congruent mod 8), cluster after cluster, so that an XCD's
-      // L2 holds two or three such streams instead of sixteen and a stream's followers hit the tiles its leader has
-      // just fetched.  Measured: FETCH_SIZE 4.17 TB against 4.27, knn_cuda 1.13-1.15 s against 1.11-1.13
-      // (profiles/r5d_knn_dispatch_order_ab.log): the blocks of a stream drift further apart than an L2 holds (a
-      // cluster's slab alone is 4 MB).  Slots a shorter list leaves empty carry the marker 0xFFFFFFFF (the kernel
-      // returns at once).  Only the order of independent blocks changes: the lists are the same.
-      std::vector<uint32_t> plan(blocks.begin() + 2 * (size_t)s.first_block,
-                                 blocks.begin() + 2 * (size_t)(s.first_block + s.nblocks));
-      uint32_t launch_blocks = s.nblocks;
-      {
-        const char *xe = getenv("KMCUDA_AMD_KNN_XCD");
-        if (use_f16 && s.nblocks >= 64 && xe && atoi(xe) != 0) {
-          constexpr uint32_t kXcds = 8;
-          std::vector<std::vector<uint32_t>> lists(kXcds);   // block numbers (into plan) per XCD
-          uint32_t b = 0;
-          while (b < s.nblocks) {
-            uint32_t e = b;
-            while (e < s.nblocks && plan[2 * (size_t)e] == plan[2 * (size_t)b]) e++;   // one cluster's blocks
-            uint32_t best = 0;
-            for (uint32_t x = 1; x < kXcds; x++)
-              if (lists[x].size() < lists[best].size()) best = x;
-            for (uint32_t q = b; q < e; q++) lists[best].push_back(q);
-            b = e;
-          }
-          size_t longest = 0;
-          for (auto &l : lists) longest = l.size() > longest ? l.size() : longest;
-          std::vector<uint32_t> ordered(2 * kXcds * longest, 0xFFFFFFFFu);
-          for (uint32_t x = 0; x < kXcds; x++)
-            for (size_t i = 0; i < lists[x].size(); i++) {
-              ordered[2 * (kXcds * i + x)] = plan[2 * (size_t)lists[x][i]];
-              ordered[2 * (kXcds * i + x) + 1] = plan[2 * (size_t)lists[x][i] + 1];
-            }
-          plan.swap(ordered);
-          launch_blocks = (uint32_t)(kXcds * longest);
-        }
-      }
-      if ((rc = s.alloc(&s.blocks, plan.size() ? plan.size() : 2))) return rc;
-      if (!plan.empty() &&
-          hipMemcpy(s.blocks, plan.data(), plan.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
-        return kmcudaMemoryCopyError;
-      KnnArgs a;
-      a.xs = s.xs; a.n2s = s.n2s; a.inv = s.inv; a.offsets = s.offsets; a.mydist = s.mydist; a.R = s.R; a.C = s.C;
-      a.blocks = s.blocks; a.stats = s.stats; a.N = N; a.D = D; a.DP = DP; a.K = K; a.k = k;
-      a.p_base = s.p_base; a.p_end = s.p_end;
-      a.eps = (float)(1.02 * ((double)D + 12.0) * ldexp(1.0, -24));  // as the Lloyd filter
-      a.heaps = s.heaps; a.out = s.out; a.calced = s.calced;
-      a.xs16 = s.xs16; a.mux = s.mux; a.kbias = s.kbias; a.mu2 = mu2;
-      // The tighter cluster test of the f16 search (knn_f16.hip: the query's own distance to every centroid instead of
-      // the triangle bound for it).  4 K bytes per query; without that memory, or with KMCUDA_AMD_KNN_TIGHT=0, the
-      // reference's prune test decides alone.  Same neighbour lists either way.
-      if (use_f16 && metric == 0 && D <= 1024 && len != 0) {
-        const char *tight = getenv("KMCUDA_AMD_KNN_TIGHT");
-        if (!(tight && atoi(tight) == 0)) {
-          float *lb = nullptr;
-          if (s.alloc(&lb, (size_t)K * len) == 0) {
-            if (launch_knn_centroid_bounds(s.xs, D, DP, s.p_base, s.p_end, s.centroids, K, s.R, lb, len, s.stream) !=
-                hipSuccess)
-              return kmcudaRuntimeError;
-            a.lb = lb;
-            a.lb_stride = len;
-            // queries that want the same clusters into the same waves (update.hip: launch_knn_query_order): by the
-            // other cluster that can come closest, then by their distance to their own centroid (mode 3);
-            // KMCUDA_AMD_KNN_ORDER=0: sorted-position order, 1: the closest other cluster alone (rounds 4-5), 2: the
-            // distance alone (A/B: 1.911 / 1.882 / 1.860 / 1.839e12 pairs scored for config D's share, profiles/r6aj_*)
-            const char *ord = getenv("KMCUDA_AMD_KNN_ORDER");
-            uint32_t *qperm = nullptr;
-            const int ord_mode = ord ? atoi(ord) : 3;
-            if (ord_mode != 0 && s.alloc(&qperm, len) == 0) {
-              if (launch_knn_query_order(lb, len, s.offsets, K, s.p_base, s.p_end, s.keys_tmp, s.vals_tmp, s.keys_sorted,
-                                         qperm, s.sort_temp, sort_bytes, s.stream, ord_mode, s.mydist, s.R))
-                a.qperm = qperm;
-              else
-                (void)hipGetLastError();
-            }
-          } else {
-            (void)hipGetLastError();
-            DEBUG("k-NN: no memory for the per-query centroid bounds, the reference's prune test alone\n");
-          }
-        }
-      }
-      const hipError_t e = !dp_filter ? launch_knn_exact(metric, a, strict_h2, s.stream)
-                           : use_f16 ? launch_knn_filter_f16(metric, a, launch_blocks, s.stream)
-                                     : launch_knn_filter(metric, a, s.nblocks, s.stream);
-      if (e != hipSuccess) return kmcudaRuntimeError;
-    }
-    // ---- outputs: rows back in sample order ----
-    // rows without a cluster (NaN samples) get no neighbours: 0xFFFFFFFF.  The filters' blocks cover the assigned
-    // positions only; the rows behind them are written here, by the call that runs the last share of the plan (with
-    // KMCUDA_AMD_KNN_SHARD, a call that does not leaves them untouched like every row of the other shares)
-    const bool fill_unassigned = dp_filter && assigned < N && plan_first + shards.size() == plan_shards;
-    unsigned long long dists_calced = 0;
-    std::vector<uint32_t> host_inv, host_out;
-    if (device_ptrs < 0) {
-      host_inv.resize(N);
-      KnnShard &f = *shards[0];
-      (void)hipSetDevice(f.dev);
-      if (hipMemcpy(host_inv.data(), f.inv, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return kmcudaMemoryCopyError;
-    }
-    for (auto &sp : shards) {
-      KnnShard &s = *sp;
-      (void)hipSetDevice(s.dev);
-      if (hipStreamSynchronize(s.stream) != hipSuccess) {
-        INFO("k-NN kernel failed: %s\n", hipGetErrorString(hipGetLastError()));
-        return kmcudaRuntimeError;
-      }
-      unsigned long long cs[KNN_STATS] = {0, 0, 0, 0, 0};
-      if (hipMemcpy(cs, s.calced, sizeof(cs), hipMemcpyDeviceToHost) != hipSuccess) return kmcudaMemoryCopyError;
-      const unsigned long long c = cs[0];
-      DEBUG("#%d dists_calced: %llu\n", s.dev, c);
-      // what the f16 search actually did (knn_f16.hip; measurement: KMCUDA_AMD_KNN_STATS=1 prints it at any verbosity)
-      if (cs[1] && (verbosity > 1 || getenv("KMCUDA_AMD_KNN_STATS")))
-        printf("#%d k-NN filter: %llu pairs by the reference's prune rule, %llu scored on the matrix cores "
-               "(%llu of them live query x real candidate; %llu if an operand set nobody visits with were skipped), "
-               "%llu exact chains\n", s.dev, cs[0], cs[1], cs[2], cs[4], cs[3]);
-      dists_calced += c;
-      const uint32_t len = s.p_end - s.p_base;
-      if (!len) continue;
-      if (device_ptrs < 0) {
-        host_out.resize((size_t)len * k);
-        if (hipMemcpy(host_out.data(), s.out, (size_t)len * k * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-          return kmcudaMemoryCopyError;
-        for (uint32_t i = 0; i < len; i++)
-          memcpy(neighbors + (size_t)host_inv[s.p_base + i] * k, host_out.data() + (size_t)i * k, k * sizeof(uint32_t));
-      } else {
-        // scatter on the caller's device
-        const uint32_t *src_out = s.out, *src_inv = s.inv;
-        uint32_t *tmp_out = nullptr, *tmp_inv = nullptr;
-        struct TmpFree { uint32_t **a, **b; ~TmpFree() { if (*a) (void)hipFree(*a); if (*b) (void)hipFree(*b); } }
-            tmp_guard{&tmp_out, &tmp_inv};   // also on the early returns below
-        if (s.dev != device_ptrs) {
-          (void)hipSetDevice(device_ptrs);
-          if (hipMalloc((void **)&tmp_out, (size_t)len * k * sizeof(uint32_t)) != hipSuccess ||
-              hipMalloc((void **)&tmp_inv, (size_t)N * sizeof(uint32_t)) != hipSuccess)
-            return kmcudaMemoryAllocationFailure;
-          if (hipMemcpyPeer(tmp_out, device_ptrs, s.out, s.dev, (size_t)len * k * sizeof(uint32_t)) != hipSuccess ||
-              hipMemcpyPeer(tmp_inv, device_ptrs, s.inv, s.dev, (size_t)N * sizeof(uint32_t)) != hipSuccess)
-            return kmcudaMemoryCopyError;
-          src_out = tmp_out;
-          src_inv = tmp_inv;
-        }
-        (void)hipSetDevice(device_ptrs);
-        hipError_t e = launch_knn_scatter(src_out, src_inv, s.p_base, s.p_end, k, neighbors, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) return kmcudaRuntimeError;
-      }
-    }
-    if (fill_unassigned && device_ptrs < 0) {  // (the reference reads out of bounds for these rows)
-      for (uint32_t p = assigned; p < N; p++)
-        for (uint32_t i = 0; i < k; i++) neighbors[(size_t)host_inv[p] * k + i] = UINT32_MAX;
-    } else if (fill_unassigned) {
-      KnnShard &l = *shards.back();
-      uint32_t *none = nullptr, *tmp_inv = nullptr;
-      struct TmpFree { uint32_t **a, **b; ~TmpFree() { if (*a) (void)hipFree(*a); if (*b) (void)hipFree(*b); } }
-          tmp_guard{&none, &tmp_inv};
-      (void)hipSetDevice(device_ptrs);
-      const uint32_t *src_inv = l.inv;
-      if (l.dev != device_ptrs) {
-        if (hipMalloc((void **)&tmp_inv, (size_t)N * sizeof(uint32_t)) != hipSuccess) return kmcudaMemoryAllocationFailure;
-        if (hipMemcpyPeer(tmp_inv, device_ptrs, l.inv, l.dev, (size_t)N * sizeof(uint32_t)) != hipSuccess)
-          return kmcudaMemoryCopyError;
-        src_inv = tmp_inv;
-      }
-      if (hipMalloc((void **)&none, (size_t)(N - assigned) * k * sizeof(uint32_t)) != hipSuccess)
-        return kmcudaMemoryAllocationFailure;
-      hipError_t e = hipMemset(none, 0xFF, (size_t)(N - assigned) * k * sizeof(uint32_t));
-      if (e == hipSuccess) e = launch_knn_scatter(none, src_inv, assigned, N, k, neighbors, nullptr);
-      if (e == hipSuccess) e = hipDeviceSynchronize();
-      if (e != hipSuccess) return kmcudaRuntimeError;
-    }
-    INFO("calculated %f of all the distances\n", (dists_calced + .0) / ((double)N * N));  // knn.cu:529-530
-    return 0;
-  }
-};
-
 // The Yinyang phase of the default schedule.  The reference hands over from Lloyd to its bounds at 11 %
 // reassignments whatever the data; its bounds refresh (kmeans_yy_init: >= G exact chains per row) costs 38 assignment
 // passes on this hardware and its filters more than a pass per row that passes them (profiles/r2n_*, r3y_*): measured on
@@ -2069,10 +1746,11 @@ KMCUDAResult knn_cuda(uint16_t k, KMCUDADistanceMetric metric, uint32_t samples_
   auto devs = setup_devices(device, verbosity);
   if (devs.empty()) return kmcudaNoSuchDevice;
   if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // as kmeans_cuda
-  KnnJob job;
-  const uint32_t feats = fp16x2 ? 2u * features_size : features_size;  // kmcuda.h:107-108
-  RETERR(job.run(devs, virtual_shards(), k, metric, samples_size, feats, clusters_size, device_ptrs, verbosity,
-                 fp16x2 != 0, samples, centroids, assignments, neighbors));
+  KnnCorpus c;
+  c.metric = metric; c.fp16 = fp16x2 != 0; c.N = samples_size; c.K = clusters_size;
+  c.D = fp16x2 ? 2u * features_size : features_size;  // kmcuda.h:107-108
+  c.samples = samples; c.centroids = centroids; c.assignments = assignments; c.device_ptrs = device_ptrs;
+  RETERR(knn_job_run(devs, virtual_shards(), k, c, verbosity, neighbors));   // (knn_job.cpp)
   DEBUG("return kmcudaSuccess\n");
   return kmcudaSuccess;
 }

@@ -1,14 +1,10 @@
-// knn_host.hpp -- host pieces the k-NN entry points share: knn_cuda()'s KnnJob (kmcuda_api.cpp) and the prepared
-// corpus of kmamd_knn_index_* (knn_index.cpp).
+// knn_host.hpp -- the one host pipeline of the k-NN search (knn_host.cpp): the switches, the corpus preparation, the
+// block plan, the search launch and the scatter to a caller's device.  Its two callers add their query side:
+// knn_cuda()'s self-join (knn_job.cpp) and the query batches of kmamd_knn_index_* (knn_index.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
-#include <cmath>
 #include <vector>
 
 #include "../../include/kmcuda.h"
@@ -16,19 +12,47 @@
 
 namespace kmx {
 
-// One GPU's copy of the corpus (and, in knn_cuda(), its slice of the queries): device buffers it owns, freed with it.
+// error plumbing of the k-NN host files: a result other than success returns at once
+#define KNN_TRY(call) do { int rc__ = (call); if (rc__ != 0) return rc__; } while (false)
+#define KMX_HIPRT(call) do { if ((call) != hipSuccess) return kmcudaRuntimeError; } while (false)
+#define KMX_HIPCP(call) do { if ((call) != hipSuccess) return kmcudaMemoryCopyError; } while (false)
+
+// What a search launch needs besides the prepared corpus: radix-sort scratch (the CSR of the rows, then the query order
+// of a search; it belongs to whoever allocated it) and the optional buffers of the f16 search for up to `rows` queries
+// per launch (knn_search allocates them on first use and keeps them for the next launch; they go with the scratch).
+struct KnnScratch {
+  uint32_t *keys_tmp = nullptr, *vals_tmp = nullptr, *keys_sorted = nullptr;
+  void *sort_temp = nullptr;
+  size_t sort_bytes = 0, rows = 0;
+  float *lb = nullptr;
+  uint32_t *qperm = nullptr;
+  ~KnnScratch() {
+    (void)hipFree(lb);
+    (void)hipFree(qperm);
+  }
+};
+
+// One GPU's prepared copy of the corpus, or the per-call buffers of a query batch: device buffers it owns, freed with
+// it.
 struct KnnShard {
   int dev = 0;
   hipStream_t stream = nullptr;
+  // the corpus (knn_prepare_corpus)
+  int metric = 0;
+  uint32_t N = 0, D = 0, DP = 0, K = 0;
+  float mu2 = 0.f;
   const float *samples = nullptr, *centroids = nullptr;
   const uint32_t *assignments = nullptr;
-  float *xs = nullptr, *n2s = nullptr, *mydist = nullptr, *rdist = nullptr, *R = nullptr, *C = nullptr, *heaps = nullptr;
+  float *xs = nullptr, *mydist = nullptr, *rdist = nullptr, *R = nullptr, *C = nullptr, *heaps = nullptr;
+  // plain squared norms and their maximum stats[0] (the f32 filter's bound; stats[1]: the half-range flag); centred
+  // ones (the f16 filter's) where the split leaves them: buffers of their own, or the plain ones overwritten
+  float *n2s = nullptr, *n2c = nullptr;
+  uint32_t *stats = nullptr, *stats_c = nullptr;
   float *mu = nullptr, *mux = nullptr, *kbias = nullptr;
   uint16_t *xs16 = nullptr;
-  uint32_t *inv = nullptr, *offsets = nullptr, *keys_tmp = nullptr, *vals_tmp = nullptr, *keys_sorted = nullptr,
-           *stats = nullptr, *blocks = nullptr, *out = nullptr;
+  uint32_t *inv = nullptr, *offsets = nullptr, *blocks = nullptr, *out = nullptr;
   unsigned long long *calced = nullptr;
-  void *sort_temp = nullptr;
+  KnnScratch scratch;
   uint32_t first_block = 0, nblocks = 0, p_base = 0, p_end = 0;
   std::vector<void *> owned;
   ~KnnShard() {
@@ -72,109 +96,72 @@ struct KnnShard {
   }
 };
 
-// brings `count` halves of a caller buffer onto the shard's device and widens them to fp32
-inline int stage_in_half(KnnShard &sh, const void *src, size_t count, int32_t device_ptrs, const float **dst) {
-  float *buf = nullptr;
-  int rc = sh.alloc(&buf, count);
-  if (rc) return rc;
-  const uint16_t *dev_half = reinterpret_cast<const uint16_t *>(src);
-  uint16_t *tmp = nullptr;
-  if (!(device_ptrs >= 0 && device_ptrs == sh.dev)) {
-    if ((rc = sh.alloc(&tmp, count))) return rc;
-    hipError_t e = device_ptrs < 0 ? hipMemcpyAsync(tmp, src, count * sizeof(uint16_t), hipMemcpyHostToDevice, sh.stream)
-                                   : hipMemcpyPeerAsync(tmp, sh.dev, src, device_ptrs, count * sizeof(uint16_t), sh.stream);
-    if (e != hipSuccess) return kmcudaMemoryCopyError;
-    dev_half = tmp;
-  }
-  if (launch_half_to_float(dev_half, count, buf, sh.stream) != hipSuccess) return kmcudaRuntimeError;
-  *dst = buf;
-  return 0;
-}
+// The KMCUDA_AMD_* switches of the k-NN entry points, read once per call (tests change them between calls).
+struct KnnSwitches {
+  bool exact = false;        // KMCUDA_AMD_KNN_EXACT: every candidate with the exact arithmetic
+  bool fp16_strict = false;  // KMCUDA_AMD_FP16_STRICT: the reference's half2 arithmetic (fp16x2 only)
+  bool filter_f32 = false;   // KMCUDA_AMD_FILTER=f32
+  bool tight = true;         // KMCUDA_AMD_KNN_TIGHT=0: the reference's cluster prune test alone
+  int order = 3;             // KMCUDA_AMD_KNN_ORDER: how a cluster's queries are grouped into waves (knn_search)
+  bool xcd = false;          // KMCUDA_AMD_KNN_XCD: one query cluster's blocks to one XCD (knn_xcd_plan)
+  bool stats = false;        // KMCUDA_AMD_KNN_STATS: the f16 search's counters at any verbosity
+  unsigned shard_i = 0, shard_n = 0;  // KMCUDA_AMD_KNN_SHARD="i/n" (shard_n = 0: unset)
+  size_t query_chunk = 0;    // KMCUDA_AMD_KNN_QUERY_CHUNK: queries per chunk of an index query (0: unset)
+};
+KnnSwitches knn_switches();
 
 // Which search runs: dp_filter = the padded width of the matrix-core filter (0: every candidate evaluated exactly), DP
 // = the row stride of the sorted copies, use_f16 = the f16 filter (else the f32 one), strict_h2 = the reference's half2
-// arithmetic.  The half range can still send a call from the f16 filter to another one.
+// arithmetic.  The half range can still send a call from the f16 filter to another one (knn_leaves_half_range).
 struct KnnPath {
   uint32_t dp_filter = 0, DP = 0;
   bool use_f16 = false, strict_h2 = false;
 };
-inline KnnPath knn_choose_path(uint32_t D, bool fp16, int verbosity) {
-  KnnPath p;
-  const char *force_exact = getenv("KMCUDA_AMD_KNN_EXACT");
-  // KMCUDA_AMD_FP16_STRICT (fp16x2 only): radii, centroid distances and every candidate distance in the reference's
-  // half2 arithmetic (knn.hip, half2_ops.hpp) -- the verification mode of half2_strict.hip for this entry point;
-  // no matrix-core filter (its bound is stated against the fp32 arithmetic)
-  const char *strict_env = getenv("KMCUDA_AMD_FP16_STRICT");
-  p.strict_h2 = fp16 && strict_env && atoi(strict_env) != 0;
-  if (p.strict_h2 && verbosity > 0) printf("k-NN: the reference's half2 arithmetic (KMCUDA_AMD_FP16_STRICT)\n");
-  const char *fenv = getenv("KMCUDA_AMD_FILTER");
-  const bool want_f32 = fenv && strcmp(fenv, "f32") == 0;
-  p.dp_filter = ((force_exact && atoi(force_exact)) || p.strict_h2) ? 0 : filter_dp_for(D);
-  // 256 < D <= 1024: the f16 filter's one-operand-set instantiations (knn_f16.hip: 512 with two blocks per CU;
-  // 768 / 1024 with one -- the queries' operands alone are 192 / 256 registers; the f32 filter stops at 256)
-  if (!p.dp_filter && !(force_exact && atoi(force_exact)) && !p.strict_h2 && !want_f32 && D > 256 && D <= 1024)
-    p.dp_filter = D <= 512 ? 512u : (D <= 768 ? 768u : 1024u);
-  p.DP = p.dp_filter ? p.dp_filter : D;
-  if (!p.dp_filter && verbosity > 0) printf("k-NN: every candidate is evaluated with the exact arithmetic (no matrix-core filter)\n");
-  // which matrix-core instruction filters the candidates: f16 on centred hi/lo-split rows (default,
-  // needs DP >= 16) or f32 (KMCUDA_AMD_FILTER=f32)
-  p.use_f16 = p.dp_filter >= 16 && !want_f32;
-  return p;
-}
+KnnPath knn_choose_path(uint32_t D, bool fp16, int verbosity, const KnnSwitches &sw);
 
-// The f16 filter's centre: mu = mean of the finite centroid rows (any vector works: distances are translation
-// invariant), mu_host[0, D) (the rest of it stays as it is: zeros), *mu2 = ||mu||^2 rounded up
-inline int knn_centroid_mean(const void *centroids, uint32_t K, uint32_t D, bool fp16, int32_t device_ptrs,
-                             std::vector<float> &mu_host, float *mu2) {
-  std::vector<float> cen((size_t)K * D);
-  if (fp16) {
-    std::vector<uint16_t> raw((size_t)K * D);
-    if (device_ptrs < 0) memcpy(raw.data(), centroids, raw.size() * sizeof(uint16_t));
-    else if (hipMemcpy(raw.data(), centroids, raw.size() * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess)
-      return kmcudaMemoryCopyError;
-    for (size_t i = 0; i < raw.size(); i++) {  // half -> float on the host
-      const uint32_t hbits = raw[i], sign = (hbits & 0x8000u) << 16, ex = (hbits >> 10) & 0x1Fu, man = hbits & 0x3FFu;
-      float v;
-      if (ex == 0) v = ldexpf((float)man, -24);
-      else if (ex == 31) v = man ? NAN : INFINITY;
-      else v = ldexpf((float)(man | 0x400u), (int)ex - 25);
-      cen[i] = sign ? -v : v;
-    }
-  } else if (device_ptrs < 0) {
-    memcpy(cen.data(), centroids, cen.size() * sizeof(float));
-  } else if (hipMemcpy(cen.data(), centroids, cen.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-    return kmcudaMemoryCopyError;
-  }
-  std::vector<double> acc(D, 0.0);
-  uint32_t nfin = 0;
-  for (uint32_t c = 0; c < K; c++) {
-    bool fin = true;
-    for (uint32_t f = 0; f < D && fin; f++) fin = std::isfinite(cen[(size_t)c * D + f]);
-    if (!fin) continue;
-    for (uint32_t f = 0; f < D; f++) acc[f] += cen[(size_t)c * D + f];
-    nfin++;
-  }
-  float m2 = 0.f;
-  for (uint32_t f = 0; f < D; f++) {
-    mu_host[f] = nfin ? (float)(acc[f] / nfin) : 0.f;
-    m2 += mu_host[f] * mu_host[f];
-  }
-  *mu2 = m2 * 1.0001f;
-  return 0;
-}
+// The half range: a finite row whose centred value is no finite half (`flag`, raised by the gather)
+// would be scored NaN by the f16 filter -- the search takes the f32 filter (D <= 256) or the exact kernel instead.
+// True if that happened (the caller says so in its own words).
+bool knn_leaves_half_range(bool *use_f16, uint32_t *dp_filter, uint32_t D, uint32_t flag);
 
-// The corpus in cluster-sorted order: the CSR of the assignments (inv, offsets), the DP-padded fp32 copy xs, its
-// plain squared norms and their maximum (stats[0]); with the f16 filter (mu) also the half-range flag stats[1]
-inline int knn_sort_and_gather(KnnShard &s, uint32_t N, uint32_t D, uint32_t DP, uint32_t K, bool use_f16,
-                               size_t sort_bytes) {
-  if (hipMemsetAsync(s.calced, 0, KNN_STATS * sizeof(unsigned long long), s.stream) != hipSuccess) return kmcudaRuntimeError;
-  if (launch_inverse_assignments(s.assignments, N, K, s.keys_tmp, s.vals_tmp, s.keys_sorted, s.inv, s.offsets,
-                                 s.sort_temp, sort_bytes, s.stream) != hipSuccess)
-    return kmcudaRuntimeError;
-  if (launch_knn_gather(s.samples, N, D, DP, s.inv, s.xs, s.n2s, s.stats, use_f16 ? s.mu : nullptr, s.offsets, K,
-                        s.stream) != hipSuccess)
-    return kmcudaRuntimeError;
-  return 0;
-}
+// The corpus as the caller hands it over (D counts single features, also for fp16x2)
+struct KnnCorpus {
+  int metric = 0;
+  bool fp16 = false;
+  uint32_t N = 0, D = 0, K = 0;
+  const void *samples = nullptr, *centroids = nullptr;
+  const uint32_t *assignments = nullptr;
+  int32_t device_ptrs = -1;
+};
+
+// Prepares the corpus on every shard (dev set by the caller): staging, the cluster-sorted copies, radii, the K x K
+// centroid distances and, for the f16 filter, the centred split.  keep_plain: the centred norms and their maximum get
+// buffers of their own (a later search may still take the f32 filter); otherwise they overwrite the plain ones.  Waits
+// for the first shard only where the half-range flag or offsets_host (K + 1, may be null) has to reach the host;
+// everything else stays enqueued on the shards' streams.  *path and *left_half_range: knn_leaves_half_range.
+int knn_prepare_corpus(KnnShard *const *shards, size_t nshards, const KnnCorpus &c, bool keep_plain, KnnPath *path,
+                       bool *left_half_range, uint32_t *offsets_host);
+
+// The block plan: (cluster, first position) pairs, qpb consecutive sorted positions of one cluster per block
+void knn_block_plan(const uint32_t *offsets, uint32_t K, uint32_t qpb, std::vector<uint32_t> *plan);
+inline uint32_t knn_qpb(bool use_f16, uint32_t DP) { return use_f16 ? knn_qpb_f16(DP) : KNN_QPB_F32; }
+// KMCUDA_AMD_KNN_XCD: the plan with the blocks of one query cluster on one XCD (empty slots: 0xFFFFFFFF)
+std::vector<uint32_t> knn_xcd_plan(const std::vector<uint32_t> &plan);
+
+// One search launch on s.stream.  The caller fills the query side of `a` (p_base / p_end, blocks, heaps, out and, with
+// self = false, the q* fields); this adds the corpus side from the prepared shard, the per-query centroid bounds and
+// the query order of the f16 search (buffers and sort scratch: `x`, with x.rows >= p_end - p_base) and picks the
+// kernel `path` names.
+int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path, const KnnSwitches &sw,
+               uint32_t nblocks, bool self, int verbosity);
+
+// Rows [p_base, p_end) of a search's output (`out` on src_dev in sorted-position order; null: 0xFFFFFFFF, no
+// neighbours) into the caller's `neighbors` on device `dev`, by `inv` of src_dev; waits for it.
+int knn_scatter_on(int dev, int src_dev, const uint32_t *out, const uint32_t *inv, uint32_t N, uint32_t p_base,
+                   uint32_t p_end, uint32_t k, uint32_t *neighbors);
+
+// knn_cuda() behind its argument checks (knn_job.cpp); nvirtual: KMCUDA_AMD_VIRTUAL_SHARDS (test hook)
+int knn_job_run(const std::vector<int> &devs, int nvirtual, uint32_t k, const KnnCorpus &corpus, int verbosity,
+                uint32_t *neighbors);
 
 }  // namespace kmx

@@ -1,6 +1,6 @@
 """The CPU oracle's k-NN on rows without a cluster (assignment >= K, what kmeans_cuda gives NaN samples): such a row
 gets an all-UINT32_MAX list, is never a candidate, and adds nothing to dists_calced -- the product's definition
-(kmcuda_api.cpp, KnnJob::run; knn.hip, knn_exact_kernel).  Every other row's list is the one of the same search
+(knn_job.cpp, KnnJob::gather_outputs; knn.hip, knn_exact_kernel).  Every other row's list is the one of the same search
 with those rows removed."""
 import numpy
 import pytest
