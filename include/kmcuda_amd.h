@@ -87,7 +87,8 @@ int kmamd_move_deltas(kmamd_engine *e, const float *samples, const uint32_t *ass
                       const uint32_t *assignments, double *delta, int32_t *dcount);
 int kmamd_apply_delta(kmamd_engine *e, const double *delta, const int32_t *dcount,
                       float *centroids, uint32_t *ccounts);
-/* The same two steps around ONE collective: buf is kmamd_reduce_len(e) = K*D + K + 4 doubles,
+/* The same two steps around ONE collective: buf is kmamd_reduce_len(e) = K*D + K + 4 doubles
+ * (K + 1 more while sample weights are set: kmamd_set_weights),
  *   [ delta (K*D) | dcount (K) | counters 0..3 ]
  * (counts and counters are exact in fp64), written by reduce_fill with no separate pack step, summed
  * over the row shards by the caller (one all-reduce per iteration, the exchange of SURVEY 8e), and
@@ -119,6 +120,29 @@ int kmamd_stop_report(kmamd_engine *e, uint32_t seq, uint32_t *host_out6);
 int kmamd_reduce_apply_prepare(kmamd_engine *e, const double *buf, float *centroids, uint32_t *ccounts,
                                float stop_threshold, uint32_t seq);
 int kmamd_stop_clear(kmamd_engine *e);
+
+/* Per-row sample weights: a row of weight w counts as w copies of the row in the centroid update and the stop rule
+ * (the assignment passes do not depend on them).  weights: n_rows float32 on the engine's GPU, every one finite and
+ * > 0 (anything else: InvalidArguments, the engine stays unweighted), kept alive and unmodified by the caller; NULL
+ * switches back.  The call checks the weights (one stream synchronisation) and ZEROES the engine's running cluster
+ * weights: call it before the first update of a run, with ccounts zeroed as for any run.
+ * While weights are set:
+ *   - kmamd_move_deltas / kmamd_reduce_fill form delta = sum(w x of the rows that moved in) - sum(w x moved out) in
+ *     fp64; dcount and ccounts stay the integer member counts;
+ *   - kmamd_reduce_len grows by K + 1 doubles,
+ *       [ delta (K*D) | dcount (K) | counters 0..3 | dweight (K) | changed_weight ]
+ *     dweight[c] = weight moved into c - weight moved out, changed_weight = the weight of the rows that joined a
+ *     cluster in this pass; both are fp64 sums in an order fixed by the move lists (no floating-point atomics), so
+ *     a call repeated gives the same bits.  Still ONE all-reduce per iteration.  With the split calls
+ *     (kmamd_move_deltas, kmamd_apply_delta) the K + 1 words stay inside the engine between the two;
+ *   - kmamd_apply_delta / kmamd_reduce_apply* compute (c * W_old + delta) / W_new (angular: normalised) with the
+ *     cluster weights W the ENGINE keeps in fp64 (W_new = W_old + dweight[c]; a cluster whose COUNT is 0 is empty,
+ *     gets NaN centroids and weight exactly 0 -- the weight itself is never asked);
+ *   - stop_threshold of kmamd_reduce_apply_stop / _prepare is tolerance * (total weight over all shards) as a float
+ *     and is compared with (float)changed_weight; the reported counters stay row counts.  kmamd_reduce_apply_prepare
+ *     updates in a launch of its own (the next kmamd_lloyd_assign prepares its centroids itself).
+ * kmamd_adjust_exact has no weighted form and ignores the weights. */
+int kmamd_set_weights(kmamd_engine *e, const float *weights);
 /* The caller has written `centroids` itself (new seeds, an imported set, a rounding pass) since the engine last
  * saw them: whatever kmamd_reduce_apply_prepare prepared for that buffer is void.  (The engine recognises the
  * buffer by its ADDRESS only; without this call the next kmamd_lloyd_assign would filter against the panels of
@@ -222,6 +246,24 @@ int kmamd_profile_enable(kmamd_engine *e, int on);
  * one-device test hook).  Lets a driver time the drop-in entry point itself (bench.py --api). */
 int kmamd_last_run_stats(uint32_t *iterations, double *loop_seconds, double *setup_seconds, uint32_t *shards,
                          uint32_t *rccl_ranks);
+
+/* kmeans_cuda() (kmcuda.h: same arguments, same meaning, same result codes; init / metric are the KMCUDAInitMethod /
+ * KMCUDADistanceMetric values) with per-row sample weights: sample_weights = samples_size float32, a host pointer
+ * when device_ptrs < 0, else a pointer on device `device_ptrs` like `samples` (always float32, also when the rows are
+ * fp16x2).  NULL: exactly kmeans_cuda() -- which is this call with NULL.  A row of weight w counts as w copies:
+ * centroids are sum(w x) / sum(w) of their members (angular: the normalised weighted sum), the run stops when the
+ * reassigned weight is at most tolerance * the total weight (Yinyang's 11 % hand-over point likewise),
+ * *average_distance is sum(w d) / sum(w), and k-means++ draws every seed after the first (uniform, as the reference)
+ * with probability proportional to w * its distance term.  init = random / imported centroids ignore the weights.
+ * InvalidArguments, before any clustering work and with the outputs untouched: a weight that is not finite and > 0;
+ * weights with init = afkmc2, with KMCUDA_AMD_EXACT_UPDATE=1 or with KMCUDA_AMD_FP16_STRICT=1 on fp16x2 rows (those
+ * restate the reference's own arithmetic, which has no weights).  KMCUDA_AMD_YY=reference works with weights: it
+ * shares the default update. */
+int kmamd_kmeans_weighted(int init, const void *init_params, float tolerance, float yinyang_t, int metric,
+                          uint32_t samples_size, uint16_t features_size, uint32_t clusters_size, uint32_t seed,
+                          uint32_t device, int32_t device_ptrs, int32_t fp16x2, int32_t verbosity, const float *samples,
+                          float *centroids, uint32_t *assignments, float *average_distance,
+                          const float *sample_weights);
 
 /* With KMCUDA_AMD_TIME_COLLECTIVE=1 in the environment of that call (several row shards): the summed duration of its
  * per-iteration all-reduces -- ncclAllReduce over the device mask, or the one-device stand-in under

@@ -18,7 +18,7 @@ _lib = None
 
 # every symbol include/kmcuda.h and include/kmcuda_amd.h declare
 EXPORTS = [
-    "kmeans_cuda", "knn_cuda",
+    "kmeans_cuda", "knn_cuda", "kmamd_kmeans_weighted", "kmamd_set_weights",
     "kmamd_engine_create", "kmamd_engine_destroy", "kmamd_engine_stream", "kmamd_engine_sync",
     "kmamd_lloyd_assign", "kmamd_lloyd_assign_exact", "kmamd_set_half_rows", "kmamd_set_row_cache", "kmamd_profile_read_coarse", "kmamd_set_filter", "kmamd_counters_read", "kmamd_counters_reset", "kmamd_yy_hint_stats",
     "kmamd_move_deltas", "kmamd_apply_delta", "kmamd_transpose", "kmamd_afkmc2_draws", "kmamd_reduce_len", "kmamd_reduce_fill",
@@ -40,6 +40,12 @@ def lib():
     L.kmeans_cuda.restype = i32
     L.kmeans_cuda.argtypes = [i32, vp, f32, f32, i32, u32, ctypes.c_uint16, u32, u32, u32, i32, i32, i32,
                               vp, vp, vp, vp]
+    # kmeans_cuda's arguments + the per-row sample weights (float32; host or device pointer like `samples`)
+    L.kmamd_kmeans_weighted.restype = i32
+    L.kmamd_kmeans_weighted.argtypes = [i32, vp, f32, f32, i32, u32, ctypes.c_uint16, u32, u32, u32, i32, i32, i32,
+                                        vp, vp, vp, vp, vp]
+    L.kmamd_set_weights.restype = i32
+    L.kmamd_set_weights.argtypes = [vp, vp]
     L.knn_cuda.restype = i32
     L.knn_cuda.argtypes = [ctypes.c_uint16, i32, u32, ctypes.c_uint16, u32, u32, i32, i32, i32, vp, vp, vp, vp]
     L.kmamd_engine_create.restype = i32

@@ -82,8 +82,12 @@ def _ptr_tuple(samples, sizes):
 
 
 def kmeans_cuda(samples, clusters, tolerance=.01, init="k-means++", yinyang_t=.1, metric="L2",
-                average_distance=False, seed=None, device=0, verbosity=0):
-    """libKMCUDA.kmeans_cuda (python.cc:159-410, README "Python API")."""
+                average_distance=False, seed=None, device=0, verbosity=0, sample_weight=None):
+    """libKMCUDA.kmeans_cuda (python.cc:159-410, README "Python API").
+
+    sample_weight (not in the reference): one float32 weight per row, finite and > 0 -- a 1-D numpy array, or a raw
+    device pointer (integer) in device-pointer mode.  A row of weight w counts as w copies in the centroid update, the
+    stop rule, k-means++ and the average distance (kmamd_kmeans_weighted, include/kmcuda_amd.h)."""
     lib = _lib.lib()
     if seed is None:
         seed = int(time.time())
@@ -126,6 +130,24 @@ def kmeans_cuda(samples, clusters, tolerance=.01, init="k-means++", yinyang_t=.1
         samples_ptr = arr.ctypes.data
     if d > 0xFFFF:
         raise ValueError("\"samples\": more than %d features is not supported" % d)
+    weights_ptr = None
+    if sample_weight is not None:
+        if device_ptrs >= 0:
+            if isinstance(sample_weight, bool) or not isinstance(sample_weight, int):
+                raise ValueError("\"sample_weight\" is not a pointer (integer)")
+            if sample_weight == 0:
+                raise ValueError("\"sample_weight\" is null")
+            weights_ptr = sample_weight
+        else:
+            if not isinstance(sample_weight, numpy.ndarray) or sample_weight.dtype != numpy.float32:
+                raise ValueError("\"sample_weight\" must be a 1D float32 numpy array")
+            if sample_weight.ndim != 1:
+                raise ValueError("\"sample_weight\" must be a 1D float32 numpy array")
+            if sample_weight.shape[0] != n:
+                raise ValueError("\"sample_weight\" must be of the same length as \"samples\"")
+            warr = numpy.ascontiguousarray(sample_weight)
+            keep.append(warr)
+            weights_ptr = warr.ctypes.data
     centroids = assignments = None
     if device_ptrs < 0:
         centroids = numpy.empty((clusters, d * 2 if fp16x2 else d), numpy.float16 if fp16x2 else numpy.float32)
@@ -154,9 +176,15 @@ def kmeans_cuda(samples, clusters, tolerance=.01, init="k-means++", yinyang_t=.1
             # python.cc:330-345: cudaMemcpy of the imported centroids into the (possibly caller-owned) buffer
             _raise_for(lib.kmamd_copy_to_device(device_ptrs, cen_ptr, imp.ctypes.data, imp.nbytes), "kmeans_cuda")
     avg = ctypes.c_float(0)
-    rc = lib.kmeans_cuda(init_id, ctypes.byref(afkmc2_m), tolerance, yinyang_t, metric_id, n, d, clusters,
-                         seed & 0xFFFFFFFF, device, device_ptrs, int(fp16x2), verbosity, samples_ptr, cen_ptr,
-                         asg_ptr, ctypes.cast(ctypes.byref(avg), ctypes.c_void_p) if average_distance else None)
+    avg_ptr = ctypes.cast(ctypes.byref(avg), ctypes.c_void_p) if average_distance else None
+    if weights_ptr is None:
+        rc = lib.kmeans_cuda(init_id, ctypes.byref(afkmc2_m), tolerance, yinyang_t, metric_id, n, d, clusters,
+                             seed & 0xFFFFFFFF, device, device_ptrs, int(fp16x2), verbosity, samples_ptr, cen_ptr,
+                             asg_ptr, avg_ptr)
+    else:
+        rc = lib.kmamd_kmeans_weighted(init_id, ctypes.byref(afkmc2_m), tolerance, yinyang_t, metric_id, n, d, clusters,
+                                       seed & 0xFFFFFFFF, device, device_ptrs, int(fp16x2), verbosity, samples_ptr,
+                                       cen_ptr, asg_ptr, avg_ptr, weights_ptr)
     _raise_for(rc, "kmeans_cuda")
     if device_ptrs < 0:
         return (centroids, assignments, avg.value) if average_distance else (centroids, assignments)

@@ -840,9 +840,12 @@ int Engine::move_deltas(const float *samples, const uint32_t *prev, const uint32
   span_begin(2);
   // (the kernel also reports the length of this pass's undecided list to the pinned words, for a LATER pass's
   // stage-2 grid: nobody waits for it)
+  // (weighted: the cluster-weight deltas and the reassigned weight go behind the fused buffer's counters, or stay in
+  //  the engine for apply_delta when the caller uses the split calls)
+  const MoveWeights mw{weights_, tail ? tail + K_ + 4 : wtail_, win_};
   KMX_HIP(launch_move_deltas(samples, N_, D_, K_, prev, cur, keys_tmp_, vals_tmp_, keys_sorted_, rows_sorted_,
                              offsets2_, sort_temp_, sort_temp_bytes_, bucket_rows_, bucket_cap_, delta, dcount, tail,
-                             counters_, move_blocks_, bucket_work_, &ms_, stream_),
+                             counters_, move_blocks_, bucket_work_, &ms_, stream_, weights_ ? &mw : nullptr),
           kRuntimeError);
   span_end();
   return kSuccess;
@@ -859,7 +862,9 @@ int Engine::apply_delta(const double *delta, const int32_t *dcount, const double
     if (rc) return rc;
   }
   span_begin(2);
-  KMX_HIP(launch_apply_delta(metric_, delta, dcount, dcount_d, K_, D_, centroids, ccounts, ctl, stream_), kRuntimeError);
+  const double *wtail = weights_ ? (dcount_d ? dcount_d + K_ + 4 : wtail_) : nullptr;
+  KMX_HIP(launch_apply_delta(metric_, delta, dcount, dcount_d, K_, D_, centroids, ccounts, ctl, stream_, wtail, cweights_),
+          kRuntimeError);
   span_end();
   // (on the engine's own stream: an event on the caller's legacy default stream would order every blocking
   // stream of the device behind it)
@@ -902,7 +907,8 @@ bool Engine::steady_state(bool exact_only) const {
 // The caller promises not to touch `centroids` before that lloyd_assign (which recognises the buffer by address).
 int Engine::apply_prepare(const double *delta, const double *dcount_d, float *centroids, uint32_t *ccounts,
                           float stop_threshold, bool report, uint32_t seq) {
-  if (!(metric_ == 0 && steady_state(false) && dcount_d)) {
+  // (weighted: the update is its own launch; the next pass prepares itself as it does for the angular metric)
+  if (!(metric_ == 0 && steady_state(false) && dcount_d) || weights_) {
     prepared_for_ = nullptr;
     return apply_delta(delta, nullptr, dcount_d, centroids, ccounts, stop_threshold, report, seq);
   }
@@ -952,6 +958,28 @@ int Engine::duo_rows(uint32_t *rows) {
   KMX_HIP(hipMemcpyAsync(&v, counters_ + kDuoCount, sizeof(v), hipMemcpyDeviceToHost, stream_), kMemoryCopyError);
   KMX_HIP(hipStreamSynchronize(stream_), kRuntimeError);
   if (rows) *rows = v;
+  return kSuccess;
+}
+
+int Engine::set_weights(const float *weights) {
+  KMX_HIP(hipSetDevice(device_), kNoSuchDevice);
+  weights_ = nullptr;
+  weight_total_ = 0.0;
+  if (!weights) return kSuccess;
+  if (!cweights_) {
+    int rc;
+    if ((rc = alloc(&cweights_, K_)) || (rc = alloc(&wtail_, (size_t)K_ + 1)) || (rc = alloc(&win_, K_)) ||
+        (rc = alloc(&wcheck_, weights_check_doubles())))
+      return rc;
+  }
+  double res[2] = {0.0, 0.0};
+  KMX_HIP(launch_weights_check(weights, N_, wcheck_, stream_), kRuntimeError);
+  KMX_HIP(hipMemcpyAsync(res, wcheck_, sizeof(res), hipMemcpyDeviceToHost, stream_), kMemoryCopyError);
+  KMX_HIP(hipMemsetAsync(cweights_, 0, K_ * sizeof(double), stream_), kRuntimeError);
+  KMX_HIP(hipStreamSynchronize(stream_), kRuntimeError);
+  if (res[1] != 0.0) return kInvalidArguments;   // a NaN, an inf, a zero or a negative weight
+  weights_ = weights;
+  weight_total_ = res[0];
   return kSuccess;
 }
 
@@ -1066,7 +1094,8 @@ int kmamd_apply_delta(kmamd_engine *e, const double *delta, const int32_t *dcoun
                       uint32_t *ccounts) {
   return e->e.apply_delta(delta, dcount, nullptr, centroids, ccounts);
 }
-size_t kmamd_reduce_len(kmamd_engine *e) { return (size_t)e->e.K_ * e->e.D_ + e->e.K_ + 4; }
+size_t kmamd_reduce_len(kmamd_engine *e) { return e->e.reduce_len(); }
+int kmamd_set_weights(kmamd_engine *e, const float *weights) { return e->e.set_weights(weights); }
 int kmamd_reduce_fill(kmamd_engine *e, const float *samples, const uint32_t *assignments_prev,
                       const uint32_t *assignments, double *buf) {
   return e->e.move_deltas(samples, assignments_prev, assignments, buf, nullptr, buf + (size_t)e->e.K_ * e->e.D_);

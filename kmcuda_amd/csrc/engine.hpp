@@ -125,6 +125,18 @@ class Engine {
   // steady state; otherwise plain apply_delta): the caller must leave `centroids` alone until that call
   int apply_prepare(const double *delta, const double *dcount_d, float *centroids, uint32_t *ccounts,
                     float stop_threshold = -1.f, bool report = false, uint32_t seq = 0);
+  // Per-row sample weights (kmamd_set_weights; device, N_ floats, kept alive by the caller; null: off).  Checks them
+  // (finite, > 0: anything else kInvalidArguments and the engine stays unweighted), leaves their fp64 total in
+  // weight_total_ and zeroes the running cluster weights.  While set, move_deltas / apply_delta are the weighted
+  // instantiations (update.hip) and the fused buffer ends in [K cluster-weight deltas | reassigned weight].
+  int set_weights(const float *weights);
+  const float *weights_ = nullptr;
+  double weight_total_ = 0.0;
+  double *cweights_ = nullptr;   // K running cluster weights (fp64), beside the caller's integer ccounts
+  double *wtail_ = nullptr;      // K + 1: [dweight | reassigned weight] of a move_deltas() without the fused buffer
+  double *win_ = nullptr;        // K: scratch, the weight that moved into every cluster
+  double *wcheck_ = nullptr;     // weights_check_doubles() of scratch
+  size_t reduce_len() const { return (size_t)K_ * D_ + K_ + 4 + (weights_ ? (size_t)K_ + 1 : 0); }
   bool steady_state(bool exact_only) const;
   int stop_ctl(float stop_threshold, bool report, uint32_t seq, StopCtl *ctl);
   const float *prepared_for_ = nullptr;   // the centroid buffer apply_prepare() has prepared the next pass for

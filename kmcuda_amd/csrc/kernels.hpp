@@ -183,20 +183,33 @@ struct MoveState {
   int force = 0;                       // kmamd_set_update_mode
   uint32_t n_radix = 0, n_direct = 0;  // calls by path (KMCUDA_AMD_UPDATE_TRACE: kmeans_cuda prints them at its end)
 };
+// per-row sample weights (kmamd_set_weights): the weighted instantiations of the sums.  dweight: K + 1 doubles,
+// [c] = weight moved into centroid c - weight moved out, [K] = the pass's reassigned weight; win: K doubles of scratch
+struct MoveWeights {
+  const float *weights;
+  double *dweight;
+  double *win;
+};
 hipError_t launch_move_deltas(const float *samples, uint32_t N, uint32_t D, uint32_t K, const uint32_t *prev,
                               const uint32_t *cur, uint32_t *keys_tmp, uint32_t *vals_tmp, uint32_t *keys_sorted,
                               uint32_t *rows_sorted, uint32_t *offsets2, void *temp, size_t temp_bytes,
                               uint32_t *bucket_rows, uint32_t cap, double *delta, int32_t *dcount /* may be null */,
                               double *tail /* fused buffer's [dcount | counters], may be null */,
                               const uint32_t *counters, uint32_t *blockoff, uint32_t *bucket_work, MoveState *ms,
-                              hipStream_t st);
+                              hipStream_t st, const MoveWeights *mw = nullptr);
 hipError_t launch_adjust_exact(int metric, const float *samples, uint32_t N, uint32_t D, uint32_t K,
                                const uint32_t *prev, const uint32_t *cur, uint32_t *keys_tmp, uint32_t *vals_tmp,
                                uint32_t *keys_sorted, uint32_t *rows_sorted, uint32_t *offsets2, void *temp,
                                size_t temp_bytes, float *work, float *centroids, uint32_t *ccounts, hipStream_t st);
 hipError_t launch_apply_delta(int metric, const double *delta, const int32_t *dcount /* or */,
                               const double *dcount_d /* the fused buffer's tail */, uint32_t K, uint32_t D,
-                              float *centroids, uint32_t *ccounts, const StopCtl &stop, hipStream_t st);
+                              float *centroids, uint32_t *ccounts, const StopCtl &stop, hipStream_t st,
+                              const double *wtail = nullptr /* weighted: [dweight K | reassigned weight], with ... */,
+                              double *cweights = nullptr /* ... the K running cluster weights */);
+// sample weights: work[0] = their fp64 total (fixed order), work[1] = how many are not finite and > 0;
+// work: weights_check_doubles() doubles
+size_t weights_check_doubles();
+hipError_t launch_weights_check(const float *weights, uint32_t N, double *work, hipStream_t st);
 // out[b][i] = sum over b of bufs[b][i] in ascending b, written to every buffer (the one-device stand-in for the
 // all-reduce: KMCUDA_AMD_VIRTUAL_SHARDS)
 hipError_t launch_sum_buffers(double *const *bufs_dev, uint32_t nbuf, size_t len, hipStream_t st);
@@ -230,7 +243,12 @@ size_t kmpp_outlier_bytes();
 size_t kmpp_totals_bytes();
 hipError_t launch_kmpp_step2(int metric, const float *samples, uint32_t N, uint32_t D, const float *centroid,
                              uint32_t cc, float *dists, void *block_stats, double *bpre, void *totals,
-                             const uint32_t *fail, const KmppOutlierBuf &out, hipStream_t st);
+                             const uint32_t *fail, const KmppOutlierBuf &out, hipStream_t st,
+                             const float *weights = nullptr, float *terms = nullptr);
+// sample weights: terms[s] = fl(weights[s] * dists[s]), what the chooser sums instead of dists[] (the steps above take
+// `weights` / `terms` and do it in front of their statistics; the host chooser calls it itself).  fail: may be null
+hipError_t launch_kmpp_weigh(const float *dists, const float *weights, uint32_t N, float *terms, const uint32_t *fail,
+                             hipStream_t st);
 // the reference's chooser (kmcuda.cc:300-326) for step `step` with random number `choice`, on the device, over the
 // concatenation of `nshards` row shards (1: the whole job on one GPU): every shard has run the step on its rows
 // (launch_kmpp_step2 / _filtered with its own length and buffers); the kernel runs on shards[0]'s device, reads the
@@ -258,7 +276,8 @@ hipError_t launch_kmpp_step_filtered(int metric, const float *samples, uint32_t 
                                      const void *xs8, const float *meta, const float *mu, uint32_t *stats,
                                      uint32_t *list, const float *centroid, uint32_t cc, float *dists,
                                      void *block_stats, double *bpre, void *totals, const uint32_t *fail,
-                                     const KmppOutlierBuf &out, hipStream_t st);
+                                     const KmppOutlierBuf &out, hipStream_t st, const float *weights = nullptr,
+                                     float *terms = nullptr);
 size_t kmpp_block_stat_bytes(uint32_t N);
 size_t kmpp_blocks(uint32_t N);
 size_t kmpp_prefix_doubles(uint32_t N);   // doubles of `bpre`

@@ -221,6 +221,8 @@ struct Shard {
   uint32_t *assignments = nullptr, *prev = nullptr, *ccounts = nullptr;
   double *reduce = nullptr;        // the iteration's ONE exchange: [delta K*D | dcount K | counters 4] (kmcuda_amd.h)
   float *dists = nullptr;          // length floats (k-means++ / average distance)
+  const float *weights = nullptr;  // length floats: the rows' sample weights (kmamd_kmeans_weighted), or null
+  float *wterms = nullptr;         // length floats: w * dists, what the weighted k-means++ chooser sums
   // Yinyang state (allocated when the Yinyang phase starts; reference: kmcuda.cc:448-470)
   float *bounds = nullptr;         // (G+1) x length, group-major (kmeans.cu:431-485 layout)
   float *drifts = nullptr;         // K*D old centroids + K per-centroid drifts
@@ -326,6 +328,13 @@ class Job {
   // (half2_strict.hip) -- the verification mode the oracle's half2 restatement is compared with
   bool strict_h2 = false;
   RunStats stats;   // this job's own counts (a nested group-clustering job has its own)
+  // Sample weights (kmamd_kmeans_weighted): sharded with the rows; the engines run the weighted update, the reduce
+  // buffers end in [K cluster-weight deltas | reassigned weight] and the stop tests compare WEIGHT: the reassigned
+  // weight against tolerance * weight_total, in the float arithmetic of the counts' rule (kmeans.cu:707)
+  bool weighted = false;
+  double weight_total = 0.0;   // the shards' fp64 totals, added in shard order
+  size_t reduce_len() const { return (size_t)K * D + K + 4 + (weighted ? (size_t)K + 1 : 0); }
+  float stop_threshold(float tolerance) const { return weighted ? tolerance * (float)weight_total : tolerance * N; }
   std::vector<std::unique_ptr<Shard>> shards;
   ShardWorkers workers;   // (after `shards`: joined before the shards go)
   Rccl rccl;
@@ -397,8 +406,10 @@ class Job {
   // on_stream: the (single) shard's engine works on this existing stream instead of creating one -- the nested job
   // that clusters the centroids into groups rides on its parent's: a stream's first launches cost milliseconds
   int setup(const std::vector<int> &devs, int nvirtual, uint32_t N_, uint32_t D_, uint32_t K_, int metric_,
-            int verbosity_, const float *samples, int32_t device_ptrs, hipStream_t on_stream = nullptr) {
+            int verbosity_, const float *samples, int32_t device_ptrs, hipStream_t on_stream = nullptr,
+            const float *sample_weights = nullptr) {
     N = N_; D = D_; K = K_; metric = metric_; verbosity = verbosity_;
+    weighted = sample_weights != nullptr;
     std::vector<int> shard_devs = devs;
     if (nvirtual > 1 && devs.size() == 1) shard_devs.assign(nvirtual, devs[0]);  // test hook
     auto plan = row_plan(N, shard_devs.size());
@@ -453,8 +464,23 @@ class Job {
       if ((rc = sh->alloc(&sh->assignments, sh->length))) return rc;
       if ((rc = sh->alloc(&sh->prev, sh->length))) return rc;
       if ((rc = sh->alloc(&sh->ccounts, K))) return rc;
-      if ((rc = sh->alloc(&sh->reduce, (size_t)K * D + K + 4))) return rc;
+      if ((rc = sh->alloc(&sh->reduce, reduce_len()))) return rc;
       if ((rc = sh->alloc(&sh->dists, sh->length))) return rc;
+      if (weighted) {
+        const float *wsrc = sample_weights + sh->offset;
+        if (device_ptrs >= 0 && device_ptrs == sh->dev) {
+          sh->weights = wsrc;   // already resident, used in place and never modified
+        } else {
+          float *wbuf = nullptr;
+          if ((rc = sh->alloc(&wbuf, sh->length))) return rc;
+          const hipError_t e =
+              device_ptrs < 0
+                  ? hipMemcpyAsync(wbuf, wsrc, (size_t)sh->length * sizeof(float), hipMemcpyHostToDevice, sh->eng->stream_)
+                  : hipMemcpyPeerAsync(wbuf, sh->dev, wsrc, device_ptrs, (size_t)sh->length * sizeof(float), sh->eng->stream_);
+          if (e != hipSuccess) return kmcudaMemoryCopyError;
+          sh->weights = wbuf;
+        }
+      }
       shards.push_back(std::move(sh));
     }
     bool distinct = shards.size() > 1;
@@ -490,7 +516,14 @@ class Job {
     }
     if (const char *v = getenv("KMCUDA_AMD_SPECULATE")) speculate = atoi(v) != 0;
     if (const char *v = getenv("KMCUDA_AMD_TIME_COLLECTIVE")) time_collective = atoi(v) != 0 && (shards.size() > 1 || !comms.empty());
-    return sync_all();  // uploads complete: later cross-stream reads of the samples are safe
+    RETERR(sync_all());  // uploads complete: later cross-stream reads of the samples are safe
+    for (auto &s : shards) {   // (every weight finite and > 0, or InvalidArguments before any clustering work)
+      if (!weighted) break;
+      (void)hipSetDevice(s->dev);
+      RETERR(s->eng->set_weights(s->weights));
+      weight_total += s->eng->weight_total_;
+    }
+    return 0;
   }
 
   int sync_all() {
@@ -655,6 +688,11 @@ class Job {
         // -- while the distances' exponent range is narrow enough, so the step kernel's exact block
         // sums give the same choice from 32 bytes per step; a step whose range is too wide (or that
         // holds a NaN / inf distance) takes the host way.
+        if (weighted)
+          for (auto &s : shards) {
+            int rc;
+            if (!s->wterms && (rc = s->alloc(&s->wterms, s->length))) return rc;
+          }
         float *host_dists = nullptr;
         struct HostFree { float **p; ~HostFree() { if (*p) (void)hipHostFree(*p); } } host_dists_guard{&host_dists};
         // Several row shards (round 5): every shard runs the step on its rows and leaves its own exact block sums; ONE
@@ -795,7 +833,10 @@ class Job {
             return kmcudaMemoryAllocationFailure;
           for (auto &s : shards) {
             (void)hipSetDevice(s->dev);
-            if (hipMemcpyAsync(host_dists + s->offset, s->dists, (size_t)s->length * sizeof(float),
+            // (weighted: the terms w * d where the reference sums d)
+            if (weighted && launch_kmpp_weigh(s->dists, s->weights, s->length, s->wterms, nullptr, s->eng->stream_) != hipSuccess)
+              return kmcudaRuntimeError;
+            if (hipMemcpyAsync(host_dists + s->offset, weighted ? s->wterms : s->dists, (size_t)s->length * sizeof(float),
                                hipMemcpyDeviceToHost, s->eng->stream_) != hipSuccess)
               return kmcudaMemoryCopyError;
           }
@@ -837,7 +878,7 @@ class Job {
           std::vector<KmppShardPtrs> views(shards.size());
           for (size_t q = 0; q < shards.size(); q++) {
             Shard &s = *shards[q];
-            views[q].dists = s.dists; views[q].bpre = kpp[q].bpre; views[q].totals = kpp[q].totals;
+            views[q].dists = weighted ? s.wterms : s.dists; views[q].bpre = kpp[q].bpre; views[q].totals = kpp[q].totals;
             views[q].samples = s.samples; views[q].centroids = s.centroids; views[q].fail = kpp[q].fail;
             views[q].offset = s.offset; views[q].length = s.length;
             views[q].out = kpp[q].out;
@@ -868,9 +909,10 @@ class Job {
                 const hipError_t se =
                     (kpp_filter && t >= 2)
                         ? launch_kmpp_step_filtered(metric, s.samples, s.length, D, kpp_dp, k.xs8, k.n2c, k.mu, k.stats, k.list,
-                                                    newest, t, s.dists, k.block_stats, k.bpre, k.totals, k.fail, k.out, st)
+                                                    newest, t, s.dists, k.block_stats, k.bpre, k.totals, k.fail, k.out, st,
+                                                    s.weights, s.wterms)
                         : launch_kmpp_step2(metric, s.samples, s.length, D, newest, t, s.dists, k.block_stats, k.bpre, k.totals,
-                                            k.fail, k.out, st);
+                                            k.fail, k.out, st, s.weights, s.wterms);
                 if (se != hipSuccess) return kmcudaRuntimeError;
                 if (many && q != 0 && hipEventRecord(k.ev_step, st) != hipSuccess) return kmcudaRuntimeError;
               }
@@ -1053,7 +1095,7 @@ class Job {
   // ---- the per-iteration collective: ONE all-reduce of [delta (fp64 K*D) | dcount K | counters 4] ----
   int allreduce_fused() {
     if (shards.size() == 1 && comms.empty()) return 0;
-    const size_t len = (size_t)K * D + K + 4;
+    const size_t len = reduce_len();   // (weighted: + the K cluster-weight deltas and the reassigned weight)
     if (!comms.empty()) {
       RETERR(collective_mark(true));
       if (rccl.GroupStart() != 0) return kmcudaRuntimeError;
@@ -1105,16 +1147,18 @@ class Job {
   int check_changed_reduced(int iter, float tolerance, bool print, uint32_t *passed_total = nullptr) {
     Shard &f = *shards[0];
     (void)hipSetDevice(f.dev);
-    double tail[4];
+    double tail[4], changed_w = 0.0;
     if (hipMemcpyAsync(tail, f.reduce + (size_t)K * D + K, sizeof(tail), hipMemcpyDeviceToHost, f.eng->stream_) != hipSuccess ||
+        (weighted && hipMemcpyAsync(&changed_w, f.reduce + reduce_len() - 1, sizeof(double), hipMemcpyDeviceToHost,
+                                    f.eng->stream_) != hipSuccess) ||
         hipStreamSynchronize(f.eng->stream_) != hipSuccess)
       return -kmcudaMemoryCopyError;
     return judge_changed(iter, tolerance, print, (uint32_t)tail[0], (uint32_t)tail[2], (uint32_t)tail[3], (uint32_t)tail[1],
-                         passed_total);
+                         passed_total, changed_w);
   }
 
   int judge_changed(int iter, float tolerance, bool print, uint32_t overall_changed, uint32_t overall_passed,
-                    uint32_t pair_rows, uint32_t scan_rows, uint32_t *passed_total) {
+                    uint32_t pair_rows, uint32_t scan_rows, uint32_t *passed_total, double changed_weight = 0.0) {
     if (print && passed_total == nullptr)
       DEBUG("filter: %u rows settled by two exact chains, %u by a full exact scan\n", pair_rows, scan_rows);
     if (print && passed_total != nullptr)
@@ -1123,7 +1167,10 @@ class Job {
     if (print) INFO("iteration %d: %u reassignments\n", iter, overall_changed);
     stamp(iter);
     for (auto &s : shards) s->eng->carry_policy_.note_changed(overall_changed);   // (how fast the run converges: engine.hpp)
-    if (overall_changed <= tolerance * N) return 1;  // counters are NOT zeroed on stop (kmeans.cu:707-709)
+    // (weighted: the reassigned weight against the total weight, in the same float arithmetic; the line above keeps
+    //  reporting rows)
+    if (weighted ? (float)changed_weight <= stop_threshold(tolerance) : overall_changed <= tolerance * N)
+      return 1;  // counters are NOT zeroed on stop (kmeans.cu:707-709)
     for (auto &s : shards)
       if (s->eng->counters_reset(0) != 0) return -kmcudaRuntimeError;
     return 0;
@@ -1262,7 +1309,7 @@ class Job {
         RETERR(adjust());
       }
     }
-    const float threshold = tolerance * N;   // the float product of kmeans.cu:707
+    const float threshold = stop_threshold(tolerance);   // the float product of kmeans.cu:707 (weighted: of the total weight)
     bool leave_next = false;
     int unjudged = 0;   // a speculative iteration whose outcome the host has not looked at yet
     if (after) {
@@ -1496,12 +1543,15 @@ class Job {
                      : launch_member_distances(metric, s->samples, s->length, D, s->centroids, s->assignments, K, s->dists,
                                                s->eng->stream_)) != hipSuccess)
         return kmcudaRuntimeError;
+      // (weighted: sum(w d) / sum(w) -- the terms w * d, rounded to fp32, through the same sums)
+      if (weighted && launch_kmpp_weigh(s->dists, s->weights, s->length, s->dists, nullptr, s->eng->stream_) != hipSuccess)
+        return kmcudaRuntimeError;
       if (hipMemcpyAsync(host.data() + s->offset, s->dists, (size_t)s->length * sizeof(float), hipMemcpyDeviceToHost,
                          s->eng->stream_) != hipSuccess)
         return kmcudaMemoryCopyError;
     }
     RETERR(sync_all());
-    *out = (float)(butterfly_sum(host.data(), N) / N);
+    *out = weighted ? (float)(butterfly_sum(host.data(), N) / weight_total) : (float)(butterfly_sum(host.data(), N) / N);
     return 0;
   }
 };
@@ -1571,6 +1621,20 @@ KMCUDAResult kmeans_cuda(KMCUDAInitMethod init, const void *init_params, float t
                          uint32_t clusters_size, uint32_t seed, uint32_t device, int32_t device_ptrs, int32_t fp16x2,
                          int32_t verbosity, const float *samples, float *centroids, uint32_t *assignments,
                          float *average_distance) {
+  return static_cast<KMCUDAResult>(kmamd_kmeans_weighted(init, init_params, tolerance, yinyang_t, metric, samples_size,
+                                                         features_size, clusters_size, seed, device, device_ptrs, fp16x2,
+                                                         verbosity, samples, centroids, assignments, average_distance,
+                                                         nullptr));
+}
+
+// kmeans_cuda() with per-row sample weights (include/kmcuda_amd.h); sample_weights == nullptr: kmeans_cuda() itself
+int kmamd_kmeans_weighted(int init_, const void *init_params, float tolerance, float yinyang_t, int metric_,
+                          uint32_t samples_size, uint16_t features_size, uint32_t clusters_size, uint32_t seed,
+                          uint32_t device, int32_t device_ptrs, int32_t fp16x2, int32_t verbosity, const float *samples,
+                          float *centroids, uint32_t *assignments, float *average_distance,
+                          const float *sample_weights) {
+  const KMCUDAInitMethod init = static_cast<KMCUDAInitMethod>(init_);
+  const KMCUDADistanceMetric metric = static_cast<KMCUDADistanceMetric>(metric_);
   kmx::g_verbosity = verbosity;
   DEBUG("arguments: %d %p %.3f %.2f %d %u %u %u %u %u %d %d %p %p %p %p\n", init, init_params, tolerance, yinyang_t,
         metric, samples_size, (unsigned)features_size, clusters_size, seed, device, fp16x2, verbosity,
@@ -1585,6 +1649,14 @@ KMCUDAResult kmeans_cuda(KMCUDAInitMethod init, const void *init_params, float t
   if (samples == nullptr || centroids == nullptr || assignments == nullptr) return kmcudaInvalidArguments;
   if (tolerance < 0 || tolerance > 1) return kmcudaInvalidArguments;
   if (yinyang_t < 0 || yinyang_t > 0.5) return kmcudaInvalidArguments;
+  if (sample_weights) {
+    // what restates the reference's own arithmetic has no weighted counterpart (refused before any device is touched)
+    const char *xu = getenv("KMCUDA_AMD_EXACT_UPDATE"), *sh = getenv("KMCUDA_AMD_FP16_STRICT");
+    if (init == kmcudaInitMethodAFKMC2 || (xu && atoi(xu) != 0) || (fp16x2 && sh && atoi(sh) != 0)) {
+      INFO("sample weights are not supported with afkmc2, KMCUDA_AMD_EXACT_UPDATE=1 or KMCUDA_AMD_FP16_STRICT=1\n");
+      return kmcudaInvalidArguments;
+    }
+  }
   INFO("reassignments threshold: %u\n", uint32_t(tolerance * samples_size));
   const uint32_t yy_groups_size = yinyang_t * clusters_size;  // float product, truncated (kmcuda.cc:417)
   DEBUG("yinyang groups: %u\n", yy_groups_size);
@@ -1614,7 +1686,7 @@ KMCUDAResult kmeans_cuda(KMCUDAInitMethod init, const void *init_params, float t
   // fp16x2: features_size counts half2 pairs (kmcuda.h:107-108); internally one feature per half
   const uint32_t feats = fp16x2 ? 2u * features_size : features_size;
   RETERR(job.setup(devs, virtual_shards(), samples_size, feats, clusters_size, metric, verbosity, samples,
-                   device_ptrs));
+                   device_ptrs, nullptr, sample_weights));
   if (const char *v = getenv("KMCUDA_AMD_EXACT_UPDATE")) job.exact_update = atoi(v) != 0;
   if (job.strict_h2) job.exact_update = true;   // the reference's serial update, in half2 arithmetic
   lap("set-up (engines, uploads)");
@@ -1652,7 +1724,9 @@ KMCUDAResult kmeans_cuda(KMCUDAInitMethod init, const void *init_params, float t
     int iter = 0;
     RETERR(job.lloyd((float)kYinyangDraftReassignments, &iter));
     lap("Lloyd down to 11 % reassignments");
-    const int st = job.check_changed(iter, tolerance, false);  // kmeans.cu:1058
+    // (weighted: the reassigned weight is in the stop iteration's reduced buffer, not in the counters)
+    const int st = job.weighted ? job.check_changed_reduced(iter, tolerance, false)
+                                : job.check_changed(iter, tolerance, false);  // kmeans.cu:1058
     if (st < 0) return static_cast<KMCUDAResult>(-st);
     if (st == 0) {
       // the reference's hand-over point: the K centroids are clustered into groups here (its progress lines are

@@ -17,6 +17,7 @@
 #include <time.h>
 
 #include "../../include/kmcuda.h"
+#include "../../include/kmcuda_amd.h"
 
 namespace {
 
@@ -211,10 +212,12 @@ PyObject *py_kmeans_cuda(PyObject *, PyObject *args, PyObject *kwargs) {
   int verbosity = 0, adflag = 0;
   float tolerance = .01f, yinyang_t = .1f;
   PyObject *samples_obj = nullptr, *init_obj = P.None, *metric_obj = P.None, *clusters_obj = nullptr;
+  PyObject *weight_obj = P.None;   // sample_weight: not in the reference's grammar (kmamd_kmeans_weighted)
   static const char *kwlist[] = {"samples", "clusters", "tolerance", "init", "yinyang_t", "metric",
-                                 "average_distance", "seed", "device", "verbosity", nullptr};
-  if (!P.ParseTupleAndKeywords(args, kwargs, "OO|fOfOpIIi", const_cast<char **>(kwlist), &samples_obj, &clusters_obj,
-                               &tolerance, &init_obj, &yinyang_t, &metric_obj, &adflag, &seed, &device, &verbosity))
+                                 "average_distance", "seed", "device", "verbosity", "sample_weight", nullptr};
+  if (!P.ParseTupleAndKeywords(args, kwargs, "OO|fOfOpIIiO", const_cast<char **>(kwlist), &samples_obj, &clusters_obj,
+                               &tolerance, &init_obj, &yinyang_t, &metric_obj, &adflag, &seed, &device, &verbosity,
+                               &weight_obj))
     return nullptr;
   {
     unsigned long long c = 0;
@@ -299,6 +302,26 @@ PyObject *py_kmeans_cuda(PyObject *, PyObject *args, PyObject *kwargs) {
     samples = reinterpret_cast<const float *>(sbuf.v.buf);
   }
   if (d > 0xFFFFu) return fail(P.ValueError, "\"samples\": more than 65535 features is not supported");
+  // sample_weight: a 1-D float32 array of one weight per row; a raw device pointer (integer) in device-pointer mode
+  const float *weights = nullptr;
+  Ref weight_arr;
+  Buf wbuf;
+  if (weight_obj != P.None) {
+    if (device_ptrs >= 0) {
+      if (!is_int(weight_obj)) return fail(P.ValueError, "\"sample_weight\" is not a pointer (integer)");
+      weights = reinterpret_cast<const float *>((uintptr_t)P.LongAsUnsignedLongLong(weight_obj));
+      if (P.ErrOccurred()) return nullptr;
+      if (!weights) return fail(P.ValueError, "\"sample_weight\" is null");
+    } else {
+      if (!dtype_is(weight_obj, "float32")) return fail(P.ValueError, "\"sample_weight\" must be a 1D float32 numpy array");
+      weight_arr.reset(P.CallMethod(P.numpy, "ascontiguousarray", "Os", weight_obj, "float32"));
+      if (!weight_arr.o || !wbuf.get(weight_arr.o, false)) return nullptr;
+      if (wbuf.v.ndim != 1) return fail(P.ValueError, "\"sample_weight\" must be a 1D float32 numpy array");
+      if ((uint32_t)wbuf.v.shape[0] != n)
+        return fail(P.ValueError, "\"sample_weight\" must be of the same length as \"samples\"");
+      weights = reinterpret_cast<const float *>(wbuf.v.buf);
+    }
+  }
   const uint32_t dwide = fp16x2 ? 2 * d : d;
   const size_t elem = fp16x2 ? 2 : 4;
   bool own_device_outputs = false;
@@ -341,9 +364,9 @@ PyObject *py_kmeans_cuda(PyObject *, PyObject *args, PyObject *kwargs) {
   int result;
   {
     PyThreadState *ts = P.SaveThread();   // Py_BEGIN_ALLOW_THREADS, python.cc:357
-    result = kmeans_cuda(init, &afkmc2_m, tolerance, yinyang_t, metric, n, (uint16_t)d, clusters, seed, device,
-                         device_ptrs, fp16x2 ? 1 : 0, verbosity, samples, centroids, assignments,
-                         adflag ? &average_distance : nullptr);
+    result = kmamd_kmeans_weighted(init, &afkmc2_m, tolerance, yinyang_t, metric, n, (uint16_t)d, clusters, seed,
+                                   device, device_ptrs, fp16x2 ? 1 : 0, verbosity, samples, centroids, assignments,
+                                   adflag ? &average_distance : nullptr, weights);
     P.RestoreThread(ts);
   }
   if (result != kmcudaSuccess) return bail(raise_for(result, "kmeans_cuda"));
@@ -458,7 +481,8 @@ PyObject *py_knn_cuda(PyObject *, PyObject *args, PyObject *kwargs) {
 const char module_doc[] = "MI355X-native K-means and K-nn (drop-in for src-d/kmcuda's libKMCUDA)";
 const char kmeans_doc[] =
     "kmeans_cuda(samples, clusters, tolerance=0.01, init=\"k-means++\", yinyang_t=0.1, metric=\"L2\", "
-    "average_distance=False, seed=time(), device=0, verbosity=0) -> (centroids, assignments[, average distance])";
+    "average_distance=False, seed=time(), device=0, verbosity=0, sample_weight=None) -> (centroids, assignments[, "
+    "average distance])";
 const char knn_doc[] =
     "knn_cuda(k, samples, centroids, assignments, metric=\"L2\", device=0, verbosity=0) -> neighbors";
 

@@ -1017,6 +1017,24 @@ __global__ __launch_bounds__(kKmppBlock) void kmpp_choose_kernel(KmppShards sh, 
   }
 }
 
+// Sample weights (kmamd_kmeans_weighted): the chooser draws a row with probability proportional to w * (its distance
+// term) -- one fp32 product, rounded to nearest, kept in a buffer of its own (dists[] stays the plain minimum the next
+// step compares with).  The statistics, the prefix sums, the chooser and the host's restatement read that buffer where
+// they read dists[] without weights; nothing else changes.
+__global__ __launch_bounds__(256) void kmpp_weigh_kernel(const float *__restrict__ dists,
+                                                         const float *__restrict__ weights, uint32_t N,
+                                                         float *__restrict__ terms, const uint32_t *__restrict__ fail) {
+  if (fail && *fail) return;   // (as the step: the terms stay as the undecided step left them)
+  for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < N; s += gridDim.x * 256u) terms[s] = __fmul_rn(weights[s], dists[s]);
+}
+hipError_t launch_kmpp_weigh(const float *dists, const float *weights, uint32_t N, float *terms, const uint32_t *fail,
+                             hipStream_t st) {
+  const uint32_t nb = (N + 255u) / 256u;
+  hipLaunchKernelGGL(kmpp_weigh_kernel, dim3(nb < 4096u ? (nb ? nb : 1u) : 4096u), dim3(256), 0, st, dists, weights, N,
+                     terms, fail);
+  return hipGetLastError();
+}
+
 // bpre: nb local prefixes, then nchunks + 1 carries, then (16-byte aligned) the nchunks chunk records
 static hipError_t launch_kmpp_reduce(const void *block_stats, uint32_t nb, double *bpre, void *totals,
                                      const uint32_t *fail, hipStream_t st) {
@@ -1033,7 +1051,8 @@ static hipError_t launch_kmpp_reduce(const void *block_stats, uint32_t nb, doubl
 
 hipError_t launch_kmpp_step2(int metric, const float *samples, uint32_t N, uint32_t D, const float *centroid,
                              uint32_t cc, float *dists, void *block_stats, double *bpre, void *totals_host,
-                             const uint32_t *fail, const KmppOutlierBuf &out, hipStream_t st) {
+                             const uint32_t *fail, const KmppOutlierBuf &out, hipStream_t st, const float *weights,
+                             float *terms) {
   const uint32_t nb = (N + kKmppBlock - 1) / kKmppBlock;
   if (metric == 0)
     hipLaunchKernelGGL((kmpp_step2_kernel<0>), dim3(nb), dim3(kKmppBlock), 0, st, samples, N, D, centroid, cc, dists,
@@ -1041,7 +1060,9 @@ hipError_t launch_kmpp_step2(int metric, const float *samples, uint32_t N, uint3
   else
     hipLaunchKernelGGL((kmpp_step2_kernel<1>), dim3(nb), dim3(kKmppBlock), 0, st, samples, N, D, centroid, cc, dists,
                        reinterpret_cast<KmppBlockStat *>(block_stats), (const uint32_t *)nullptr, (const uint32_t *)nullptr, fail);
-  hipLaunchKernelGGL(kmpp_stats_kernel, dim3((nb + 3) / 4 < 2048u ? (nb + 3) / 4 : 2048u), dim3(256), 0, st, dists, N,
+  if (weights && launch_kmpp_weigh(dists, weights, N, terms, fail, st) != hipSuccess) return hipGetLastError();
+  hipLaunchKernelGGL(kmpp_stats_kernel, dim3((nb + 3) / 4 < 2048u ? (nb + 3) / 4 : 2048u), dim3(256), 0, st,
+                     weights ? terms : dists, N,
                      reinterpret_cast<KmppBlockStat *>(block_stats), (uint32_t *)nullptr, fail, out.ecut,
                      reinterpret_cast<KmppOutlier *>(out.outl), out.outl_count);
   return launch_kmpp_reduce(block_stats, nb, bpre, totals_host, fail, st);
@@ -1069,7 +1090,7 @@ hipError_t launch_kmpp_step_filtered(int metric, const float *samples, uint32_t 
                                      const void *xs8, const float *meta, const float *mu, uint32_t *stats,
                                      uint32_t *list, const float *centroid, uint32_t cc, float *dists,
                                      void *block_stats, double *bpre, void *totals_host, const uint32_t *fail,
-                                     const KmppOutlierBuf &out, hipStream_t st) {
+                                     const KmppOutlierBuf &out, hipStream_t st, const float *weights, float *terms) {
   const uint32_t nb = (N + kKmppBlock - 1) / kKmppBlock;
   const float eps = (float)(1.02 * ((double)D + 12.0) * 5.9604644775390625e-8);   // as the k-NN filter
   const uint32_t fgrid = (N + 127) / 128 < 1024u ? (N + 127) / 128 : 1024u;   // 16 waves per CU; one list atomic per wave
@@ -1097,7 +1118,9 @@ hipError_t launch_kmpp_step_filtered(int metric, const float *samples, uint32_t 
   else
     hipLaunchKernelGGL((kmpp_step2_kernel<1>), dim3(lgrid), dim3(kKmppBlock), 0, st, samples, N, D, centroid, cc, dists,
                        (KmppBlockStat *)nullptr, list, stats + 1, fail);
-  hipLaunchKernelGGL(kmpp_stats_kernel, dim3((nb + 3) / 4 < 2048u ? (nb + 3) / 4 : 2048u), dim3(256), 0, st, dists, N,
+  if (weights && launch_kmpp_weigh(dists, weights, N, terms, fail, st) != hipSuccess) return hipGetLastError();
+  hipLaunchKernelGGL(kmpp_stats_kernel, dim3((nb + 3) / 4 < 2048u ? (nb + 3) / 4 : 2048u), dim3(256), 0, st,
+                     weights ? terms : dists, N,
                      reinterpret_cast<KmppBlockStat *>(block_stats), stats + 1, fail, out.ecut,
                      reinterpret_cast<KmppOutlier *>(out.outl), out.outl_count);
   return launch_kmpp_reduce(block_stats, nb, bpre, totals_host, fail, st);

@@ -326,25 +326,42 @@ struct SumArgs {
   uint32_t *host;                       // pinned, device-visible: [0] events, [1] largest list, [2] counters[4], [4] counters[kDuoCount]
 };
 
-__device__ __forceinline__ double list_sum(const float *__restrict__ samples, uint32_t D, const uint32_t *rows,
-                                           uint32_t r0, uint32_t r1, uint32_t f) {
+// WEIGHTED: every row's term is (double)w * (double)x -- exact in fp64 (24 x 24 bits), so the sum rounds where the
+// unweighted one does.  The weight's address depends on rows[] alone, like the row's: the two loads of a list entry
+// are issued together and the weight never stands in front of the row (one 4-byte gather beside 4 D bytes).
+template <bool WEIGHTED>
+__device__ __forceinline__ double list_sum(const float *__restrict__ samples, const float *__restrict__ weights,
+                                           uint32_t D, const uint32_t *rows, uint32_t r0, uint32_t r1, uint32_t f) {
   double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint32_t r = r0;
   for (; r + 8 <= r1; r += 8) {
-    float x[8];
+    float x[8], w[8];
 #pragma unroll
-    for (int j = 0; j < 8; j++) x[j] = samples[(size_t)rows[r + j] * D + f];
+    for (int j = 0; j < 8; j++) {
+      const uint32_t row = rows[r + j];
+      x[j] = samples[(size_t)row * D + f];
+      if constexpr (WEIGHTED) w[j] = weights[row];
+    }
 #pragma unroll
-    for (int j = 0; j < 8; j++) a[j] += (double)x[j];
+    for (int j = 0; j < 8; j++) {
+      if constexpr (WEIGHTED) a[j] += (double)w[j] * (double)x[j];
+      else a[j] += (double)x[j];
+    }
   }
-  for (uint32_t j = 0; r < r1; r++, j++) a[j] += (double)samples[(size_t)rows[r] * D + f];
+  for (uint32_t j = 0; r < r1; r++, j++) {
+    const uint32_t row = rows[r];
+    if constexpr (WEIGHTED) a[j] += (double)weights[row] * (double)samples[(size_t)row * D + f];
+    else a[j] += (double)samples[(size_t)row * D + f];
+  }
   return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
 }
 
 // the same for four consecutive features per lane (16-byte loads; D % 4 == 0, aligned rows): four accumulator
 // sets by row position, folded as (a0 + a1) + (a2 + a3)
-__device__ __forceinline__ void list_sum4(const float *__restrict__ samples, uint32_t D, const uint32_t *rows,
-                                          uint32_t r0, uint32_t r1, uint32_t f, double (&out)[4]) {
+template <bool WEIGHTED>
+__device__ __forceinline__ void list_sum4(const float *__restrict__ samples, const float *__restrict__ weights,
+                                          uint32_t D, const uint32_t *rows, uint32_t r0, uint32_t r1, uint32_t f,
+                                          double (&out)[4]) {
   double a[4][4];
 #pragma unroll
   for (int j = 0; j < 4; j++)
@@ -353,19 +370,35 @@ __device__ __forceinline__ void list_sum4(const float *__restrict__ samples, uin
   uint32_t r = r0;
   for (; r + 4 <= r1; r += 4) {
     float4 x[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) x[j] = *reinterpret_cast<const float4 *>(samples + (size_t)rows[r + j] * D + f);
+    double w[4] = {1.0, 1.0, 1.0, 1.0};
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      a[j][0] += (double)x[j].x; a[j][1] += (double)x[j].y; a[j][2] += (double)x[j].z; a[j][3] += (double)x[j].w;
+      const uint32_t row = rows[r + j];
+      x[j] = *reinterpret_cast<const float4 *>(samples + (size_t)row * D + f);
+      if constexpr (WEIGHTED) w[j] = (double)weights[row];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if constexpr (WEIGHTED) {
+        a[j][0] += w[j] * (double)x[j].x; a[j][1] += w[j] * (double)x[j].y;
+        a[j][2] += w[j] * (double)x[j].z; a[j][3] += w[j] * (double)x[j].w;
+      } else {
+        a[j][0] += (double)x[j].x; a[j][1] += (double)x[j].y; a[j][2] += (double)x[j].z; a[j][3] += (double)x[j].w;
+      }
     }
   }
   for (uint32_t j = 0; r < r1; r++, j++) {
-    const float4 x = *reinterpret_cast<const float4 *>(samples + (size_t)rows[r] * D + f);
+    const uint32_t row = rows[r];
+    float4 x = *reinterpret_cast<const float4 *>(samples + (size_t)row * D + f);
+    double x0 = (double)x.x, x1 = (double)x.y, x2 = (double)x.z, x3 = (double)x.w;
+    if constexpr (WEIGHTED) {
+      const double w = (double)weights[row];
+      x0 *= w; x1 *= w; x2 *= w; x3 *= w;
+    }
     // (j < 4: static indexing after unrolling)
-    if (j == 0) { a[0][0] += (double)x.x; a[0][1] += (double)x.y; a[0][2] += (double)x.z; a[0][3] += (double)x.w; }
-    else if (j == 1) { a[1][0] += (double)x.x; a[1][1] += (double)x.y; a[1][2] += (double)x.z; a[1][3] += (double)x.w; }
-    else { a[2][0] += (double)x.x; a[2][1] += (double)x.y; a[2][2] += (double)x.z; a[2][3] += (double)x.w; }
+    if (j == 0) { a[0][0] += x0; a[0][1] += x1; a[0][2] += x2; a[0][3] += x3; }
+    else if (j == 1) { a[1][0] += x0; a[1][1] += x1; a[1][2] += x2; a[1][3] += x3; }
+    else { a[2][0] += x0; a[2][1] += x1; a[2][2] += x2; a[2][3] += x3; }
   }
 #pragma unroll
   for (int e = 0; e < 4; e++) out[e] = (a[0][e] + a[1][e]) + (a[2][e] + a[3][e]);
@@ -374,8 +407,20 @@ __device__ __forceinline__ void list_sum4(const float *__restrict__ samples, uin
 // VEC4: lanes own four consecutive features each (16-byte loads), so a 1-KB row takes 64 lanes and the block's
 // 1024 threads are 16 row groups instead of 4: the lists of a steady iteration (tens to hundreds of rows) are
 // read in one or two trips.  D % 4 == 0 and 16-byte aligned rows; anything else takes the scalar mapping.
-template <bool DIRECT, bool VEC4>
-__global__ __launch_bounds__(kSumThreads) void cluster_sums_kernel(SumArgs a) {
+//
+// WEIGHTED (kmamd_set_weights): its own instantiations of the same body -- the unweighted kernels compile to what they
+// were.  Beside the sums of w * x it leaves, per centroid, the weight that moved in minus the weight that moved out
+// (wa.dweight) and the weight that moved in (wa.win: weight_changed_kernel adds them up to the pass's reassigned
+// weight).  Both are fp64 sums of a list's weights in an order that depends on the list alone: thread t takes entries
+// t, t + 1024, ..., lane l of the first wave adds threads l, l + 64, ... and the wave folds by xor butterfly.
+struct SumWeightArgs {
+  const float *weights;   // N, finite and > 0 (Engine::set_weights has checked)
+  double *dweight;        // K
+  double *win;            // K
+};
+
+template <bool DIRECT, bool VEC4, bool WEIGHTED>
+__device__ __forceinline__ void cluster_sums_body(const SumArgs &a, const SumWeightArgs &wa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sums_lds[];
   double *part = reinterpret_cast<double *>(sums_lds);                               // VEC4: 4 per thread, else 1
   uint32_t (*srt)[kBucketCapMax] = reinterpret_cast<uint32_t (*)[kBucketCapMax]>(sums_lds + kSumThreads * 4 * sizeof(double));
@@ -483,6 +528,28 @@ __global__ __launch_bounds__(kSumThreads) void cluster_sums_kernel(SumArgs a) {
     rows[1] = a.rows_sorted + o1;
   }
 
+  double wsum[2] = {0.0, 0.0};   // WEIGHTED: the lists' weights (valid in the first wave)
+  if constexpr (WEIGHTED) {
+#pragma unroll
+    for (int sg = 0; sg < 2; sg++) {
+      double t = 0.0;
+      for (uint32_t r = tid; r < n[sg]; r += kSumThreads) t += (double)wa.weights[rows[sg][r]];
+      part[sg * kSumThreads + tid] = t;
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int sg = 0; sg < 2; sg++) {
+        double t = part[sg * kSumThreads + lane];
+        for (uint32_t k = 1; k < kSumThreads / 64; k++) t += part[sg * kSumThreads + k * 64 + lane];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+        wsum[sg] = t;
+      }
+    }
+    __syncthreads();   // `part` goes to the feature sums
+  }
+
   // ---- sums: fl lanes across the features, groups of rows ----
   // Two mappings, chosen by the centroid's longer list (a function of the lists alone: the same on every path).
   // Long lists (the first iterations; steady iterations of a many-row shard): a lane owns four consecutive
@@ -502,7 +569,7 @@ __global__ __launch_bounds__(kSumThreads) void cluster_sums_kernel(SumArgs a) {
         const uint32_t cnt = n[sg], chunk = (cnt + groups - 1) / groups;
         const uint32_t r0 = min(cnt, g * chunk), r1 = min(cnt, r0 + chunk);
         double mine[4] = {0.0, 0.0, 0.0, 0.0};
-        if (fv && r1 > r0) list_sum4(a.samples, D, rows[sg], r0, r1, f, mine);
+        if (fv && r1 > r0) list_sum4<WEIGHTED>(a.samples, wa.weights, D, rows[sg], r0, r1, f, mine);
 #pragma unroll
         for (int e = 0; e < 4; e++) part[(size_t)tid * 4 + e] = mine[e];
         __syncthreads();
@@ -532,7 +599,7 @@ __global__ __launch_bounds__(kSumThreads) void cluster_sums_kernel(SumArgs a) {
     for (int sg = 0; sg < 2; sg++) {
       const uint32_t cnt = n[sg], chunk = (cnt + groups - 1) / groups;
       const uint32_t r0 = min(cnt, g * chunk), r1 = min(cnt, r0 + chunk);
-      part[tid] = (fv && r1 > r0) ? list_sum(a.samples, D, rows[sg], r0, r1, f) : 0.0;
+      part[tid] = (fv && r1 > r0) ? list_sum<WEIGHTED>(a.samples, wa.weights, D, rows[sg], r0, r1, f) : 0.0;
       __syncthreads();
       if (g == 0) {
         double t = part[lf];
@@ -548,6 +615,10 @@ __global__ __launch_bounds__(kSumThreads) void cluster_sums_kernel(SumArgs a) {
     const int32_t dc = (int32_t)n[0] - (int32_t)n[1];
     if (a.dcount) a.dcount[c] = dc;
     if (a.tail) a.tail[c] = (double)dc;
+    if constexpr (WEIGHTED) {
+      wa.dweight[c] = wsum[0] - wsum[1];
+      wa.win[c] = wsum[0];
+    }
     atomicAdd(&a.res[0], n[0] + n[1]);
     atomicMax(&a.res[1], max(n[0], n[1]));
     __threadfence();
@@ -567,6 +638,74 @@ __global__ __launch_bounds__(kSumThreads) void cluster_sums_kernel(SumArgs a) {
     }
   }
   if (a.tail && c == 0 && tid < 4) a.tail[a.K + tid] = (double)a.counters[tid];
+}
+
+template <bool DIRECT, bool VEC4>
+__global__ __launch_bounds__(kSumThreads) void cluster_sums_kernel(SumArgs a) {
+  cluster_sums_body<DIRECT, VEC4, false>(a, SumWeightArgs{nullptr, nullptr, nullptr});
+}
+template <bool DIRECT, bool VEC4>
+__global__ __launch_bounds__(kSumThreads) void cluster_sums_w_kernel(SumArgs a, SumWeightArgs wa) {
+  cluster_sums_body<DIRECT, VEC4, true>(a, wa);
+}
+
+// the pass's reassigned weight: the weights that moved into the K centroids, added in a fixed order (thread t takes
+// centroids t, t + 256, ...; LDS tree) -- one small block behind cluster_sums_w_kernel
+__global__ __launch_bounds__(256) void weight_changed_kernel(const double *__restrict__ win, uint32_t K,
+                                                             double *__restrict__ out) {
+  __shared__ double red[256];
+  double t = 0.0;
+  for (uint32_t c = threadIdx.x; c < K; c += 256) t += win[c];
+  red[threadIdx.x] = t;
+  __syncthreads();
+  for (uint32_t s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = red[0];
+}
+
+// Engine::set_weights: every weight finite and > 0, and their fp64 total in a fixed order -- block b takes the
+// rows [b * chunk, (b + 1) * chunk), thread t of it rows t, t + 256, ..., LDS tree; one block then adds the
+// blocks' sums the same way.  out[0] = total, out[1] = number of refused weights.
+constexpr uint32_t kWeightBlocks = 1024;
+__global__ __launch_bounds__(256) void weights_check_kernel(const float *__restrict__ w, uint32_t N, uint32_t chunk,
+                                                            double *__restrict__ part) {
+  __shared__ double red[256], bad[256];
+  const uint32_t lo = blockIdx.x * chunk, hi = min(N, lo + chunk);
+  double t = 0.0, b = 0.0;
+  for (uint32_t s = lo + threadIdx.x; s < hi; s += 256) {
+    const float v = w[s];
+    if (v > 0.f && v < INFINITY) t += (double)v; else b += 1.0;   // (a NaN fails both)
+  }
+  red[threadIdx.x] = t; bad[threadIdx.x] = b;
+  __syncthreads();
+  for (uint32_t s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) { red[threadIdx.x] += red[threadIdx.x + s]; bad[threadIdx.x] += bad[threadIdx.x + s]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { part[2 * blockIdx.x] = red[0]; part[2 * blockIdx.x + 1] = bad[0]; }
+}
+__global__ __launch_bounds__(256) void weights_total_kernel(const double *__restrict__ part, uint32_t nb,
+                                                            double *__restrict__ out) {
+  __shared__ double red[256], bad[256];
+  double t = 0.0, b = 0.0;
+  for (uint32_t i = threadIdx.x; i < nb; i += 256) { t += part[2 * i]; b += part[2 * i + 1]; }
+  red[threadIdx.x] = t; bad[threadIdx.x] = b;
+  __syncthreads();
+  for (uint32_t s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) { red[threadIdx.x] += red[threadIdx.x + s]; bad[threadIdx.x] += bad[threadIdx.x + s]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] = red[0]; out[1] = bad[0]; }
+}
+size_t weights_check_doubles() { return 2 * (size_t)kWeightBlocks + 2; }
+hipError_t launch_weights_check(const float *weights, uint32_t N, double *work, hipStream_t st) {
+  const uint32_t chunk = ((N + kWeightBlocks - 1) / kWeightBlocks + 255u) / 256u * 256u;
+  const uint32_t nb = chunk ? (N + chunk - 1) / chunk : 0;
+  if (nb) hipLaunchKernelGGL(weights_check_kernel, dim3(nb), dim3(256), 0, st, weights, N, chunk, work + 2);
+  hipLaunchKernelGGL(weights_total_kernel, dim3(1), dim3(256), 0, st, work + 2, nb, work);
+  return hipGetLastError();
 }
 
 // counters one cache line apart while that stays under ~1 MB per array
@@ -610,7 +749,7 @@ hipError_t launch_move_deltas(const float *samples, uint32_t N, uint32_t D, uint
                               uint32_t *rows_sorted, uint32_t *offsets2, void *temp, size_t temp_bytes,
                               uint32_t *bucket_rows, uint32_t cap, double *delta, int32_t *dcount, double *tail,
                               const uint32_t *counters, uint32_t *blockoff, uint32_t *bucket_work, MoveState *ms,
-                              hipStream_t st) {
+                              hipStream_t st, const MoveWeights *mw) {
   // blockoff: N / 1024 + 2 words; bucket_work: move_bucket_words(K) words, zero on entry and on exit;
   // ms->host / host_dev: 4 pinned words
   const uint32_t stride = move_bucket_stride(K);
@@ -625,6 +764,21 @@ hipError_t launch_move_deltas(const float *samples, uint32_t N, uint32_t D, uint
   const bool vec4 = (D & 3u) == 0 && (((uintptr_t)samples) & 15u) == 0;
   const size_t sums_lds = kSumThreads * 4 * sizeof(double) + 2 * kBucketCapMax * sizeof(uint32_t);   // 64 KB
   auto launch_sums = [&](bool direct) {
+    if (mw) {   // weighted instantiations + the reassigned weight behind them
+      const SumWeightArgs wa{mw->weights, mw->dweight, mw->win};
+      const void *fn = direct ? (vec4 ? (const void *)cluster_sums_w_kernel<true, true> : (const void *)cluster_sums_w_kernel<true, false>)
+                              : (vec4 ? (const void *)cluster_sums_w_kernel<false, true> : (const void *)cluster_sums_w_kernel<false, false>);
+      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sums_lds) != hipSuccess) return;
+      if (direct) {
+        if (vec4) hipLaunchKernelGGL((cluster_sums_w_kernel<true, true>), dim3(K), dim3(kSumThreads), sums_lds, st, a, wa);
+        else hipLaunchKernelGGL((cluster_sums_w_kernel<true, false>), dim3(K), dim3(kSumThreads), sums_lds, st, a, wa);
+      } else {
+        if (vec4) hipLaunchKernelGGL((cluster_sums_w_kernel<false, true>), dim3(K), dim3(kSumThreads), sums_lds, st, a, wa);
+        else hipLaunchKernelGGL((cluster_sums_w_kernel<false, false>), dim3(K), dim3(kSumThreads), sums_lds, st, a, wa);
+      }
+      hipLaunchKernelGGL(weight_changed_kernel, dim3(1), dim3(256), 0, st, mw->win, K, mw->dweight + K);
+      return;
+    }
     const void *fn = direct ? (vec4 ? (const void *)cluster_sums_kernel<true, true> : (const void *)cluster_sums_kernel<true, false>)
                             : (vec4 ? (const void *)cluster_sums_kernel<false, true> : (const void *)cluster_sums_kernel<false, false>);
     // (per launch: the attribute belongs to the current device's copy of the kernel)
@@ -703,14 +857,25 @@ hipError_t launch_move_deltas(const float *samples, uint32_t N, uint32_t D, uint
 // state as the reference returns it: assignments of this iteration, centroids one update behind).  Going on:
 // counters[0] is zeroed for the next pass (kmeans.cu:710-714).  The host learns the outcome from the pinned
 // words, without a stream synchronisation in front of the next pass.
-template <int METRIC>
-__global__ void apply_delta_kernel(const double *__restrict__ delta, const int32_t *__restrict__ dcount,
-                                   const double *__restrict__ dcount_d, uint32_t D, float *__restrict__ centroids,
-                                   uint32_t *__restrict__ ccounts, StopCtl ctl) {
+// WEIGHTED (kmamd_set_weights): wtail = [K cluster-weight deltas | the reassigned weight] (the reduce buffer's end, or
+// the engine's own words behind kmamd_move_deltas), cweights = the engine's K running cluster weights in fp64.  The
+// step is the same (c * W_old + delta) / W_new with weights where the counts stood; the stop rule compares the
+// reassigned WEIGHT with the threshold (tolerance * total weight, in float as the counts' rule).  A cluster is empty
+// when its COUNT is 0 -- the weight is never asked -- and an empty cluster's running weight is exactly 0.
+template <int METRIC, bool WEIGHTED>
+__device__ __forceinline__ void apply_delta_body(const double *__restrict__ delta, const int32_t *__restrict__ dcount,
+                                                 const double *__restrict__ dcount_d, uint32_t D,
+                                                 float *__restrict__ centroids, uint32_t *__restrict__ ccounts,
+                                                 const StopCtl &ctl, const double *__restrict__ wtail,
+                                                 double *__restrict__ cweights) {
   const uint32_t c = blockIdx.x;
   if (ctl.counters) {
     bool stop = ctl.counters[kStopFlag] != 0u;   // once stopped, stay stopped
-    if (ctl.threshold >= 0.f && dcount_d) stop = stop || (float)(uint32_t)dcount_d[gridDim.x] <= ctl.threshold;
+    if constexpr (WEIGHTED) {
+      if (ctl.threshold >= 0.f && dcount_d) stop = stop || (float)wtail[gridDim.x] <= ctl.threshold;
+    } else {
+      if (ctl.threshold >= 0.f && dcount_d) stop = stop || (float)(uint32_t)dcount_d[gridDim.x] <= ctl.threshold;
+    }
     if (c == 0 && threadIdx.x == 0) {
       if (stop) ctl.counters[kStopFlag] = 1u;
       else if (ctl.threshold >= 0.f) ctl.counters[0] = 0u;
@@ -729,7 +894,14 @@ __global__ void apply_delta_kernel(const double *__restrict__ delta, const int32
   const uint32_t cnt_old = ccounts[c];
   // (dcount_d: the fused reduce buffer's tail -- sums of int32 counts, exact in fp64)
   const uint32_t cnt_new = cnt_old + (uint32_t)(dcount_d ? (int32_t)dcount_d[c] : dcount[c]);
-  const double w = (double)cnt_old;
+  double w, cn;
+  if constexpr (WEIGHTED) {
+    w = cnt_old ? cweights[c] : 0.0;
+    cn = w + wtail[c];
+  } else {
+    w = (double)cnt_old;
+    cn = (double)cnt_new;  // 0 -> 0/0 = NaN or x/0 = inf: never chosen again
+  }
   if (cnt_new == 0) {
     // empty cluster => NaN centroid row, never chosen again (kmeans.cu:425-426, README "NaN
     // centroid").  The reference gets there through 0 * (1/0); its fp32 residual c*count - sum is
@@ -737,7 +909,6 @@ __global__ void apply_delta_kernel(const double *__restrict__ delta, const int32
     // k-means++ of the Yinyang group clustering -- so the contract value is written directly.
     for (uint32_t f = threadIdx.x; f < D; f += blockDim.x) cen[f] = __builtin_nanf("");
   } else if (METRIC == 0) {
-    const double cn = (double)cnt_new;  // 0 -> 0/0 = NaN or x/0 = inf: never chosen again
     for (uint32_t f = threadIdx.x; f < D; f += blockDim.x) cen[f] = (float)(((double)cen[f] * w + d[f]) / cn);
   } else {
     __shared__ double red[256];
@@ -756,13 +927,39 @@ __global__ void apply_delta_kernel(const double *__restrict__ delta, const int32
     for (uint32_t f = threadIdx.x; f < D; f += blockDim.x) cen[f] = (float)(((double)cen[f] * w + d[f]) / nrm);
   }
   __syncthreads();
-  if (threadIdx.x == 0) ccounts[c] = cnt_new;
+  if (threadIdx.x == 0) {
+    ccounts[c] = cnt_new;
+    if constexpr (WEIGHTED) cweights[c] = cnt_new ? cn : 0.0;
+  }
+}
+
+template <int METRIC>
+__global__ void apply_delta_kernel(const double *__restrict__ delta, const int32_t *__restrict__ dcount,
+                                   const double *__restrict__ dcount_d, uint32_t D, float *__restrict__ centroids,
+                                   uint32_t *__restrict__ ccounts, StopCtl ctl) {
+  apply_delta_body<METRIC, false>(delta, dcount, dcount_d, D, centroids, ccounts, ctl, nullptr, nullptr);
+}
+template <int METRIC>
+__global__ void apply_delta_w_kernel(const double *__restrict__ delta, const int32_t *__restrict__ dcount,
+                                     const double *__restrict__ dcount_d, uint32_t D, float *__restrict__ centroids,
+                                     uint32_t *__restrict__ ccounts, StopCtl ctl, const double *__restrict__ wtail,
+                                     double *__restrict__ cweights) {
+  apply_delta_body<METRIC, true>(delta, dcount, dcount_d, D, centroids, ccounts, ctl, wtail, cweights);
 }
 
 hipError_t launch_apply_delta(int metric, const double *delta, const int32_t *dcount, const double *dcount_d,
                               uint32_t K, uint32_t D, float *centroids, uint32_t *ccounts, const StopCtl &stop,
-                              hipStream_t st) {
+                              hipStream_t st, const double *wtail, double *cweights) {
   const uint32_t bs = D >= 256 ? 256 : (D > 64 ? 128 : 64);
+  if (wtail) {
+    if (metric == 0)
+      hipLaunchKernelGGL((apply_delta_w_kernel<0>), dim3(K), dim3(bs), 0, st, delta, dcount, dcount_d, D, centroids,
+                         ccounts, stop, wtail, cweights);
+    else
+      hipLaunchKernelGGL((apply_delta_w_kernel<1>), dim3(K), dim3(bs), 0, st, delta, dcount, dcount_d, D, centroids,
+                         ccounts, stop, wtail, cweights);
+    return hipGetLastError();
+  }
   if (metric == 0)
     hipLaunchKernelGGL((apply_delta_kernel<0>), dim3(K), dim3(bs), 0, st, delta, dcount, dcount_d, D, centroids, ccounts,
                        stop);

@@ -34,8 +34,11 @@ def row_block(n_total, rank, world):
 class HipBackend:
     """This rank's rows on its GPU; all compute is libKMCUDA.so kernels."""
 
-    def __init__(self, samples, clusters, metric="L2", device_index=0, half_rows=None, row_cache=True):
-        """half_rows: the same rows as a float16 tensor (fp16x2 path): the assignment filter then runs
+    def __init__(self, samples, clusters, metric="L2", device_index=0, half_rows=None, row_cache=True, weights=None):
+        """weights: this rank's per-row sample weights (float32 tensor on the same GPU, finite and > 0; Engine.set_weights)
+        -- the update and the stop rule then count a row of weight w as w copies, the reduce buffer carries K + 1 more
+        doubles, and ShardedLloyd's `n_total` must be the GLOBAL total weight (its stop threshold is tolerance * n_total).
+        half_rows: the same rows as a float16 tensor (fp16x2 path): the assignment filter then runs
         on the f16 matrix cores reading the halves; `samples` stays the widened fp32 copy the exact
         refine / update kernels read.  row_cache: this backend's rows never change, so the coarse filter
         stage may keep its centred half copy of them across iterations (Engine.set_row_cache)."""
@@ -52,6 +55,8 @@ class HipBackend:
         self.half = half_rows is not None
         if row_cache:
             self.engine.set_row_cache(True)
+        if weights is not None:   # (before new_reduce_buffer(): the buffer grows)
+            self.engine.set_weights(weights)
         i32 = dict(dtype=torch.int32, device=self.device)
         self.assignments = torch.full((self.n_local,), -1, **i32)   # 0xFFFFFFFF (prepare_mem)
         self.assignments_prev = torch.full((self.n_local,), -1, **i32)

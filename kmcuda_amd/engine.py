@@ -127,12 +127,29 @@ class Engine:
         _lib.check(self.lib.kmamd_apply_delta(self.h, self._p(delta), self._p(dcount), self._p(centroids),
                                               self._p(ccounts)), "kmamd_apply_delta")
 
+    def set_weights(self, weights):
+        """Per-row sample weights (kmamd_set_weights): a float32 CUDA tensor of n_rows finite weights > 0, or None to
+        switch back.  A row of weight w then counts as w copies in move_deltas / apply_delta and reduce_fill /
+        reduce_apply*: delta holds sums of w * x, reduce_len() grows by K + 1 doubles ([... | dweight K | changed
+        weight]), the engine keeps the running cluster weights in fp64 beside the caller's integer ccounts (zeroed by
+        this call), and a stop threshold is tolerance * total weight.  ValueError for a weight that is not finite
+        and > 0 (the engine then stays unweighted)."""
+        if weights is not None and (weights.dtype != torch.float32 or weights.dim() != 1
+                                    or weights.shape[0] != self.n_rows or not weights.is_contiguous()):
+            raise ValueError("weights must be a contiguous 1-D float32 tensor of n_rows elements")
+        rc = self.lib.kmamd_set_weights(self.h, self._p(weights) if weights is not None else None)
+        if rc == 1:
+            raise ValueError("sample weights must be finite and > 0")
+        _lib.check(rc, "kmamd_set_weights")
+        self._weights = weights  # keep alive
+
     def adjust_exact(self, samples, prev, cur, centroids, ccounts):
         _lib.check(self.lib.kmamd_adjust_exact(self.h, self._p(samples), self._p(prev), self._p(cur),
                                                self._p(centroids), self._p(ccounts)), "kmamd_adjust_exact")
 
     def reduce_len(self):
-        """Doubles in the fused reduce buffer: [delta K*D | dcount K | counters 4]."""
+        """Doubles in the fused reduce buffer: [delta K*D | dcount K | counters 4]; with set_weights() K + 1 more,
+        [... | dweight K | changed weight]."""
         return int(self.lib.kmamd_reduce_len(self.h))
 
     def reduce_fill(self, samples, prev, cur, buf):
