@@ -109,6 +109,142 @@ def test_sharded_hip_backend_world2_matches_single(tmp_path):
     assert (got["first"] == ref).all()
 
 
+# ---- the same loop with per-row weights --------------------------------------------------------------------------
+_W_TOL = 0.01
+_W_K = 24
+
+
+def _weighted_data():
+    """Exactly summable rows and weights (tests/_weighted_inputs.py): every fp64 move sum is exact, so neither the
+    split across ranks nor the order of the all-reduce changes a bit of it.  Imported centroids that are rows."""
+    from _weighted_inputs import exact_rows, exact_weights
+    rs = numpy.random.RandomState(23)
+    x = exact_rows(rs, 12000, 16)
+    w = exact_weights(rs, len(x))
+    init = x[rs.choice(len(x), _W_K, replace=False)].copy()
+    return x, w, init
+
+
+def _weighted_loop(loop, init_t, dev, max_iter=80):
+    """ShardedLloyd.step() until the device-side rule has fired; the assignments after every enqueued pass (once the
+    rule has fired later passes are no-ops and leave them alone).  Returns (log, [assignments per pass])."""
+    loop.set_centroids(init_t)
+    log, hist = [], []
+    for _ in range(max_iter):
+        changed = loop.step(_W_TOL)
+        if changed is not None:
+            log.append(changed)
+        torch.cuda.synchronize(dev)
+        hist.append(loop.b.assignments.cpu().numpy().view(numpy.uint32).copy())
+        if loop.stopped:
+            break
+    return log, hist
+
+
+def _weighted_worker(rank, world, port, out):
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    if os.path.join(ROOT, "tests") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import torch.distributed as dist
+    from kmcuda_amd.distributed import HipBackend, ShardedLloyd, row_block
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+    x, w, init = _weighted_data()
+    lo, hi = row_block(len(x), rank, world)
+    xs = torch.from_numpy(x[lo:hi]).to(dev)
+    ws = torch.from_numpy(w[lo:hi]).to(dev)
+    try:
+        probe = torch.ones(4, dtype=torch.float64, device=dev)
+        dist.all_reduce(probe)
+        torch.cuda.synchronize(dev)
+        assert float(probe[0].item()) == world
+    except (RuntimeError, AssertionError) as e:   # a gloo build without device-tensor support
+        if rank == 0:
+            numpy.savez(out, skipped=numpy.array([1]), why=numpy.array([str(e)[:200]]))
+        dist.destroy_process_group()
+        return
+    total = float(w.astype(numpy.float64).sum())          # the GLOBAL total weight, not this rank's
+    loop = ShardedLloyd(HipBackend(xs, len(init), "L2", device_index=0, weights=ws), total)
+    c0 = torch.from_numpy(init).to(dev) if rank == 0 else torch.zeros((len(init), x.shape[1]), device=dev)
+    log, hist = _weighted_loop(loop, c0, dev)
+    hists, lens = [None] * world, [None] * world
+    dist.all_gather_object(hists, hist)
+    dist.all_gather_object(lens, int(loop.buf.numel()))
+    if rank == 0:
+        passes = min(len(h) for h in hists)
+        assert all(len(h) == passes for h in hists)
+        numpy.savez(out, skipped=numpy.array([0]), log=numpy.array(log), buflen=numpy.array(lens),
+                    hist=numpy.stack([numpy.concatenate([h[i] for h in hists]) for i in range(passes)]),
+                    cen=loop.b.centroids.cpu().numpy())
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(600)
+def test_sharded_hip_backend_world2_weighted(tmp_path):
+    """HipBackend(weights=) under ShardedLloyd with the global total weight, two gloo ranks on GPU 0: the all-reduce of
+    the longer buffer [delta | dcount | counters | dweight K | changed weight] and the weighted device-side stop rule.
+
+    Against ONE process over all rows with the same weights: per-iteration log, every pass's assignments and the
+    centroid BITS identical (the sums are exact).  Against kmeans_cuda(..., sample_weight=w) from the same centroids: the
+    same iteration count and assignments.  The stop iteration is derived in float64 on the CPU from the assignments the
+    GPU reports per pass -- the weight of the rows that changed cluster against tolerance * total weight -- and the
+    weights are such that the ROW count falls under that threshold at an earlier pass: a loop that compared row counts
+    with tolerance * total weight stops too early and fails here."""
+    import ctypes
+    import torch.multiprocessing as mp
+    from kmcuda_amd import _lib, kmeans_cuda
+    from kmcuda_amd.distributed import HipBackend, ShardedLloyd, stop_threshold
+    assert torch.cuda.is_available(), "-m gpu tests need a GPU"
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    out = str(tmp_path / "w2w.npz")
+    mp.spawn(_weighted_worker, args=(2, port, out), nprocs=2, join=True)
+    got = numpy.load(out)
+    if int(got["skipped"][0]):
+        pytest.skip("gloo cannot reduce device tensors here: %s" % got["why"][0])
+    x, w, init = _weighted_data()
+    n, d = x.shape
+    w64 = w.astype(numpy.float64)
+    total = float(w64.sum())
+    assert list(got["buflen"]) == [_W_K * d + _W_K + 4 + _W_K + 1] * 2
+    dev = torch.device("cuda", 0)
+    loop = ShardedLloyd(HipBackend(torch.from_numpy(x).to(dev), _W_K, "L2", device_index=0,
+                                   weights=torch.from_numpy(w).to(dev)), total)
+    log, hist = _weighted_loop(loop, torch.from_numpy(init).to(dev), dev)
+    assert loop.buf.numel() == _W_K * d + _W_K + 4 + _W_K + 1
+    assert loop.stopped and list(got["log"]) == log and len(log) > 3
+    assert got["hist"].shape == (len(hist), n) and (got["hist"] == numpy.stack(hist)).all()
+    assert numpy.array_equal(got["cen"].view(numpy.uint32), loop.b.centroids.cpu().numpy().view(numpy.uint32))
+    # the stop rule, restated on the CPU from the per-pass assignments (float64 sums; the comparison in float, as the
+    # kernel and kmeans.cu:707 make it)
+    thr = numpy.float32(stop_threshold(_W_TOL, total))
+    before = numpy.full(n, 0xFFFFFFFF, numpy.uint32)
+    rows_changed, weight_changed = [], []
+    for asg in hist[:len(log)]:
+        moved = asg != before
+        rows_changed.append(int(moved.sum()))
+        weight_changed.append(w64[moved & (asg < _W_K)].sum())
+        before = asg
+    assert rows_changed == log                           # the report keeps counting rows
+    stop_by_weight = [i for i, v in enumerate(weight_changed) if numpy.float32(v) <= thr]
+    stop_by_rows = [i for i, v in enumerate(rows_changed) if numpy.float32(v) <= thr]
+    print("threshold %.6g; rows %s; weight %s" % (thr, rows_changed, ["%.6g" % v for v in weight_changed]))
+    assert stop_by_weight == [len(log) - 1]              # the weighted rule fires at the last pass and at no earlier one
+    assert stop_by_rows and stop_by_rows[0] < len(log) - 1   # the row count is under the same threshold earlier
+    assert (hist[-1] == hist[len(log) - 1]).all()        # the pass enqueued behind the stop touched nothing
+    # kmeans_cuda with the same weights from the same centroids
+    cen, asg = kmeans_cuda(x, _W_K, init=init, sample_weight=w, tolerance=_W_TOL, yinyang_t=0, device=1, seed=3)
+    it = ctypes.c_uint32(0)
+    assert _lib.lib().kmamd_last_run_stats(ctypes.byref(it), None, None, None, None) == 0
+    assert it.value == len(log)
+    assert (asg == hist[-1]).all()
+
+
 def _rccl_worker(rank, port, out):
     """ONE rank, backend "nccl" (= RCCL on ROCm): the all-reduce of the loop's fp64 buffer goes through RCCL on the
     buffer the engine's kernels fill and consume (KMCUDA_AMD reduce_always hook)."""

@@ -118,20 +118,39 @@ def test_native_module_takes_the_keyword():
 # ------------------------------------------------------------------------------------------------------------------
 # 2. integer weights equal materialised copies, bit for bit (L2)
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shards", [None, "3"])
-@pytest.mark.parametrize("tolerance,yinyang_t", [(0.0, 0.0), (0.01, 0.0), (0.01, 0.1)])
-def test_integer_weights_equal_copies(tolerance, yinyang_t, shards, monkeypatch):
+_COPIES_LAYOUTS = {
+    # name: (d, dtype, KMCUDA_AMD_UPDATE)
+    "d16": (16, numpy.float32, None),
+    "d15": (15, numpy.float32, None),          # D % 4 != 0: the scalar cluster_sums_w kernels
+    "d258": (258, numpy.float32, None),        # ... with two feature trips
+    "fp16-d16": (16, numpy.float16, None),     # m / 1024 is exact in half; the centroids are rounded to half after the update
+    "bucket-d16": (16, numpy.float32, "bucket"),
+    "radix-d16": (16, numpy.float32, "radix"),
+}
+
+
+@pytest.mark.parametrize("tolerance,yinyang_t,shards,layout", [
+    pytest.param(tol, yy, shards, "d16", id="%s-%s-%s" % (tol, yy, shards))
+    for tol, yy in [(0.0, 0.0), (0.01, 0.0), (0.01, 0.1)] for shards in [None, "3"]
+] + [pytest.param(0.01, 0.0, None, layout, id=layout) for layout in ("d15", "d258", "fp16-d16", "bucket-d16", "radix-d16")])
+def test_integer_weights_equal_copies(tolerance, yinyang_t, shards, layout, monkeypatch):
     """Rows are multiples of 2^-10 in [0, 1), weights in {1, 2, 3, 4}, at most 2^20 expanded rows: every partial sum of
     w x is a multiple of 2^-10 below 2^22, exact in fp64 in any order and any partition into shards, buckets or move
     lists, and both runs apply the identical (c W_old + delta) / W_new.  The weighted call on the distinct rows and the
     unweighted call on the expanded rows return identical centroids, iteration counts and assignments.  tolerance =
-    0.01 is the stop-rule check (the reassigned weight against the total weight)."""
+    0.01 is the stop-rule check (the reassigned weight against the total weight).  The layouts beside d = 16 put
+    non-constant weights through the scalar kernels (d = 15, d = 258), float16 rows (exact here; both runs round the
+    same centroids to half) and the forced direct and radix paths: the argument is the same for each."""
     from kmcuda_amd import kmeans_cuda
     if shards:
         monkeypatch.setenv("KMCUDA_AMD_VIRTUAL_SHARDS", shards)
+    d, dtype, update = _COPIES_LAYOUTS[layout]
+    if update:
+        monkeypatch.setenv("KMCUDA_AMD_UPDATE", update)
     rs = numpy.random.RandomState(11)
-    n, d, k = 30000, 16, 32
-    x = (rs.randint(0, 1024, size=(n, d)) / 1024.0).astype(numpy.float32)
+    n, k = 30000, 32
+    x = (rs.randint(0, 1024, size=(n, d)) / 1024.0).astype(numpy.float32).astype(dtype)
+    assert (x.astype(numpy.float64) * 1024 == numpy.round(x.astype(numpy.float64) * 1024)).all()
     w = rs.randint(1, 5, size=n)
     big = numpy.repeat(x, w, axis=0)
     first = numpy.concatenate([[0], numpy.cumsum(w)[:-1]])
@@ -143,7 +162,8 @@ def test_integer_weights_equal_copies(tolerance, yinyang_t, shards, monkeypatch)
     cb, ab = kmeans_cuda(big, k, **kw)
     itb = _iterations()
     assert itw == itb and itw > 3
-    assert numpy.array_equal(cw.view(numpy.uint32), cb.view(numpy.uint32))
+    bits = numpy.uint16 if dtype == numpy.float16 else numpy.uint32
+    assert cw.dtype == dtype and numpy.array_equal(cw.view(bits), cb.view(bits))
     assert numpy.array_equal(aw, ab[first])
     assert (ab == numpy.repeat(aw, w)).all()
 

@@ -96,3 +96,39 @@ def test_c_abi_refuses_reference_arithmetic_modes_with_weights_without_gpu(monke
     for K, D, N in ((1, 4, 100), (10, 0, 100), (10, 4, 5)):
         assert L.kmamd_kmeans_weighted(0, None, 0.01, 0.1, 0, N, D, K, 3, 0, -1, 0, 0, x.ctypes.data, cen.ctypes.data,
                                        asg.ctypes.data, None, w.ctypes.data) == 1
+
+
+def test_exactly_summable_inputs_sum_the_same_in_every_order():
+    """The premise of tests/test_gpu_weighted_update.py, kept checked without a GPU: rows m / 1024 and weights j 2^e
+    (tests/_weighted_inputs.py) at the largest row count the GPU tests may use.  The per-cluster float64 sums of w * x
+    and of w, added one row after the other in three random orders, are identical bit for bit, and on a small cluster
+    they equal the rational sum (fractions.Fraction: no rounding anywhere)."""
+    from fractions import Fraction
+    from _weighted_inputs import MAX_ROWS, cluster_sums, exact_rows, exact_weights, index_weights
+    rs = numpy.random.RandomState(3)
+    n, d, k = MAX_ROWS, 5, 7
+    x = exact_rows(rs, n, d)
+    assert x.dtype == numpy.float32 and x.min() >= 0 and x.max() < 1 and (x * 1024 == numpy.round(x * 1024)).all()
+    labels = rs.randint(0, k - 1, n).astype(numpy.int32)
+    labels[rs.choice(n, 300, replace=False)] = k - 1          # the small cluster
+    labels[rs.choice(n, 50, replace=False)] = -1              # rows of no cluster
+    small = numpy.nonzero(labels == k - 1)[0]
+    assert 200 < len(small) <= 300
+    for w in (exact_weights(rs, n), index_weights(n)):
+        assert w.dtype == numpy.float32 and w.min() >= 2.0 ** -6 and w.max() <= 15 * 2.0 ** 6
+        assert (w * 64 == numpy.round(w * 64)).all()          # multiples of 2^-6 ...
+        p = w.astype(numpy.float64)[:, None] * x.astype(numpy.float64) * 65536
+        assert (p == numpy.round(p)).all() and p.max() < 2.0 ** 26   # ... products multiples of 2^-16 below 2^10
+        sums = [cluster_sums(x, w, labels, k, order=rs.permutation(n)) for _ in range(3)]
+        for sx, sw in sums[1:]:
+            assert sx.tobytes() == sums[0][0].tobytes() and sw.tobytes() == sums[0][1].tobytes()
+        assert sums[0][0].max() < 2.0 ** 26 and sums[0][1].max() < 2.0 ** 26
+        fw = sum(Fraction(float(w[i])) for i in small)
+        assert Fraction(float(sums[0][1][k - 1])) == fw
+        for f in range(d):
+            fx = sum(Fraction(float(w[i])) * Fraction(float(x[i, f])) for i in small)
+            assert Fraction(float(sums[0][0][k - 1, f])) == fx
+        # the pairwise order of numpy.sum (what the GPU tests' reference uses) gives the same bits again
+        rows = numpy.nonzero(labels == 2)[0]
+        assert ((w[rows].astype(numpy.float64)[:, None] * x[rows].astype(numpy.float64)).sum(0).tobytes()
+                == sums[0][0][2].tobytes())
