@@ -84,6 +84,8 @@ def lib():
         L.kmo_knn_cluster_distances.argtypes = [i32, u32, u32, _f32p, _f32p]
         L.kmo_knn.restype = i32
         L.kmo_knn.argtypes = [u32, i32, u32, u32, u32, _f32p, _f32p, _u32p, _u32p, _u64p]
+        L.kmo_knn_query.restype = i32
+        L.kmo_knn_query.argtypes = [u32, i32, u32, u32, u32, _f32p, _f32p, _u32p, u32, _f32p, _u32p, _u32p, _f32p]
         _lib = L
     return _lib
 
@@ -227,6 +229,38 @@ def knn(k, samples, centroids, assignments, metric="L2", half2=False):
     if rc:
         raise ValueError("kmo_knn failed: %d" % rc)
     return nb, calced.value
+
+
+def knn_query(k, samples, centroids, assignments, queries, query_assignments=None, metric="L2", half2=False):
+    """KnnIndex.query on the CPU oracle (DESIGN.md 4.8 point 2): knn()'s search for every query as one more row of its
+    cluster, without the self-skip.  Returns (neighbors uint32 Q x k, distances float32 Q x k = what the heap compared;
+    a slot no candidate filled holds index 0 and FLT_MAX).  query_assignments=None: lloyd_assign(queries, centroids),
+    in fp32 arithmetic whatever half2 says (4.8 point 1).  A query with a non-finite feature or a cluster id >= K gets
+    0xFFFFFFFF and NaN.  half2=True (float16 inputs): the reference's half2 arithmetic, as knn()."""
+    if half2 and not (samples.dtype == np.float16 and centroids.dtype == np.float16
+                      and queries.dtype == np.float16):
+        raise ValueError("half2 arithmetic needs float16 samples, centroids and queries")
+    x, c, q = _c32(samples), _c32(centroids), _c32(queries)
+    if q.ndim != 2 or q.shape[1] != x.shape[1] or c.shape[1] != x.shape[1]:
+        raise ValueError("samples, centroids and queries must have the same number of features")
+    a = np.ascontiguousarray(assignments, dtype=np.uint32)
+    if query_assignments is None:
+        qa, _, _ = lloyd_assign(q, c, metric=metric)
+    else:
+        qa = np.ascontiguousarray(query_assignments, dtype=np.uint32)
+        if qa.shape != (q.shape[0],):
+            raise ValueError("query_assignments must have one entry per query")
+    nb = np.empty((q.shape[0], k), np.uint32)
+    dist = np.empty((q.shape[0], k), np.float32)
+    lib().kmo_set_fp16_mode(2 if half2 else 0)
+    try:
+        rc = lib().kmo_knn_query(k, _metric(metric), x.shape[0], x.shape[1], c.shape[0], _fp(x), _fp(c), _up(a),
+                                 q.shape[0], _fp(q), _up(qa), _up(nb), _fp(dist))
+    finally:
+        lib().kmo_set_fp16_mode(0)
+    if rc:
+        raise ValueError("kmo_knn_query failed: %d" % rc)
+    return nb, dist
 
 
 def yy_init(samples, centroids, assignments, groups, n_groups, metric=L2):

@@ -1173,18 +1173,66 @@ static void push_sample(uint32_t k, float dist, uint32_t index, float *heap) {
   }
 }
 
-/* knn.cu:177-243 (knn_assign_shmem; the gmem variant yields the same list) */
+/* knn.cu:177-243 (knn_assign_shmem; the gmem variant yields the same list): the search of ONE row x of cluster mycls.
+ * self = the row's own corpus index, skipped in its cluster (knn.cu:204-206), or UINT32_MAX for a row that is not in
+ * the corpus (a query: nothing is skipped).  heap: 2k floats of scratch.  distances may be NULL.  Returns the number of
+ * candidates of the clusters it visited (the reference's dists_calced). */
+static uint64_t knn_search_row(uint32_t k, int metric, uint32_t D, uint32_t K, const float *samples,
+                               const float *centroids, const float *x, uint32_t mycls, uint32_t self,
+                               const uint32_t *inv, const uint32_t *offsets, const float *radiuses, const float *cdist,
+                               float *heap, uint32_t *neighbors, float *distances) {
+  uint64_t calced = 0;
+  const float mydist = kmo_distance(metric, x, centroids + (size_t)mycls * D, D);
+  float mndist = FLT_MAX;
+  for (uint32_t i = 0; i < k; i++) { heap[2 * i] = FLT_MAX; ((uint32_t *)heap)[2 * i + 1] = 0; }
+  calced += offsets[mycls + 1] - offsets[mycls];
+  for (uint32_t pos = offsets[mycls]; pos < offsets[mycls + 1]; pos++) {
+    const uint32_t other = inv[pos];
+    if (other == self) continue;
+    const float dist = kmo_distance(metric, x, samples + (size_t)other * D, D);
+    if (dist <= mndist) { push_sample(k, dist, other, heap); mndist = heap[0]; }
+  }
+  for (uint32_t cls = 0; cls < K; cls++) {
+    if (cls == mycls) continue;
+    const float cd = cdist[(size_t)cls * K + mycls];
+    if (cd != cd) continue;
+    const float lim = cd - mydist - radiuses[cls];
+    if (lim > mndist) continue;
+    calced += offsets[cls + 1] - offsets[cls];
+    for (uint32_t pos = offsets[cls]; pos < offsets[cls + 1]; pos++) {
+      const uint32_t other = inv[pos];
+      const float dist = kmo_distance(metric, x, samples + (size_t)other * D, D);
+      if (dist <= mndist) { push_sample(k, dist, other, heap); mndist = heap[0]; }
+    }
+  }
+  for (int i = (int)k - 1; i >= 0; i--) {
+    neighbors[i] = ((uint32_t *)heap)[1];
+    if (distances) distances[i] = heap[0];
+    push_sample(k, -1.f, UINT32_MAX, heap);
+  }
+  return calced;
+}
+
+/* The corpus side of a search: CSR, radii, centroid distances (kmcuda.cc:648-691, knn.cu:19-131) */
+typedef struct { uint32_t *inv, *offsets; float *radiuses, *cdist; } knn_corpus_t;
+static void knn_corpus_init(knn_corpus_t *p, int metric, uint32_t N, uint32_t D, uint32_t K, const float *samples,
+                            const float *centroids, const uint32_t *assignments) {
+  p->inv = (uint32_t *)malloc(sizeof(uint32_t) * N);
+  p->offsets = (uint32_t *)malloc(sizeof(uint32_t) * (K + 2));
+  p->radiuses = (float *)malloc(sizeof(float) * K);
+  p->cdist = (float *)malloc(sizeof(float) * (size_t)K * K);
+  kmo_knn_inverse(N, K, assignments, p->inv, p->offsets);
+  kmo_knn_radiuses(metric, N, D, K, samples, centroids, p->inv, p->offsets, p->radiuses);
+  kmo_knn_cluster_distances(metric, D, K, centroids, p->cdist);
+}
+static void knn_corpus_free(knn_corpus_t *p) { free(p->inv); free(p->offsets); free(p->radiuses); free(p->cdist); }
+
 int kmo_knn(uint32_t k, int metric, uint32_t N, uint32_t D, uint32_t K, const float *samples,
             const float *centroids, const uint32_t *assignments, uint32_t *neighbors,
             uint64_t *dists_calced) {
   if (k == 0 || K < 2 || D == 0 || N < K) return 1;
-  uint32_t *inv = (uint32_t *)malloc(sizeof(uint32_t) * N);
-  uint32_t *offsets = (uint32_t *)malloc(sizeof(uint32_t) * (K + 2));
-  float *radiuses = (float *)malloc(sizeof(float) * K);
-  float *cdist = (float *)malloc(sizeof(float) * (size_t)K * K);
-  kmo_knn_inverse(N, K, assignments, inv, offsets);
-  kmo_knn_radiuses(metric, N, D, K, samples, centroids, inv, offsets, radiuses);
-  kmo_knn_cluster_distances(metric, D, K, centroids, cdist);
+  knn_corpus_t p;
+  knn_corpus_init(&p, metric, N, D, K, samples, centroids, assignments);
   uint64_t calced = 0;
 #pragma omp parallel for schedule(dynamic, 16) reduction(+ : calced)
   for (uint32_t s = 0; s < N; s++) {
@@ -1194,37 +1242,40 @@ int kmo_knn(uint32_t k, int metric, uint32_t N, uint32_t D, uint32_t K, const fl
       continue;
     }
     float *heap = (float *)malloc(sizeof(float) * 2 * k);
-    const float *x = samples + (size_t)s * D;
-    const float mydist = kmo_distance(metric, x, centroids + (size_t)mycls * D, D);
-    float mndist = FLT_MAX;
-    for (uint32_t i = 0; i < k; i++) { heap[2 * i] = FLT_MAX; ((uint32_t *)heap)[2 * i + 1] = 0; }
-    calced += offsets[mycls + 1] - offsets[mycls];
-    for (uint32_t pos = offsets[mycls]; pos < offsets[mycls + 1]; pos++) {
-      const uint32_t other = inv[pos];
-      if (other == s) continue;
-      const float dist = kmo_distance(metric, x, samples + (size_t)other * D, D);
-      if (dist <= mndist) { push_sample(k, dist, other, heap); mndist = heap[0]; }
-    }
-    for (uint32_t cls = 0; cls < K; cls++) {
-      if (cls == mycls) continue;
-      const float cd = cdist[(size_t)cls * K + mycls];
-      if (cd != cd) continue;
-      const float lim = cd - mydist - radiuses[cls];
-      if (lim > mndist) continue;
-      calced += offsets[cls + 1] - offsets[cls];
-      for (uint32_t pos = offsets[cls]; pos < offsets[cls + 1]; pos++) {
-        const uint32_t other = inv[pos];
-        const float dist = kmo_distance(metric, x, samples + (size_t)other * D, D);
-        if (dist <= mndist) { push_sample(k, dist, other, heap); mndist = heap[0]; }
-      }
-    }
-    for (int i = (int)k - 1; i >= 0; i--) {
-      neighbors[(size_t)s * k + i] = ((uint32_t *)heap)[1];
-      push_sample(k, -1.f, UINT32_MAX, heap);
-    }
+    calced += knn_search_row(k, metric, D, K, samples, centroids, samples + (size_t)s * D, mycls, s, p.inv, p.offsets,
+                             p.radiuses, p.cdist, heap, neighbors + (size_t)s * k, NULL);
     free(heap);
   }
   if (dists_calced) *dists_calced = calced;
-  free(inv); free(offsets); free(radiuses); free(cdist);
+  knn_corpus_free(&p);
+  return 0;
+}
+
+/* k-NN of rows that are NOT in the corpus (this repository's index, DESIGN.md 4.8 point 2): the list of query q is
+ * what the search above gives for q as one more row of cluster query_assignments[q], nothing skipped; distances = the
+ * values the heap compared (FLT_MAX in the slots no candidate filled, whose index is 0).  A query with a non-finite
+ * feature or a cluster id >= K has no cluster: indices UINT32_MAX, distances NaN. */
+int kmo_knn_query(uint32_t k, int metric, uint32_t N, uint32_t D, uint32_t K, const float *samples,
+                  const float *centroids, const uint32_t *assignments, uint32_t Q, const float *queries,
+                  const uint32_t *query_assignments, uint32_t *neighbors, float *distances) {
+  if (k == 0 || K == 0 || D == 0 || N == 0) return 1;
+  knn_corpus_t p;
+  knn_corpus_init(&p, metric, N, D, K, samples, centroids, assignments);
+#pragma omp parallel for schedule(dynamic, 16)
+  for (uint32_t q = 0; q < Q; q++) {
+    const float *x = queries + (size_t)q * D;
+    uint32_t mycls = query_assignments[q];
+    for (uint32_t f = 0; f < D; f++)
+      if (!(x[f] - x[f] == 0.f)) mycls = K;
+    if (mycls >= K) {
+      for (uint32_t i = 0; i < k; i++) { neighbors[(size_t)q * k + i] = UINT32_MAX; distances[(size_t)q * k + i] = NAN; }
+      continue;
+    }
+    float *heap = (float *)malloc(sizeof(float) * 2 * k);
+    knn_search_row(k, metric, D, K, samples, centroids, x, mycls, UINT32_MAX, p.inv, p.offsets, p.radiuses, p.cdist, heap,
+                   neighbors + (size_t)q * k, distances + (size_t)q * k);
+    free(heap);
+  }
+  knn_corpus_free(&p);
   return 0;
 }

@@ -114,6 +114,13 @@ void kmo_knn_cluster_distances(int metric, uint32_t D, uint32_t K, const float *
 int kmo_knn(uint32_t k, int metric, uint32_t N, uint32_t D, uint32_t K, const float *samples,
             const float *centroids, const uint32_t *assignments, uint32_t *neighbors,
             uint64_t *dists_calced);
+/* k-NN of Q rows that are not in the corpus (this repository's index; DESIGN.md 4.8 point 2 in plain C): kmo_knn's
+ * search for the query as one more row of cluster query_assignments[q], without the self-skip; neighbors and distances
+ * are Q x k, distances the values the heap compared (unfilled slots: index 0, FLT_MAX).  A query with a non-finite
+ * feature or a cluster id >= K: indices UINT32_MAX, distances NaN. */
+int kmo_knn_query(uint32_t k, int metric, uint32_t N, uint32_t D, uint32_t K, const float *samples,
+                  const float *centroids, const uint32_t *assignments, uint32_t Q, const float *queries,
+                  const uint32_t *query_assignments, uint32_t *neighbors, float *distances);
 
 #ifdef __cplusplus
 }

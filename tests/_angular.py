@@ -27,19 +27,21 @@ def assert_only_acos_matters(x, c, got, ref, what="", max_fraction=2e-3):
     return int(bad.size)
 
 
-def assert_knn_only_acos_matters(x, got, ref, what=""):
-    """got / ref: k-NN lists of the rows x (device / oracle).  An entry may differ only where the two lists' oracle
+def assert_knn_only_acos_matters(x, got, ref, what="", queries=None):
+    """got / ref: k-NN lists of the rows x (device / oracle); with `queries`, the lists of those rows among the rows x
+    (row i of got / ref belongs to queries[i]).  An entry may differ only where the two lists' oracle
     distances, each list in sorted order, agree within 2 float32 ulp at that slot.  Every other entry is equal.  (Unlike
     an assignment, a tie at the clamp's 0 is no exception here: which clusters a query visits depends on the acos of the
     centroid distances and radii, and a candidate at the heap's top distance is pushed when visited.)  Returns the
     number of rows that differ."""
     x = numpy.asarray(x, dtype=numpy.float32)
+    q = x if queries is None else numpy.asarray(queries, dtype=numpy.float32)
     got, ref = numpy.asarray(got), numpy.asarray(ref)
     rows = numpy.nonzero((got != ref).any(axis=1))[0]
     for i in rows:
         assert (got[i] < len(x)).all() and (ref[i] < len(x)).all(), (what, int(i), got[i], ref[i])
-        dg = numpy.sort([oracle.distance(x[i], x[j], metric=oracle.COS) for j in got[i]]).astype(numpy.float32)
-        dr = numpy.sort([oracle.distance(x[i], x[j], metric=oracle.COS) for j in ref[i]]).astype(numpy.float32)
+        dg = numpy.sort([oracle.distance(q[i], x[j], metric=oracle.COS) for j in got[i]]).astype(numpy.float32)
+        dr = numpy.sort([oracle.distance(q[i], x[j], metric=oracle.COS) for j in ref[i]]).astype(numpy.float32)
         for s in numpy.nonzero(got[i] != ref[i])[0]:
             assert abs(dg[s] - dr[s]) <= 2 * numpy.spacing(max(dg[s], dr[s])), \
                 "%s: row %d slot %d: distances %r / %r are not a last-place matter" % (what, i, s, dg, dr)
