@@ -301,6 +301,30 @@ int kmamd_knn_index_query(kmamd_knn_index *ix, uint32_t k, uint32_t n_queries, c
                           uint32_t *query_assignments_out, int32_t device_ptrs);
 void kmamd_knn_index_destroy(kmamd_knn_index *ix);
 
+/* Radius search on the same index: the hits of a query are the corpus rows that have a cluster
+ * (assignment < clusters) and whose distance to it is <= radius -- the exact distance kmamd_knn_index_query returns and
+ * compares (L2 distance / the angular metric's acos value; a NaN distance is no hit; a query with a NaN or inf feature
+ * has none).  The result is the brute-force set over the clustered rows, in ascending (cluster id, corpus row index)
+ * order, whatever query_assignments say (they only group the queries and feed the cluster prune) and however the batch
+ * is chunked.  radius: float32, finite, >= 0 (else InvalidArguments).  Two stateless, synchronous calls; the caller
+ * owns all memory and the search runs once in each:
+ *   count    counts[q] = number of hits (n_queries).  query_assignments / query_assignments_out as in query.
+ *   fill     offsets: n_queries + 1 non-decreasing positions (the exclusive prefix sum of the counts); query q's hits
+ *            go to [offsets[q], offsets[q + 1]) of neighbors (corpus row indices) and distances (optional).
+ *            InvalidArguments before anything is written if offsets decreases somewhere; InvalidArguments after the
+ *            search if a query's hit count differs from its range -- nothing has been written outside the ranges.
+ * Buffers and device_ptrs as in query (-1: host; else the index's device, all of the call's buffers).  n_queries == 0
+ * is success.  KMCUDA_AMD_KNN_QUERY_CHUNK applies (default: a chunk's centroid bounds within 4 GiB; with host buffers a
+ * chunk's range of hits is staged on the device within 4 GiB more).  KMCUDA_AMD_KNN_EXACT, KMCUDA_AMD_FP16_STRICT and
+ * KMCUDA_AMD_FILTER=f32 take the exact radius kernel (there is no f32-filtered one); KMCUDA_AMD_KNN_TIGHT does not
+ * apply (the per-query centroid bounds are the prune test); KMCUDA_AMD_KNN_STATS prints the search's counters. */
+int kmamd_knn_index_radius_count(kmamd_knn_index *ix, float radius, uint32_t n_queries, const void *queries,
+                                 const uint32_t *query_assignments, uint32_t *counts,
+                                 uint32_t *query_assignments_out, int32_t device_ptrs);
+int kmamd_knn_index_radius_fill(kmamd_knn_index *ix, float radius, uint32_t n_queries, const void *queries,
+                                const uint32_t *query_assignments, const uint64_t *offsets /* n_queries + 1 */,
+                                uint32_t *neighbors, float *distances /* optional */, int32_t device_ptrs);
+
 /* host -> raw device pointer copy on `device` (what python.cc:330-345 does with cudaMemcpy for imported
  * centroids in device-pointer mode; lets a binding without a HIP runtime of its own fill caller-owned memory). */
 int kmamd_copy_to_device(int device, void *dst, const void *host_src, size_t bytes);

@@ -4,7 +4,8 @@ Drop-in surface (mirrors the reference's `libKMCUDA` Python module, src/python.c
     from kmcuda_amd import kmeans_cuda, knn_cuda, supports_fp16
 Step-level surface for row-sharded multi-process operation: kmcuda_amd.engine.Engine,
 kmcuda_amd.distributed.
-k-NN of new rows against a clustered corpus (beyond the reference): KnnIndex, knn_query.
+k-NN of new rows against a clustered corpus (beyond the reference): KnnIndex, knn_query; radius search on
+the same index: KnnIndex.query_radius, knn_query_radius.
 """
 from .api import kmeans_cuda, knn_cuda, supports_fp16  # noqa: F401
-from .knn_index import KnnIndex, knn_query  # noqa: F401
+from .knn_index import KnnIndex, knn_query, knn_query_radius  # noqa: F401

@@ -459,6 +459,31 @@ hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks,
 hipError_t launch_knn_scatter(const uint32_t *sorted_out, const uint32_t *inv, uint32_t p_base, uint32_t p_end,
                               uint32_t k, uint32_t *neighbors, hipStream_t st);
 
+// knn_radius.hip -- radius search of a query batch (kmamd_knn_index_radius_*).  `a` is the query mode's
+// KnnArgs (heaps / out / outd / k unread).  Query i of the chunk (caller's order; qinv: sorted query position -> i)
+// gets counts[i], or its hits at [offsets[i], offsets[i + 1]) of neighbors / distances, both addressed relative to
+// out_base (the chunk's staged range starts there; 0: the caller's own buffers).
+struct KnnRadiusArgs {
+  KnnArgs a;
+  float radius;
+  // the triangle prune's margin where a.lb is null: prune_abs + prune_rel * (C + d + R); prune_abs = inf: no prune
+  float prune_abs, prune_rel;
+  const uint32_t *qinv;
+  uint32_t *counts;           // count form
+  const uint64_t *offsets;    // fill form: n + 1 entries, non-decreasing
+  uint64_t out_base;
+  uint32_t *neighbors;
+  float *distances;           // optional
+  uint32_t *flag;             // fill form: |= 1 if a query's hit count differs from its range
+};
+hipError_t launch_knn_radius_f16(int metric, const KnnRadiusArgs &ra, uint32_t nblocks, bool fill, hipStream_t st);
+// every sorted query position of [a.p_base, a.p_end), the queries without a cluster included (no hits)
+hipError_t launch_knn_radius_exact(int metric, const KnnRadiusArgs &ra, bool strict_h2, bool fill, hipStream_t st);
+// the queries of [a.p_base, a.p_end) the f16 kernel's block plan leaves out (no cluster): count 0 / an empty range
+hipError_t launch_knn_radius_rest(const KnnRadiusArgs &ra, bool fill, hipStream_t st);
+// *flag |= 1 if offsets[0 .. n] (device) decreases somewhere
+hipError_t launch_knn_radius_offsets_check(const uint64_t *offsets, uint32_t n, uint32_t *flag, hipStream_t st);
+
 // fp16x2 boundary conversions (seeding.hip)
 hipError_t launch_half_to_float(const void *src, size_t n, float *dst, hipStream_t st);
 hipError_t launch_float_to_half(const float *src, size_t n, void *dst, hipStream_t st);

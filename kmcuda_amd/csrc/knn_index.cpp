@@ -10,6 +10,7 @@
 // other clusters in ascending id under the triangle prune, push iff distance <= kth, output popped from the heap.  c_q
 // is its nearest centroid (kmamd_lloyd_assign's arithmetic and tie rule) unless the caller passes one; any cluster id
 // gives the same lists (the prune is rigorous), only the work differs.
+#include <math.h>
 #include <stdio.h>
 
 #include <memory>
@@ -63,79 +64,79 @@ class KnnIndex {
 
   int query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
             float *distances, uint32_t *qassign_out, int32_t device_ptrs);
+  int radius(bool fill, float r, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *counts,
+             uint32_t *qassign_out, const uint64_t *offsets, uint32_t *neighbors, float *distances, int32_t device_ptrs);
 };
 
-// One query batch, in chunks of at most `chunk` queries; every buffer is sized for one chunk and reused.
-int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
-                    float *distances, uint32_t *qassign_out, int32_t device_ptrs) {
-  if (Q == 0) return 0;
-  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
-  const uint32_t D = s.D, DP = s.DP, K = s.K;
-  const int metric = s.metric;
-  const hipStream_t st = s.stream;
-  const KnnSwitches sw = knn_switches();
-  size_t chunk = kQueryChunkBytes / (4 * ((size_t)K + 2 * (size_t)k));
-  if (sw.query_chunk) chunk = sw.query_chunk;   // test hook: queries per chunk
-  if (chunk < 1) chunk = 1;
-  const uint32_t Qc = (uint32_t)(chunk < Q ? chunk : Q);
-  const bool host = device_ptrs < 0;
-
-  // per-call buffers (freed with `w`), among them the sort scratch and the optional buffers of knn_search
-  KnnShard w;
-  w.dev = s.dev;
-  w.stream = nullptr;   // (enqueues on the index's stream; nothing to release)
+// The per-call buffers of a query batch (sized for one chunk of at most Qc queries, reused by every chunk) and the
+// preparation of a chunk, shared by query() and the radius calls: upload and half widening, the queries' clusters,
+// the CSR of the chunk, the cluster-sorted rows with their norms and member distances, the f16 split and the block plan.
+struct QueryChunk {
+  KnnShard w;   // owns the buffers; enqueues on the index's stream (nothing to release)
+  uint32_t Qc = 0;
   float *qrows = nullptr, *qxs = nullptr, *qn2p = nullptr, *qn2c = nullptr, *qmydist = nullptr, *qrdist = nullptr,
-        *qmux = nullptr, *qkbias = nullptr, *heaps = nullptr, *outd = nullptr, *dist_dev = nullptr;
+        *qmux = nullptr, *qkbias = nullptr;
   uint16_t *qhalf = nullptr, *qxs16 = nullptr;
   uint32_t *qassign = nullptr, *qprev = nullptr, *qeff = nullptr, *qinv = nullptr, *qoffsets = nullptr,
-           *qstats = nullptr, *blocks = nullptr, *out = nullptr, *nb_dev = nullptr;
-  KNN_TRY(w.alloc(&qrows, (size_t)Qc * D));
-  if (fp16) KNN_TRY(w.alloc(&qhalf, (size_t)Qc * D));
-  KNN_TRY(w.alloc(&qassign, Qc));
-  KNN_TRY(w.alloc(&qprev, Qc));
-  KNN_TRY(w.alloc(&qeff, Qc));
-  KNN_TRY(w.alloc(&qinv, Qc));
-  KNN_TRY(w.alloc(&qoffsets, (size_t)K + 2));
-  KNN_TRY(w.alloc(&w.scratch.keys_tmp, Qc));
-  KNN_TRY(w.alloc(&w.scratch.vals_tmp, Qc));
-  KNN_TRY(w.alloc(&w.scratch.keys_sorted, Qc));
-  KNN_TRY(w.alloc(&qstats, 4));
-  KNN_TRY(w.alloc(&qxs, (size_t)Qc * DP));
-  KNN_TRY(w.alloc(&qn2p, Qc));
-  KNN_TRY(w.alloc(&qmydist, Qc));
-  KNN_TRY(w.alloc(&qrdist, Qc));
-  if (path.use_f16) {
-    KNN_TRY(w.alloc(&qxs16, ((size_t)Qc + KNN16_PAD_ROWS) * DP));
-    KNN_TRY(w.alloc(&qn2c, Qc));
-    KNN_TRY(w.alloc(&qmux, Qc));
-    KNN_TRY(w.alloc(&qkbias, (size_t)Qc + KNN16_PAD_ROWS));
-  }
-  KNN_TRY(w.alloc(&heaps, (size_t)Qc * 2 * k));
-  KNN_TRY(w.alloc(&out, (size_t)Qc * k));
-  KNN_TRY(w.alloc(&outd, (size_t)Qc * k));
-  const size_t max_blocks = (size_t)Qc / 32 + K + 1;   // (every plan packs >= 32 queries per block but one per cluster)
-  KNN_TRY(w.alloc(&blocks, 2 * max_blocks));
-  if (host) {
-    KNN_TRY(w.alloc(&nb_dev, (size_t)Qc * k));
-    if (distances) KNN_TRY(w.alloc(&dist_dev, (size_t)Qc * k));
-  }
-  // radix sorts: the CSR of the chunk (keys <= K) and the query order (keys of up to 32 bits)
-  w.scratch.rows = Qc;
-  w.scratch.sort_bytes = sort_temp_bytes(Qc, 0xFFFFFFFFu);
-  char *sort_temp = nullptr;
-  KNN_TRY(w.alloc(&sort_temp, w.scratch.sort_bytes + 16));
-  w.scratch.sort_temp = sort_temp;
-  // the queries' clusters: the engine's assignment pass (kmamd_lloyd_assign; D > 256 through lloyd_wide), on fp32 rows
+           *qstats = nullptr, *blocks = nullptr;
   std::unique_ptr<Engine> eng;
-  if (!qassign_in) {
-    eng.reset(new Engine());
-    KNN_TRY(eng->init(s.dev, Qc, D, K, metric, 0, st));
+  std::vector<uint32_t> offs, plan;
+  // what prepare() found out about the chunk
+  KnnPath cp;
+  uint32_t assigned = 0;   // sorted positions >= assigned: queries without a cluster (NaN / inf features)
+
+  int init(const KnnIndex &ix, uint32_t Qc_, bool assign) {
+    const KnnShard &s = ix.s;
+    const uint32_t D = s.D, DP = s.DP, K = s.K;
+    Qc = Qc_;
+    w.dev = s.dev;
+    w.stream = nullptr;
+    KNN_TRY(w.alloc(&qrows, (size_t)Qc * D));
+    if (ix.fp16) KNN_TRY(w.alloc(&qhalf, (size_t)Qc * D));
+    KNN_TRY(w.alloc(&qassign, Qc));
+    KNN_TRY(w.alloc(&qprev, Qc));
+    KNN_TRY(w.alloc(&qeff, Qc));
+    KNN_TRY(w.alloc(&qinv, Qc));
+    KNN_TRY(w.alloc(&qoffsets, (size_t)K + 2));
+    KNN_TRY(w.alloc(&w.scratch.keys_tmp, Qc));
+    KNN_TRY(w.alloc(&w.scratch.vals_tmp, Qc));
+    KNN_TRY(w.alloc(&w.scratch.keys_sorted, Qc));
+    KNN_TRY(w.alloc(&qstats, 4));
+    KNN_TRY(w.alloc(&qxs, (size_t)Qc * DP));
+    KNN_TRY(w.alloc(&qn2p, Qc));
+    KNN_TRY(w.alloc(&qmydist, Qc));
+    KNN_TRY(w.alloc(&qrdist, Qc));
+    if (ix.path.use_f16) {
+      KNN_TRY(w.alloc(&qxs16, ((size_t)Qc + KNN16_PAD_ROWS) * DP));
+      KNN_TRY(w.alloc(&qn2c, Qc));
+      KNN_TRY(w.alloc(&qmux, Qc));
+      KNN_TRY(w.alloc(&qkbias, (size_t)Qc + KNN16_PAD_ROWS));
+    }
+    const size_t max_blocks = (size_t)Qc / 32 + K + 1;   // (every plan packs >= 32 queries per block but one per cluster)
+    KNN_TRY(w.alloc(&blocks, 2 * max_blocks));
+    // radix sorts: the CSR of the chunk (keys <= K) and the query order (keys of up to 32 bits)
+    w.scratch.rows = Qc;
+    w.scratch.sort_bytes = sort_temp_bytes(Qc, 0xFFFFFFFFu);
+    char *sort_temp = nullptr;
+    KNN_TRY(w.alloc(&sort_temp, w.scratch.sort_bytes + 16));
+    w.scratch.sort_temp = sort_temp;
+    // the queries' clusters: the engine's assignment pass (kmamd_lloyd_assign; D > 256 through lloyd_wide), on fp32 rows
+    if (assign) {
+      eng.reset(new Engine());
+      KNN_TRY(eng->init(s.dev, Qc, D, K, s.metric, 0, s.stream));
+    }
+    offs.resize((size_t)K + 1);
+    return 0;
   }
-  std::vector<uint32_t> offs(K + 1), plan;
-  for (uint32_t q0 = 0; q0 < Q; q0 += Qc) {
-    const uint32_t n = Q - q0 < Qc ? Q - q0 : Qc;
+
+  // queries [q0, q0 + n) of the batch; waits for the stream once (the CSR offsets and the flags reach the host)
+  int prepare(const KnnIndex &ix, uint32_t q0, uint32_t n, const void *queries, const uint32_t *qassign_in,
+              uint32_t *qassign_out, bool host) {
+    const KnnShard &s = ix.s;
+    const uint32_t D = s.D, DP = s.DP, K = s.K;
+    const hipStream_t st = s.stream;
     // ---- the chunk's rows, fp32 on this device ----
-    if (fp16) {
+    if (ix.fp16) {
       const uint16_t *src = static_cast<const uint16_t *>(queries) + (size_t)q0 * D;
       KMX_HIPCP(hipMemcpyAsync(qhalf, src, (size_t)n * D * sizeof(uint16_t), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
       KMX_HIPRT(launch_half_to_float(qhalf, (size_t)n * D, qrows, st));
@@ -148,7 +149,7 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
       KMX_HIPCP(hipMemcpyAsync(qassign, qassign_in + q0, (size_t)n * sizeof(uint32_t),
                                host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
     } else {
-      // (rows [n, Qc) of a last, shorter chunk hold the previous chunk's rows: assigned and ignored)
+      // (rows [n, Qc) of a shorter chunk hold an earlier chunk's rows, or radius()'s zeros: assigned and ignored)
       KMX_HIPRT(hipMemsetAsync(qassign, 0, (size_t)Qc * sizeof(uint32_t), st));
       KNN_TRY(eng->lloyd_assign(qrows, s.centroids, qassign, qprev, false));
     }
@@ -161,8 +162,8 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
     KMX_HIPRT(launch_inverse_assignments(qeff, n, K, w.scratch.keys_tmp, w.scratch.vals_tmp, w.scratch.keys_sorted, qinv, qoffsets, w.scratch.sort_temp,
                                          w.scratch.sort_bytes, st));
     // (with mu: the queries raise the half-range flag qstats[1] as the corpus rows do)
-    KMX_HIPRT(launch_knn_gather(qrows, n, D, DP, qinv, qxs, qn2p, qstats, path.use_f16 ? s.mu : nullptr, qoffsets, K, st));
-    KMX_HIPRT(launch_knn_member(metric, qxs, n, D, DP, qoffsets, K, s.centroids, qmydist, qrdist, path.strict_h2, st));
+    KMX_HIPRT(launch_knn_gather(qrows, n, D, DP, qinv, qxs, qn2p, qstats, ix.path.use_f16 ? s.mu : nullptr, qoffsets, K, st));
+    KMX_HIPRT(launch_knn_member(s.metric, qxs, n, D, DP, qoffsets, K, s.centroids, qmydist, qrdist, ix.path.strict_h2, st));
     uint32_t flags[4] = {0, 0, 0, 0};
     KMX_HIPCP(hipMemcpyAsync(offs.data(), qoffsets, (K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KMX_HIPCP(hipMemcpyAsync(flags, qstats, sizeof(flags), hipMemcpyDeviceToHost, st));
@@ -170,30 +171,82 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
     if (flags[2]) return kmcudaInvalidArguments;   // a caller-supplied cluster id >= K or with a non-finite centroid
     // which search this chunk takes: a query that leaves the half range sends it from the f16 filter to the f32 one
     // (D <= 256) or to the exact search, as a corpus row sends knn_cuda()
-    KnnPath cp = path;
-    if (knn_leaves_half_range(&cp.use_f16, &cp.dp_filter, D, flags[1]) && verbosity > 0)
+    cp = ix.path;
+    if (knn_leaves_half_range(&cp.use_f16, &cp.dp_filter, D, flags[1]) && ix.verbosity > 0)
       printf("k-NN query: a centred query leaves the half range, %s\n",
              cp.dp_filter ? "the f32 matrix-core filter" : "the exact search");
-    const bool f16 = cp.use_f16;
-    if (f16) KMX_HIPRT(launch_knn_split(metric, qxs, n, D, DP, s.mu, qxs16, qn2c, qmux, qkbias, qstats + 3, st));
-    const uint32_t assigned = offs[K];   // positions >= assigned: queries without a cluster (NaN / inf features)
-    knn_block_plan(offs.data(), K, knn_qpb(f16, DP), &plan);
+    if (cp.use_f16) KMX_HIPRT(launch_knn_split(s.metric, qxs, n, D, DP, s.mu, qxs16, qn2c, qmux, qkbias, qstats + 3, st));
+    assigned = offs[K];
+    knn_block_plan(offs.data(), K, knn_qpb(cp.use_f16, DP), &plan);
     if (!plan.empty())
       KMX_HIPCP(hipMemcpyAsync(blocks, plan.data(), plan.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    return 0;
+  }
+
+  // the query side of a search launch over this chunk
+  void fill_args(KnnArgs *a) const {
+    a->blocks = blocks;
+    a->p_base = 0;
+    a->qxs = qxs; a->qn2s = cp.use_f16 ? qn2c : qn2p; a->qmux = qmux; a->qmydist = qmydist; a->qxs16 = qxs16; a->qoffsets = qoffsets;
+  }
+};
+
+// KMCUDA_AMD_KNN_STATS: what the searches of a radius call did (KnnArgs::calced), then the counters start over
+int report_stats(const KnnIndex &ix, const char *what) {
+  unsigned long long cs[KNN_STATS] = {0, 0, 0, 0, 0};
+  KMX_HIPCP(hipMemcpy(cs, ix.s.calced, sizeof(cs), hipMemcpyDeviceToHost));
+  printf("k-NN index %s: %llu pairs in visited clusters, %llu scored on the matrix cores (%llu of them live query x "
+         "real candidate; %llu by operand sets with a visiting query), %llu exact chains\n", what, cs[0], cs[1], cs[2],
+         cs[4], cs[3]);
+  fflush(stdout);
+  KMX_HIPRT(hipMemset(ix.s.calced, 0, sizeof(cs)));
+  return 0;
+}
+
+// One query batch, in chunks of at most `chunk` queries; every buffer is sized for one chunk and reused.
+int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
+                    float *distances, uint32_t *qassign_out, int32_t device_ptrs) {
+  if (Q == 0) return 0;
+  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
+  const uint32_t K = s.K;
+  const hipStream_t st = s.stream;
+  const KnnSwitches sw = knn_switches();
+  size_t chunk = kQueryChunkBytes / (4 * ((size_t)K + 2 * (size_t)k));
+  if (sw.query_chunk) chunk = sw.query_chunk;   // test hook: queries per chunk
+  if (chunk < 1) chunk = 1;
+  const uint32_t Qc = (uint32_t)(chunk < Q ? chunk : Q);
+  const bool host = device_ptrs < 0;
+
+  // per-call buffers (freed with `c`), among them the sort scratch and the optional buffers of knn_search
+  QueryChunk c;
+  KNN_TRY(c.init(*this, Qc, !qassign_in));
+  KnnShard &w = c.w;
+  float *heaps = nullptr, *outd = nullptr, *dist_dev = nullptr;
+  uint32_t *out = nullptr, *nb_dev = nullptr;
+  KNN_TRY(w.alloc(&heaps, (size_t)Qc * 2 * k));
+  KNN_TRY(w.alloc(&out, (size_t)Qc * k));
+  KNN_TRY(w.alloc(&outd, (size_t)Qc * k));
+  if (host) {
+    KNN_TRY(w.alloc(&nb_dev, (size_t)Qc * k));
+    if (distances) KNN_TRY(w.alloc(&dist_dev, (size_t)Qc * k));
+  }
+  for (uint32_t q0 = 0; q0 < Q; q0 += Qc) {
+    const uint32_t n = Q - q0 < Qc ? Q - q0 : Qc;
+    KNN_TRY(c.prepare(*this, q0, n, queries, qassign_in, qassign_out, host));
     // unassigned queries: indices 0xFFFFFFFF, distances NaN (the filters leave their slots alone)
     KMX_HIPRT(hipMemsetAsync(out, 0xFF, (size_t)n * k * sizeof(uint32_t), st));
     KMX_HIPRT(hipMemsetAsync(outd, 0xFF, (size_t)n * k * sizeof(float), st));
     KnnArgs a;
-    a.blocks = blocks; a.k = k; a.heaps = heaps; a.out = out; a.outd = outd;
-    a.p_base = 0; a.p_end = cp.dp_filter ? assigned : n;   // (the exact kernel also fills the unassigned queries)
-    a.qxs = qxs; a.qn2s = f16 ? qn2c : qn2p; a.qmux = qmux; a.qmydist = qmydist; a.qxs16 = qxs16; a.qoffsets = qoffsets;
-    KNN_TRY(knn_search(s, w.scratch, a, cp, sw, (uint32_t)(plan.size() / 2), false, verbosity));
+    c.fill_args(&a);
+    a.k = k; a.heaps = heaps; a.out = out; a.outd = outd;
+    a.p_end = c.cp.dp_filter ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
+    KNN_TRY(knn_search(s, w.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity));
     // ---- back in query order ----
     uint32_t *nb = host ? nb_dev : neighbors + (size_t)q0 * k;
-    KMX_HIPRT(launch_knn_scatter(out, qinv, 0, n, k, nb, st));
+    KMX_HIPRT(launch_knn_scatter(out, c.qinv, 0, n, k, nb, st));
     if (distances) {
       float *dd = host ? dist_dev : distances + (size_t)q0 * k;
-      KMX_HIPRT(launch_knn_scatter(reinterpret_cast<const uint32_t *>(outd), qinv, 0, n, k, reinterpret_cast<uint32_t *>(dd), st));
+      KMX_HIPRT(launch_knn_scatter(reinterpret_cast<const uint32_t *>(outd), c.qinv, 0, n, k, reinterpret_cast<uint32_t *>(dd), st));
     }
     if (host) {
       KMX_HIPCP(hipMemcpyAsync(neighbors + (size_t)q0 * k, nb_dev, (size_t)n * k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -207,6 +260,178 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
     return kmcudaRuntimeError;
   }
   return 0;
+}
+
+// Radius search of one query batch: counts (fill = false) or the hits at the caller's CSR offsets.
+// Chunked as query(); a chunk's lb table (L2, up to 1024 features: the prune test) stays within kQueryChunkBytes.
+int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *counts,
+                     uint32_t *qassign_out, const uint64_t *offsets, uint32_t *neighbors, float *distances,
+                     int32_t device_ptrs) {
+  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
+  const uint32_t D = s.D, DP = s.DP, K = s.K;
+  const int metric = s.metric;
+  const hipStream_t st = s.stream;
+  const KnnSwitches sw = knn_switches();
+  const bool host = device_ptrs < 0;
+  size_t chunk = kQueryChunkBytes / (4 * (size_t)K);
+  if (sw.query_chunk) chunk = sw.query_chunk;
+  if (chunk < 1) chunk = 1;
+  const uint32_t Qc = (uint32_t)(chunk < Q ? chunk : Q);
+
+  KnnShard own;   // this call's own device buffers
+  own.dev = s.dev;
+  own.stream = nullptr;
+  uint32_t *flag = nullptr, *counts_dev = nullptr;
+  uint64_t *offsets_dev = nullptr;
+  KNN_TRY(own.alloc(&flag, 1));
+  KMX_HIPRT(hipMemsetAsync(flag, 0, sizeof(uint32_t), st));
+  auto flag_raised = [&](bool *raised) -> int {
+    uint32_t f = 0;
+    KMX_HIPCP(hipMemcpyAsync(&f, flag, sizeof(f), hipMemcpyDeviceToHost, st));
+    KMX_HIPRT(hipStreamSynchronize(st));
+    *raised = f != 0;
+    return 0;
+  };
+  // ---- fill: the offsets must not decrease, checked before anything is written ----
+  if (fill) {
+    if (host) {
+      for (uint32_t i = 0; i < Q; i++)
+        if (offsets[i] > offsets[i + 1]) return kmcudaInvalidArguments;
+      KNN_TRY(own.alloc(&offsets_dev, (size_t)Qc + 1));
+    } else {
+      KMX_HIPRT(launch_knn_radius_offsets_check(offsets, Q, flag, st));
+      bool raised = false;
+      KNN_TRY(flag_raised(&raised));
+      if (raised) return kmcudaInvalidArguments;
+    }
+  } else if (host) {
+    KNN_TRY(own.alloc(&counts_dev, Qc));
+  }
+  // host buffers: one chunk's CSR range is staged on the device, within this budget (a chunk is split until it fits)
+  const size_t hit_bytes = sizeof(uint32_t) + (distances ? sizeof(float) : 0);
+  struct Staging {
+    void *nb = nullptr, *dist = nullptr;
+    uint64_t cap = 0;
+    ~Staging() { (void)hipFree(nb); (void)hipFree(dist); }
+  } stage;
+
+  QueryChunk c;
+  KNN_TRY(c.init(*this, Qc, !qassign_in));
+  // (a fill's first chunk may be shorter than Qc, and the assignment pass reads Qc rows: defined values for them)
+  if (fill && host && !qassign_in) KMX_HIPRT(hipMemsetAsync(c.qrows, 0, (size_t)Qc * D * sizeof(float), st));
+  // the cluster prune: the lb table (L2, D <= 1024, rows the bounds kernel can read four features at a time), else
+  // the triangle test with a margin for the rounding of its computed terms; the half2 arithmetic's
+  // distances carry half-precision errors no such margin covers: nothing is pruned there
+  const bool use_lb = metric == 0 && D <= 1024 && (DP & 3u) == 0 && !path.strict_h2;
+  // (tests/test_radius_bound_model.py restates these constants and reads them back from this file: change both)
+  float prune_abs = 0.f, prune_rel = 0.f;
+  if (path.strict_h2) {
+    prune_abs = INFINITY;
+  } else if (metric == 0) {
+    prune_rel = (float)(1e-5 + 4e-9 * (double)D);
+  } else {
+    // four computed angles, each acos of a product that is off by at most dp: |acos(a) - acos(b)| <= sqrt(2 |a - b|) * 1.01
+    const double dp = (fp16 ? 1.0e-3 : 1.0e-6) + 1.0e-8 * (double)D;
+    prune_abs = (float)(4.0 * 1.01 * sqrt(2.0 * dp));
+  }
+  if (use_lb && hipMalloc((void **)&c.w.scratch.lb, (size_t)K * Qc * sizeof(float)) != hipSuccess) {
+    c.w.scratch.lb = nullptr;
+    (void)hipGetLastError();
+    return kmcudaMemoryAllocationFailure;
+  }
+  if (use_lb && path.use_f16 && sw.order != 0 && hipMalloc((void **)&c.w.scratch.qperm, (size_t)Qc * sizeof(uint32_t)) != hipSuccess) {
+    c.w.scratch.qperm = nullptr;   // (the query order is an optimisation: sorted-position order without it)
+    (void)hipGetLastError();
+  }
+  if (sw.stats) KMX_HIPRT(hipMemsetAsync(s.calced, 0, KNN_STATS * sizeof(unsigned long long), st));
+
+  uint32_t n = 0;
+  for (uint32_t q0 = 0; q0 < Q; q0 += n) {
+    n = Q - q0 < Qc ? Q - q0 : Qc;
+    uint64_t range = 0;
+    if (fill && host) {
+      while (n > 1 && (offsets[q0 + n] - offsets[q0]) > kQueryChunkBytes / hit_bytes) n = (n + 1) / 2;
+      range = offsets[q0 + n] - offsets[q0];
+      if (range > stage.cap) {
+        (void)hipStreamSynchronize(st);   // (the copies out of the old buffers)
+        (void)hipFree(stage.nb); (void)hipFree(stage.dist);
+        stage.nb = stage.dist = nullptr;
+        stage.cap = 0;
+        if (hipMalloc(&stage.nb, range * sizeof(uint32_t)) != hipSuccess ||
+            (distances && hipMalloc(&stage.dist, range * sizeof(float)) != hipSuccess)) {
+          (void)hipGetLastError();
+          return kmcudaMemoryAllocationFailure;
+        }
+        stage.cap = range;
+      }
+    }
+    KNN_TRY(c.prepare(*this, q0, n, queries, qassign_in, qassign_out, host));
+    const bool f16 = c.cp.use_f16;   // (no f32-filtered radius kernel: that path takes the exact one)
+    KnnRadiusArgs ra;
+    KnnArgs &a = ra.a;
+    c.fill_args(&a);
+    a.k = 0; a.heaps = nullptr; a.out = nullptr; a.outd = nullptr;
+    a.p_end = f16 ? c.assigned : n;
+    a.xs = s.xs; a.n2s = f16 ? s.n2c : s.n2s; a.inv = s.inv; a.offsets = s.offsets; a.mydist = s.mydist; a.R = s.R;
+    a.C = s.C; a.stats = f16 ? s.stats_c : s.stats; a.N = s.N; a.D = D; a.DP = DP; a.K = K;
+    a.eps = (float)(1.02 * ((double)D + 12.0) * ldexp(1.0, -24));  // the filter's slack, as knn_search
+    a.calced = s.calced;
+    a.xs16 = s.xs16; a.mux = s.mux; a.kbias = s.kbias; a.mu2 = s.mu2;
+    if (use_lb && c.assigned) {
+      KMX_HIPRT(launch_knn_centroid_bounds(c.qxs, D, DP, 0, c.assigned, s.centroids, K, s.R, c.w.scratch.lb, c.assigned, st));
+      a.lb = c.w.scratch.lb;
+      a.lb_stride = c.assigned;
+      // queries that want the same clusters into the same waves, as knn_search orders them
+      if (f16 && c.w.scratch.qperm) {
+        KnnScratch &x = c.w.scratch;
+        if (launch_knn_query_order(x.lb, c.assigned, c.qoffsets, K, 0, c.assigned, x.keys_tmp, x.vals_tmp, x.keys_sorted,
+                                   x.qperm, x.sort_temp, x.sort_bytes, st, sw.order, c.qmydist, s.R))
+          a.qperm = x.qperm;
+        else
+          (void)hipGetLastError();
+      }
+    }
+    ra.radius = r; ra.prune_abs = prune_abs; ra.prune_rel = prune_rel;
+    ra.qinv = c.qinv;
+    ra.counts = host ? counts_dev : (counts ? counts + q0 : nullptr);
+    ra.offsets = nullptr; ra.out_base = 0; ra.neighbors = nullptr; ra.distances = nullptr; ra.flag = flag;
+    if (fill) {
+      if (host) {
+        KMX_HIPCP(hipMemcpyAsync(offsets_dev, offsets + q0, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        // (slots of a range the search does not fill -- the call then fails -- read 0xFF)
+        if (range) KMX_HIPRT(hipMemsetAsync(stage.nb, 0xFF, range * sizeof(uint32_t), st));
+        if (range && distances) KMX_HIPRT(hipMemsetAsync(stage.dist, 0xFF, range * sizeof(float), st));
+        ra.offsets = offsets_dev; ra.out_base = offsets[q0];
+        ra.neighbors = static_cast<uint32_t *>(stage.nb); ra.distances = static_cast<float *>(stage.dist);
+      } else {
+        ra.offsets = offsets + q0;
+        ra.neighbors = neighbors; ra.distances = distances;
+      }
+    }
+    if (f16) {
+      KMX_HIPRT(launch_knn_radius_f16(metric, ra, (uint32_t)(c.plan.size() / 2), fill, st));
+      KnnRadiusArgs rest = ra;
+      rest.a.p_base = c.assigned; rest.a.p_end = n;
+      KMX_HIPRT(launch_knn_radius_rest(rest, fill, st));
+    } else {
+      KMX_HIPRT(launch_knn_radius_exact(metric, ra, c.cp.strict_h2, fill, st));
+    }
+    if (host && !fill)
+      KMX_HIPCP(hipMemcpyAsync(counts + q0, counts_dev, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (host && fill && range) {
+      KMX_HIPCP(hipMemcpyAsync(neighbors + offsets[q0], stage.nb, range * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      if (distances)
+        KMX_HIPCP(hipMemcpyAsync(distances + offsets[q0], stage.dist, range * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    // (the next chunk overwrites these buffers: the stream orders it behind this one's kernels and copies)
+  }
+  bool raised = false;
+  if (flag_raised(&raised) != 0) {
+    if (verbosity > 0) printf("k-NN radius search failed: %s\n", hipGetErrorString(hipGetLastError()));
+    return kmcudaRuntimeError;
+  }
+  if (sw.stats) KNN_TRY(report_stats(*this, fill ? "radius fill" : "radius count"));
+  return raised ? kmcudaInvalidArguments : 0;   // a query's hit count differs from its range
 }
 
 }  // namespace
@@ -255,6 +480,34 @@ int kmamd_knn_index_query(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, co
   if (!queries || !neighbors) return kmcudaInvalidArguments;
   if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
   return ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs);
+}
+
+static bool radius_call_ok(kmamd_knn_index *h, float radius, int32_t device_ptrs) {
+  if (!h) return false;
+  if (!(radius >= 0.f) || radius > 3.402823466e+38f) return false;   // NaN, negative or infinite
+  return device_ptrs < 0 || device_ptrs == h->ix.s.dev;
+}
+
+int kmamd_knn_index_radius_count(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
+                                 const uint32_t *query_assignments, uint32_t *counts, uint32_t *query_assignments_out,
+                                 int32_t device_ptrs) {
+  if (!radius_call_ok(h, radius, device_ptrs)) return kmcudaInvalidArguments;
+  if (n_queries == 0) return kmcudaSuccess;
+  if (!queries || !counts) return kmcudaInvalidArguments;
+  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
+  return h->ix.radius(false, radius, n_queries, queries, query_assignments, counts, query_assignments_out, nullptr,
+                      nullptr, nullptr, device_ptrs);
+}
+
+int kmamd_knn_index_radius_fill(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
+                                const uint32_t *query_assignments, const uint64_t *offsets, uint32_t *neighbors,
+                                float *distances, int32_t device_ptrs) {
+  if (!radius_call_ok(h, radius, device_ptrs)) return kmcudaInvalidArguments;
+  if (n_queries == 0) return kmcudaSuccess;
+  if (!queries || !offsets || !neighbors) return kmcudaInvalidArguments;
+  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
+  return h->ix.radius(true, radius, n_queries, queries, query_assignments, nullptr, nullptr, offsets, neighbors,
+                      distances, device_ptrs);
 }
 
 void kmamd_knn_index_destroy(kmamd_knn_index *h) { delete h; }

@@ -8,7 +8,9 @@ batches against it on the same search kernels:
     neighbors, distances = index.query(queries, k)
     index.close()
 
-or, once, knn_query(k, samples, centroids, assignments, queries).  A query's list is what the reference's procedure
+or, once, knn_query(k, samples, centroids, assignments, queries).  index.query_radius(queries, radius) /
+knn_query_radius(...) answer the other question, "which rows lie within distance r", as a CSR (offsets, neighbors,
+distances) -- the brute-force set, not the outcome of a visiting procedure.  A query's list is what the reference's procedure
 gives for it as one more row of its cluster (its nearest centroid unless `query_assignments` says otherwise), WITHOUT
 skipping anything: own cluster first, then the others in ascending id under the triangle prune.
 
@@ -126,6 +128,40 @@ def _check_queries(queries, fp16, d, clusters, query_assignments, device):
     return q, nq, q_dev, qa
 
 
+def _check_radius(radius):
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, numpy.integer, numpy.floating)):
+        raise TypeError("\"radius\" must be a real number")
+    try:
+        with numpy.errstate(over="ignore"):
+            r = numpy.float32(radius)
+    except OverflowError:
+        r = numpy.float32(numpy.inf)
+    if not numpy.isfinite(r) or r < 0:
+        raise ValueError("\"radius\" must be finite in float32 and >= 0")
+    return float(r)
+
+
+def _check_radius_flags(return_distances, sort, count_only):
+    if sort and not count_only and not return_distances:
+        raise ValueError("\"sort\" orders by distance: it needs return_distances=True")
+
+
+def _sort_slices(offsets, neighbors, distances):
+    """Every query's slice reordered by (distance, row index)."""
+    if _is_torch(neighbors):
+        import torch
+        if neighbors.numel() == 0:
+            return neighbors, distances
+        q = torch.repeat_interleave(torch.arange(offsets.numel() - 1, device=neighbors.device), offsets[1:] - offsets[:-1])
+        order = torch.argsort(neighbors.to(torch.int64) & 0xFFFFFFFF, stable=True)
+        order = order[torch.argsort(distances[order], stable=True)]
+        order = order[torch.argsort(q[order], stable=True)]
+        return neighbors[order], distances[order]
+    q = numpy.repeat(numpy.arange(len(offsets) - 1), numpy.diff(offsets))
+    order = numpy.lexsort((neighbors, distances, q))
+    return neighbors[order], distances[order]
+
+
 def _ptr(x):
     return ctypes.c_void_p(x.data_ptr() if _is_torch(x) else x.ctypes.data)
 
@@ -171,6 +207,57 @@ class KnnIndex:
         out = (nb,) + ((dist,) if return_distances else ()) + ((asg,) if return_assignments else ())
         return out[0] if len(out) == 1 else out
 
+    def query_radius(self, queries, radius, query_assignments=None, return_distances=True, sort=False,
+                     count_only=False):
+        """The corpus rows within `radius` of every query row: the brute-force set over the rows that
+        have a cluster, by the exact distance query() returns.  count_only: counts (Q).  Else (offsets, neighbors[,
+        distances]): offsets int64 of Q + 1 entries, neighbors / distances flat of length offsets[-1], query i owning
+        [offsets[i]:offsets[i + 1]] in ascending (cluster id, row index) order, or by (distance, row index) with sort.
+        The search runs twice, once to count and once to fill; the queries' clusters are computed once."""
+        if not getattr(self, "h", None):
+            raise ValueError("the index is closed")
+        r = _check_radius(radius)
+        _check_radius_flags(return_distances, sort, count_only)
+        q, nq, q_dev, qa = _check_queries(queries, self.fp16, self.features, self.clusters, query_assignments,
+                                          self.device)
+        dptr = self.device if q_dev else -1
+        if q_dev:
+            import torch
+            dev = torch.device("cuda", self.device)
+            counts = torch.zeros((nq,), dtype=torch.int32, device=dev)
+            asg = torch.empty((nq,), dtype=torch.int32, device=dev) if qa is None else None
+        else:
+            counts = numpy.zeros((nq,), numpy.uint32)
+            asg = numpy.empty((nq,), numpy.uint32) if qa is None else None
+        if nq:
+            rc = self.lib.kmamd_knn_index_radius_count(self.h, r, nq, _ptr(q), _ptr(qa) if qa is not None else None,
+                                                       _ptr(counts), _ptr(asg) if asg is not None else None, dptr)
+            _raise_for(rc, "kmamd_knn_index_radius_count")
+        if count_only:
+            return counts
+        if qa is None:
+            qa = asg   # the fill groups the queries as the count did
+        if q_dev:
+            offsets = torch.zeros((nq + 1,), dtype=torch.int64, device=dev)
+            # (a count reads as a negative int32 from 2^31 on)
+            torch.cumsum(counts.to(torch.int64) & 0xFFFFFFFF, 0, out=offsets[1:])
+            total = int(offsets[-1])   # the one value that reaches the host
+            nb = torch.empty((total,), dtype=torch.int32, device=dev)
+            dist = torch.empty((total,), dtype=torch.float32, device=dev) if return_distances else None
+        else:
+            offsets = numpy.zeros((nq + 1,), numpy.int64)
+            numpy.cumsum(counts, out=offsets[1:])
+            total = int(offsets[-1])
+            nb = numpy.empty((total,), numpy.uint32)
+            dist = numpy.empty((total,), numpy.float32) if return_distances else None
+        if nq and total:
+            rc = self.lib.kmamd_knn_index_radius_fill(self.h, r, nq, _ptr(q), _ptr(qa), _ptr(offsets), _ptr(nb),
+                                                      _ptr(dist) if dist is not None else None, dptr)
+            _raise_for(rc, "kmamd_knn_index_radius_fill")
+        if sort:
+            nb, dist = _sort_slices(offsets, nb, dist)
+        return (offsets, nb, dist) if return_distances else (offsets, nb)
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.kmamd_knn_index_destroy(self.h)
@@ -200,3 +287,17 @@ def knn_query(k, samples, centroids, assignments, queries, metric="L2", device=0
     with KnnIndex(samples, centroids, assignments, metric=metric, device=device, verbosity=verbosity) as ix:
         return ix.query(queries, k, query_assignments=query_assignments, return_distances=return_distances,
                         return_assignments=return_assignments)
+
+
+def knn_query_radius(radius, samples, centroids, assignments, queries, metric="L2", device=0, query_assignments=None,
+                     return_distances=True, sort=False, count_only=False, verbosity=0):
+    """One-shot KnnIndex(samples, centroids, assignments, metric, device).query_radius(queries, radius, ...): every
+    argument is checked before the device is touched."""
+    _get_metric(metric)
+    _, _, _, fp16, n, d, clusters, _ = _check_corpus(samples, centroids, assignments, device)
+    _check_radius(radius)
+    _check_radius_flags(return_distances, sort, count_only)
+    _check_queries(queries, fp16, d, clusters, query_assignments, device)
+    with KnnIndex(samples, centroids, assignments, metric=metric, device=device, verbosity=verbosity) as ix:
+        return ix.query_radius(queries, radius, query_assignments=query_assignments,
+                               return_distances=return_distances, sort=sort, count_only=count_only)
