@@ -325,6 +325,49 @@ int kmamd_knn_index_radius_fill(kmamd_knn_index *ix, float radius, uint32_t n_qu
                                 const uint32_t *query_assignments, const uint64_t *offsets /* n_queries + 1 */,
                                 uint32_t *neighbors, float *distances /* optional */, int32_t device_ptrs);
 
+/* Assigns rows to GIVEN centroids -- the "predict" of a trained K-means (no counterpart in the reference, whose
+ * kmeans_cuda returns the assignments of the rows it was trained on only) -- with, as asked, the distance of every row
+ * to its centroid and per-cluster statistics.  Stateless and synchronous; the caller owns all memory.
+ *   metric, fp16x2     as kmeans_cuda: 0 L2 / 1 angular (rows expected at unit length, nothing is normalised); fp16x2 != 0:
+ *                      rows and centroids are IEEE halves, features_size counts halves and must be even (as
+ *                      kmamd_knn_index_create), fp32 arithmetic on the half values
+ *   device             ONE device id, as for the k-NN index (not kmeans_cuda's mask)
+ *   device_ptrs        -1: every buffer is on the host; else every buffer is on that device, which must be `device`
+ *   assignments[s]     what ONE kmamd_lloyd_assign pass leaves when every assignment starts at clusters_size: the
+ *                      nearest centroid in the reference's arithmetic (round-down-FMA Kahan dot, lloyd_distance), strict
+ *                      `<` in ascending centroid order (the lowest index wins a tie, a NaN centroid never wins);
+ *                      clusters_size -- "no cluster", what kmeans_cuda returns and the k-NN index accepts -- for a row
+ *                      whose first feature is NaN or whose distances are all NaN
+ *   distances[s]       optional: the reference's distance(row, centroid[assignments[s]]) (metric_abstraction.h:59-72 /
+ *                      :179-191, the per-sample term of kmeans_calc_average_distance), NaN for a row without a cluster
+ *                      (angular: the angle of the reference's Kahan product by the C library's acosf, restated on the
+ *                      device operation for operation -- the CPU oracle's bits; kmeans_cuda / the k-NN index take the
+ *                      device library's acosf, which can differ by one in the last place)
+ *   cluster_counts[c]  optional: the number of rows assigned to c
+ *   cluster_distance_sums[c]  optional: the fp64 sum of the float32 distances of the rows assigned to c (0.0 for an
+ *                      empty cluster; the distances are computed in scratch if they are not asked for).  No
+ *                      floating-point atomics: per chunk the members in ascending row order through a fixed reduction
+ *                      tree, the chunks added in chunk order -- two identical calls give identical bits; another chunk
+ *                      size may change the last places.
+ * clusters_size >= 2.  samples_size == 0 is success (counts and sums zero).  InvalidArguments before any device work,
+ * with the outputs untouched: bad sizes, null pointers, device_ptrs naming another device, and KMCUDA_AMD_FP16_STRICT=1
+ * with fp16x2 rows (the reference's half2 arithmetic has no predict form).  The rows go through in chunks whose staged
+ * fp32 copy stays within 4 GiB; env KMCUDA_AMD_ASSIGN_CHUNK=<rows> (tests) sets the chunk.  KMCUDA_AMD_FILTER=f32
+ * applies as to any engine.  KMCUDA_AMD_ASSIGN_DIST=member: the distance pass on kmeans_cuda's per-thread kernel
+ * (its instantiation with the acosf above) instead of the LDS-tiled one (the same bits; A/B runs). */
+int kmamd_kmeans_assign(int metric, uint32_t samples_size, uint16_t features_size, uint32_t clusters_size, int device,
+                        int32_t device_ptrs, int32_t fp16x2, int32_t verbosity, const void *samples,
+                        const void *centroids, uint32_t *assignments /* samples_size */,
+                        float *distances /* optional, samples_size */,
+                        uint32_t *cluster_counts /* optional, clusters_size */,
+                        double *cluster_distance_sums /* optional, clusters_size */);
+/* The distance pass of kmamd_kmeans_assign on its own, enqueued on hip_stream (device pointers on `device`, fp32):
+ * distances[s] = distance(row s, centroid assignments[s]), NaN where assignments[s] >= clusters (no centroid is read).
+ * KMCUDA_AMD_ASSIGN_DIST=member applies.  A window for tests and for timing the kernel (scripts/assign_bench.py). */
+int kmamd_assigned_distances(int metric, uint32_t n_rows, uint32_t features, uint32_t clusters, int device,
+                             const float *samples, const float *centroids, const uint32_t *assignments,
+                             float *distances, void *hip_stream);
+
 /* host -> raw device pointer copy on `device` (what python.cc:330-345 does with cudaMemcpy for imported
  * centroids in device-pointer mode; lets a binding without a HIP runtime of its own fill caller-owned memory). */
 int kmamd_copy_to_device(int device, void *dst, const void *host_src, size_t bytes);

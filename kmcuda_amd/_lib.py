@@ -25,6 +25,7 @@ EXPORTS = [
     "kmamd_reduce_apply", "kmamd_reduce_apply_stop", "kmamd_reduce_apply_prepare", "kmamd_stop_report", "kmamd_stop_clear", "kmamd_centroids_written", "kmamd_set_carry", "kmamd_carry_stats", "kmamd_carry_pair_stats", "kmamd_duo_rows", "kmamd_carry_policy_sim", "kmamd_set_update_mode", "kmamd_last_run_stats", "kmamd_last_run_collective", "kmamd_adjust_exact", "kmamd_yy_configure", "kmamd_yy_init", "kmamd_yy_drifts", "kmamd_yy_filters",
     "kmamd_knn_index_create", "kmamd_knn_index_query", "kmamd_knn_index_destroy",
     "kmamd_knn_index_radius_count", "kmamd_knn_index_radius_fill",
+    "kmamd_kmeans_assign", "kmamd_assigned_distances",
     "kmamd_copy_to_device", "kmamd_profile_reset", "kmamd_profile_read", "kmamd_profile_enable", "kmamd_filter_kind", "kmamd_build_arch",
 ]
 
@@ -146,6 +147,10 @@ def lib():
     L.kmamd_knn_index_radius_fill.argtypes = [vp, f32, u32, vp, vp, vp, vp, vp, i32]
     L.kmamd_knn_index_destroy.restype = None
     L.kmamd_knn_index_destroy.argtypes = [vp]
+    L.kmamd_kmeans_assign.restype = i32
+    L.kmamd_kmeans_assign.argtypes = [i32, u32, ctypes.c_uint16, u32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.kmamd_assigned_distances.restype = i32
+    L.kmamd_assigned_distances.argtypes = [i32, u32, u32, u32, i32, vp, vp, vp, vp, vp]
     L.kmamd_copy_to_device.restype = i32
     L.kmamd_copy_to_device.argtypes = [i32, vp, vp, ctypes.c_size_t]
     L.kmamd_build_arch.restype = ctypes.c_char_p

@@ -114,6 +114,63 @@ __device__ __forceinline__ float angular_from_prod(float fp) {
   return acosf(fp);
 }
 
+// acosf as the C library of the CPU side computes it (the oracle's acosf: glibc's flt-32 e_acosf.c, fdlibm's float
+// acos), operation for operation: fp32 +, -, *, / and sqrt only, each correctly rounded here as there (this family is
+// built with -ffp-contract=off).  A restatement in C equals that library's acosf on every float of [-1, 1]
+// (DESIGN_LOG 22.4).  angular_from_prod above keeps the device library's acosf, up to one last place away: what every
+// kernel of kmeans_cuda / knn_cuda / the k-NN index computes stays what it was; kmamd_kmeans_assign's distances use
+// this one (assign_dist.hip, member_distances_kernel<.., true>).
+//
+// The algorithm and its constants are fdlibm's e_acosf.c (float version by Ian Lance Taylor, Cygnus Support):
+// ====================================================
+// Copyright (C) 1993 by Sun Microsystems, Inc. All rights reserved.
+//
+// Developed at SunPro, a Sun Microsystems, Inc. business.
+// Permission to use, copy, modify, and distribute this
+// software is freely granted, provided that this notice
+// is preserved.
+// ====================================================
+__device__ __forceinline__ float acosf_fdlibm(float x) {
+  const float pi = 3.1415925026e+00f, pio2_hi = 1.5707962513e+00f, pio2_lo = 7.5497894159e-08f,
+              pS0 = 1.6666667163e-01f, pS1 = -3.2556581497e-01f, pS2 = 2.0121252537e-01f, pS3 = -4.0055535734e-02f,
+              pS4 = 7.9153501429e-04f, pS5 = 3.4793309169e-05f, qS1 = -2.4033949375e+00f, qS2 = 2.0209457874e+00f,
+              qS3 = -6.8828397989e-01f, qS4 = 7.7038154006e-02f;
+  const int32_t hx = (int32_t)__float_as_uint(x), ix = hx & 0x7fffffff;
+  if (ix == 0x3f800000) return hx > 0 ? 0.0f : pi + 2.0f * pio2_lo;   // |x| == 1
+  if (ix > 0x3f800000) return (x - x) / (x - x);                      // |x| > 1 or NaN: NaN
+  if (ix < 0x3f000000) {                                              // |x| < 0.5
+    if (ix <= 0x32800000) return pio2_hi + pio2_lo;                   // |x| <= 2^-26
+    const float z = x * x;
+    const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+    const float q = 1.0f + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+    const float r = p / q;
+    return pio2_hi - (x - (pio2_lo - x * r));
+  }
+  if (hx < 0) {                                                       // x < -0.5
+    const float z = (1.0f + x) * 0.5f;
+    const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+    const float q = 1.0f + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+    const float s = sqrtf(z), r = p / q;
+    const float w = r * s - pio2_lo;
+    return pi - 2.0f * (s + w);
+  }
+  const float z = (1.0f - x) * 0.5f;                                  // x > 0.5
+  const float s = sqrtf(z);
+  const float df = __uint_as_float(__float_as_uint(s) & 0xfffff000u);
+  const float c = (z - df * df) / (s + df);
+  const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+  const float q = 1.0f + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+  const float r = p / q;
+  const float w = r * s + c;
+  return 2.0f * (df + w);
+}
+// angular_from_prod with that acosf: bit for bit the oracle's cos_dist_from_prod
+__device__ __forceinline__ float angular_from_prod_libm(float fp) {
+  if (fp >= 1.f) return 0.f;
+  if (fp <= -1.f) return 3.14159265358979323846f;
+  return acosf_fdlibm(fp);
+}
+
 // Serial chains over contiguous vectors; 16-byte loads when both rows allow it (the chain order
 // is unchanged: the four elements of a load are folded in feature order).
 template <int METRIC>

@@ -294,7 +294,19 @@ hipError_t launch_afk_min_dist(int metric, uint32_t m, uint32_t k, const float *
                                const uint32_t *choices, const float *centroids, float *min_dists, hipStream_t st);
 hipError_t launch_member_distances(int metric, const float *samples, uint32_t N, uint32_t D,
                                    const float *centroids, const uint32_t *assignments, uint32_t K,
-                                   float *dists, hipStream_t st);
+                                   float *dists, hipStream_t st,
+                                   bool libm_acos = false /* angular: acosf_fdlibm (exact.hpp), kmamd_kmeans_assign's */);
+
+// assign_dist.hip -- what kmamd_kmeans_assign adds to the assignment pass (assign_job.cpp)
+// dists[s] = distance(row s, centroid assignments[s]) as launch_member_distances(..., libm_acos = true) gives it (the
+// same bits: distance_vv's under L2, the C library's acosf of distance_vv's product under the angular metric), NaN
+// for an assignment >= K (no centroid is read for it); both operands through LDS tiles instead of one line per lane
+hipError_t launch_assigned_distances(int metric, const float *samples, uint32_t N, uint32_t D, const float *centroids,
+                                     const uint32_t *assignments, uint32_t K, float *dists, hipStream_t st);
+// counts[c] += the rows of cluster c, sums[c] += the fp64 sum of their dists[] in a fixed order (either may be null),
+// over the CSR launch_inverse_assignments leaves (inv, offsets: K + 1 entries)
+hipError_t launch_cluster_stats(const float *dists, const uint32_t *inv, const uint32_t *offsets, uint32_t K,
+                                uint32_t *counts, double *sums, hipStream_t st);
 
 // yinyang.hip (reference: kmeans.cu:431-672)
 hipError_t launch_yy_init(int metric, const float *xt, uint32_t len, uint32_t D, uint32_t G, const float *centroids,

@@ -1296,26 +1296,34 @@ hipError_t launch_afk_min_dist(int metric, uint32_t m, uint32_t k, const float *
   return hipGetLastError();
 }
 
-template <int METRIC>
+// LIBM_ACOS (kmamd_kmeans_assign's distance pass under KMCUDA_AMD_ASSIGN_DIST=member): the angle by acosf_fdlibm,
+// the C library's acosf restated (exact.hpp), instead of the device library's; the chain is the same
+template <int METRIC, bool LIBM_ACOS>
 __global__ void member_distances_kernel(const float *__restrict__ samples, uint32_t N, uint32_t D,
                                         const float *__restrict__ centroids, const uint32_t *__restrict__ assignments,
                                         uint32_t K, float *__restrict__ dists) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= N) return;
   const uint32_t a = assignments[s];
-  dists[s] = a < K ? distance_vv<METRIC>(samples + (size_t)s * D, centroids + (size_t)a * D, D) : NAN;
+  if (METRIC == 1 && LIBM_ACOS)
+    dists[s] = a < K ? angular_from_prod_libm(chain_vv<1>(samples + (size_t)s * D, centroids + (size_t)a * D, D)) : NAN;
+  else
+    dists[s] = a < K ? distance_vv<METRIC>(samples + (size_t)s * D, centroids + (size_t)a * D, D) : NAN;
 }
 
 hipError_t launch_member_distances(int metric, const float *samples, uint32_t N, uint32_t D,
                                    const float *centroids, const uint32_t *assignments, uint32_t K,
-                                   float *dists, hipStream_t st) {
+                                   float *dists, hipStream_t st, bool libm_acos) {
   const dim3 grid((N + 127) / 128), block(128);
   if (metric == 0)
-    hipLaunchKernelGGL((member_distances_kernel<0>), grid, block, 0, st, samples, N, D, centroids, assignments, K,
-                       dists);
+    hipLaunchKernelGGL((member_distances_kernel<0, false>), grid, block, 0, st, samples, N, D, centroids, assignments,
+                       K, dists);
+  else if (libm_acos)
+    hipLaunchKernelGGL((member_distances_kernel<1, true>), grid, block, 0, st, samples, N, D, centroids, assignments,
+                       K, dists);
   else
-    hipLaunchKernelGGL((member_distances_kernel<1>), grid, block, 0, st, samples, N, D, centroids, assignments, K,
-                       dists);
+    hipLaunchKernelGGL((member_distances_kernel<1, false>), grid, block, 0, st, samples, N, D, centroids, assignments,
+                       K, dists);
   return hipGetLastError();
 }
 
