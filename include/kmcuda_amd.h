@@ -361,6 +361,36 @@ int kmamd_kmeans_assign(int metric, uint32_t samples_size, uint16_t features_siz
                         float *distances /* optional, samples_size */,
                         uint32_t *cluster_counts /* optional, clusters_size */,
                         double *cluster_distance_sums /* optional, clusters_size */);
+/* The m nearest centroids of every row, in the order one assignment pass would find them (beyond the reference;
+ * DESIGN.md 4.11).  Stateless and synchronous; device, device_ptrs, fp16x2, the chunks (KMCUDA_AMD_ASSIGN_CHUNK) and a
+ * shorter last chunk as kmamd_kmeans_assign.
+ *   key(s, c)  what kmamd_lloyd_assign compares: L2 RD(-2 prod(s, c) + (0 + csqr(c))) with the reference's round-down-FMA
+ *              Kahan chains; angular the clamp rule on the Kahan product (>= 1: 0, <= -1: pi, else acos) with the C
+ *              library's acosf restated on the device (the CPU oracle's bits, not the device library's acosf).
+ *              A centroid qualifies for a row iff key < FLT_MAX (the reference's strict `<` from FLT_MAX): a NaN, inf or
+ *              overflowing centroid never does.
+ *   top_assignments[s * m + j]  the j-th qualifying centroid of row s by (key ascending, centroid index ascending);
+ *              clusters_size ("no cluster") in the slots beyond the number of qualifying centroids, and in all m slots
+ *              of a row whose first feature is NaN.  Slot 0 is what kmamd_kmeans_assign assigns.
+ *   top_distances[s * m + j]    optional: the reference's distance(row, centroid) as kmamd_kmeans_assign reports it
+ *              -- L2: the square root of the Kahan sum of squared differences, NOT the key, so that the distances of
+ *              neighbouring ranks may step backwards by a last place; angular: the key itself -- NaN for "no cluster".
+ * 1 <= m <= min(clusters_size, 64).  samples_size == 0 is success.  InvalidArguments before any device work, with the
+ * outputs untouched: m out of range, and everything kmamd_kmeans_assign refuses (bad sizes, null pointers, device_ptrs
+ * naming another device, KMCUDA_AMD_FP16_STRICT=1 with fp16x2 rows).
+ * Rows of up to 256 features (and up to 2^19 centroids) are filtered on the matrix cores: exact keys are evaluated only
+ * for the centroids whose score lies within the filter's error bound of the m-th best; wider rows take the exhaustive
+ * exact kernel.  KMCUDA_AMD_ASSIGN_TOP=exact: that kernel alone for every shape (the cross-check; the same bits).
+ * KMCUDA_AMD_ASSIGN_TOP_ROWS=<rows> (tests): rows per score matrix of the filtered path.  No floating-point atomics: two
+ * identical calls give identical bits. */
+int kmamd_kmeans_assign_top(int metric, uint32_t samples_size, uint16_t features_size, uint32_t clusters_size,
+                            uint32_t m, int device, int32_t device_ptrs, int32_t fp16x2, int32_t verbosity,
+                            const void *samples, const void *centroids,
+                            uint32_t *top_assignments /* samples_size x m */,
+                            float *top_distances /* optional, samples_size x m */);
+/* the last kmamd_kmeans_assign_top call of this process that succeeded: the exact keys it evaluated and its row-centroid
+ * pairs in all (samples_size * clusters_size); either pointer may be null */
+int kmamd_assign_top_stats(uint64_t *pairs_exact, uint64_t *pairs_total);
 /* The distance pass of kmamd_kmeans_assign on its own, enqueued on hip_stream (device pointers on `device`, fp32):
  * distances[s] = distance(row s, centroid assignments[s]), NaN where assignments[s] >= clusters (no centroid is read).
  * KMCUDA_AMD_ASSIGN_DIST=member applies.  A window for tests and for timing the kernel (scripts/assign_bench.py). */

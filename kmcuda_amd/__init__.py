@@ -6,8 +6,9 @@ Step-level surface for row-sharded multi-process operation: kmcuda_amd.engine.En
 kmcuda_amd.distributed.
 k-NN of new rows against a clustered corpus (beyond the reference): KnnIndex, knn_query; radius search on
 the same index: KnnIndex.query_radius, knn_query_radius.
-New rows assigned to given centroids, with distances and cluster statistics (beyond the reference): kmeans_predict.
+New rows assigned to given centroids, with distances and cluster statistics (beyond the reference): kmeans_predict;
+the m nearest centroids of every row, in the order an assignment pass would find them: kmeans_predict_top.
 """
 from .api import kmeans_cuda, knn_cuda, supports_fp16  # noqa: F401
 from .knn_index import KnnIndex, knn_query, knn_query_radius  # noqa: F401
-from .predict import kmeans_predict  # noqa: F401
+from .predict import kmeans_predict, kmeans_predict_top  # noqa: F401

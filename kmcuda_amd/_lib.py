@@ -26,6 +26,7 @@ EXPORTS = [
     "kmamd_knn_index_create", "kmamd_knn_index_query", "kmamd_knn_index_destroy",
     "kmamd_knn_index_radius_count", "kmamd_knn_index_radius_fill",
     "kmamd_kmeans_assign", "kmamd_assigned_distances",
+    "kmamd_kmeans_assign_top", "kmamd_assign_top_stats",
     "kmamd_copy_to_device", "kmamd_profile_reset", "kmamd_profile_read", "kmamd_profile_enable", "kmamd_filter_kind", "kmamd_build_arch",
 ]
 
@@ -151,6 +152,10 @@ def lib():
     L.kmamd_kmeans_assign.argtypes = [i32, u32, ctypes.c_uint16, u32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.kmamd_assigned_distances.restype = i32
     L.kmamd_assigned_distances.argtypes = [i32, u32, u32, u32, i32, vp, vp, vp, vp, vp]
+    L.kmamd_kmeans_assign_top.restype = i32
+    L.kmamd_kmeans_assign_top.argtypes = [i32, u32, ctypes.c_uint16, u32, u32, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.kmamd_assign_top_stats.restype = i32
+    L.kmamd_assign_top_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.kmamd_copy_to_device.restype = i32
     L.kmamd_copy_to_device.argtypes = [i32, vp, vp, ctypes.c_size_t]
     L.kmamd_build_arch.restype = ctypes.c_char_p

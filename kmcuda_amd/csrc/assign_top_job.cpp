@@ -1,0 +1,236 @@
+// assign_top_job.cpp -- kmamd_kmeans_assign_top of include/kmcuda_amd.h: for every row its m nearest centroids in the
+// order one assignment pass would find them, with the reference's distances.
+//
+// The rows go through in chunks, by kmamd_kmeans_assign's pipeline (assign_job.cpp): copy in (a device-resident fp32
+// chunk is used in place), widen the halves, the kernels of assign_top.hip, copy out.  The centroids are prepared once
+// per call (launch_centroid_prep: exact squared norms, the transposed panel, the centred panel and its bound).  Rows of
+// up to 256 features take the filtered path, a sub-chunk's score matrix at a time (budgeted like the k-NN search's
+// bound matrix); wider rows, KMCUDA_AMD_ASSIGN_TOP=exact and the rows the filter hands over take the exhaustive kernel.
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <mutex>
+
+#include "../../include/kmcuda_amd.h"
+#include "knn_host.hpp"
+
+using namespace kmx;
+
+namespace {
+
+constexpr size_t kTopChunkBytes = (size_t)4 << 30;     // a chunk's staged fp32 rows, as kmamd_kmeans_assign's
+constexpr size_t kTopScoreBytes = (size_t)256 << 20;   // a sub-chunk's score matrix
+
+std::mutex g_top_stats_mutex;
+uint64_t g_top_pairs_exact = 0, g_top_pairs_total = 0;
+
+struct AssignTopJob {
+  int metric = 0, device = 0, verbosity = 0;
+  bool fp16 = false, host = true;
+  uint32_t N = 0, D = 0, K = 0, m = 0;
+  const void *samples = nullptr, *centroids_in = nullptr;
+  uint32_t *top = nullptr;
+  float *distances = nullptr;
+  uint64_t evaluated_host = 0;
+
+  int run() {
+    size_t chunk = kTopChunkBytes / ((size_t)D * sizeof(float));
+    if (const char *v = getenv("KMCUDA_AMD_ASSIGN_CHUNK")) {
+      const long long n = atoll(v);
+      if (n > 0) chunk = (size_t)n;
+    }
+    if (chunk < 1) chunk = 1;
+    bool exact_only = false;
+    if (const char *v = getenv("KMCUDA_AMD_ASSIGN_TOP")) exact_only = strcmp(v, "exact") == 0;
+
+    KnnShard w;   // owns the call's buffers and its pooled stream
+    w.dev = device;
+    w.stream = pooled_stream_acquire(device);
+    if (!w.stream) return kmcudaRuntimeError;
+    const hipStream_t st = w.stream;
+
+    // ---- the centroids, fp32 on this device ----
+    const float *cen = nullptr;
+    if (fp16) {
+      float *c32 = nullptr;
+      KNN_TRY(w.alloc(&c32, (size_t)K * D));
+      const void *src = centroids_in;
+      if (host) {
+        uint16_t *c16 = nullptr;
+        KNN_TRY(w.alloc(&c16, (size_t)K * D));
+        KMX_HIPCP(hipMemcpyAsync(c16, centroids_in, (size_t)K * D * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        src = c16;
+      }
+      KMX_HIPRT(launch_half_to_float(src, (size_t)K * D, c32, st));
+      cen = c32;
+    } else {
+      KNN_TRY(w.stage_in(static_cast<const float *>(centroids_in), (size_t)K * D, host ? -1 : device, &cen));
+    }
+
+    // ---- their preparation: csqr and the transposed panel for the exact keys, the centred panel for the filter ----
+    const uint32_t K_pad = (K + 31) / 32 * 32, Kt = (K + 63) / 64 * 64;
+    uint32_t DP = exact_only ? 0 : filter_dp_for(D);
+    // (128 rows of scores are the least a launch writes: a panel too wide for the budget takes the exact kernel)
+    if ((size_t)K_pad * sizeof(float) * 128 > kTopScoreBytes) DP = 0;
+    float *csqr = nullptr, *ct = nullptr;
+    KNN_TRY(w.alloc(&csqr, K));
+    KNN_TRY(w.alloc(&ct, (size_t)D * Kt));
+    unsigned long long *evaluated = nullptr;
+    KNN_TRY(w.alloc(&evaluated, 1));
+    KMX_HIPRT(hipMemsetAsync(evaluated, 0, sizeof(unsigned long long), st));
+    AssignTopFilter fa{};
+    if (DP) {
+      float *bias = nullptr, *bias2 = nullptr, *cfil = nullptr, *mu = nullptr;
+      uint32_t *finite = nullptr, *stats = nullptr;
+      KNN_TRY(w.alloc(&bias, K_pad));
+      KNN_TRY(w.alloc(&bias2, K_pad));
+      KNN_TRY(w.alloc(&cfil, (size_t)K_pad * DP));
+      KNN_TRY(w.alloc(&mu, DP));
+      KNN_TRY(w.alloc(&finite, Kt));
+      KNN_TRY(w.alloc(&stats, 16));
+      KMX_HIPRT(hipMemsetAsync(stats, 0, 16 * sizeof(uint32_t), st));
+      KMX_HIPRT(launch_centroid_prep(metric, cen, K, D, K_pad, DP, Kt, csqr, bias, bias2, cfil, ct, mu, false, finite,
+                                     stats, nullptr, nullptr, nullptr, st));
+      fa.metric = metric; fa.D = D; fa.DP = DP; fa.K = K; fa.K_pad = K_pad; fa.m = m;
+      fa.centroids = cen; fa.csqr = csqr; fa.cfil = cfil; fa.bias = bias; fa.mu = mu; fa.stats = stats;
+      // the coefficient of the filter bound, as the engine's
+      fa.eps = (float)(1.02 * ((double)D + 12.0) * ldexp(1.0, -24));
+      fa.evaluated = evaluated;
+    } else {
+      KMX_HIPRT(launch_centroid_rows(metric, cen, K, D, Kt, csqr, ct, st));
+    }
+
+    // ---- one chunk's buffers, reused by every chunk ----
+    const uint32_t Nc = (uint32_t)(chunk < N ? chunk : N);
+    float *rows32 = nullptr, *dist_buf = nullptr;
+    uint16_t *rows16 = nullptr;
+    uint32_t *top_buf = nullptr;
+    if (host || fp16) KNN_TRY(w.alloc(&rows32, (size_t)Nc * D));
+    if (host && fp16) KNN_TRY(w.alloc(&rows16, (size_t)Nc * D));
+    if (host) KNN_TRY(w.alloc(&top_buf, (size_t)Nc * m));
+    if (host && distances) KNN_TRY(w.alloc(&dist_buf, (size_t)Nc * m));
+    uint32_t sub = 0;   // rows per score matrix: a multiple of the score kernel's 128-row blocks
+    if (DP) {
+      size_t r = kTopScoreBytes / ((size_t)K_pad * sizeof(float)) / 128 * 128;
+      if (const char *v = getenv("KMCUDA_AMD_ASSIGN_TOP_ROWS")) {   // (tests: several score matrices per chunk)
+        const long long n = atoll(v);
+        if (n > 0 && ((size_t)n + 127) / 128 * 128 < r) r = ((size_t)n + 127) / 128 * 128;
+      }
+      if (r > Nc) r = ((size_t)Nc + 127) / 128 * 128;
+      sub = (uint32_t)r;
+      KNN_TRY(w.alloc(&fa.scores, (size_t)sub * K_pad));
+      KNN_TRY(w.alloc(&fa.meta, sub));
+      KNN_TRY(w.alloc(&fa.fb_rows, Nc));
+      KNN_TRY(w.alloc(&fa.fb_count, 1));
+    }
+
+    for (uint32_t q0 = 0; q0 < N; q0 += Nc) {
+      const uint32_t n = N - q0 < Nc ? N - q0 : Nc;
+      // ---- the chunk's rows, fp32 on this device ----
+      const float *rows = nullptr;
+      if (fp16) {
+        const uint16_t *src = static_cast<const uint16_t *>(samples) + (size_t)q0 * D;
+        if (host) {
+          KMX_HIPCP(hipMemcpyAsync(rows16, src, (size_t)n * D * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+          src = rows16;
+        }
+        KMX_HIPRT(launch_half_to_float(src, (size_t)n * D, rows32, st));
+        rows = rows32;
+      } else if (host) {
+        KMX_HIPCP(hipMemcpyAsync(rows32, static_cast<const float *>(samples) + (size_t)q0 * D,
+                                 (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, st));
+        rows = rows32;
+      } else {
+        rows = static_cast<const float *>(samples) + (size_t)q0 * D;
+      }
+      uint32_t *t = host ? top_buf : top + (size_t)q0 * m;
+      if (DP) {
+        KMX_HIPRT(hipMemsetAsync(fa.fb_count, 0, sizeof(uint32_t), st));
+        for (uint32_t r0 = 0; r0 < n; r0 += sub) {
+          const uint32_t nr = n - r0 < sub ? n - r0 : sub;
+          KMX_HIPRT(launch_assign_top_filter(fa, rows + (size_t)r0 * D, nr, r0, t + (size_t)r0 * m, st));
+        }
+        KMX_HIPRT(launch_assign_top_exact(metric, rows, n, D, ct, csqr, K, Kt, m, fa.fb_rows, fa.fb_count, t,
+                                          evaluated, st));
+      } else {
+        KMX_HIPRT(launch_assign_top_exact(metric, rows, n, D, ct, csqr, K, Kt, m, nullptr, nullptr, t, evaluated, st));
+      }
+      float *dist = nullptr;
+      if (distances) {
+        dist = host ? dist_buf : distances + (size_t)q0 * m;
+        KMX_HIPRT(launch_assign_top_distances(metric, rows, n, D, cen, K, m, t, dist, st));
+      }
+      if (host) {
+        KMX_HIPCP(hipMemcpyAsync(top + (size_t)q0 * m, t, (size_t)n * m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (distances)
+          KMX_HIPCP(hipMemcpyAsync(distances + (size_t)q0 * m, dist, (size_t)n * m * sizeof(float),
+                                   hipMemcpyDeviceToHost, st));
+      }
+      // (the next chunk overwrites these buffers: the stream orders it behind this one's kernels and copies)
+    }
+    unsigned long long ev = 0;
+    KMX_HIPCP(hipMemcpyAsync(&ev, evaluated, sizeof(ev), hipMemcpyDeviceToHost, st));
+    if (hipStreamSynchronize(st) != hipSuccess) {
+      if (verbosity > 0) printf("kmamd_kmeans_assign_top failed: %s\n", hipGetErrorString(hipGetLastError()));
+      return kmcudaRuntimeError;
+    }
+    evaluated_host = ev;
+    if (verbosity > 1)
+      printf("kmamd_kmeans_assign_top: %s path, %llu exact keys of %llu pairs\n", DP ? "filtered" : "exact", ev,
+             (unsigned long long)N * K);
+    return kmcudaSuccess;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int kmamd_kmeans_assign_top(int metric, uint32_t samples_size, uint16_t features_size, uint32_t clusters_size,
+                            uint32_t m, int device, int32_t device_ptrs, int32_t fp16x2, int32_t verbosity,
+                            const void *samples, const void *centroids, uint32_t *top_assignments,
+                            float *top_distances) {
+  // ---- everything that is refused is refused here, before any device work, with the outputs untouched ----
+  if (metric != 0 && metric != 1) return kmcudaInvalidArguments;
+  if (features_size == 0 || clusters_size < 2 || clusters_size >= 0x7FFFFFFFu) return kmcudaInvalidArguments;
+  if (m < 1 || m > 64 || m > clusters_size) return kmcudaInvalidArguments;
+  if (fp16x2 && (features_size & 1u)) return kmcudaInvalidArguments;
+  if (!centroids || (samples_size != 0 && (!samples || !top_assignments))) return kmcudaInvalidArguments;
+  if (device < 0 || (device_ptrs >= 0 && device_ptrs != device)) return kmcudaInvalidArguments;
+  // the reference's half2 arithmetic has no predict form (kmamd_kmeans_assign refuses it likewise)
+  if (fp16x2)
+    if (const char *v = getenv("KMCUDA_AMD_FP16_STRICT"))
+      if (atoi(v) != 0) return kmcudaInvalidArguments;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return kmcudaNoSuchDevice;
+  if (hipSetDevice(device) != hipSuccess) return kmcudaNoSuchDevice;
+  g_verbosity = verbosity;
+  uint64_t evaluated = 0;
+  if (samples_size != 0) {
+    if (device_ptrs >= 0) (void)hipDeviceSynchronize();   // the caller's writes, as kmamd_kmeans_assign
+    AssignTopJob job;
+    job.metric = metric; job.device = device; job.verbosity = verbosity;
+    job.fp16 = fp16x2 != 0; job.host = device_ptrs < 0;
+    job.N = samples_size; job.D = features_size; job.K = clusters_size; job.m = m;
+    job.samples = samples; job.centroids_in = centroids;
+    job.top = top_assignments; job.distances = top_distances;
+    const int rc = job.run();
+    if (rc != kmcudaSuccess) return rc;
+    evaluated = job.evaluated_host;
+  }
+  std::lock_guard<std::mutex> lock(g_top_stats_mutex);
+  g_top_pairs_exact = evaluated;
+  g_top_pairs_total = (uint64_t)samples_size * clusters_size;
+  return kmcudaSuccess;
+}
+
+int kmamd_assign_top_stats(uint64_t *pairs_exact, uint64_t *pairs_total) {
+  std::lock_guard<std::mutex> lock(g_top_stats_mutex);
+  if (pairs_exact) *pairs_exact = g_top_pairs_exact;
+  if (pairs_total) *pairs_total = g_top_pairs_total;
+  return kmcudaSuccess;
+}
+
+}  // extern "C"

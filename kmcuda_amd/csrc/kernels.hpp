@@ -308,6 +308,34 @@ hipError_t launch_assigned_distances(int metric, const float *samples, uint32_t 
 hipError_t launch_cluster_stats(const float *dists, const uint32_t *inv, const uint32_t *offsets, uint32_t K,
                                 uint32_t *counts, double *sums, hipStream_t st);
 
+// assign_top.hip -- the m nearest centroids of every row (kmamd_kmeans_assign_top, assign_top_job.cpp)
+// top[s * m + j] = the j-th centroid of row s by (key, index), K where fewer qualify; *evaluated += the exact keys
+// computed.  The exhaustive kernel: every row of [0, N) (rows == nullptr) or rows[0 .. *nrows), N then bounding the grid
+hipError_t launch_assign_top_exact(int metric, const float *samples, uint32_t N, uint32_t D, const float *ct,
+                                   const float *csqr, uint32_t K, uint32_t Kt, uint32_t m, const uint32_t *rows,
+                                   const uint32_t *nrows, uint32_t *top, unsigned long long *evaluated, hipStream_t st);
+// the filtered path: what centroid_prep left (cfil, bias, mu, stats: launch_centroid_prep; DP = filter_dp_for(D) != 0)
+// and the buffers of one sub-chunk: scores (rows x K_pad floats), meta (rows x 4 floats); fb_rows / fb_count: the rows
+// handed to launch_assign_top_exact (chunk-relative indices; fb_count zeroed by the owner)
+struct AssignTopFilter {
+  int metric;
+  uint32_t D, DP, K, K_pad, m;
+  const float *centroids, *csqr, *cfil, *bias, *mu;
+  const uint32_t *stats;
+  float eps;
+  float *scores;
+  float4 *meta;
+  uint32_t *fb_rows, *fb_count;
+  unsigned long long *evaluated;
+};
+// rows [row0, row0 + n) of a chunk: `samples` and `top` point at row row0
+hipError_t launch_assign_top_filter(const AssignTopFilter &a, const float *samples, uint32_t n, uint32_t row0,
+                                    uint32_t *top, hipStream_t st);
+// dists[s * m + j] = distance(row s, centroid top[s * m + j]) as launch_assigned_distances gives it, NaN for K
+hipError_t launch_assign_top_distances(int metric, const float *samples, uint32_t N, uint32_t D,
+                                       const float *centroids, uint32_t K, uint32_t m, const uint32_t *top,
+                                       float *dists, hipStream_t st);
+
 // yinyang.hip (reference: kmeans.cu:431-672)
 hipError_t launch_yy_init(int metric, const float *xt, uint32_t len, uint32_t D, uint32_t G, const float *centroids,
                           const uint32_t *assignments, const uint32_t *cperm, const uint32_t *gstart, float *bounds,

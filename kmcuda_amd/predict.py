@@ -17,6 +17,8 @@ numpy in, numpy out (assignments / counts uint32, distances float32, distance_su
 with torch's work on the device (it waits for the device first and its outputs are complete when it returns).
 float16 inputs select fp16x2: fp32 arithmetic on the half values, as kmeans_cuda().
 """
+import os
+
 import numpy
 
 from . import _lib
@@ -73,3 +75,42 @@ def kmeans_predict(samples, centroids, metric="L2", device=0, return_distances=F
     _raise_for(rc, "kmamd_kmeans_assign")
     out = (asg,) + ((dist,) if return_distances else ()) + (((counts, sums),) if return_cluster_stats else ())
     return out[0] if len(out) == 1 else out
+
+
+def kmeans_predict_top(samples, centroids, m, metric="L2", device=0, return_distances=True, verbosity=0):
+    """(indices, distances), or indices alone, of the `m` nearest centroids of every row: (n, m) arrays, row i holding
+    its qualifying centroids by (key ascending, centroid index ascending), where the key is what an assignment pass
+    compares (C ABI: kmamd_kmeans_assign_top).  Column 0 is kmeans_predict's assignment.  Slots beyond
+    the number of qualifying centroids -- a NaN, inf or overflowing centroid never qualifies -- and every slot of a row
+    whose first feature is NaN hold len(centroids) and distance NaN.  distances are the reference's distances as
+    kmeans_predict returns them (under L2 not the key: neighbouring ranks may step backwards by a last place).
+    1 <= m <= min(len(centroids), 64).  Kinds and dtypes as kmeans_predict; every argument is checked before the
+    device is touched."""
+    metric_id, device, s, c, fp16, n, d, clusters, on_dev = _check(samples, centroids, metric, device)
+    if isinstance(m, bool) or not isinstance(m, (int, numpy.integer)):
+        raise TypeError("\"m\" must be an integer")
+    m = int(m)
+    if m < 1 or m > min(clusters, 64):
+        raise ValueError("\"m\" must be in [1, min(len(centroids), 64)]")
+    if fp16 and _fp16_strict():
+        raise ValueError("KMCUDA_AMD_FP16_STRICT=1: the reference's half2 arithmetic has no predict form")
+    if on_dev:
+        import torch
+        dev = torch.device("cuda", device)
+        top = torch.empty((n, m), dtype=torch.int32, device=dev)
+        dist = torch.empty((n, m), dtype=torch.float32, device=dev) if return_distances else None
+    else:
+        top = numpy.empty((n, m), numpy.uint32)
+        dist = numpy.empty((n, m), numpy.float32) if return_distances else None
+    rc = _lib.lib().kmamd_kmeans_assign_top(metric_id, n, d, clusters, m, device, device if on_dev else -1, int(fp16),
+                                            int(verbosity), _ptr(s), _ptr(c), _ptr(top),
+                                            _ptr(dist) if dist is not None else None)
+    _raise_for(rc, "kmamd_kmeans_assign_top")
+    return (top, dist) if return_distances else top
+
+
+def _fp16_strict():
+    try:
+        return int(os.environ.get("KMCUDA_AMD_FP16_STRICT", "0") or 0) != 0
+    except ValueError:
+        return False
