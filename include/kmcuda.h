@@ -30,7 +30,10 @@ typedef enum {
   kmcudaInitMethodRandom = 0,  /* first K entries of a random_shuffle over rand() */
   kmcudaInitMethodPlusPlus,    /* k-means++ (distance-proportional, as the reference does it) */
   kmcudaInitMethodAFKMC2,      /* AFK-MC2 (init_params: uint32_t* m, 0 => 200); draws restated from the published XORWOW */
-  kmcudaInitMethodImport       /* caller supplies the centroids in `centroids` */
+  kmcudaInitMethodImport,      /* caller supplies the centroids in `centroids` */
+  kmcudaInitMethodParallel     /* = 4, beyond the reference: k-means|| (kmcuda_amd.h: kmamd_kmeans_seed_parallel;
+                                  init_params: NULL or a kmamd_seed_parallel_params {uint32_t rounds; float oversampling;},
+                                  0 => the default) */
 } KMCUDAInitMethod;
 
 /* Distance metric (reference kmcuda.h:75-81). */
@@ -47,7 +50,8 @@ extern "C" {
  * K-means (Lloyd, optionally Yinyang-accelerated) on the GPUs named by `device`.
  * Replaces reference src/kmcuda.h:118-123 / src/kmcuda.cc:402-531.
  *
- *   init, init_params  seeding method; init_params is a uint32_t* (m) for AFK-MC2, else ignored
+ *   init, init_params  seeding method; init_params is a uint32_t* (m) for AFK-MC2, {rounds, oversampling} for
+ *                      k-means||, else ignored
  *   tolerance          stop when the reassigned fraction drops to <= tolerance   [0, 1]
  *   yinyang_t          relative number of Yinyang groups, 0 disables Yinyang     [0, 0.5]
  *   metric             L2 or angular
@@ -96,7 +100,9 @@ namespace kmcuda {
 const std::unordered_map<std::string, KMCUDAInitMethod> init_methods{
     {"kmeans++", kmcudaInitMethodPlusPlus}, {"k-means++", kmcudaInitMethodPlusPlus},
     {"afkmc2", kmcudaInitMethodAFKMC2},     {"afk-mc2", kmcudaInitMethodAFKMC2},
-    {"random", kmcudaInitMethodRandom}};
+    {"random", kmcudaInitMethodRandom},
+    {"k-means||", kmcudaInitMethodParallel}, {"kmeans||", kmcudaInitMethodParallel},
+    {"scalable-k-means++", kmcudaInitMethodParallel}};
 const std::unordered_map<std::string, KMCUDADistanceMetric> metrics{
     {"euclidean", kmcudaDistanceMetricL2}, {"L2", kmcudaDistanceMetricL2},
     {"l2", kmcudaDistanceMetricL2},        {"cos", kmcudaDistanceMetricCosine},

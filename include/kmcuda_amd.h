@@ -398,6 +398,55 @@ int kmamd_assigned_distances(int metric, uint32_t n_rows, uint32_t features, uin
                              const float *samples, const float *centroids, const uint32_t *assignments,
                              float *distances, void *hip_stream);
 
+/* k-means|| seeding (Bahmani et al., "Scalable K-Means++"; no counterpart in the reference): K seeds, each
+ * bit-equal to an input row, from a handful of passes over the rows instead of k-means++'s K - 1 dependent ones.
+ * Stateless and synchronous.  metric, fp16x2, device and device_ptrs as kmamd_kmeans_assign (features_size counts halves
+ * under fp16x2); samples and centroids are host buffers (device_ptrs = -1) or buffers on `device`; every other pointer
+ * is HOST memory.
+ *   h(seed, r, s)   splitmix64's finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *                   z ^= z >> 31) of z = ((uint64)r << 32 | s) + ((uint64)seed + 1) * 0x9E3779B97F4A7C15 mod 2^64;
+ *                   U(seed, r, s) = (h >> 11) * 2^-53.  No generator state: a row's draw depends on (seed, r, s) alone.
+ *   term t[s]       the float32 distance (kmamd_kmeans_assign's `distances`, not squared: what k-means++ draws with) of
+ *                   row s to its nearest candidate so far; 0 for good for a row whose first feature is NaN; a term that
+ *                   is NaN or inf counts as 0 in everything below, and a term of 0 is never drawn.
+ *   round 0         the first candidate is the first row at or cyclically after h(seed, 0, 0) % N whose first feature is
+ *                   not NaN (none: InvalidArguments); t[s] = distance(row s, that row), where that is not NaN.
+ *   round 1..R      phi = the fp64 sum of the terms (per 256 rows in a fixed tree, the blocks in a fixed order: two
+ *                   identical calls give identical bits); row s is drawn iff U(seed, r, s) * phi <
+ *                   (double)oversampling * (double)t[s], each side one fp64 product.  The drawn rows in ascending order
+ *                   are the round's M new candidates (no cap).  M >= 2: t[s] <- d[s] where d[s] < t[s], d being
+ *                   kmamd_kmeans_assign's distances against the new candidates; M == 1: d[s] the distance to that row.
+ *                   phi == 0 draws nothing.
+ *   weights         counts[j] = kmamd_kmeans_assign(rows, all candidates).cluster_counts[j] (the lowest index wins a
+ *                   tie); a candidate of count 0 -- a duplicate of an earlier one -- is dropped, the live ones keep
+ *                   their order.
+ *   seeds           the K seeds kmamd_kmeans_weighted(init = k-means++, tolerance = 1, yinyang_t = 0, seed) draws over
+ *                   the live candidates with weights (float)count: no Lloyd iteration runs on the candidates.  With
+ *                   fewer than K live candidates: that call on the ROWS, unweighted -- plain k-means++ -- and
+ *                   *fell_back = 1.
+ * rounds: 1..64, 0 = 5.  oversampling: the expected number of draws per round, finite and > 0; 0 = 2 * clusters_size.
+ * Optional reports: candidate_rows / candidate_counts receive the row ids and counts of the first candidate_capacity
+ * candidates (dropped ones included, with count 0), *n_candidates their number in all, round_ends[r] (rounds + 1
+ * entries) the number of candidates after round r, *fell_back 0 or 1.
+ * InvalidArguments before any device work, with the outputs untouched: bad sizes, clusters_size < 2 or > samples_size,
+ * rounds > 64, oversampling not finite or < 0, null samples / centroids, device_ptrs naming another device,
+ * KMCUDA_AMD_FP16_STRICT=1 with fp16x2 rows.  KMCUDA_AMD_TIMING=1: the phases' wall-clock laps on stderr. */
+int kmamd_kmeans_seed_parallel(int metric, uint32_t samples_size, uint16_t features_size, uint32_t clusters_size,
+                               uint32_t rounds /* 0: 5 */, float oversampling /* 0: 2 * K */, uint32_t seed,
+                               int device, int32_t device_ptrs, int32_t fp16x2, int32_t verbosity,
+                               const void *samples, void *centroids /* K x D out, the rows' dtype */,
+                               uint32_t *candidate_rows /* optional */, uint32_t *candidate_counts /* optional */,
+                               uint32_t candidate_capacity,
+                               uint32_t *n_candidates /* optional out: all candidates, dropped included */,
+                               uint32_t *round_ends /* optional, rounds + 1: candidates after round 0..R */,
+                               int32_t *fell_back /* optional */);
+/* kmeans_cuda's init = kmcudaInitMethodParallel (kmcuda.h): init_params of that init is NULL or points to one of
+ * these; 0 means the default. */
+typedef struct {
+  uint32_t rounds;
+  float oversampling;
+} kmamd_seed_parallel_params;
+
 /* host -> raw device pointer copy on `device` (what python.cc:330-345 does with cudaMemcpy for imported
  * centroids in device-pointer mode; lets a binding without a HIP runtime of its own fill caller-owned memory). */
 int kmamd_copy_to_device(int device, void *dst, const void *host_src, size_t bytes);

@@ -8,7 +8,9 @@ k-NN of new rows against a clustered corpus (beyond the reference): KnnIndex, kn
 the same index: KnnIndex.query_radius, knn_query_radius.
 New rows assigned to given centroids, with distances and cluster statistics (beyond the reference): kmeans_predict;
 the m nearest centroids of every row, in the order an assignment pass would find them: kmeans_predict_top.
+k-means|| seeding (beyond the reference), stand-alone -- kmeans_seed_parallel -- and as kmeans_cuda(init="k-means||").
 """
 from .api import kmeans_cuda, knn_cuda, supports_fp16  # noqa: F401
 from .knn_index import KnnIndex, knn_query, knn_query_radius  # noqa: F401
 from .predict import kmeans_predict, kmeans_predict_top  # noqa: F401
+from .seed import kmeans_seed_parallel  # noqa: F401

@@ -27,6 +27,7 @@ EXPORTS = [
     "kmamd_knn_index_radius_count", "kmamd_knn_index_radius_fill",
     "kmamd_kmeans_assign", "kmamd_assigned_distances",
     "kmamd_kmeans_assign_top", "kmamd_assign_top_stats",
+    "kmamd_kmeans_seed_parallel",
     "kmamd_copy_to_device", "kmamd_profile_reset", "kmamd_profile_read", "kmamd_profile_enable", "kmamd_filter_kind", "kmamd_build_arch",
 ]
 
@@ -156,6 +157,9 @@ def lib():
     L.kmamd_kmeans_assign_top.argtypes = [i32, u32, ctypes.c_uint16, u32, u32, i32, i32, i32, i32, vp, vp, vp, vp]
     L.kmamd_assign_top_stats.restype = i32
     L.kmamd_assign_top_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    L.kmamd_kmeans_seed_parallel.restype = i32
+    L.kmamd_kmeans_seed_parallel.argtypes = [i32, u32, ctypes.c_uint16, u32, u32, f32, u32, i32, i32, i32, i32, vp, vp,
+                                             vp, vp, u32, vp, vp, vp]
     L.kmamd_copy_to_device.restype = i32
     L.kmamd_copy_to_device.argtypes = [i32, vp, vp, ctypes.c_size_t]
     L.kmamd_build_arch.restype = ctypes.c_char_p

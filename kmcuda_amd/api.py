@@ -15,7 +15,38 @@ from . import _lib
 
 supports_fp16 = True  # fp16x2 boundary: half buffers, fp32 arithmetic on the half values
 
-_INIT = {"kmeans++": 1, "k-means++": 1, "afkmc2": 2, "afk-mc2": 2, "random": 0}  # kmcuda.h:168-174
+_INIT = {"kmeans++": 1, "k-means++": 1, "afkmc2": 2, "afk-mc2": 2, "random": 0,  # kmcuda.h:168-174
+         "k-means||": 4, "kmeans||": 4, "scalable-k-means++": 4}  # beyond the reference: kmamd_kmeans_seed_parallel
+
+
+class _SeedParallelParams(ctypes.Structure):
+    """kmamd_seed_parallel_params (include/kmcuda_amd.h): 0 means the default."""
+    _fields_ = [("rounds", ctypes.c_uint32), ("oversampling", ctypes.c_float)]
+
+
+def _seed_parallel_params(rounds, oversampling):
+    """The checked (rounds, oversampling) of k-means|| as the C ABI takes them; None: the default (0)."""
+    if rounds is None:
+        rounds = 0
+    else:
+        if isinstance(rounds, (bool, float)) or not hasattr(rounds, "__index__"):
+            raise TypeError("k-means||'s rounds must be an integer")
+        rounds = operator.index(rounds)
+        if rounds < 1 or rounds > 64:
+            raise ValueError("k-means||'s rounds must be in [1, 64]")
+    if oversampling is None:
+        oversampling = 0.0
+    else:
+        if isinstance(oversampling, bool):
+            raise TypeError("k-means||'s oversampling must be a number")
+        try:
+            with numpy.errstate(over="ignore"):   # (beyond float32's range: inf, refused below)
+                oversampling = float(numpy.float32(oversampling))
+        except (TypeError, ValueError):
+            raise TypeError("k-means||'s oversampling must be a number")
+        if not (oversampling > 0 and oversampling != float("inf")):
+            raise ValueError("k-means||'s oversampling must be a finite number > 0")
+    return rounds, oversampling
 _METRIC = {"euclidean": 0, "L2": 0, "l2": 0, "cos": 1, "cosine": 1, "angular": 1}  # kmcuda.h:177-184
 
 
@@ -113,6 +144,12 @@ def kmeans_cuda(samples, clusters, tolerance=.01, init="k-means++", yinyang_t=.1
     else:
         init_id = 3
     afkmc2_m = ctypes.c_uint32(operator.index(init[1]) if isinstance(init, tuple) and len(init) > 1 and init_id == 2 else 0)
+    init_params = afkmc2_m
+    if init_id == 4:   # "k-means||" | ("k-means||", rounds[, oversampling])
+        extra = init[1:3] if isinstance(init, tuple) else ()
+        init_params = _SeedParallelParams(*_seed_parallel_params(*(tuple(extra) + (None, None))[:2]))
+        if sample_weight is not None:
+            raise ValueError("\"sample_weight\" is not supported with init=\"k-means||\"")
     metric_id = _get_metric(metric)
     if clusters < 2 or clusters >= 0xFFFFFFFF:
         raise ValueError("\"clusters\" must be greater than 1 and less than (1 << 32) - 1")
@@ -178,7 +215,7 @@ def kmeans_cuda(samples, clusters, tolerance=.01, init="k-means++", yinyang_t=.1
     avg = ctypes.c_float(0)
     avg_ptr = ctypes.cast(ctypes.byref(avg), ctypes.c_void_p) if average_distance else None
     if weights_ptr is None:
-        rc = lib.kmeans_cuda(init_id, ctypes.byref(afkmc2_m), tolerance, yinyang_t, metric_id, n, d, clusters,
+        rc = lib.kmeans_cuda(init_id, ctypes.byref(init_params), tolerance, yinyang_t, metric_id, n, d, clusters,
                              seed & 0xFFFFFFFF, device, device_ptrs, int(fp16x2), verbosity, samples_ptr, cen_ptr,
                              asg_ptr, avg_ptr)
     else:

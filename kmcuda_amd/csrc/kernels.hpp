@@ -308,6 +308,35 @@ hipError_t launch_assigned_distances(int metric, const float *samples, uint32_t 
 hipError_t launch_cluster_stats(const float *dists, const uint32_t *inv, const uint32_t *offsets, uint32_t K,
                                 uint32_t *counts, double *sums, hipStream_t st);
 
+// seed_par.hip -- the sampling side of k-means|| seeding (kmamd_kmeans_seed_parallel, seed_par_job.cpp).
+// A block is 256 consecutive rows: seed_par_block_count(N) of them, in seed_par_chunk_count(N) chunks of 1024.
+size_t seed_par_block_count(uint32_t N);
+size_t seed_par_chunk_count(uint32_t N);
+// t[s] <- d[s] where d[s] < t[s] (a NaN d changes nothing); rows_first != null: the first update -- t starts at +inf
+// and a row whose first feature is NaN (rows_first: the N x D fp32 rows) gets the term 0.  bsum[b] = the fp64 sum of
+// block b's terms (NaN and inf count as 0) in a fixed tree, *phi = their sum in a fixed order.
+hipError_t launch_seed_par_update(float *t, const float *d, uint32_t N, const float *rows_first, uint32_t D,
+                                  double *bsum, double *phi, hipStream_t st);
+// Row s is drawn iff U(seed, round, s) * *phi < (double)oversampling * (double)t[s] (include/kmcuda_amd.h).  draw:
+// bcount[b] = block b's drawn rows, boff[b] their exclusive prefix inside b's chunk, aux[c] the chunks' totals,
+// carry[c] their exclusive prefix and carry[chunk count] the number of drawn rows M.  fill: ids[0 .. M) the drawn rows
+// in ascending order, cand32 (M x D) their rows.
+hipError_t launch_seed_par_draw(const float *t, uint32_t N, uint32_t seed, uint32_t round, const double *phi,
+                                float oversampling, uint32_t *bcount, uint32_t *boff, uint32_t *aux, uint32_t *carry,
+                                hipStream_t st);
+hipError_t launch_seed_par_fill(const float *t, uint32_t N, uint32_t seed, uint32_t round, const double *phi,
+                                float oversampling, const uint32_t *boff, const uint32_t *carry, uint32_t M,
+                                const float *rows32, uint32_t D, uint32_t *ids, float *cand32, hipStream_t st);
+// counts[a] += 1 for every row whose assignment a is below M
+hipError_t launch_seed_par_weights(const uint32_t *assignments, uint32_t N, uint32_t M, uint32_t *counts,
+                                   hipStream_t st);
+// out[j] = in[idx[j]] for j < M, rows of D floats (in32 -> out32) and / or of D halves (in16 -> out16)
+hipError_t launch_seed_par_gather(const float *in32, const void *in16, const uint32_t *idx, uint32_t M, uint32_t D,
+                                  float *out32, void *out16, hipStream_t st);
+// *best = min over the rows whose first feature is not NaN of (s - start) mod N (the caller sets it to all ones)
+hipError_t launch_seed_par_first_valid(const float *rows, uint32_t N, uint32_t D, uint32_t start,
+                                       unsigned long long *best, hipStream_t st);
+
 // assign_top.hip -- the m nearest centroids of every row (kmamd_kmeans_assign_top, assign_top_job.cpp)
 // top[s * m + j] = the j-th centroid of row s by (key, index), K where fewer qualify; *evaluated += the exact keys
 // computed.  The exhaustive kernel: every row of [0, N) (rows == nullptr) or rows[0 .. *nrows), N then bounding the grid

@@ -1071,6 +1071,8 @@ class Job {
         RETERR(sync_all());
         break;
       }
+      case kmcudaInitMethodParallel:   // (runs at the entry of kmamd_kmeans_weighted and arrives here as Import)
+        return kmcudaInvalidArguments;
     }
     INFO("\rdone            \n");
     return 0;
@@ -1633,7 +1635,7 @@ int kmamd_kmeans_weighted(int init_, const void *init_params, float tolerance, f
                           uint32_t device, int32_t device_ptrs, int32_t fp16x2, int32_t verbosity, const float *samples,
                           float *centroids, uint32_t *assignments, float *average_distance,
                           const float *sample_weights) {
-  const KMCUDAInitMethod init = static_cast<KMCUDAInitMethod>(init_);
+  KMCUDAInitMethod init = static_cast<KMCUDAInitMethod>(init_);
   const KMCUDADistanceMetric metric = static_cast<KMCUDADistanceMetric>(metric_);
   kmx::g_verbosity = verbosity;
   DEBUG("arguments: %d %p %.3f %.2f %d %u %u %u %u %u %d %d %p %p %p %p\n", init, init_params, tolerance, yinyang_t,
@@ -1657,11 +1659,28 @@ int kmamd_kmeans_weighted(int init_, const void *init_params, float tolerance, f
       return kmcudaInvalidArguments;
     }
   }
+  if (init == kmcudaInitMethodParallel && sample_weights) {   // (weighted k-means|| does not exist: refused as afkmc2)
+    INFO("sample weights are not supported with k-means||\n");
+    return kmcudaInvalidArguments;
+  }
   INFO("reassignments threshold: %u\n", uint32_t(tolerance * samples_size));
   const uint32_t yy_groups_size = yinyang_t * clusters_size;  // float product, truncated (kmcuda.cc:417)
   DEBUG("yinyang groups: %u\n", yy_groups_size);
   auto devs = setup_devices(device, verbosity);
   if (devs.empty()) return kmcudaNoSuchDevice;
+  if (init == kmcudaInitMethodParallel) {
+    // k-means|| (seed_par_job.cpp): the stand-alone seeding writes `centroids` on the first device of the mask (the
+    // rows' own device in device-pointer mode), and the call goes on exactly as with imported centroids.  Host rows
+    // are uploaded twice, once by the seeding and once below.
+    const auto *sp = static_cast<const kmamd_seed_parallel_params *>(init_params);
+    INFO("performing k-means||...\n");
+    RETERR(kmamd_kmeans_seed_parallel(metric, samples_size, fp16x2 ? (uint16_t)(2u * features_size) : features_size,
+                                      clusters_size, sp ? sp->rounds : 0u, sp ? sp->oversampling : 0.f, seed,
+                                      device_ptrs >= 0 ? device_ptrs : devs[0], device_ptrs, fp16x2, verbosity, samples,
+                                      centroids, nullptr, nullptr, 0, nullptr, nullptr, nullptr));
+    kmx::g_verbosity = verbosity;
+    init = kmcudaInitMethodImport;
+  }
 
   // device-pointer inputs: whatever the caller still has in flight on that GPU (any stream) must have
   // landed before our own non-blocking streams read it -- the reference got this from the legacy

@@ -40,6 +40,7 @@ struct Api {
   void (*IncRef)(PyObject *);
   unsigned long long (*LongAsUnsignedLongLong)(PyObject *);
   long (*LongAsLong)(PyObject *);
+  double (*FloatAsDouble)(PyObject *);
   Py_ssize_t (*TupleSize)(PyObject *);
   PyObject *(*TupleGetItem)(PyObject *, Py_ssize_t);
   int (*IsTrue)(PyObject *);
@@ -72,6 +73,7 @@ bool bind_python() {
             sym(P.GetBuffer, "PyObject_GetBuffer") && sym(P.BufferRelease, "PyBuffer_Release") &&
             sym(P.DecRef, "Py_DecRef") && sym(P.IncRef, "Py_IncRef") &&
             sym(P.LongAsUnsignedLongLong, "PyLong_AsUnsignedLongLong") && sym(P.LongAsLong, "PyLong_AsLong") &&
+            sym(P.FloatAsDouble, "PyFloat_AsDouble") &&
             sym(P.TupleSize, "PyTuple_Size") && sym(P.TupleGetItem, "PyTuple_GetItem") &&
             sym(P.IsTrue, "PyObject_IsTrue") && sym(P.SaveThread, "PyEval_SaveThread") &&
             sym(P.RestoreThread, "PyEval_RestoreThread") && sym(P.NumberIndex, "PyNumber_Index") &&
@@ -234,6 +236,7 @@ PyObject *py_kmeans_cuda(PyObject *, PyObject *args, PyObject *kwargs) {
   // init: string | (string, m) | array (kmcuda.h:168-174, python.cc:196-217)
   KMCUDAInitMethod init = kmcudaInitMethodPlusPlus;
   uint32_t afkmc2_m = 0;
+  kmamd_seed_parallel_params par_params = {0, 0.f};   // ("k-means||", rounds, oversampling); 0: the default
   PyObject *import_obj = nullptr;
   auto init_from_string = [&](PyObject *s) -> bool {
     const char *c = P.UnicodeAsUTF8(s);
@@ -241,6 +244,8 @@ PyObject *py_kmeans_cuda(PyObject *, PyObject *args, PyObject *kwargs) {
     if (!strcmp(c, "kmeans++") || !strcmp(c, "k-means++")) init = kmcudaInitMethodPlusPlus;
     else if (!strcmp(c, "afkmc2") || !strcmp(c, "afk-mc2")) init = kmcudaInitMethodAFKMC2;
     else if (!strcmp(c, "random")) init = kmcudaInitMethodRandom;
+    else if (!strcmp(c, "k-means||") || !strcmp(c, "kmeans||") || !strcmp(c, "scalable-k-means++"))
+      init = kmcudaInitMethodParallel;
     else {
       fail(P.ValueError, "Unknown centroids initialization method. Supported values are \"kmeans++\", \"random\" "
                          "and <numpy array>.");
@@ -262,6 +267,23 @@ PyObject *py_kmeans_cuda(PyObject *, PyObject *args, PyObject *kwargs) {
         return fail(P.ValueError, "afkmc2's m must be a non-negative integer below (1 << 32)");
       }
       afkmc2_m = (uint32_t)m;
+    }
+    if (init == kmcudaInitMethodParallel && P.TupleSize(init_obj) > 1 && P.TupleGetItem(init_obj, 1) != P.None) {
+      unsigned long long r = 0;
+      if (!as_index(P.TupleGetItem(init_obj, 1), &r) || r < 1 || r > 64) {
+        P.ErrClear();
+        return fail(P.ValueError, "k-means||'s rounds must be an integer in [1, 64]");
+      }
+      par_params.rounds = (uint32_t)r;
+    }
+    if (init == kmcudaInitMethodParallel && P.TupleSize(init_obj) > 2 && P.TupleGetItem(init_obj, 2) != P.None) {
+      const double l = P.FloatAsDouble(P.TupleGetItem(init_obj, 2));
+      const float lf = (float)l;
+      if (P.ErrOccurred() || !(lf > 0.f) || lf - lf != 0.f) {
+        P.ErrClear();
+        return fail(P.ValueError, "k-means||'s oversampling must be a finite number > 0");
+      }
+      par_params.oversampling = lf;
     }
   } else {
     init = kmcudaInitMethodImport;
@@ -364,7 +386,8 @@ PyObject *py_kmeans_cuda(PyObject *, PyObject *args, PyObject *kwargs) {
   int result;
   {
     PyThreadState *ts = P.SaveThread();   // Py_BEGIN_ALLOW_THREADS, python.cc:357
-    result = kmamd_kmeans_weighted(init, &afkmc2_m, tolerance, yinyang_t, metric, n, (uint16_t)d, clusters, seed,
+    const void *init_params = init == kmcudaInitMethodParallel ? (const void *)&par_params : (const void *)&afkmc2_m;
+    result = kmamd_kmeans_weighted(init, init_params, tolerance, yinyang_t, metric, n, (uint16_t)d, clusters, seed,
                                    device, device_ptrs, fp16x2 ? 1 : 0, verbosity, samples, centroids, assignments,
                                    adflag ? &average_distance : nullptr, weights);
     P.RestoreThread(ts);
