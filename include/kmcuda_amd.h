@@ -301,6 +301,33 @@ int kmamd_knn_index_query(kmamd_knn_index *ix, uint32_t k, uint32_t n_queries, c
                           uint32_t *query_assignments_out, int32_t device_ptrs);
 void kmamd_knn_index_destroy(kmamd_knn_index *ix);
 
+/* Multi-probe (approximate) search on the same index: every query looks only at the clusters of its
+ * probe list P(q), nprobe ids wide, 1 <= nprobe <= min(clusters, 64).  The result is a defined object, not "roughly the
+ * neighbours": the list of kmamd_knn_index_query with one more skip rule -- a cluster outside the effective probe set
+ * is never visited.  Own cluster c_q = P(q)[0] first, in ascending corpus order; then the other probed clusters in
+ * ascending id under the same triangle prune; push iff distance <= kth; output in the heap's sorted order with the
+ * exact distances the heap compared.  The effective probe set is the distinct entries of P(q) below `clusters`:
+ * entries equal to `clusters` (kmamd_kmeans_assign_top's filler) and repeated entries are ignored, and the order after
+ * column 0 does not matter.  Slots no probed row fills hold index 0 at FLT_MAX, as in query.  With nprobe = clusters
+ * the lists are those of query with query_assignments = column 0.
+ *   probes      (optional, in) n_queries x nprobe.  Column 0 must be < clusters and name a finite centroid, later
+ *               columns may hold any id <= clusters; anything else is InvalidArguments.  NULL: the lists are
+ *               kmamd_kmeans_assign_top(queries, centroids, nprobe)'s top_assignments, by the same kernels (clusters
+ *               == 1: {0}); a query it finds no centroid for has no cluster.  KMCUDA_AMD_ASSIGN_TOP and
+ *               KMCUDA_AMD_ASSIGN_TOP_ROWS apply.  With KMCUDA_AMD_FP16_STRICT and half rows the ranking is refused
+ *               (InvalidArguments), the caller's lists work.
+ *   probes_out  (optional) n_queries x nprobe: the lists used, in query order.
+ * A query with a NaN or inf feature: indices 0xFFFFFFFF, distances NaN.  k, neighbors, distances, device_ptrs,
+ * KMCUDA_AMD_KNN_QUERY_CHUNK (default: a chunk's heaps and lists within 4 GiB) as in query; n_queries == 0 is success.
+ * The f16-filtered search runs where query's would; every other case (KMCUDA_AMD_KNN_EXACT, KMCUDA_AMD_FP16_STRICT,
+ * KMCUDA_AMD_FILTER=f32, more than 1024 features, data beyond the half range, more than 65536 clusters) takes the
+ * exact probe kernel -- there is no f32-filtered one.  The per-query centroid bounds (KMCUDA_AMD_KNN_TIGHT) are not
+ * used.  KMCUDA_AMD_KNN_STATS prints the search's counters at the end of the call. */
+int kmamd_knn_index_query_probe(kmamd_knn_index *ix, uint32_t k, uint32_t nprobe, uint32_t n_queries,
+                                const void *queries, const uint32_t *probes /* optional, n_queries x nprobe */,
+                                uint32_t *neighbors, float *distances /* optional */,
+                                uint32_t *probes_out /* optional, n_queries x nprobe */, int32_t device_ptrs);
+
 /* Radius search on the same index: the hits of a query are the corpus rows that have a cluster
  * (assignment < clusters) and whose distance to it is <= radius -- the exact distance kmamd_knn_index_query returns and
  * compares (L2 distance / the angular metric's acos value; a NaN distance is no hit; a query with a NaN or inf feature

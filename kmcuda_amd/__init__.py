@@ -5,7 +5,8 @@ Drop-in surface (mirrors the reference's `libKMCUDA` Python module, src/python.c
 Step-level surface for row-sharded multi-process operation: kmcuda_amd.engine.Engine,
 kmcuda_amd.distributed.
 k-NN of new rows against a clustered corpus (beyond the reference): KnnIndex, knn_query; radius search on
-the same index: KnnIndex.query_radius, knn_query_radius.
+the same index: KnnIndex.query_radius, knn_query_radius; multi-probe (approximate) search, only the nprobe nearest
+clusters of every query or the clusters the caller lists: KnnIndex.query / knn_query with nprobe= or probes=.
 New rows assigned to given centroids, with distances and cluster statistics (beyond the reference): kmeans_predict;
 the m nearest centroids of every row, in the order an assignment pass would find them: kmeans_predict_top.
 k-means|| seeding (beyond the reference), stand-alone -- kmeans_seed_parallel -- and as kmeans_cuda(init="k-means||").

@@ -23,7 +23,7 @@ EXPORTS = [
     "kmamd_lloyd_assign", "kmamd_lloyd_assign_exact", "kmamd_set_half_rows", "kmamd_set_row_cache", "kmamd_profile_read_coarse", "kmamd_set_filter", "kmamd_counters_read", "kmamd_counters_reset", "kmamd_yy_hint_stats",
     "kmamd_move_deltas", "kmamd_apply_delta", "kmamd_transpose", "kmamd_afkmc2_draws", "kmamd_reduce_len", "kmamd_reduce_fill",
     "kmamd_reduce_apply", "kmamd_reduce_apply_stop", "kmamd_reduce_apply_prepare", "kmamd_stop_report", "kmamd_stop_clear", "kmamd_centroids_written", "kmamd_set_carry", "kmamd_carry_stats", "kmamd_carry_pair_stats", "kmamd_duo_rows", "kmamd_carry_policy_sim", "kmamd_set_update_mode", "kmamd_last_run_stats", "kmamd_last_run_collective", "kmamd_adjust_exact", "kmamd_yy_configure", "kmamd_yy_init", "kmamd_yy_drifts", "kmamd_yy_filters",
-    "kmamd_knn_index_create", "kmamd_knn_index_query", "kmamd_knn_index_destroy",
+    "kmamd_knn_index_create", "kmamd_knn_index_query", "kmamd_knn_index_query_probe", "kmamd_knn_index_destroy",
     "kmamd_knn_index_radius_count", "kmamd_knn_index_radius_fill",
     "kmamd_kmeans_assign", "kmamd_assigned_distances",
     "kmamd_kmeans_assign_top", "kmamd_assign_top_stats",
@@ -143,6 +143,8 @@ def lib():
     L.kmamd_knn_index_create.argtypes = [ctypes.POINTER(vp), i32, i32, i32, u32, u32, u32, vp, vp, vp, i32, i32]
     L.kmamd_knn_index_query.restype = i32
     L.kmamd_knn_index_query.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, i32]
+    L.kmamd_knn_index_query_probe.restype = i32
+    L.kmamd_knn_index_query_probe.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, vp, i32]
     L.kmamd_knn_index_radius_count.restype = i32
     L.kmamd_knn_index_radius_count.argtypes = [vp, f32, u32, vp, vp, vp, vp, i32]
     L.kmamd_knn_index_radius_fill.restype = i32

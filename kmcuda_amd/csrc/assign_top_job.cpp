@@ -6,6 +6,8 @@
 // per call (launch_centroid_prep: exact squared norms, the transposed panel, the centred panel and its bound).  Rows of
 // up to 256 features take the filtered path, a sub-chunk's score matrix at a time (budgeted like the k-NN search's
 // bound matrix); wider rows, KMCUDA_AMD_ASSIGN_TOP=exact and the rows the filter hands over take the exhaustive kernel.
+// The centroid preparation and the per-chunk ranking are AssignTopRanker's two halves (knn_host.hpp): the k-NN index
+// prepares once and ranks the chunks of its probed queries with them (knn_index.cpp).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,9 +21,88 @@
 using namespace kmx;
 
 namespace {
+constexpr size_t kTopScoreBytes = (size_t)256 << 20;   // a sub-chunk's score matrix
+}  // namespace
+
+namespace kmx {
+
+bool assign_top_exact_only() {
+  const char *v = getenv("KMCUDA_AMD_ASSIGN_TOP");
+  return v && strcmp(v, "exact") == 0;
+}
+
+int AssignTopRanker::prepare(KnnShard &w, int metric_, const float *cen_, uint32_t K_, uint32_t D_, bool exact_only) {
+  metric = metric_; cen = cen_; K = K_; D = D_;
+  const hipStream_t st = w.stream;
+  K_pad = (K + 31) / 32 * 32; Kt = (K + 63) / 64 * 64;
+  DP = exact_only ? 0 : filter_dp_for(D);
+  // (128 rows of scores are the least a launch writes: a panel too wide for the budget takes the exact kernel)
+  if ((size_t)K_pad * sizeof(float) * 128 > kTopScoreBytes) DP = 0;
+  KNN_TRY(w.alloc(&csqr, K));
+  KNN_TRY(w.alloc(&ct, (size_t)D * Kt));
+  KNN_TRY(w.alloc(&evaluated, 1));
+  KMX_HIPRT(hipMemsetAsync(evaluated, 0, sizeof(unsigned long long), st));
+  fa = AssignTopFilter{};
+  if (DP) {
+    float *bias = nullptr, *bias2 = nullptr, *cfil = nullptr, *mu = nullptr;
+    uint32_t *finite = nullptr, *stats = nullptr;
+    KNN_TRY(w.alloc(&bias, K_pad));
+    KNN_TRY(w.alloc(&bias2, K_pad));
+    KNN_TRY(w.alloc(&cfil, (size_t)K_pad * DP));
+    KNN_TRY(w.alloc(&mu, DP));
+    KNN_TRY(w.alloc(&finite, Kt));
+    KNN_TRY(w.alloc(&stats, 16));
+    KMX_HIPRT(hipMemsetAsync(stats, 0, 16 * sizeof(uint32_t), st));
+    KMX_HIPRT(launch_centroid_prep(metric, cen, K, D, K_pad, DP, Kt, csqr, bias, bias2, cfil, ct, mu, false, finite,
+                                   stats, nullptr, nullptr, nullptr, st));
+    fa.metric = metric; fa.D = D; fa.DP = DP; fa.K = K; fa.K_pad = K_pad;
+    fa.centroids = cen; fa.csqr = csqr; fa.cfil = cfil; fa.bias = bias; fa.mu = mu; fa.stats = stats;
+    // the coefficient of the filter bound, as the engine's
+    fa.eps = (float)(1.02 * ((double)D + 12.0) * ldexp(1.0, -24));
+    fa.evaluated = evaluated;
+  } else {
+    KMX_HIPRT(launch_centroid_rows(metric, cen, K, D, Kt, csqr, ct, st));
+  }
+  return 0;
+}
+
+int AssignTopRanker::reserve(KnnShard &w, uint32_t Nc) {
+  sub = 0;   // rows per score matrix: a multiple of the score kernel's 128-row blocks
+  if (!DP) return 0;
+  size_t r = kTopScoreBytes / ((size_t)K_pad * sizeof(float)) / 128 * 128;
+  if (const char *v = getenv("KMCUDA_AMD_ASSIGN_TOP_ROWS")) {   // (tests: several score matrices per chunk)
+    const long long n = atoll(v);
+    if (n > 0 && ((size_t)n + 127) / 128 * 128 < r) r = ((size_t)n + 127) / 128 * 128;
+  }
+  if (r > Nc) r = ((size_t)Nc + 127) / 128 * 128;
+  sub = (uint32_t)r;
+  KNN_TRY(w.alloc(&fa.scores, (size_t)sub * K_pad));
+  KNN_TRY(w.alloc(&fa.meta, sub));
+  KNN_TRY(w.alloc(&fa.fb_rows, Nc));
+  KNN_TRY(w.alloc(&fa.fb_count, 1));
+  return 0;
+}
+
+int AssignTopRanker::rank(const float *rows, uint32_t n, uint32_t m, uint32_t *top, bool exact_only, hipStream_t st) {
+  if (DP && !exact_only) {
+    fa.m = m;
+    KMX_HIPRT(hipMemsetAsync(fa.fb_count, 0, sizeof(uint32_t), st));
+    for (uint32_t r0 = 0; r0 < n; r0 += sub) {
+      const uint32_t nr = n - r0 < sub ? n - r0 : sub;
+      KMX_HIPRT(launch_assign_top_filter(fa, rows + (size_t)r0 * D, nr, r0, top + (size_t)r0 * m, st));
+    }
+    KMX_HIPRT(launch_assign_top_exact(metric, rows, n, D, ct, csqr, K, Kt, m, fa.fb_rows, fa.fb_count, top, evaluated, st));
+  } else {
+    KMX_HIPRT(launch_assign_top_exact(metric, rows, n, D, ct, csqr, K, Kt, m, nullptr, nullptr, top, evaluated, st));
+  }
+  return 0;
+}
+
+}  // namespace kmx
+
+namespace {
 
 constexpr size_t kTopChunkBytes = (size_t)4 << 30;     // a chunk's staged fp32 rows, as kmamd_kmeans_assign's
-constexpr size_t kTopScoreBytes = (size_t)256 << 20;   // a sub-chunk's score matrix
 
 std::mutex g_top_stats_mutex;
 uint64_t g_top_pairs_exact = 0, g_top_pairs_total = 0;
@@ -42,8 +123,7 @@ struct AssignTopJob {
       if (n > 0) chunk = (size_t)n;
     }
     if (chunk < 1) chunk = 1;
-    bool exact_only = false;
-    if (const char *v = getenv("KMCUDA_AMD_ASSIGN_TOP")) exact_only = strcmp(v, "exact") == 0;
+    const bool exact_only = assign_top_exact_only();
 
     KnnShard w;   // owns the call's buffers and its pooled stream
     w.dev = device;
@@ -70,37 +150,10 @@ struct AssignTopJob {
     }
 
     // ---- their preparation: csqr and the transposed panel for the exact keys, the centred panel for the filter ----
-    const uint32_t K_pad = (K + 31) / 32 * 32, Kt = (K + 63) / 64 * 64;
-    uint32_t DP = exact_only ? 0 : filter_dp_for(D);
-    // (128 rows of scores are the least a launch writes: a panel too wide for the budget takes the exact kernel)
-    if ((size_t)K_pad * sizeof(float) * 128 > kTopScoreBytes) DP = 0;
-    float *csqr = nullptr, *ct = nullptr;
-    KNN_TRY(w.alloc(&csqr, K));
-    KNN_TRY(w.alloc(&ct, (size_t)D * Kt));
-    unsigned long long *evaluated = nullptr;
-    KNN_TRY(w.alloc(&evaluated, 1));
-    KMX_HIPRT(hipMemsetAsync(evaluated, 0, sizeof(unsigned long long), st));
-    AssignTopFilter fa{};
-    if (DP) {
-      float *bias = nullptr, *bias2 = nullptr, *cfil = nullptr, *mu = nullptr;
-      uint32_t *finite = nullptr, *stats = nullptr;
-      KNN_TRY(w.alloc(&bias, K_pad));
-      KNN_TRY(w.alloc(&bias2, K_pad));
-      KNN_TRY(w.alloc(&cfil, (size_t)K_pad * DP));
-      KNN_TRY(w.alloc(&mu, DP));
-      KNN_TRY(w.alloc(&finite, Kt));
-      KNN_TRY(w.alloc(&stats, 16));
-      KMX_HIPRT(hipMemsetAsync(stats, 0, 16 * sizeof(uint32_t), st));
-      KMX_HIPRT(launch_centroid_prep(metric, cen, K, D, K_pad, DP, Kt, csqr, bias, bias2, cfil, ct, mu, false, finite,
-                                     stats, nullptr, nullptr, nullptr, st));
-      fa.metric = metric; fa.D = D; fa.DP = DP; fa.K = K; fa.K_pad = K_pad; fa.m = m;
-      fa.centroids = cen; fa.csqr = csqr; fa.cfil = cfil; fa.bias = bias; fa.mu = mu; fa.stats = stats;
-      // the coefficient of the filter bound, as the engine's
-      fa.eps = (float)(1.02 * ((double)D + 12.0) * ldexp(1.0, -24));
-      fa.evaluated = evaluated;
-    } else {
-      KMX_HIPRT(launch_centroid_rows(metric, cen, K, D, Kt, csqr, ct, st));
-    }
+    AssignTopRanker r;
+    KNN_TRY(r.prepare(w, metric, cen, K, D, exact_only));
+    unsigned long long *evaluated = r.evaluated;
+    const uint32_t DP = r.DP;
 
     // ---- one chunk's buffers, reused by every chunk ----
     const uint32_t Nc = (uint32_t)(chunk < N ? chunk : N);
@@ -111,20 +164,7 @@ struct AssignTopJob {
     if (host && fp16) KNN_TRY(w.alloc(&rows16, (size_t)Nc * D));
     if (host) KNN_TRY(w.alloc(&top_buf, (size_t)Nc * m));
     if (host && distances) KNN_TRY(w.alloc(&dist_buf, (size_t)Nc * m));
-    uint32_t sub = 0;   // rows per score matrix: a multiple of the score kernel's 128-row blocks
-    if (DP) {
-      size_t r = kTopScoreBytes / ((size_t)K_pad * sizeof(float)) / 128 * 128;
-      if (const char *v = getenv("KMCUDA_AMD_ASSIGN_TOP_ROWS")) {   // (tests: several score matrices per chunk)
-        const long long n = atoll(v);
-        if (n > 0 && ((size_t)n + 127) / 128 * 128 < r) r = ((size_t)n + 127) / 128 * 128;
-      }
-      if (r > Nc) r = ((size_t)Nc + 127) / 128 * 128;
-      sub = (uint32_t)r;
-      KNN_TRY(w.alloc(&fa.scores, (size_t)sub * K_pad));
-      KNN_TRY(w.alloc(&fa.meta, sub));
-      KNN_TRY(w.alloc(&fa.fb_rows, Nc));
-      KNN_TRY(w.alloc(&fa.fb_count, 1));
-    }
+    KNN_TRY(r.reserve(w, Nc));
 
     for (uint32_t q0 = 0; q0 < N; q0 += Nc) {
       const uint32_t n = N - q0 < Nc ? N - q0 : Nc;
@@ -146,17 +186,7 @@ struct AssignTopJob {
         rows = static_cast<const float *>(samples) + (size_t)q0 * D;
       }
       uint32_t *t = host ? top_buf : top + (size_t)q0 * m;
-      if (DP) {
-        KMX_HIPRT(hipMemsetAsync(fa.fb_count, 0, sizeof(uint32_t), st));
-        for (uint32_t r0 = 0; r0 < n; r0 += sub) {
-          const uint32_t nr = n - r0 < sub ? n - r0 : sub;
-          KMX_HIPRT(launch_assign_top_filter(fa, rows + (size_t)r0 * D, nr, r0, t + (size_t)r0 * m, st));
-        }
-        KMX_HIPRT(launch_assign_top_exact(metric, rows, n, D, ct, csqr, K, Kt, m, fa.fb_rows, fa.fb_count, t,
-                                          evaluated, st));
-      } else {
-        KMX_HIPRT(launch_assign_top_exact(metric, rows, n, D, ct, csqr, K, Kt, m, nullptr, nullptr, t, evaluated, st));
-      }
+      KNN_TRY(r.rank(rows, n, m, t, false, st));
       float *dist = nullptr;
       if (distances) {
         dist = host ? dist_buf : distances + (size_t)q0 * m;

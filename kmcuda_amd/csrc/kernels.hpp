@@ -492,8 +492,15 @@ struct KnnArgs {
   const void *qxs16 = nullptr;
   const uint32_t *qoffsets = nullptr;
   float *outd = nullptr;       // query mode, optional: (p_end - p_base) x k distances beside `out`
+  // Probe mode (kmamd_knn_index_query_probe, the search kernels' PROBE instantiations): the query at
+  // sorted position p visits its own cluster, then only the clusters of plist[(p - p_base) * pw ..]: pw ids in
+  // ascending order without the own cluster, padded with 0xFFFFFFFF (launch_knn_probe_lists).  Unread otherwise.
+  const uint32_t *plist = nullptr;
+  uint32_t pw = 0;
 };
 constexpr int KNN_STATS = 5;
+constexpr uint32_t KNN_PROBE_MAX = 64;        // the widest probe list: one entry per lane
+constexpr uint32_t KNN_PROBE_BITMAP_K = 65536;  // the f16 probe search keeps a K-bit visit map in LDS: 8 KB at most
 // mu (the f16 filter's centre, else null): stats[1] = 1 if a finite row of a cluster leaves the half range once centred
 hipError_t launch_knn_gather(const float *samples, uint32_t N, uint32_t D, uint32_t DP, const uint32_t *inv,
                              float *xs, float *n2s, uint32_t *stats, const float *mu, const uint32_t *offsets, uint32_t K,
@@ -520,11 +527,26 @@ bool launch_knn_query_order(const float *lb, size_t stride, const uint32_t *offs
                             uint32_t p_end, uint32_t *keys_tmp, uint32_t *vals_tmp, uint32_t *keys_sorted,
                             uint32_t *qperm, void *temp, size_t temp_bytes, hipStream_t st, int mode,
                             const float *mydist, const float *R);
+// Probe mode.  probes: Q x pw raw lists in the caller's query order (column 0: the own cluster; K: a filler); qinv:
+// sorted query position -> query.  lists[p * pw ..]: the list of the query at sorted position p as KnnArgs::plist
+// wants it.  An entry > K raises *flag.
+hipError_t launch_knn_probe_lists(const uint32_t *probes, uint32_t pw, uint32_t Q, const uint32_t *qinv, uint32_t K,
+                                  uint32_t *lists, uint32_t *flag, hipStream_t st);
+// qassign[i] = probes[i * pw]: a chunk's own clusters
+hipError_t launch_knn_probe_column0(const uint32_t *probes, uint32_t pw, uint32_t Q, uint32_t *qassign, hipStream_t st);
+// launch_knn_query_order with the key (own cluster, second entry of the raw probe list): pw >= 2
+bool launch_knn_probe_order(const uint32_t *probes, uint32_t pw, const uint32_t *qinv, const uint32_t *offsets,
+                            uint32_t K, uint32_t p_base, uint32_t p_end, uint32_t *keys_tmp, uint32_t *vals_tmp,
+                            uint32_t *keys_sorted, uint32_t *qperm, void *temp, size_t temp_bytes, hipStream_t st);
 // strict_h2 (both): the reference's half2 arithmetic on rows that hold half values (KMCUDA_AMD_FP16_STRICT)
-hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st, bool self = true);
+// probe (query mode only): own cluster, then KnnArgs::plist
+hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st, bool self = true,
+                            bool probe = false);
 hipError_t launch_knn_split(int metric, const float *xs, uint32_t N, uint32_t D, uint32_t DP, const float *mu,
                             void *xs16, float *n2c, float *mux, float *kbias, uint32_t *stats, hipStream_t st);
-hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self = true);
+// probe (query mode only, K <= KNN_PROBE_BITMAP_K): the PROBE instantiations
+hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self = true,
+                                 bool probe = false);
 hipError_t launch_knn_scatter(const uint32_t *sorted_out, const uint32_t *inv, uint32_t p_base, uint32_t p_end,
                               uint32_t k, uint32_t *neighbors, hipStream_t st);
 

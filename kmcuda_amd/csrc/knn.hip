@@ -481,8 +481,11 @@ __global__ __launch_bounds__(256, 2) void knn_filter_kernel(KnnArgs a) {
 // the unfiltered search: one thread per sorted position, every candidate evaluated exactly
 // ---------------------------------------------------------------------------------------
 // SELF as in knn_filter_kernel: the self-join, or a query batch from the KnnArgs::q* buffers (nothing skipped)
-template <int METRIC, bool H2, bool SELF>
+// PROBE (query mode): the own cluster, then the query's probe list (KnnArgs::plist: ascending ids, the own cluster left
+// out, 0xFFFFFFFF behind the last) instead of every cluster -- DESIGN.md 4.12
+template <int METRIC, bool H2, bool SELF, bool PROBE = false>
 __global__ __launch_bounds__(64) void knn_exact_kernel(KnnArgs a) {
+  static_assert(!(PROBE && SELF), "probe lists belong to a query batch");
   const uint32_t qp = a.p_base + blockIdx.x * blockDim.x + threadIdx.x;
   if (qp >= a.p_end) return;
   const uint32_t K = a.K, k = a.k, D = a.D, DP = a.DP;
@@ -505,8 +508,16 @@ __global__ __launch_bounds__(64) void knn_exact_kernel(KnnArgs a) {
   }
   float mndist = 3.402823466e+38f;
   unsigned long long calced = 0;
-  for (uint32_t step = 0; step <= K; step++) {
-    const uint32_t cls = step == 0 ? mycls : step - 1;
+  const uint32_t *plist = PROBE ? a.plist + (size_t)(qp - a.p_base) * a.pw : nullptr;
+  const uint32_t nsteps = PROBE ? a.pw : K;
+  for (uint32_t step = 0; step <= nsteps; step++) {
+    uint32_t cls = step == 0 ? mycls : step - 1;
+    if constexpr (PROBE) {
+      if (step > 0) {
+        cls = plist[step - 1];
+        if (cls >= K) break;   // the list's end
+      }
+    }
     if (step > 0) {
       if (cls == mycls) continue;
       const float cd = a.C[(size_t)cls * K + mycls];
@@ -716,6 +727,62 @@ hipError_t launch_knn_query_clusters(const float *rows, uint32_t Q, uint32_t D, 
   return hipGetLastError();
 }
 
+// Probe mode: the list of the query at sorted position p as the PROBE searches read it.  One wave per
+// query, an entry of the raw list per lane (pw <= 64): the own cluster (column 0), the fillers (K) and repeated ids go,
+// the rest is ranked by counting the smaller survivors and written in ascending order, 0xFFFFFFFF behind the last.
+// An entry > K raises *flag.  (Column 0 itself -- below K, a finite centroid -- is knn_query_clusters_kernel's check:
+// it feeds that kernel as a caller's query_assignments do.)
+__global__ __launch_bounds__(256) void knn_probe_lists_kernel(const uint32_t *__restrict__ probes, uint32_t pw, uint32_t Q,
+                                                              const uint32_t *__restrict__ qinv, uint32_t K,
+                                                              uint32_t *__restrict__ lists, uint32_t *__restrict__ flag) {
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint32_t p = blockIdx.x * 4 + (threadIdx.x >> 6); p < Q; p += gridDim.x * 4) {   // (kernels.hpp: wave_row_grid)
+    const uint32_t *src = probes + (size_t)qinv[p] * pw;
+    const uint32_t v = lane < pw ? src[lane] : 0xFFFFFFFFu;
+    const uint32_t own = __shfl(v, 0);
+    const bool bad = lane < pw && v > K;
+    const bool cand = lane > 0 && lane < pw && v < K && v != own;
+    const unsigned long long cmask = __ballot(cand);
+    bool dup = false;
+    for (uint32_t j = 0; j < pw; j++) {
+      const uint32_t vj = __shfl(v, (int)j);
+      dup |= j < lane && ((cmask >> j) & 1ull) && vj == v;
+    }
+    const bool keep = cand && !dup;
+    const unsigned long long kmask = __ballot(keep);
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < pw; j++) {
+      const uint32_t vj = __shfl(v, (int)j);
+      rank += (((kmask >> j) & 1ull) && vj < v) ? 1u : 0u;
+    }
+    const uint32_t n = (uint32_t)__popcll(kmask);
+    uint32_t *dst = lists + (size_t)p * pw;
+    if (keep) dst[rank] = v;                              // distinct survivors: ranks 0 .. n - 1, each once
+    if (lane >= n && lane < pw) dst[lane] = 0xFFFFFFFFu;
+    if (__any(bad) && lane == 0) atomicOr(flag, 1u);
+  }
+}
+
+__global__ void knn_probe_column0_kernel(const uint32_t *__restrict__ probes, uint32_t pw, uint32_t Q,
+                                         uint32_t *__restrict__ qassign) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < Q) qassign[i] = probes[(size_t)i * pw];
+}
+
+hipError_t launch_knn_probe_column0(const uint32_t *probes, uint32_t pw, uint32_t Q, uint32_t *qassign, hipStream_t st) {
+  if (Q == 0) return hipSuccess;
+  hipLaunchKernelGGL(knn_probe_column0_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, probes, pw, Q, qassign);
+  return hipGetLastError();
+}
+
+hipError_t launch_knn_probe_lists(const uint32_t *probes, uint32_t pw, uint32_t Q, const uint32_t *qinv, uint32_t K,
+                                  uint32_t *lists, uint32_t *flag, hipStream_t st) {
+  if (Q == 0) return hipSuccess;
+  if (pw == 0 || pw > KNN_PROBE_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(knn_probe_lists_kernel, dim3(wave_row_grid(Q)), dim3(256), 0, st, probes, pw, Q, qinv, K, lists, flag);
+  return hipGetLastError();
+}
+
 template <int DP, int METRIC>
 static hipError_t launch_knn_filter_t(const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self) {
   const size_t lds_bytes = (2 * 32 * (DP + 4) + 64 + 8) * sizeof(float);
@@ -752,9 +819,20 @@ static void launch_knn_exact_t(int metric, const KnnArgs &a, bool strict_h2, uin
   }
 }
 
-hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st, bool self) {
+hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st, bool self, bool probe) {
   if (a.p_end <= a.p_base) return hipSuccess;
   const uint32_t grid = (a.p_end - a.p_base + 63) / 64;
+  if (probe) {
+    if (self || !a.plist || a.pw == 0) return hipErrorInvalidValue;
+    if (metric == 0) {
+      if (strict_h2) hipLaunchKernelGGL((knn_exact_kernel<0, true, false, true>), dim3(grid), dim3(64), 0, st, a);
+      else hipLaunchKernelGGL((knn_exact_kernel<0, false, false, true>), dim3(grid), dim3(64), 0, st, a);
+    } else {
+      if (strict_h2) hipLaunchKernelGGL((knn_exact_kernel<1, true, false, true>), dim3(grid), dim3(64), 0, st, a);
+      else hipLaunchKernelGGL((knn_exact_kernel<1, false, false, true>), dim3(grid), dim3(64), 0, st, a);
+    }
+    return hipGetLastError();
+  }
   if (self) launch_knn_exact_t<true>(metric, a, strict_h2, grid, st);
   else launch_knn_exact_t<false>(metric, a, strict_h2, grid, st);
   return hipGetLastError();

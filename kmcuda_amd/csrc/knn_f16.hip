@@ -107,8 +107,14 @@ __global__ __launch_bounds__(256) void knn_split_kernel(const float *__restrict_
 // KnnArgs::q* buffers and nothing is skipped (kmamd_knn_index_query).  The candidate side is the same either way, and
 // so is the bound: it is stated for x = the query (its own centred norm, mu.x') against any candidate y (stats[0], the
 // corpus maximum) and never assumes that x is a corpus row.
-template <int DP, int METRIC, bool FASTX, bool SELF>
+// PROBE (query mode): a query visits its own cluster and the clusters of its probe list only
+// (KnnArgs::plist).  The block walks the UNION of its queries' lists -- a K-bit map in LDS, built in the prologue --
+// instead of 0..K-1, so the barrier per step is paid per cluster somebody probes; a query takes part in a step iff the
+// cluster is the next entry of its own list (a cursor per operand set: the lists and the walk both ascend).  Whatever
+// skips a barrier is decided from the map, offsets and C alone: block-uniform.
+template <int DP, int METRIC, bool FASTX, bool SELF, bool PROBE = false>
 __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void knn_filter_f16_kernel(KnnArgs a) {
+  static_assert(!(PROBE && SELF), "probe lists belong to a query batch");
   constexpr int WV = knn16_waves(DP), NSET = knn16_nset(DP);
   constexpr int NKH = DP / 2;   // features per half-wave
   constexpr int KS = NKH / 8;   // k-steps = 16-byte chunks per half row
@@ -125,6 +131,7 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
   constexpr uint32_t TILES = (uint32_t)(NBUF * TILEB);
   const uint32_t bias0 = lds0 + TILES;                       // NBUF x 64 floats
   uint32_t *flags = reinterpret_cast<uint32_t *>(lds2 + TILES + NBUF * 256);  // 2 x WV words
+  uint32_t *const visit_map = flags + 2 * WV;   // PROBE: (K + 31) / 32 words
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 31, h = lane >> 5;
   const uint32_t K = a.K, k = a.k, D = a.D;
@@ -280,15 +287,66 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
     qn_[e] = 0;
   };
 
+  // PROBE: the block's visit map (the union of its queries' lists) and, per operand set, my query's place in its own
+  // list: pcur entries consumed, pnext the id that comes next (0xFFFFFFFF: none)
+  uint32_t pcur[NSET], pnext[NSET];
+  const uint32_t map_words = PROBE ? (K + 31u) / 32u : 0u;
+  uint32_t map_pos = 0;   // the walk has visited every set bit below this id
+  if constexpr (PROBE) {
+    for (uint32_t i = (uint32_t)tid; i < map_words; i += (uint32_t)(WV * 64)) visit_map[i] = 0u;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < NSET; e++) {
+      pcur[e] = 0;
+      pnext[e] = 0xFFFFFFFFu;
+      if (live[e]) {
+        const uint32_t *pl = a.plist + (size_t)(qp[e] - a.p_base) * a.pw;
+        pnext[e] = pl[0];
+        if (h == 0) {
+          for (uint32_t j = 0; j < a.pw; j++) {
+            const uint32_t c = pl[j];
+            if (c >= K) break;   // the list's end
+            atomicOr(&visit_map[c >> 5], 1u << (c & 31u));
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+
   unsigned long long calced = 0, scored = 0, useful = 0, scored_sets = 0;   // wave-uniform (scalar registers)
   int ph = 0;
-  for (uint32_t step = 0; step <= K; step++) {
-    const uint32_t cls = step == 0 ? cls0 : step - 1;
+  for (uint32_t step = 0; PROBE || step <= K; step++) {
+    uint32_t cls = step == 0 ? cls0 : step - 1;
+    if constexpr (PROBE) {
+      if (step > 0) {
+        // the next set bit of the map (every lane reads the same words: block-uniform)
+        uint32_t w = map_pos >> 5, m = 0;
+        if (w < map_words) m = visit_map[w] & (0xFFFFFFFFu << (map_pos & 31u));
+        while (m == 0u && ++w < map_words) m = visit_map[w];
+        if (m == 0u) break;
+        cls = __builtin_amdgcn_readfirstlane((w << 5) + (uint32_t)__ffs((int)m) - 1u);
+        map_pos = cls + 1u;
+      }
+    }
     if (step > 0 && cls == cls0) continue;
     const uint32_t beg = a.offsets[cls], end = a.offsets[cls + 1];
     bool pruned[NSET];
 #pragma unroll
     for (int e = 0; e < NSET; e++) pruned[e] = !live[e];
+    if constexpr (PROBE) {
+      if (step > 0) {   // (ahead of every `continue`: the cursors follow the walk)
+#pragma unroll
+        for (int e = 0; e < NSET; e++) {
+          const bool member = pnext[e] == cls;
+          if (member) {
+            pcur[e]++;
+            pnext[e] = pcur[e] < a.pw ? a.plist[(size_t)(qp[e] - a.p_base) * a.pw + pcur[e]] : 0xFFFFFFFFu;
+          }
+          pruned[e] = pruned[e] || !member;
+        }
+      }
+    }
     if (step > 0) {
       const float cd = a.C[(size_t)cls * K + cls0];
       if (cd != cd) continue;                     // knn.cu:219-221 (block-uniform)
@@ -535,9 +593,47 @@ static hipError_t launch_knn_f16_t(const KnnArgs &a, uint32_t nblocks, hipStream
   return hipGetLastError();
 }
 
-hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self) {
+// the PROBE instantiations (query mode): the tile ring's LDS plus the K-bit visit map
+template <int DP, int METRIC>
+static hipError_t launch_knn_f16_probe_t(const KnnArgs &a, uint32_t nblocks, hipStream_t st) {
+  const size_t lds_bytes = (size_t)knn16_nbuf(DP) * (32 * knn16_sub(DP) * DP * 2) + knn16_nbuf(DP) * 256 + 2 * knn16_waves(DP) * 4 +
+                           (size_t)((a.K + 31u) / 32u) * 4;
+  if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, true, false, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, false, false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+  }
+  if (a.D == (uint32_t)DP)
+    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, true, false, true>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
+  else
+    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, false, false, true>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self, bool probe) {
   if (nblocks == 0) return hipSuccess;
-#define KMX_KNN16_CASE(dp)                                                                                 \
+  if (probe) {
+    if (self || !a.plist || a.pw == 0 || a.K > KNN_PROBE_BITMAP_K) return hipErrorInvalidValue;
+#define KMX_KNN16_PROBE_CASE(dp) \
+  case dp:                       \
+    return metric == 0 ? launch_knn_f16_probe_t<dp, 0>(a, nblocks, st) : launch_knn_f16_probe_t<dp, 1>(a, nblocks, st)
+    switch (a.DP) {
+      KMX_KNN16_PROBE_CASE(16);
+      KMX_KNN16_PROBE_CASE(32);
+      KMX_KNN16_PROBE_CASE(64);
+      KMX_KNN16_PROBE_CASE(128);
+      KMX_KNN16_PROBE_CASE(256);
+      KMX_KNN16_PROBE_CASE(512);
+      KMX_KNN16_PROBE_CASE(768);
+      KMX_KNN16_PROBE_CASE(1024);
+      default: return hipErrorInvalidValue;
+    }
+#undef KMX_KNN16_PROBE_CASE
+  }
+#define KMX_KNN16_CASE(dp)                                                                                \
   case dp:                                                                                                 \
     return self ? (metric == 0 ? launch_knn_f16_t<dp, 0, true>(a, nblocks, st) : launch_knn_f16_t<dp, 1, true>(a, nblocks, st)) \
                 : (metric == 0 ? launch_knn_f16_t<dp, 0, false>(a, nblocks, st) : launch_knn_f16_t<dp, 1, false>(a, nblocks, st))

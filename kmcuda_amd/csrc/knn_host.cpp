@@ -243,8 +243,9 @@ std::vector<uint32_t> knn_xcd_plan(const std::vector<uint32_t> &plan) {
 }
 
 int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path, const KnnSwitches &sw,
-               uint32_t nblocks, bool self, int verbosity) {
+               uint32_t nblocks, bool self, int verbosity, const uint32_t *probes, const uint32_t *qinv) {
   const bool f16 = path.use_f16;
+  const bool probe = a.plist != nullptr;
   const hipStream_t st = s.stream;
   a.xs = s.xs; a.n2s = f16 ? s.n2c : s.n2s; a.inv = s.inv; a.offsets = s.offsets; a.mydist = s.mydist; a.R = s.R;
   a.C = s.C; a.stats = f16 ? s.stats_c : s.stats; a.N = s.N; a.D = s.D; a.DP = s.DP; a.K = s.K;
@@ -255,7 +256,20 @@ int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path,
   // the triangle bound for it).  4 K bytes per query; without that memory, or with KMCUDA_AMD_KNN_TIGHT=0, the
   // reference's prune test decides alone.  Same neighbour lists either way.
   const uint32_t len = a.p_end - a.p_base;
-  if (f16 && s.metric == 0 && s.D <= 1024 && len != 0 && sw.tight) {
+  if (probe) {
+    // Probe mode: no second cluster test -- the probed clusters are the nearest ones, where it rarely
+    // fires, and its table is K floats per query.  The queries of a cluster go into waves by the second entry of their
+    // raw lists instead (the query order is an optimisation: sorted-position order without it).
+    if (self) return kmcudaInvalidArguments;
+    if (f16 && len != 0 && sw.order != 0 && probes && qinv && a.pw >= 2) {
+      if (!x.qperm && hipMalloc((void **)&x.qperm, x.rows * sizeof(uint32_t)) != hipSuccess) x.qperm = nullptr;
+      if (x.qperm && launch_knn_probe_order(probes, a.pw, qinv, a.qoffsets, s.K, a.p_base, a.p_end, x.keys_tmp, x.vals_tmp,
+                                            x.keys_sorted, x.qperm, x.sort_temp, x.sort_bytes, st))
+        a.qperm = x.qperm;
+      else
+        (void)hipGetLastError();
+    }
+  } else if (f16 && s.metric == 0 && s.D <= 1024 && len != 0 && sw.tight) {
     if (!x.lb && hipMalloc((void **)&x.lb, (size_t)s.K * x.rows * sizeof(float)) != hipSuccess) {
       x.lb = nullptr;
       (void)hipGetLastError();
@@ -280,9 +294,13 @@ int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path,
         (void)hipGetLastError();
     }
   }
-  KMX_HIPRT(!path.dp_filter ? launch_knn_exact(s.metric, a, path.strict_h2, st, self)
-            : f16           ? launch_knn_filter_f16(s.metric, a, nblocks, st, self)
-                            : launch_knn_filter(s.metric, a, nblocks, st, self));
+  if (probe)   // (no f32-filtered probe kernel: that path takes the exact one, as the radius search's does)
+    KMX_HIPRT(f16 ? launch_knn_filter_f16(s.metric, a, nblocks, st, false, true)
+                  : launch_knn_exact(s.metric, a, path.strict_h2, st, false, true));
+  else
+    KMX_HIPRT(!path.dp_filter ? launch_knn_exact(s.metric, a, path.strict_h2, st, self)
+              : f16           ? launch_knn_filter_f16(s.metric, a, nblocks, st, self)
+                              : launch_knn_filter(s.metric, a, nblocks, st, self));
   return 0;
 }
 

@@ -151,14 +151,38 @@ std::vector<uint32_t> knn_xcd_plan(const std::vector<uint32_t> &plan);
 // One search launch on s.stream.  The caller fills the query side of `a` (p_base / p_end, blocks, heaps, out and, with
 // self = false, the q* fields); this adds the corpus side from the prepared shard, the per-query centroid bounds and
 // the query order of the f16 search (buffers and sort scratch: `x`, with x.rows >= p_end - p_base) and picks the
-// kernel `path` names.
+// kernel `path` names.  Probe mode (a.plist set, self = false): the PROBE kernels -- the f16 one where
+// `path` names the f16 filter, else the exact one -- without the centroid bounds; probes / qinv (the chunk's raw lists
+// and sorted position -> query, optional) give the f16 search its query order.
 int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path, const KnnSwitches &sw,
-               uint32_t nblocks, bool self, int verbosity);
+               uint32_t nblocks, bool self, int verbosity, const uint32_t *probes = nullptr,
+               const uint32_t *qinv = nullptr);
 
 // Rows [p_base, p_end) of a search's output (`out` on src_dev in sorted-position order; null: 0xFFFFFFFF, no
 // neighbours) into the caller's `neighbors` on device `dev`, by `inv` of src_dev; waits for it.
 int knn_scatter_on(int dev, int src_dev, const uint32_t *out, const uint32_t *inv, uint32_t N, uint32_t p_base,
                    uint32_t p_end, uint32_t k, uint32_t *neighbors);
+
+// The ranking of kmamd_kmeans_assign_top in its two parts (assign_top_job.cpp), so that the k-NN index
+// can prepare its centroids once and rank every chunk of probed queries with the same kernels.
+struct AssignTopRanker {
+  int metric = 0;
+  uint32_t D = 0, K = 0, K_pad = 0, Kt = 0;
+  uint32_t DP = 0;   // the filter's width; 0: the exhaustive kernel alone
+  const float *cen = nullptr;
+  float *csqr = nullptr, *ct = nullptr;
+  unsigned long long *evaluated = nullptr;   // exact keys computed so far (zeroed by prepare)
+  AssignTopFilter fa{};
+  uint32_t sub = 0;   // rows per score matrix
+  // The centroid preparation, enqueued on w.stream; the buffers belong to `w`.  cen: K x D fp32 on w's device.
+  // exact_only: no filter panel (KMCUDA_AMD_ASSIGN_TOP=exact for the whole call)
+  int prepare(KnnShard &w, int metric, const float *cen, uint32_t K, uint32_t D, bool exact_only);
+  // the buffers of one chunk of up to Nc rows (KMCUDA_AMD_ASSIGN_TOP_ROWS applies); they belong to `w`
+  int reserve(KnnShard &w, uint32_t Nc);
+  // top[n x m] of the chunk's n rows (fp32, on the device), enqueued on st; exact_only: the exhaustive kernel this time
+  int rank(const float *rows, uint32_t n, uint32_t m, uint32_t *top, bool exact_only, hipStream_t st);
+};
+bool assign_top_exact_only();   // KMCUDA_AMD_ASSIGN_TOP=exact
 
 // knn_cuda() behind its argument checks (knn_job.cpp); nvirtual: KMCUDA_AMD_VIRTUAL_SHARDS (test hook)
 int knn_job_run(const std::vector<int> &devs, int nvirtual, uint32_t k, const KnnCorpus &corpus, int verbosity,

@@ -10,6 +10,10 @@
 // other clusters in ascending id under the triangle prune, push iff distance <= kth, output popped from the heap.  c_q
 // is its nearest centroid (kmamd_lloyd_assign's arithmetic and tie rule) unless the caller passes one; any cluster id
 // gives the same lists (the prune is rigorous), only the work differs.
+//
+// query_probe() is the approximate mode: the same procedure with one more skip rule -- a cluster that
+// is not in the query's probe list is never visited.  The lists are the caller's, or the ranking of
+// kmamd_kmeans_assign_top run here on the index's own centroids (AssignTopRanker, assign_top_job.cpp).
 #include <math.h>
 #include <stdio.h>
 
@@ -31,10 +35,12 @@ class KnnIndex {
   KnnPath path;
   int verbosity = 0;
   bool fp16 = false;
+  bool said_exact = false;   // the path's "no matrix-core filter" line has been printed (probe mode says it otherwise)
 
   int build(int device, const KnnCorpus &c, int verbosity_) {
     fp16 = c.fp16; verbosity = verbosity_;
     path = knn_choose_path(c.D, fp16, verbosity, knn_switches());
+    said_exact = !path.dp_filter;
     s.dev = device;
     KnnShard *one = &s;
     bool left_half_range = false;
@@ -62,8 +68,15 @@ class KnnIndex {
     return 0;
   }
 
+  // probe mode: the centroid preparation of the ranking (kmamd_kmeans_assign_top's), made on the first probed query
+  // that brings no lists of its own and kept until the index goes (its buffers belong to `s`)
+  AssignTopRanker ranker;
+  bool ranker_ready = false;
+
   int query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
             float *distances, uint32_t *qassign_out, int32_t device_ptrs);
+  int query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queries, const uint32_t *probes_in,
+                  uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs);
   int radius(bool fill, float r, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *counts,
              uint32_t *qassign_out, const uint64_t *offsets, uint32_t *neighbors, float *distances, int32_t device_ptrs);
 };
@@ -71,6 +84,17 @@ class KnnIndex {
 // The per-call buffers of a query batch (sized for one chunk of at most Qc queries, reused by every chunk) and the
 // preparation of a chunk, shared by query() and the radius calls: upload and half widening, the queries' clusters,
 // the CSR of the chunk, the cluster-sorted rows with their norms and member distances, the f16 split and the block plan.
+// The probe side of a chunk: raw = the chunk's n x pw lists in query order (the caller's slice, or the
+// ranking's), lists = what the PROBE kernels read, per sorted query position (launch_knn_probe_lists)
+struct ProbeSide {
+  uint32_t pw = 0;
+  const uint32_t *probes_in = nullptr;   // the caller's lists (whole batch), or null: ranked here
+  uint32_t *probes_out = nullptr;        // optional (whole batch)
+  AssignTopRanker ranker;                // (computed lists, K >= 2)
+  bool rank_exact = false;
+  uint32_t *raw = nullptr, *lists = nullptr;
+};
+
 struct QueryChunk {
   KnnShard w;   // owns the buffers; enqueues on the index's stream (nothing to release)
   uint32_t Qc = 0;
@@ -130,8 +154,9 @@ struct QueryChunk {
   }
 
   // queries [q0, q0 + n) of the batch; waits for the stream once (the CSR offsets and the flags reach the host)
+  // pr: probe mode -- the chunk's lists are fetched or ranked, their column 0 stands in for qassign_in
   int prepare(const KnnIndex &ix, uint32_t q0, uint32_t n, const void *queries, const uint32_t *qassign_in,
-              uint32_t *qassign_out, bool host) {
+              uint32_t *qassign_out, bool host, ProbeSide *pr = nullptr) {
     const KnnShard &s = ix.s;
     const uint32_t D = s.D, DP = s.DP, K = s.K;
     const hipStream_t st = s.stream;
@@ -145,7 +170,20 @@ struct QueryChunk {
       KMX_HIPCP(hipMemcpyAsync(qrows, src, (size_t)n * D * sizeof(float), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
     }
     // ---- their clusters ----
-    if (qassign_in) {
+    if (pr) {
+      const size_t cnt = (size_t)n * pr->pw;
+      if (pr->probes_in)
+        KMX_HIPCP(hipMemcpyAsync(pr->raw, pr->probes_in + (size_t)q0 * pr->pw, cnt * sizeof(uint32_t),
+                                 host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+      else if (K == 1)   // (the ranking kernels need two centroids: P = {0})
+        KMX_HIPRT(hipMemsetAsync(pr->raw, 0, cnt * sizeof(uint32_t), st));
+      else
+        KNN_TRY(pr->ranker.rank(qrows, n, pr->pw, pr->raw, pr->rank_exact, st));
+      if (pr->probes_out)
+        KMX_HIPCP(hipMemcpyAsync(pr->probes_out + (size_t)q0 * pr->pw, pr->raw, cnt * sizeof(uint32_t),
+                                 host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+      KMX_HIPRT(launch_knn_probe_column0(pr->raw, pr->pw, n, qassign, st));
+    } else if (qassign_in) {
       KMX_HIPCP(hipMemcpyAsync(qassign, qassign_in + q0, (size_t)n * sizeof(uint32_t),
                                host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
     } else {
@@ -161,6 +199,7 @@ struct QueryChunk {
     KMX_HIPRT(launch_knn_query_clusters(qrows, n, D, qassign, K, s.centroids, qeff, qstats + 2, st));
     KMX_HIPRT(launch_inverse_assignments(qeff, n, K, w.scratch.keys_tmp, w.scratch.vals_tmp, w.scratch.keys_sorted, qinv, qoffsets, w.scratch.sort_temp,
                                          w.scratch.sort_bytes, st));
+    if (pr) KMX_HIPRT(launch_knn_probe_lists(pr->raw, pr->pw, n, qinv, K, pr->lists, qstats + 2, st));
     // (with mu: the queries raise the half-range flag qstats[1] as the corpus rows do)
     KMX_HIPRT(launch_knn_gather(qrows, n, D, DP, qinv, qxs, qn2p, qstats, ix.path.use_f16 ? s.mu : nullptr, qoffsets, K, st));
     KMX_HIPRT(launch_knn_member(s.metric, qxs, n, D, DP, qoffsets, K, s.centroids, qmydist, qrdist, ix.path.strict_h2, st));
@@ -168,13 +207,15 @@ struct QueryChunk {
     KMX_HIPCP(hipMemcpyAsync(offs.data(), qoffsets, (K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KMX_HIPCP(hipMemcpyAsync(flags, qstats, sizeof(flags), hipMemcpyDeviceToHost, st));
     KMX_HIPRT(hipStreamSynchronize(st));
-    if (flags[2]) return kmcudaInvalidArguments;   // a caller-supplied cluster id >= K or with a non-finite centroid
+    // a caller-supplied cluster id >= K or with a non-finite centroid, or an entry > K in a caller's probe list (a row
+    // the ranking fills with K has no cluster: no error)
+    if (flags[2] && !(pr && !pr->probes_in)) return kmcudaInvalidArguments;
     // which search this chunk takes: a query that leaves the half range sends it from the f16 filter to the f32 one
     // (D <= 256) or to the exact search, as a corpus row sends knn_cuda()
     cp = ix.path;
     if (knn_leaves_half_range(&cp.use_f16, &cp.dp_filter, D, flags[1]) && ix.verbosity > 0)
       printf("k-NN query: a centred query leaves the half range, %s\n",
-             cp.dp_filter ? "the f32 matrix-core filter" : "the exact search");
+             cp.dp_filter && !pr ? "the f32 matrix-core filter" : "the exact search");
     if (cp.use_f16) KMX_HIPRT(launch_knn_split(s.metric, qxs, n, D, DP, s.mu, qxs16, qn2c, qmux, qkbias, qstats + 3, st));
     assigned = offs[K];
     knn_block_plan(offs.data(), K, knn_qpb(cp.use_f16, DP), &plan);
@@ -191,7 +232,7 @@ struct QueryChunk {
   }
 };
 
-// KMCUDA_AMD_KNN_STATS: what the searches of a radius call did (KnnArgs::calced), then the counters start over
+// KMCUDA_AMD_KNN_STATS: what the searches of a radius or probe call did (KnnArgs::calced), then the counters start over
 int report_stats(const KnnIndex &ix, const char *what) {
   unsigned long long cs[KNN_STATS] = {0, 0, 0, 0, 0};
   KMX_HIPCP(hipMemcpy(cs, ix.s.calced, sizeof(cs), hipMemcpyDeviceToHost));
@@ -259,6 +300,89 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
     if (verbosity > 0) printf("k-NN query failed: %s\n", hipGetErrorString(hipGetLastError()));
     return kmcudaRuntimeError;
   }
+  return 0;
+}
+
+// One probed query batch: query() with the cluster loop driven by every query's probe list.
+int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queries, const uint32_t *probes_in,
+                          uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs) {
+  if (Q == 0) return 0;
+  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
+  const uint32_t K = s.K;
+  const hipStream_t st = s.stream;
+  const KnnSwitches sw = knn_switches();
+  // (no lb table here: the heaps and the lists of a chunk within the budget)
+  size_t chunk = kQueryChunkBytes / (4 * ((size_t)pw + 2 * (size_t)k));
+  if (sw.query_chunk) chunk = sw.query_chunk;
+  if (chunk < 1) chunk = 1;
+  const uint32_t Qc = (uint32_t)(chunk < Q ? chunk : Q);
+  const bool host = device_ptrs < 0;
+
+  QueryChunk c;
+  KNN_TRY(c.init(*this, Qc, false));
+  KnnShard &w = c.w;
+  ProbeSide pr;
+  pr.pw = pw; pr.probes_in = probes_in; pr.probes_out = probes_out;
+  KNN_TRY(w.alloc(&pr.raw, (size_t)Qc * pw));
+  KNN_TRY(w.alloc(&pr.lists, (size_t)Qc * pw));
+  if (!probes_in && K >= 2) {
+    if (!ranker_ready) {
+      KNN_TRY(ranker.prepare(s, s.metric, s.centroids, K, s.D, false));
+      ranker_ready = true;
+    }
+    pr.ranker = ranker;
+    pr.rank_exact = assign_top_exact_only();
+    KNN_TRY(pr.ranker.reserve(w, Qc));
+  }
+  float *heaps = nullptr, *outd = nullptr, *dist_dev = nullptr;
+  uint32_t *out = nullptr, *nb_dev = nullptr;
+  KNN_TRY(w.alloc(&heaps, (size_t)Qc * 2 * k));
+  KNN_TRY(w.alloc(&out, (size_t)Qc * k));
+  KNN_TRY(w.alloc(&outd, (size_t)Qc * k));
+  if (host) {
+    KNN_TRY(w.alloc(&nb_dev, (size_t)Qc * k));
+    if (distances) KNN_TRY(w.alloc(&dist_dev, (size_t)Qc * k));
+  }
+  if (sw.stats) KMX_HIPRT(hipMemsetAsync(s.calced, 0, KNN_STATS * sizeof(unsigned long long), st));
+  bool said = said_exact || verbosity <= 0;
+  for (uint32_t q0 = 0; q0 < Q; q0 += Qc) {
+    const uint32_t n = Q - q0 < Qc ? Q - q0 : Qc;
+    KNN_TRY(c.prepare(*this, q0, n, queries, nullptr, nullptr, host, &pr));
+    // There is no f32-filtered probe search (as there is no such radius search): whatever is not the f16 filter takes
+    // the exact kernel, and so does a K the f16 search's visit map has no room for.  (The chunk was split and planned
+    // for the f16 search only if it stays one.)
+    if (c.cp.use_f16 && K > KNN_PROBE_BITMAP_K) c.cp.use_f16 = false;
+    if (!c.cp.use_f16 && !said) {
+      printf("k-NN probe query: every candidate is evaluated with the exact arithmetic (no f32-filtered probe search)\n");
+      said = true;
+    }
+    KMX_HIPRT(hipMemsetAsync(out, 0xFF, (size_t)n * k * sizeof(uint32_t), st));
+    KMX_HIPRT(hipMemsetAsync(outd, 0xFF, (size_t)n * k * sizeof(float), st));
+    KnnArgs a;
+    c.fill_args(&a);
+    a.k = k; a.heaps = heaps; a.out = out; a.outd = outd;
+    a.p_end = c.cp.use_f16 ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
+    a.plist = pr.lists; a.pw = pw;
+    KNN_TRY(knn_search(s, w.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity, pr.raw, c.qinv));
+    // ---- back in query order ----
+    uint32_t *nb = host ? nb_dev : neighbors + (size_t)q0 * k;
+    KMX_HIPRT(launch_knn_scatter(out, c.qinv, 0, n, k, nb, st));
+    if (distances) {
+      float *dd = host ? dist_dev : distances + (size_t)q0 * k;
+      KMX_HIPRT(launch_knn_scatter(reinterpret_cast<const uint32_t *>(outd), c.qinv, 0, n, k, reinterpret_cast<uint32_t *>(dd), st));
+    }
+    if (host) {
+      KMX_HIPCP(hipMemcpyAsync(neighbors + (size_t)q0 * k, nb_dev, (size_t)n * k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      if (distances)
+        KMX_HIPCP(hipMemcpyAsync(distances + (size_t)q0 * k, dist_dev, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    // (the next chunk overwrites these buffers: the stream orders it behind this one's scatter and copies)
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    if (verbosity > 0) printf("k-NN probe query failed: %s\n", hipGetErrorString(hipGetLastError()));
+    return kmcudaRuntimeError;
+  }
+  if (sw.stats) KNN_TRY(report_stats(*this, "probe query"));
   return 0;
 }
 
@@ -480,6 +604,22 @@ int kmamd_knn_index_query(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, co
   if (!queries || !neighbors) return kmcudaInvalidArguments;
   if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
   return ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs);
+}
+
+int kmamd_knn_index_query_probe(kmamd_knn_index *h, uint32_t k, uint32_t nprobe, uint32_t n_queries,
+                                const void *queries, const uint32_t *probes, uint32_t *neighbors, float *distances,
+                                uint32_t *probes_out, int32_t device_ptrs) {
+  if (!h) return kmcudaInvalidArguments;
+  KnnIndex &ix = h->ix;
+  if (k == 0 || k > 65535u || k > ix.s.N) return kmcudaInvalidArguments;
+  if (nprobe < 1 || nprobe > KNN_PROBE_MAX || nprobe > ix.s.K) return kmcudaInvalidArguments;
+  if (device_ptrs >= 0 && device_ptrs != ix.s.dev) return kmcudaInvalidArguments;
+  // the reference's half2 arithmetic has no ranking (kmamd_kmeans_assign_top refuses it likewise): the caller's lists only
+  if (!probes && ix.fp16 && (ix.path.strict_h2 || knn_switches().fp16_strict)) return kmcudaInvalidArguments;
+  if (n_queries == 0) return kmcudaSuccess;
+  if (!queries || !neighbors) return kmcudaInvalidArguments;
+  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
+  return ix.query_probe(k, nprobe, n_queries, queries, probes, neighbors, distances, probes_out, device_ptrs);
 }
 
 static bool radius_call_ok(kmamd_knn_index *h, float radius, int32_t device_ptrs) {

@@ -163,6 +163,45 @@ bool launch_knn_query_order(const float *lb, size_t stride, const uint32_t *offs
          hipGetLastError() == hipSuccess;
 }
 
+// Probe mode: key = (own cluster, the second entry of the query's raw probe list: its second-nearest
+// centroid when the ranking made the list).  Queries with the same neighbour cluster share most of their probe sets, so
+// the union a block walks, and the tiles a wave scores for one query alone, shrink.  Nothing but the grouping changes.
+__global__ void knn_probe_keys_kernel(const uint32_t *__restrict__ probes, uint32_t pw, const uint32_t *__restrict__ qinv,
+                                      const uint32_t *__restrict__ offsets, uint32_t K, uint32_t p_base, uint32_t p_end,
+                                      uint32_t *__restrict__ keys, uint32_t *__restrict__ vals) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p_end - p_base) return;
+  const uint32_t p = p_base + i;
+  uint32_t lo = 0, hi = K;   // the cluster of sorted position p: offsets[cls] <= p < offsets[cls + 1]
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (offsets[mid] <= p) lo = mid; else hi = mid;
+  }
+  const uint32_t second = probes[(size_t)qinv[p] * pw + 1];
+  vals[i] = p;
+  keys[i] = lo * (K + 1) + (second < K ? second : K);
+}
+
+bool launch_knn_probe_order(const uint32_t *probes, uint32_t pw, const uint32_t *qinv, const uint32_t *offsets,
+                            uint32_t K, uint32_t p_base, uint32_t p_end, uint32_t *keys_tmp, uint32_t *vals_tmp,
+                            uint32_t *keys_sorted, uint32_t *qperm, void *temp, size_t temp_bytes, hipStream_t st) {
+  if (p_end <= p_base || pw < 2 || K > 65535u) return false;
+  const uint64_t key_max = (uint64_t)K * (K + 1);
+  if (key_max > 0xFFFFFFFFull) return false;
+  const uint32_t n = p_end - p_base;
+  size_t need = 0;
+  if (rocprim::radix_sort_pairs(nullptr, need, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr,
+                                (uint32_t *)nullptr, (size_t)n, 0u, bits_for(key_max), st) != hipSuccess ||
+      need > temp_bytes)
+    return false;
+  hipLaunchKernelGGL(knn_probe_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, st, probes, pw, qinv, offsets, K, p_base,
+                     p_end, keys_tmp, vals_tmp);
+  size_t bytes = temp_bytes;
+  return rocprim::radix_sort_pairs(temp, bytes, (const uint32_t *)keys_tmp, keys_sorted, (const uint32_t *)vals_tmp,
+                                   qperm, (size_t)n, 0u, bits_for(key_max), st) == hipSuccess &&
+         hipGetLastError() == hipSuccess;
+}
+
 // ---- move events --------------------------------------------------------------------------
 // uncompacted form (two slots per row, sentinel keys): the strict-parity update sorts all of them
 __global__ void move_events_kernel(const uint32_t *__restrict__ prev, const uint32_t *__restrict__ cur, uint32_t N,

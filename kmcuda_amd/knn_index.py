@@ -14,12 +14,19 @@ distances) -- the brute-force set, not the outcome of a visiting procedure (DESI
 gives for it as one more row of its cluster (its nearest centroid unless `query_assignments` says otherwise), WITHOUT
 skipping anything: own cluster first, then the others in ascending id under the triangle prune.
 
+Multi-probe (approximate) search, DESIGN.md 4.12: index.query(queries, k, nprobe=p) looks only at every query's p
+nearest clusters (kmeans_predict_top's ranking, by the same kernels), index.query(queries, k, probes=P) at the clusters
+the caller names (Q x p; column 0 is the query's own cluster, K is a filler).  The list is exactly what the procedure
+above yields when a cluster outside the probe set is never visited: reproducible, and equal to the exact list at p = K.
+return_probes appends the lists used.
+
 numpy in, numpy out (neighbors uint32, distances float32, assignments uint32).  torch tensors on the index's device
 in, torch tensors on that device out (neighbors / assignments int32: 0xFFFFFFFF reads -1), with no host round trip;
 the call orders with torch's work on the device (it waits for the device first and its outputs are complete when
 it returns).  float16 inputs select fp16x2: fp32 arithmetic on the half values, as knn_cuda().
 """
 import ctypes
+import os
 
 import numpy
 
@@ -128,6 +135,73 @@ def _check_queries(queries, fp16, d, clusters, query_assignments, device):
     return q, nq, q_dev, qa
 
 
+PROBE_MAX = 64   # the widest probe list (kmamd_knn_index_query_probe)
+
+
+def _fp16_strict():
+    try:
+        return int(os.environ.get("KMCUDA_AMD_FP16_STRICT", "0") or 0) != 0
+    except ValueError:
+        return False
+
+
+def _check_probes(nprobe, probes, nq, clusters, q_dev, query_assignments, device, fp16=False):
+    """(nprobe, probes or None) of a probed query, or (None, None): the exact one."""
+    if nprobe is None and probes is None:
+        return None, None
+    if probes is None and fp16 and _fp16_strict():
+        raise ValueError("KMCUDA_AMD_FP16_STRICT=1: the reference's half2 arithmetic has no ranking of the centroids "
+                         "(kmeans_predict_top refuses it too): pass \"probes\"")
+    if query_assignments is not None:
+        raise ValueError("\"query_assignments\" cannot be combined with \"nprobe\" / \"probes\": column 0 of the probe "
+                         "list is the query's own cluster")
+    if nprobe is not None:
+        if isinstance(nprobe, bool) or not isinstance(nprobe, (int, numpy.integer)):
+            raise TypeError("\"nprobe\" must be an integer")
+        nprobe = int(nprobe)
+    p = None
+    if probes is not None:
+        if _is_torch(probes) != q_dev:
+            raise TypeError("\"probes\" must be of the same kind as \"queries\" (numpy array or torch tensor)")
+        if _is_torch(probes):
+            import torch
+            if probes.dtype.is_floating_point or probes.dtype == torch.bool:
+                raise TypeError("\"probes\" must be a 2D integer tensor")
+            if probes.dim() != 2:
+                raise ValueError("\"probes\" must be a 2D tensor (queries x nprobe)")
+            if not probes.is_cuda or probes.device.index != device:
+                raise ValueError("\"probes\" must be on the index's device")
+            shape = tuple(int(v) for v in probes.shape)
+            out_of_range = bool(shape[0] and shape[1] and bool(((probes < 0) | (probes > clusters)).any()))
+            p = probes.to(torch.int32).contiguous()
+        else:
+            if not isinstance(probes, numpy.ndarray):
+                probes = numpy.asarray(probes)
+            if probes.dtype.kind not in "iu":
+                raise TypeError("\"probes\" must be a 2D integer numpy array")
+            if probes.ndim != 2:
+                raise ValueError("\"probes\" must be a 2D numpy array (queries x nprobe)")
+            shape = probes.shape
+            out_of_range = bool(probes.size and (probes.min() < 0 or probes.max() > clusters))
+            p = numpy.ascontiguousarray(probes, dtype=numpy.uint32) if not out_of_range else None
+        if shape[0] != nq:
+            raise ValueError("\"probes\" must have one row per query (%d)" % nq)
+        if nprobe is None:
+            nprobe = int(shape[1])
+        elif nprobe != shape[1]:
+            raise ValueError("\"nprobe\" (%d) must equal the width of \"probes\" (%d)" % (nprobe, shape[1]))
+        if out_of_range:
+            raise ValueError("\"probes\" must hold cluster ids in [0, %d] (%d: no cluster)" % (clusters, clusters))
+    if nprobe < 1 or nprobe > min(clusters, PROBE_MAX):
+        raise ValueError("\"nprobe\" must be in [1, min(number of clusters, %d)] = [1, %d]"
+                         % (PROBE_MAX, min(clusters, PROBE_MAX)))
+    if p is not None and nq:
+        col0 = p[:, 0]
+        if bool((col0 >= clusters).any()):
+            raise ValueError("column 0 of \"probes\" (the query's own cluster) must be below %d" % clusters)
+    return nprobe, p
+
+
 def _check_radius(radius):
     if isinstance(radius, bool) or not isinstance(radius, (int, float, numpy.integer, numpy.floating)):
         raise TypeError("\"radius\" must be a real number")
@@ -181,14 +255,23 @@ class KnnIndex:
         _raise_for(rc, "kmamd_knn_index_create")
         self.h = h
 
-    def query(self, queries, k, query_assignments=None, return_distances=True, return_assignments=False):
+    def query(self, queries, k, query_assignments=None, return_distances=True, return_assignments=False,
+              nprobe=None, probes=None, return_probes=False):
         """The k nearest corpus rows of every query row: neighbors (Q x k corpus row indices), then, as asked,
-        distances (Q x k float32, the exact distances the search compared) and the queries' clusters (Q)."""
+        distances (Q x k float32, the exact distances the search compared) and the queries' clusters (Q).
+        nprobe / probes: the multi-probe search (module docstring) -- only the clusters of every
+        query's probe list are visited; return_assignments is then column 0 of the lists and return_probes appends the
+        Q x nprobe lists used (uint32 numpy / int32 tensor, K where fewer qualify)."""
         if not getattr(self, "h", None):
             raise ValueError("the index is closed")
         k = _check_k(k, self.n_rows)
         q, nq, q_dev, qa = _check_queries(queries, self.fp16, self.features, self.clusters, query_assignments,
                                           self.device)
+        nprobe, pr = _check_probes(nprobe, probes, nq, self.clusters, q_dev, query_assignments, self.device, self.fp16)
+        if nprobe is not None:
+            return self._query_probe(q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes)
+        if return_probes:
+            raise ValueError("\"return_probes\" needs \"nprobe\" or \"probes\"")
         if q_dev:
             import torch
             dev = torch.device("cuda", self.device)
@@ -205,6 +288,31 @@ class KnnIndex:
                                                 _ptr(asg) if asg is not None else None, self.device if q_dev else -1)
             _raise_for(rc, "kmamd_knn_index_query")
         out = (nb,) + ((dist,) if return_distances else ()) + ((asg,) if return_assignments else ())
+        return out[0] if len(out) == 1 else out
+
+    def _query_probe(self, q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes):
+        want_lists = return_assignments or return_probes
+        if q_dev:
+            import torch
+            dev = torch.device("cuda", self.device)
+            nb = torch.empty((nq, k), dtype=torch.int32, device=dev)
+            dist = torch.empty((nq, k), dtype=torch.float32, device=dev) if return_distances else None
+            used = torch.empty((nq, nprobe), dtype=torch.int32, device=dev) if want_lists else None
+        else:
+            nb = numpy.empty((nq, k), numpy.uint32)
+            dist = numpy.empty((nq, k), numpy.float32) if return_distances else None
+            used = numpy.empty((nq, nprobe), numpy.uint32) if want_lists else None
+        if nq:
+            rc = self.lib.kmamd_knn_index_query_probe(self.h, k, nprobe, nq, _ptr(q), _ptr(pr) if pr is not None else None,
+                                                      _ptr(nb), _ptr(dist) if dist is not None else None,
+                                                      _ptr(used) if used is not None else None,
+                                                      self.device if q_dev else -1)
+            _raise_for(rc, "kmamd_knn_index_query_probe")
+        out = (nb,) + ((dist,) if return_distances else ())
+        if return_assignments:
+            out += ((used[:, 0].contiguous() if q_dev else numpy.ascontiguousarray(used[:, 0])),)
+        if return_probes:
+            out += (used,)
         return out[0] if len(out) == 1 else out
 
     def query_radius(self, queries, radius, query_assignments=None, return_distances=True, sort=False,
@@ -277,16 +385,21 @@ class KnnIndex:
 
 
 def knn_query(k, samples, centroids, assignments, queries, metric="L2", device=0, query_assignments=None,
-              return_distances=True, return_assignments=False, verbosity=0):
+              return_distances=True, return_assignments=False, verbosity=0, nprobe=None, probes=None,
+              return_probes=False):
     """One-shot KnnIndex(samples, centroids, assignments, metric, device).query(queries, k, ...): every argument is
     checked before the device is touched."""
     _get_metric(metric)
     _, _, _, fp16, n, d, clusters, _ = _check_corpus(samples, centroids, assignments, device)
     _check_k(k, n)
-    _check_queries(queries, fp16, d, clusters, query_assignments, device)
+    _, nq, q_dev, _ = _check_queries(queries, fp16, d, clusters, query_assignments, device)
+    np_, _ = _check_probes(nprobe, probes, nq, clusters, q_dev, query_assignments, device, fp16)
+    if np_ is None and return_probes:
+        raise ValueError("\"return_probes\" needs \"nprobe\" or \"probes\"")
     with KnnIndex(samples, centroids, assignments, metric=metric, device=device, verbosity=verbosity) as ix:
         return ix.query(queries, k, query_assignments=query_assignments, return_distances=return_distances,
-                        return_assignments=return_assignments)
+                        return_assignments=return_assignments, nprobe=nprobe, probes=probes,
+                        return_probes=return_probes)
 
 
 def knn_query_radius(radius, samples, centroids, assignments, queries, metric="L2", device=0, query_assignments=None,
