@@ -1,41 +1,26 @@
 // assign_job.cpp -- kmamd_kmeans_assign of include/kmcuda_amd.h: new rows assigned to given centroids (the "predict"
 // of a trained K-means), with the distance of every row to its centroid and per-cluster statistics.
 //
-// The rows go through in chunks, by the pipeline knn_index.cpp runs for its queries: copy in (a device-resident fp32
-// chunk is used in place), widen the halves, assignments <- K, ONE assignment pass of the engine (the filtered,
-// bit-exact kmamd_lloyd_assign; no row cache, no carried bounds: a chunk is seen once), the distance kernel, the
-// cluster statistics, copy out.  A shorter last chunk gets an ENGINE OF ITS OWN, sized for it: the
-// assignment pass then covers exactly the chunk's rows, nothing is read behind a caller's device buffer and no padding
-// row is assigned or counted.
+// The rows go through in chunks (host_job.hpp: assign_chunk_rows, RowStage): assignments <- K, ONE assignment pass of
+// the engine (the filtered, bit-exact kmamd_lloyd_assign; no row cache, no carried bounds: a chunk is seen once), the
+// distance kernel, the cluster statistics, copy out.  A shorter last chunk gets an ENGINE OF ITS OWN, sized for it
+// (EngineSlot): the assignment pass then covers exactly the chunk's rows, nothing is read behind a
+// caller's device buffer and no padding row is assigned or counted.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <memory>
-
 #include "../../include/kmcuda_amd.h"
-#include "knn_host.hpp"
+#include "host_job.hpp"
 
 using namespace kmx;
 
 namespace {
 
-// a chunk's staged fp32 rows stay within this budget, as the index's chunks do (knn_index.cpp)
-constexpr size_t kAssignChunkBytes = (size_t)4 << 30;
-
-struct AssignSwitches {
-  size_t chunk = 0;      // KMCUDA_AMD_ASSIGN_CHUNK: rows per chunk (0: unset; the tests force small chunks)
-  bool member = false;   // KMCUDA_AMD_ASSIGN_DIST=member: the distance pass on member_distances_kernel (the A/B)
-};
-
-AssignSwitches assign_switches() {
-  AssignSwitches sw;
-  if (const char *v = getenv("KMCUDA_AMD_ASSIGN_CHUNK")) {
-    const long long n = atoll(v);
-    if (n > 0) sw.chunk = (size_t)n;
-  }
-  if (const char *v = getenv("KMCUDA_AMD_ASSIGN_DIST")) sw.member = strcmp(v, "member") == 0;
-  return sw;
+// KMCUDA_AMD_ASSIGN_DIST=member: the distance pass on member_distances_kernel (the A/B)
+bool assign_dist_member() {
+  const char *v = getenv("KMCUDA_AMD_ASSIGN_DIST");
+  return v && strcmp(v, "member") == 0;
 }
 
 hipError_t distance_pass(bool member, int metric, const float *rows, uint32_t n, uint32_t D, const float *centroids,
@@ -54,8 +39,8 @@ struct AssignJob {
   double *sums = nullptr;
 
   int run() {
-    const AssignSwitches sw = assign_switches();
-    KnnShard w;   // owns the call's buffers and its pooled stream (destroyed after the engine below)
+    const bool member = assign_dist_member();
+    DeviceArena w;   // owns the call's buffers and its pooled stream (destroyed after the engine below)
     w.dev = device;
     w.stream = pooled_stream_acquire(device);
     if (!w.stream) return kmcudaRuntimeError;
@@ -72,36 +57,20 @@ struct AssignJob {
 
     if (N != 0) {
       // ---- the centroids, fp32 on this device ----
+      RowStage cstage, rstage;
       const float *cen = nullptr;
-      if (fp16) {
-        float *c32 = nullptr;
-        KNN_TRY(w.alloc(&c32, (size_t)K * D));
-        const void *src = centroids_in;
-        if (host) {
-          uint16_t *c16 = nullptr;
-          KNN_TRY(w.alloc(&c16, (size_t)K * D));
-          KMX_HIPCP(hipMemcpyAsync(c16, centroids_in, (size_t)K * D * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-          src = c16;
-        }
-        KMX_HIPRT(launch_half_to_float(src, (size_t)K * D, c32, st));
-        cen = c32;
-      } else {
-        KNN_TRY(w.stage_in(static_cast<const float *>(centroids_in), (size_t)K * D, host ? -1 : device, &cen));
-      }
+      KNN_TRY(cstage.reserve(w, K, D, fp16, host));
+      KNN_TRY(cstage.stage(centroids_in, 0, K, &cen));
 
       // ---- one chunk's buffers, reused by every chunk ----
-      size_t chunk = kAssignChunkBytes / ((size_t)D * sizeof(float));
-      if (sw.chunk) chunk = sw.chunk;
-      if (chunk < 1) chunk = 1;
+      const size_t chunk = assign_chunk_rows(D);
       const uint32_t Nc = (uint32_t)(chunk < N ? chunk : N);
-      float *rows32 = nullptr, *dist_buf = nullptr;
-      uint16_t *rows16 = nullptr;
+      float *dist_buf = nullptr;
       uint32_t *asg_buf = nullptr, *prev = nullptr, *inv = nullptr, *offsets = nullptr, *keys_tmp = nullptr,
                *vals_tmp = nullptr, *keys_sorted = nullptr;
       char *sort_temp = nullptr;
       size_t sort_bytes = 0;
-      if (host || fp16) KNN_TRY(w.alloc(&rows32, (size_t)Nc * D));
-      if (host && fp16) KNN_TRY(w.alloc(&rows16, (size_t)Nc * D));
+      KNN_TRY(rstage.reserve(w, Nc, D, fp16, host));
       if (host) KNN_TRY(w.alloc(&asg_buf, Nc));
       KNN_TRY(w.alloc(&prev, Nc));
       if (want_dist && (host || !distances)) KNN_TRY(w.alloc(&dist_buf, Nc));
@@ -115,36 +84,14 @@ struct AssignJob {
         KNN_TRY(w.alloc(&sort_temp, sort_bytes + 16));
       }
 
-      std::unique_ptr<Engine> eng;   // sized for the chunk at hand: Nc rows, then the shorter last chunk's
-      uint32_t eng_rows = 0;
+      EngineSlot slot;   // sized for the chunk at hand: Nc rows, then the shorter last chunk's
       for (uint32_t q0 = 0; q0 < N; q0 += Nc) {
         const uint32_t n = N - q0 < Nc ? N - q0 : Nc;
-        if (!eng || eng_rows != n) {
-          if (eng) KMX_HIPRT(hipStreamSynchronize(st));   // (the passes of the engine that goes)
-          eng.reset(new Engine());
-          KNN_TRY(eng->init(device, n, D, K, metric, 0, st));
-          eng_rows = n;
-        }
-        // ---- the chunk's rows, fp32 on this device (+ the halves for the filter where they lie aligned) ----
+        // ---- the engine, then the chunk's rows, fp32 on this device (+ the halves for the filter) ----
         const float *rows = nullptr;
-        const void *halves = nullptr;
-        if (fp16) {
-          const uint16_t *src = static_cast<const uint16_t *>(samples) + (size_t)q0 * D;
-          if (host) {
-            KMX_HIPCP(hipMemcpyAsync(rows16, src, (size_t)n * D * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-            src = rows16;
-          }
-          KMX_HIPRT(launch_half_to_float(src, (size_t)n * D, rows32, st));
-          rows = rows32;
-          halves = src;
-        } else if (host) {
-          KMX_HIPCP(hipMemcpyAsync(rows32, static_cast<const float *>(samples) + (size_t)q0 * D,
-                                   (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, st));
-          rows = rows32;
-        } else {
-          rows = static_cast<const float *>(samples) + (size_t)q0 * D;
-        }
-        eng->half_rows_ = ((uintptr_t)halves & 15u) == 0 ? halves : nullptr;
+        Engine *eng = nullptr;
+        KNN_TRY(slot.get(device, n, D, K, metric, st, rstage.halves_at(samples, q0), &eng));
+        KNN_TRY(rstage.stage(samples, q0, n, &rows));
         // ---- assignments <- K ("no cluster"), then one pass: a row without a nearest centroid keeps K ----
         uint32_t *asg = host ? asg_buf : assignments + q0;
         KMX_HIPRT(hipMemsetD32Async((hipDeviceptr_t)asg, (int)K, n, st));
@@ -153,7 +100,7 @@ struct AssignJob {
         float *dist = nullptr;
         if (want_dist) {
           dist = (!host && distances) ? distances + q0 : dist_buf;
-          KMX_HIPRT(distance_pass(sw.member, metric, rows, n, D, cen, asg, K, dist, st));
+          KMX_HIPRT(distance_pass(member, metric, rows, n, D, cen, asg, K, dist, st));
         }
         if (want_stats) {
           KMX_HIPRT(launch_inverse_assignments(asg, n, K, keys_tmp, vals_tmp, keys_sorted, inv, offsets, sort_temp,
@@ -190,19 +137,9 @@ int kmamd_kmeans_assign(int metric, uint32_t samples_size, uint16_t features_siz
                         const void *centroids, uint32_t *assignments, float *distances, uint32_t *cluster_counts,
                         double *cluster_distance_sums) {
   // ---- everything that is refused is refused here, before any device work, with the outputs untouched ----
-  if (metric != 0 && metric != 1) return kmcudaInvalidArguments;
-  if (features_size == 0 || clusters_size < 2 || clusters_size >= 0x7FFFFFFFu) return kmcudaInvalidArguments;
-  if (fp16x2 && (features_size & 1u)) return kmcudaInvalidArguments;
+  if (clusters_size < 2 || clusters_size >= 0x7FFFFFFFu) return kmcudaInvalidArguments;
   if (!centroids || (samples_size != 0 && (!samples || !assignments))) return kmcudaInvalidArguments;
-  if (device < 0 || (device_ptrs >= 0 && device_ptrs != device)) return kmcudaInvalidArguments;
-  // the reference's half2 arithmetic has no predict form (sample weights refuse it for the same reason)
-  if (fp16x2)
-    if (const char *v = getenv("KMCUDA_AMD_FP16_STRICT"))
-      if (atoi(v) != 0) return kmcudaInvalidArguments;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return kmcudaNoSuchDevice;
-  if (hipSetDevice(device) != hipSuccess) return kmcudaNoSuchDevice;
-  g_verbosity = verbosity;
+  KNN_TRY(rows_call_begin(metric, features_size, fp16x2, device, device_ptrs, verbosity));
   if (device_ptrs >= 0) (void)hipDeviceSynchronize();   // the caller's writes, as the k-NN index's calls
   AssignJob job;
   job.metric = metric; job.device = device; job.verbosity = verbosity;
@@ -221,7 +158,7 @@ int kmamd_assigned_distances(int metric, uint32_t n_rows, uint32_t features, uin
   if (n_rows == 0) return kmcudaSuccess;
   if (!samples || !centroids || !assignments || !distances) return kmcudaInvalidArguments;
   if (hipSetDevice(device) != hipSuccess) return kmcudaNoSuchDevice;
-  KMX_HIPRT(distance_pass(assign_switches().member, metric, samples, n_rows, features, centroids, assignments,
+  KMX_HIPRT(distance_pass(assign_dist_member(), metric, samples, n_rows, features, centroids, assignments,
                           clusters, distances, (hipStream_t)hip_stream));
   return kmcudaSuccess;
 }

@@ -1,11 +1,11 @@
 // assign_top_job.cpp -- kmamd_kmeans_assign_top of include/kmcuda_amd.h: for every row its m nearest centroids in the
 // order one assignment pass would find them, with the reference's distances.
 //
-// The rows go through in chunks, by kmamd_kmeans_assign's pipeline (assign_job.cpp): copy in (a device-resident fp32
-// chunk is used in place), widen the halves, the kernels of assign_top.hip, copy out.  The centroids are prepared once
-// per call (launch_centroid_prep: exact squared norms, the transposed panel, the centred panel and its bound).  Rows of
-// up to 256 features take the filtered path, a sub-chunk's score matrix at a time (budgeted like the k-NN search's
-// bound matrix); wider rows, KMCUDA_AMD_ASSIGN_TOP=exact and the rows the filter hands over take the exhaustive kernel.
+// The rows go through in chunks (host_job.hpp: assign_chunk_rows, RowStage): the kernels of assign_top.hip, copy out.
+// The centroids are prepared once per call (launch_centroid_prep: exact squared norms, the transposed panel, the centred
+// panel and its bound).  Rows of up to 256 features take the filtered path, a sub-chunk's score matrix at a time
+// (budgeted like the k-NN search's bound matrix); wider rows, KMCUDA_AMD_ASSIGN_TOP=exact and the rows the filter hands
+// over take the exhaustive kernel.
 // The centroid preparation and the per-chunk ranking are AssignTopRanker's two halves (knn_host.hpp): the k-NN index
 // prepares once and ranks the chunks of its probed queries with them (knn_index.cpp).
 #include <math.h>
@@ -31,7 +31,7 @@ bool assign_top_exact_only() {
   return v && strcmp(v, "exact") == 0;
 }
 
-int AssignTopRanker::prepare(KnnShard &w, int metric_, const float *cen_, uint32_t K_, uint32_t D_, bool exact_only) {
+int AssignTopRanker::prepare(DeviceArena &w, int metric_, const float *cen_, uint32_t K_, uint32_t D_, bool exact_only) {
   metric = metric_; cen = cen_; K = K_; D = D_;
   const hipStream_t st = w.stream;
   K_pad = (K + 31) / 32 * 32; Kt = (K + 63) / 64 * 64;
@@ -66,7 +66,7 @@ int AssignTopRanker::prepare(KnnShard &w, int metric_, const float *cen_, uint32
   return 0;
 }
 
-int AssignTopRanker::reserve(KnnShard &w, uint32_t Nc) {
+int AssignTopRanker::reserve(DeviceArena &w, uint32_t Nc) {
   sub = 0;   // rows per score matrix: a multiple of the score kernel's 128-row blocks
   if (!DP) return 0;
   size_t r = kTopScoreBytes / ((size_t)K_pad * sizeof(float)) / 128 * 128;
@@ -102,8 +102,6 @@ int AssignTopRanker::rank(const float *rows, uint32_t n, uint32_t m, uint32_t *t
 
 namespace {
 
-constexpr size_t kTopChunkBytes = (size_t)4 << 30;     // a chunk's staged fp32 rows, as kmamd_kmeans_assign's
-
 std::mutex g_top_stats_mutex;
 uint64_t g_top_pairs_exact = 0, g_top_pairs_total = 0;
 
@@ -117,37 +115,20 @@ struct AssignTopJob {
   uint64_t evaluated_host = 0;
 
   int run() {
-    size_t chunk = kTopChunkBytes / ((size_t)D * sizeof(float));
-    if (const char *v = getenv("KMCUDA_AMD_ASSIGN_CHUNK")) {
-      const long long n = atoll(v);
-      if (n > 0) chunk = (size_t)n;
-    }
-    if (chunk < 1) chunk = 1;
+    const size_t chunk = assign_chunk_rows(D);
     const bool exact_only = assign_top_exact_only();
 
-    KnnShard w;   // owns the call's buffers and its pooled stream
+    DeviceArena w;   // owns the call's buffers and its pooled stream
     w.dev = device;
     w.stream = pooled_stream_acquire(device);
     if (!w.stream) return kmcudaRuntimeError;
     const hipStream_t st = w.stream;
 
     // ---- the centroids, fp32 on this device ----
+    RowStage cstage, rstage;
     const float *cen = nullptr;
-    if (fp16) {
-      float *c32 = nullptr;
-      KNN_TRY(w.alloc(&c32, (size_t)K * D));
-      const void *src = centroids_in;
-      if (host) {
-        uint16_t *c16 = nullptr;
-        KNN_TRY(w.alloc(&c16, (size_t)K * D));
-        KMX_HIPCP(hipMemcpyAsync(c16, centroids_in, (size_t)K * D * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-        src = c16;
-      }
-      KMX_HIPRT(launch_half_to_float(src, (size_t)K * D, c32, st));
-      cen = c32;
-    } else {
-      KNN_TRY(w.stage_in(static_cast<const float *>(centroids_in), (size_t)K * D, host ? -1 : device, &cen));
-    }
+    KNN_TRY(cstage.reserve(w, K, D, fp16, host));
+    KNN_TRY(cstage.stage(centroids_in, 0, K, &cen));
 
     // ---- their preparation: csqr and the transposed panel for the exact keys, the centred panel for the filter ----
     AssignTopRanker r;
@@ -157,11 +138,9 @@ struct AssignTopJob {
 
     // ---- one chunk's buffers, reused by every chunk ----
     const uint32_t Nc = (uint32_t)(chunk < N ? chunk : N);
-    float *rows32 = nullptr, *dist_buf = nullptr;
-    uint16_t *rows16 = nullptr;
+    float *dist_buf = nullptr;
     uint32_t *top_buf = nullptr;
-    if (host || fp16) KNN_TRY(w.alloc(&rows32, (size_t)Nc * D));
-    if (host && fp16) KNN_TRY(w.alloc(&rows16, (size_t)Nc * D));
+    KNN_TRY(rstage.reserve(w, Nc, D, fp16, host));
     if (host) KNN_TRY(w.alloc(&top_buf, (size_t)Nc * m));
     if (host && distances) KNN_TRY(w.alloc(&dist_buf, (size_t)Nc * m));
     KNN_TRY(r.reserve(w, Nc));
@@ -170,21 +149,7 @@ struct AssignTopJob {
       const uint32_t n = N - q0 < Nc ? N - q0 : Nc;
       // ---- the chunk's rows, fp32 on this device ----
       const float *rows = nullptr;
-      if (fp16) {
-        const uint16_t *src = static_cast<const uint16_t *>(samples) + (size_t)q0 * D;
-        if (host) {
-          KMX_HIPCP(hipMemcpyAsync(rows16, src, (size_t)n * D * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-          src = rows16;
-        }
-        KMX_HIPRT(launch_half_to_float(src, (size_t)n * D, rows32, st));
-        rows = rows32;
-      } else if (host) {
-        KMX_HIPCP(hipMemcpyAsync(rows32, static_cast<const float *>(samples) + (size_t)q0 * D,
-                                 (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, st));
-        rows = rows32;
-      } else {
-        rows = static_cast<const float *>(samples) + (size_t)q0 * D;
-      }
+      KNN_TRY(rstage.stage(samples, q0, n, &rows));
       uint32_t *t = host ? top_buf : top + (size_t)q0 * m;
       KNN_TRY(r.rank(rows, n, m, t, false, st));
       float *dist = nullptr;
@@ -223,20 +188,10 @@ int kmamd_kmeans_assign_top(int metric, uint32_t samples_size, uint16_t features
                             const void *samples, const void *centroids, uint32_t *top_assignments,
                             float *top_distances) {
   // ---- everything that is refused is refused here, before any device work, with the outputs untouched ----
-  if (metric != 0 && metric != 1) return kmcudaInvalidArguments;
-  if (features_size == 0 || clusters_size < 2 || clusters_size >= 0x7FFFFFFFu) return kmcudaInvalidArguments;
+  if (clusters_size < 2 || clusters_size >= 0x7FFFFFFFu) return kmcudaInvalidArguments;
   if (m < 1 || m > 64 || m > clusters_size) return kmcudaInvalidArguments;
-  if (fp16x2 && (features_size & 1u)) return kmcudaInvalidArguments;
   if (!centroids || (samples_size != 0 && (!samples || !top_assignments))) return kmcudaInvalidArguments;
-  if (device < 0 || (device_ptrs >= 0 && device_ptrs != device)) return kmcudaInvalidArguments;
-  // the reference's half2 arithmetic has no predict form (kmamd_kmeans_assign refuses it likewise)
-  if (fp16x2)
-    if (const char *v = getenv("KMCUDA_AMD_FP16_STRICT"))
-      if (atoi(v) != 0) return kmcudaInvalidArguments;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return kmcudaNoSuchDevice;
-  if (hipSetDevice(device) != hipSuccess) return kmcudaNoSuchDevice;
-  g_verbosity = verbosity;
+  KNN_TRY(rows_call_begin(metric, features_size, fp16x2, device, device_ptrs, verbosity));
   uint64_t evaluated = 0;
   if (samples_size != 0) {
     if (device_ptrs >= 0) (void)hipDeviceSynchronize();   // the caller's writes, as kmamd_kmeans_assign

@@ -2,20 +2,11 @@
 // block plan, the search launch and the scatter to a caller's device.  Its two callers add their query side:
 // knn_cuda()'s self-join (knn_job.cpp) and the query batches of kmamd_knn_index_* (knn_index.cpp).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include <vector>
 
-#include "../../include/kmcuda.h"
-#include "engine.hpp"
+#include "host_job.hpp"
 
 namespace kmx {
-
-// error plumbing of the k-NN host files: a result other than success returns at once
-#define KNN_TRY(call) do { int rc__ = (call); if (rc__ != 0) return rc__; } while (false)
-#define KMX_HIPRT(call) do { if ((call) != hipSuccess) return kmcudaRuntimeError; } while (false)
-#define KMX_HIPCP(call) do { if ((call) != hipSuccess) return kmcudaMemoryCopyError; } while (false)
 
 // What a search launch needs besides the prepared corpus: radix-sort scratch (the CSR of the rows, then the query order
 // of a search; it belongs to whoever allocated it) and the optional buffers of the f16 search for up to `rows` queries
@@ -32,12 +23,8 @@ struct KnnScratch {
   }
 };
 
-// One GPU's prepared copy of the corpus, or the per-call buffers of a query batch: device buffers it owns, freed with
-// it.
-struct KnnShard {
-  int dev = 0;
-  hipStream_t stream = nullptr;
-  // the corpus (knn_prepare_corpus)
+// One GPU's prepared copy of the corpus: the arena's buffers and stream, and what knn_prepare_corpus leaves in them.
+struct KnnShard : DeviceArena {
   int metric = 0;
   uint32_t N = 0, D = 0, DP = 0, K = 0;
   float mu2 = 0.f;
@@ -54,46 +41,6 @@ struct KnnShard {
   unsigned long long *calced = nullptr;
   KnnScratch scratch;
   uint32_t first_block = 0, nblocks = 0, p_base = 0, p_end = 0;
-  std::vector<void *> owned;
-  ~KnnShard() {
-    (void)hipSetDevice(dev);
-    for (void *p : owned) (void)hipFree(p);
-    pooled_stream_release(dev, stream);
-  }
-  template <typename T>
-  int alloc(T **p, size_t count) {
-    void *q = nullptr;
-    if (hipMalloc(&q, count ? count * sizeof(T) : sizeof(T)) != hipSuccess) return kmcudaMemoryAllocationFailure;
-    owned.push_back(q);
-    *p = static_cast<T *>(q);
-    return 0;
-  }
-  // frees one buffer of alloc() early (a no-op for anything else, e.g. a caller's buffer used in place)
-  void release(const void *p) {
-    for (size_t i = 0; i < owned.size(); i++)
-      if (owned[i] == p) {
-        (void)hipFree(owned[i]);
-        owned.erase(owned.begin() + i);
-        return;
-      }
-  }
-  // brings `count` elements of a caller buffer onto this device (or uses it in place)
-  template <typename T>
-  int stage_in(const T *src, size_t count, int32_t device_ptrs, const T **dst) {
-    if (device_ptrs >= 0 && device_ptrs == dev) {
-      *dst = src;
-      return 0;
-    }
-    T *buf = nullptr;
-    int rc = alloc(&buf, count);
-    if (rc) return rc;
-    hipError_t e = device_ptrs < 0
-                       ? hipMemcpyAsync(buf, src, count * sizeof(T), hipMemcpyHostToDevice, stream)
-                       : hipMemcpyPeerAsync(buf, dev, src, device_ptrs, count * sizeof(T), stream);
-    if (e != hipSuccess) return kmcudaMemoryCopyError;
-    *dst = buf;
-    return 0;
-  }
 };
 
 // The KMCUDA_AMD_* switches of the k-NN entry points, read once per call (tests change them between calls).
@@ -176,9 +123,9 @@ struct AssignTopRanker {
   uint32_t sub = 0;   // rows per score matrix
   // The centroid preparation, enqueued on w.stream; the buffers belong to `w`.  cen: K x D fp32 on w's device.
   // exact_only: no filter panel (KMCUDA_AMD_ASSIGN_TOP=exact for the whole call)
-  int prepare(KnnShard &w, int metric, const float *cen, uint32_t K, uint32_t D, bool exact_only);
+  int prepare(DeviceArena &w, int metric, const float *cen, uint32_t K, uint32_t D, bool exact_only);
   // the buffers of one chunk of up to Nc rows (KMCUDA_AMD_ASSIGN_TOP_ROWS applies); they belong to `w`
-  int reserve(KnnShard &w, uint32_t Nc);
+  int reserve(DeviceArena &w, uint32_t Nc);
   // top[n x m] of the chunk's n rows (fp32, on the device), enqueued on st; exact_only: the exhaustive kernel this time
   int rank(const float *rows, uint32_t n, uint32_t m, uint32_t *top, bool exact_only, hipStream_t st);
 };

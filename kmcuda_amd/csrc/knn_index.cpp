@@ -96,7 +96,8 @@ struct ProbeSide {
 };
 
 struct QueryChunk {
-  KnnShard w;   // owns the buffers; enqueues on the index's stream (nothing to release)
+  DeviceArena w;   // owns the buffers; enqueues on the index's stream (nothing to release)
+  KnnScratch scratch;   // the sort scratch (w's) and the optional buffers of knn_search
   uint32_t Qc = 0;
   float *qrows = nullptr, *qxs = nullptr, *qn2p = nullptr, *qn2c = nullptr, *qmydist = nullptr, *qrdist = nullptr,
         *qmux = nullptr, *qkbias = nullptr;
@@ -122,9 +123,9 @@ struct QueryChunk {
     KNN_TRY(w.alloc(&qeff, Qc));
     KNN_TRY(w.alloc(&qinv, Qc));
     KNN_TRY(w.alloc(&qoffsets, (size_t)K + 2));
-    KNN_TRY(w.alloc(&w.scratch.keys_tmp, Qc));
-    KNN_TRY(w.alloc(&w.scratch.vals_tmp, Qc));
-    KNN_TRY(w.alloc(&w.scratch.keys_sorted, Qc));
+    KNN_TRY(w.alloc(&scratch.keys_tmp, Qc));
+    KNN_TRY(w.alloc(&scratch.vals_tmp, Qc));
+    KNN_TRY(w.alloc(&scratch.keys_sorted, Qc));
     KNN_TRY(w.alloc(&qstats, 4));
     KNN_TRY(w.alloc(&qxs, (size_t)Qc * DP));
     KNN_TRY(w.alloc(&qn2p, Qc));
@@ -139,11 +140,11 @@ struct QueryChunk {
     const size_t max_blocks = (size_t)Qc / 32 + K + 1;   // (every plan packs >= 32 queries per block but one per cluster)
     KNN_TRY(w.alloc(&blocks, 2 * max_blocks));
     // radix sorts: the CSR of the chunk (keys <= K) and the query order (keys of up to 32 bits)
-    w.scratch.rows = Qc;
-    w.scratch.sort_bytes = sort_temp_bytes(Qc, 0xFFFFFFFFu);
+    scratch.rows = Qc;
+    scratch.sort_bytes = sort_temp_bytes(Qc, 0xFFFFFFFFu);
     char *sort_temp = nullptr;
-    KNN_TRY(w.alloc(&sort_temp, w.scratch.sort_bytes + 16));
-    w.scratch.sort_temp = sort_temp;
+    KNN_TRY(w.alloc(&sort_temp, scratch.sort_bytes + 16));
+    scratch.sort_temp = sort_temp;
     // the queries' clusters: the engine's assignment pass (kmamd_lloyd_assign; D > 256 through lloyd_wide), on fp32 rows
     if (assign) {
       eng.reset(new Engine());
@@ -197,8 +198,8 @@ struct QueryChunk {
     // ---- the chunk in cluster-sorted order: rows, norms, distances to the own centroid ----
     KMX_HIPRT(hipMemsetAsync(qstats, 0, 4 * sizeof(uint32_t), st));
     KMX_HIPRT(launch_knn_query_clusters(qrows, n, D, qassign, K, s.centroids, qeff, qstats + 2, st));
-    KMX_HIPRT(launch_inverse_assignments(qeff, n, K, w.scratch.keys_tmp, w.scratch.vals_tmp, w.scratch.keys_sorted, qinv, qoffsets, w.scratch.sort_temp,
-                                         w.scratch.sort_bytes, st));
+    KMX_HIPRT(launch_inverse_assignments(qeff, n, K, scratch.keys_tmp, scratch.vals_tmp, scratch.keys_sorted, qinv, qoffsets, scratch.sort_temp,
+                                         scratch.sort_bytes, st));
     if (pr) KMX_HIPRT(launch_knn_probe_lists(pr->raw, pr->pw, n, qinv, K, pr->lists, qstats + 2, st));
     // (with mu: the queries raise the half-range flag qstats[1] as the corpus rows do)
     KMX_HIPRT(launch_knn_gather(qrows, n, D, DP, qinv, qxs, qn2p, qstats, ix.path.use_f16 ? s.mu : nullptr, qoffsets, K, st));
@@ -261,7 +262,7 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
   // per-call buffers (freed with `c`), among them the sort scratch and the optional buffers of knn_search
   QueryChunk c;
   KNN_TRY(c.init(*this, Qc, !qassign_in));
-  KnnShard &w = c.w;
+  DeviceArena &w = c.w;
   float *heaps = nullptr, *outd = nullptr, *dist_dev = nullptr;
   uint32_t *out = nullptr, *nb_dev = nullptr;
   KNN_TRY(w.alloc(&heaps, (size_t)Qc * 2 * k));
@@ -281,7 +282,7 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
     c.fill_args(&a);
     a.k = k; a.heaps = heaps; a.out = out; a.outd = outd;
     a.p_end = c.cp.dp_filter ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
-    KNN_TRY(knn_search(s, w.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity));
+    KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity));
     // ---- back in query order ----
     uint32_t *nb = host ? nb_dev : neighbors + (size_t)q0 * k;
     KMX_HIPRT(launch_knn_scatter(out, c.qinv, 0, n, k, nb, st));
@@ -320,7 +321,7 @@ int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queri
 
   QueryChunk c;
   KNN_TRY(c.init(*this, Qc, false));
-  KnnShard &w = c.w;
+  DeviceArena &w = c.w;
   ProbeSide pr;
   pr.pw = pw; pr.probes_in = probes_in; pr.probes_out = probes_out;
   KNN_TRY(w.alloc(&pr.raw, (size_t)Qc * pw));
@@ -363,7 +364,7 @@ int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queri
     a.k = k; a.heaps = heaps; a.out = out; a.outd = outd;
     a.p_end = c.cp.use_f16 ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
     a.plist = pr.lists; a.pw = pw;
-    KNN_TRY(knn_search(s, w.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity, pr.raw, c.qinv));
+    KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity, pr.raw, c.qinv));
     // ---- back in query order ----
     uint32_t *nb = host ? nb_dev : neighbors + (size_t)q0 * k;
     KMX_HIPRT(launch_knn_scatter(out, c.qinv, 0, n, k, nb, st));
@@ -402,7 +403,7 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
   if (chunk < 1) chunk = 1;
   const uint32_t Qc = (uint32_t)(chunk < Q ? chunk : Q);
 
-  KnnShard own;   // this call's own device buffers
+  DeviceArena own;   // this call's own device buffers (nothing to release: the index's stream)
   own.dev = s.dev;
   own.stream = nullptr;
   uint32_t *flag = nullptr, *counts_dev = nullptr;
@@ -458,13 +459,13 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
     const double dp = (fp16 ? 1.0e-3 : 1.0e-6) + 1.0e-8 * (double)D;
     prune_abs = (float)(4.0 * 1.01 * sqrt(2.0 * dp));
   }
-  if (use_lb && hipMalloc((void **)&c.w.scratch.lb, (size_t)K * Qc * sizeof(float)) != hipSuccess) {
-    c.w.scratch.lb = nullptr;
+  if (use_lb && hipMalloc((void **)&c.scratch.lb, (size_t)K * Qc * sizeof(float)) != hipSuccess) {
+    c.scratch.lb = nullptr;
     (void)hipGetLastError();
     return kmcudaMemoryAllocationFailure;
   }
-  if (use_lb && path.use_f16 && sw.order != 0 && hipMalloc((void **)&c.w.scratch.qperm, (size_t)Qc * sizeof(uint32_t)) != hipSuccess) {
-    c.w.scratch.qperm = nullptr;   // (the query order is an optimisation: sorted-position order without it)
+  if (use_lb && path.use_f16 && sw.order != 0 && hipMalloc((void **)&c.scratch.qperm, (size_t)Qc * sizeof(uint32_t)) != hipSuccess) {
+    c.scratch.qperm = nullptr;   // (the query order is an optimisation: sorted-position order without it)
     (void)hipGetLastError();
   }
   if (sw.stats) KMX_HIPRT(hipMemsetAsync(s.calced, 0, KNN_STATS * sizeof(unsigned long long), st));
@@ -502,12 +503,12 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
     a.calced = s.calced;
     a.xs16 = s.xs16; a.mux = s.mux; a.kbias = s.kbias; a.mu2 = s.mu2;
     if (use_lb && c.assigned) {
-      KMX_HIPRT(launch_knn_centroid_bounds(c.qxs, D, DP, 0, c.assigned, s.centroids, K, s.R, c.w.scratch.lb, c.assigned, st));
-      a.lb = c.w.scratch.lb;
+      KMX_HIPRT(launch_knn_centroid_bounds(c.qxs, D, DP, 0, c.assigned, s.centroids, K, s.R, c.scratch.lb, c.assigned, st));
+      a.lb = c.scratch.lb;
       a.lb_stride = c.assigned;
       // queries that want the same clusters into the same waves, as knn_search orders them
-      if (f16 && c.w.scratch.qperm) {
-        KnnScratch &x = c.w.scratch;
+      if (f16 && c.scratch.qperm) {
+        KnnScratch &x = c.scratch;
         if (launch_knn_query_order(x.lb, c.assigned, c.qoffsets, K, 0, c.assigned, x.keys_tmp, x.vals_tmp, x.keys_sorted,
                                    x.qperm, x.sort_temp, x.sort_bytes, st, sw.order, c.qmydist, s.R))
           a.qperm = x.qperm;

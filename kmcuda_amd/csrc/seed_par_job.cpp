@@ -3,9 +3,9 @@
 // of (seed, round, row); the few thousand candidates are weighted by the rows they attract and reclustered to K seeds
 // by this library's weighted k-means++.
 //
-// The rows stay on the device for the whole call (host rows are uploaded once, halves widened once).  A round is
-// kmamd_kmeans_assign's pipeline (assign_job.cpp) against the round's NEW candidates -- assignments <- M, one
-// assignment pass of the engine, the distance kernel -- followed by the kernels of seed_par.hip: the term update with
+// The rows stay on the device for the whole call (host_job.hpp: one RowStage of all N rows).  A round is what
+// kmamd_kmeans_assign does with a chunk, against the round's NEW candidates -- assignments <- M, one assignment pass of
+// the engine (EngineSlot), the distance kernel -- followed by the kernels of seed_par.hip: the term update with
 // its block sums, phi, the draw's count / prefix / fill.  The host reads one word per round: the number of drawn rows.
 #include <math.h>
 #include <stdio.h>
@@ -13,11 +13,10 @@
 #include <string.h>
 
 #include <chrono>
-#include <memory>
 #include <vector>
 
 #include "../../include/kmcuda_amd.h"
-#include "knn_host.hpp"
+#include "host_job.hpp"
 
 using namespace kmx;
 
@@ -52,7 +51,7 @@ struct SeedParJob {
   };
 
   int run() {
-    KnnShard w;   // owns the call's buffers and its pooled stream (destroyed after the engine below)
+    DeviceArena w;   // owns the call's buffers and its pooled stream (destroyed after the engine below)
     w.dev = device;
     w.stream = pooled_stream_acquire(device);
     if (!w.stream) return kmcudaRuntimeError;
@@ -70,26 +69,11 @@ struct SeedParJob {
     };
 
     // ---- the rows: fp32 on this device, and the halves they were widened from ----
+    RowStage stage;
     const float *rows32 = nullptr;
-    const uint16_t *rows16 = nullptr;
-    const size_t nd = (size_t)N * D;
-    if (fp16) {
-      const uint16_t *src = static_cast<const uint16_t *>(samples);
-      if (host) {
-        uint16_t *h = nullptr;
-        KNN_TRY(w.alloc(&h, nd));
-        KMX_HIPCP(hipMemcpyAsync(h, samples, nd * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-        src = h;
-      }
-      float *r32 = nullptr;
-      KNN_TRY(w.alloc(&r32, nd));
-      KMX_HIPRT(launch_half_to_float(src, nd, r32, st));
-      rows32 = r32;
-      rows16 = src;
-    } else {
-      KNN_TRY(w.stage_in(static_cast<const float *>(samples), nd, host ? -1 : device, &rows32));
-    }
-    const void *halves = ((uintptr_t)rows16 & 15u) == 0 ? rows16 : nullptr;   // (the filter wants them aligned)
+    const void *rows16 = nullptr;
+    KNN_TRY(stage.reserve(w, N, D, fp16, host));
+    KNN_TRY(stage.stage(samples, 0, N, &rows32, &rows16));
 
     // ---- per-row and per-block state ----
     const size_t nb = seed_par_block_count(N), nchunks = seed_par_chunk_count(N);
@@ -131,22 +115,13 @@ struct SeedParJob {
     std::vector<Batch> batches;
     std::vector<uint32_t> ends;   // candidates after round 0 .. R
     uint32_t total = 0;
-    std::unique_ptr<Engine> eng;   // sized for (N rows, the round's M candidates); re-created when M changes
-    uint32_t eng_k = 0;
-    auto engine_for = [&](uint32_t M) -> int {
-      if (eng && eng_k == M) return 0;
-      if (eng) KMX_HIPRT(hipStreamSynchronize(st));   // (the passes of the engine that goes)
-      eng.reset(new Engine());
-      KNN_TRY(eng->init(device, N, D, M, metric, 0, st));
-      eng->half_rows_ = halves;
-      eng_k = M;
-      return 0;
-    };
+    EngineSlot slot;   // sized for (N rows, the round's M candidates); re-created when M changes
+    Engine *eng = nullptr;
     // dist[s] = the distance of row s to its nearest of the batch's candidates, as kmeans_predict gives it (one
     // candidate: to that row, no engine); then the term update
     auto absorb = [&](const Batch &b, bool is_first, uint32_t r) -> int {
       if (b.M >= 2) {
-        KNN_TRY(engine_for(b.M));
+        KNN_TRY(slot.get(device, N, D, b.M, metric, st, rows16, &eng));
         KMX_HIPRT(hipMemsetD32Async((hipDeviceptr_t)asg, (int)b.M, N, st));
         KNN_TRY(eng->lloyd_assign(rows32, b.rows, asg, prev, false));
         lap("assignment", r);
@@ -213,7 +188,7 @@ struct SeedParJob {
     }
     std::vector<uint32_t> ids_host(total), counts_host(total);
     if (total >= 2) {
-      KNN_TRY(engine_for(total));
+      KNN_TRY(slot.get(device, N, D, total, metric, st, rows16, &eng));
       KMX_HIPRT(hipMemsetD32Async((hipDeviceptr_t)asg, (int)total, N, st));
       KNN_TRY(eng->lloyd_assign(rows32, cand_all, asg, prev, false));
       KMX_HIPRT(hipMemsetAsync(counts_dev, 0, (size_t)total * sizeof(uint32_t), st));
@@ -225,7 +200,7 @@ struct SeedParJob {
     }
     KMX_HIPCP(hipMemcpyAsync(ids_host.data(), ids_all, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KMX_HIPRT(hipStreamSynchronize(st));
-    eng.reset();
+    slot.reset();
     lap("weighting pass", rounds);
 
     // ---- the live candidates, in order ----
@@ -306,22 +281,11 @@ int kmamd_kmeans_seed_parallel(int metric, uint32_t samples_size, uint16_t featu
                                uint32_t *candidate_rows, uint32_t *candidate_counts, uint32_t candidate_capacity,
                                uint32_t *n_candidates, uint32_t *round_ends, int32_t *fell_back) {
   // ---- everything that is refused is refused here, before any device work, with the outputs untouched ----
-  if (metric != 0 && metric != 1) return kmcudaInvalidArguments;
-  if (features_size == 0 || samples_size == 0) return kmcudaInvalidArguments;
-  if (clusters_size < 2 || clusters_size > samples_size) return kmcudaInvalidArguments;
-  if (fp16x2 && (features_size & 1u)) return kmcudaInvalidArguments;
+  if (samples_size == 0 || clusters_size < 2 || clusters_size > samples_size) return kmcudaInvalidArguments;
   if (rounds > 64) return kmcudaInvalidArguments;
   if (!(oversampling >= 0.f) || isinf(oversampling)) return kmcudaInvalidArguments;   // (NaN fails the first test)
   if (!samples || !centroids) return kmcudaInvalidArguments;
-  if (device < 0 || device > 31 || (device_ptrs >= 0 && device_ptrs != device)) return kmcudaInvalidArguments;
-  // the reference's half2 arithmetic has no predict form, and a round is a predict call
-  if (fp16x2)
-    if (const char *v = getenv("KMCUDA_AMD_FP16_STRICT"))
-      if (atoi(v) != 0) return kmcudaInvalidArguments;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return kmcudaNoSuchDevice;
-  if (hipSetDevice(device) != hipSuccess) return kmcudaNoSuchDevice;
-  g_verbosity = verbosity;
+  KNN_TRY(rows_call_begin(metric, features_size, fp16x2, device, device_ptrs, verbosity, 31));
   if (device_ptrs >= 0) (void)hipDeviceSynchronize();   // the caller's writes, as kmamd_kmeans_assign
   SeedParJob job;
   job.metric = metric; job.device = device; job.verbosity = verbosity;

@@ -168,6 +168,23 @@ def test_repeatable_and_host_equals_device(name):
         assert list(i0["round_ends"]) == list(i["round_ends"]) and i0["fell_back"] == i["fell_back"]
 
 
+# 7b. half rows on the device that do not lie 16-byte aligned: the engine's filter gets no halves, the same result
+def test_misaligned_half_device_view():
+    name = "fp16-5003x32"
+    x, metric = ref.fixture(name)
+    want = ref.restated(name)
+    buf = torch.empty(x.size + 2, dtype=torch.float16, device=_dev())
+    xs = buf[2:].view(x.shape)   # one half2 pair into the buffer
+    xs.copy_(torch.from_numpy(x.copy()))
+    assert xs.data_ptr() % 16 != 0 and xs.is_contiguous()
+    cen, info = _run(xs, metric)
+    _check_candidates(info, want)
+    cen = cen.cpu().numpy()
+    assert cen.dtype == x.dtype and cen.shape == (ref.K, x.shape[1])
+    assert _are_rows(cen, x)
+    assert numpy.array_equal(_bits(cen), _bits(_public_seeds(x, metric, info["rows"], info["counts"], ref.K, ref.SEED)))
+
+
 # 8. the blob fixture: every blob holds a seed
 def test_every_blob_holds_a_seed():
     """16 blobs, the call's defaults, K = 32: why not K = 16 is written at tests/_seed_parallel_ref.py: BLOBS (this
