@@ -474,6 +474,55 @@ typedef struct {
   float oversampling;
 } kmamd_seed_parallel_params;
 
+/* Mini-batch K-means (Sculley, "Web-Scale K-Means Clustering"; the per-centre learning rate of scikit-learn's
+ * MiniBatchKMeans.partial_fit; no counterpart in the reference): a model that stays on the device
+ * between calls and is updated with new rows, a stream, or draws from a corpus of any size.
+ *   state      K x D float32 centroids C, K float64 cluster weights W >= 0, a step counter t.  The centroids are float32
+ *              also when the rows are halves: a half centroid would swallow updates smaller than its last place.
+ *   one step   n rows X (float32, or halves with fp16x2 != 0: fp32 arithmetic on the half values) and optional float32
+ *              weights w, finite and > 0 (none: every w = 1):
+ *              1. a = kmamd_kmeans_assign(X, C).assignments: one filtered, bit-exact pass.  A row whose first feature is
+ *                 NaN or whose distances are all NaN gets K and takes no part; a NaN centroid is never chosen.
+ *              2. for every cluster c with members in the batch: n_c = sum of w_i in fp64, S_c = sum of
+ *                 (double)w_i * (double)x_i in fp64 over the members in ascending batch position, in a FIXED association
+ *                 that depends on the member list alone (DESIGN.md 4.3's list_sum).  No floating-point atomics: two
+ *                 identical calls give identical bits.
+ *              3. W'_c = W_c + n_c;  L2: C'_c[f] = (float)(((double)C_c[f] * W_c + S_c[f]) / W'_c);  angular:
+ *                 v = C_c * W_c + S_c, C'_c = (float)(v / |v|) (|v|: the fp64 root of the sum of squares, in a fixed
+ *                 order).  A cluster without a member in the batch keeps C_c and W_c bit for bit -- an unvisited centre
+ *                 stays where it is; it is NOT set to NaN as an emptied cluster of kmeans_cuda is.  With W_c = 0 the
+ *                 seed is forgotten: the centre becomes the batch mean of its members.
+ *              4. t += 1 (also for n == 0, which changes nothing else).
+ *   fit        over a corpus of N rows: `steps` steps of `batch` rows each.  Slot j of the step with counter t holds row
+ *              floor(h(seed, (uint32)t, j) * N / 2^64) -- h: k-means||'s hash above; the high 64 bits of the 128-bit
+ *              product: rows are drawn with replacement --, with its weight.  t is the handle's running counter, so
+ *              fit(.., 10) twice is fit(.., 20).  No early stop.
+ * create: centroids K x D float32 and cluster_weights (K float64, or NULL: zeros) are copied; device_ptrs -1: host
+ * buffers, else buffers on `device`.  step / fit: rows, weights and assignments (optional out, n words) are host buffers
+ * (device_ptrs -1) or buffers on the handle's device; a step holds at most kmamd_kmeans_assign's chunk of rows (env
+ * KMCUDA_AMD_ASSIGN_CHUNK).  read: any of the three outputs may be NULL; steps_done is host memory.  All calls are
+ * synchronous.  A fit on a device-resident corpus draws and gathers on the device and reads nothing back between its
+ * steps; on a host corpus the host gathers every batch into pinned memory while the device works on the step before.
+ * InvalidArguments before any device work, with the outputs and the state untouched and *out left NULL: a bad metric,
+ * features == 0 or > 65535, an odd feature count with fp16x2, clusters < 2, device_ptrs naming another device, null
+ * pointers (handle, centroids, rows), more rows than the chunk, batch == 0 or samples_size == 0 in fit, a cluster
+ * weight that is negative or not finite, KMCUDA_AMD_FP16_STRICT=1 with fp16x2 rows.  (Cluster weights passed on the
+ * device are looked at after they were copied; nothing has been handed out by then.)  A sample weight that is not
+ * finite and > 0 is InvalidArguments with C, W and t unchanged. */
+typedef struct kmamd_minibatch kmamd_minibatch;
+int kmamd_minibatch_create(kmamd_minibatch **out, int metric, uint32_t features, uint32_t clusters, int device,
+                           int32_t device_ptrs, int32_t verbosity, const float *centroids,
+                           const double *cluster_weights /* optional */);
+int kmamd_minibatch_step(kmamd_minibatch *h, uint32_t n_rows, int32_t fp16x2, const void *rows,
+                         const float *weights /* optional */, uint32_t *assignments /* optional out */,
+                         int32_t device_ptrs);
+int kmamd_minibatch_fit(kmamd_minibatch *h, uint64_t samples_size, int32_t fp16x2, const void *samples,
+                        const float *weights /* optional */, uint32_t batch, uint32_t steps, uint32_t seed,
+                        int32_t device_ptrs);
+int kmamd_minibatch_read(kmamd_minibatch *h, float *centroids, double *cluster_weights, uint64_t *steps_done,
+                         int32_t device_ptrs);
+void kmamd_minibatch_destroy(kmamd_minibatch *h);
+
 /* host -> raw device pointer copy on `device` (what python.cc:330-345 does with cudaMemcpy for imported
  * centroids in device-pointer mode; lets a binding without a HIP runtime of its own fill caller-owned memory). */
 int kmamd_copy_to_device(int device, void *dst, const void *host_src, size_t bytes);

@@ -10,8 +10,11 @@ clusters of every query or the clusters the caller lists: KnnIndex.query / knn_q
 New rows assigned to given centroids, with distances and cluster statistics (beyond the reference): kmeans_predict;
 the m nearest centroids of every row, in the order an assignment pass would find them: kmeans_predict_top.
 k-means|| seeding (beyond the reference), stand-alone -- kmeans_seed_parallel -- and as kmeans_cuda(init="k-means||").
+Mini-batch K-means on a model that stays on the GPU (beyond the reference): MiniBatchKMeans (partial_fit, fit) and the
+one-shot kmeans_minibatch.
 """
 from .api import kmeans_cuda, knn_cuda, supports_fp16  # noqa: F401
 from .knn_index import KnnIndex, knn_query, knn_query_radius  # noqa: F401
 from .predict import kmeans_predict, kmeans_predict_top  # noqa: F401
 from .seed import kmeans_seed_parallel  # noqa: F401
+from .minibatch import MiniBatchKMeans, kmeans_minibatch  # noqa: F401

@@ -28,6 +28,8 @@ EXPORTS = [
     "kmamd_kmeans_assign", "kmamd_assigned_distances",
     "kmamd_kmeans_assign_top", "kmamd_assign_top_stats",
     "kmamd_kmeans_seed_parallel",
+    "kmamd_minibatch_create", "kmamd_minibatch_step", "kmamd_minibatch_fit", "kmamd_minibatch_read",
+    "kmamd_minibatch_destroy",
     "kmamd_copy_to_device", "kmamd_profile_reset", "kmamd_profile_read", "kmamd_profile_enable", "kmamd_filter_kind", "kmamd_build_arch",
 ]
 
@@ -162,6 +164,16 @@ def lib():
     L.kmamd_kmeans_seed_parallel.restype = i32
     L.kmamd_kmeans_seed_parallel.argtypes = [i32, u32, ctypes.c_uint16, u32, u32, f32, u32, i32, i32, i32, i32, vp, vp,
                                              vp, vp, u32, vp, vp, vp]
+    L.kmamd_minibatch_create.restype = i32
+    L.kmamd_minibatch_create.argtypes = [ctypes.POINTER(vp), i32, u32, u32, i32, i32, i32, vp, vp]
+    L.kmamd_minibatch_step.restype = i32
+    L.kmamd_minibatch_step.argtypes = [vp, u32, i32, vp, vp, vp, i32]
+    L.kmamd_minibatch_fit.restype = i32
+    L.kmamd_minibatch_fit.argtypes = [vp, ctypes.c_uint64, i32, vp, vp, u32, u32, u32, i32]
+    L.kmamd_minibatch_read.restype = i32
+    L.kmamd_minibatch_read.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_uint64), i32]
+    L.kmamd_minibatch_destroy.restype = None
+    L.kmamd_minibatch_destroy.argtypes = [vp]
     L.kmamd_copy_to_device.restype = i32
     L.kmamd_copy_to_device.argtypes = [i32, vp, vp, ctypes.c_size_t]
     L.kmamd_build_arch.restype = ctypes.c_char_p

@@ -337,6 +337,21 @@ hipError_t launch_seed_par_gather(const float *in32, const void *in16, const uin
 hipError_t launch_seed_par_first_valid(const float *rows, uint32_t N, uint32_t D, uint32_t start,
                                        unsigned long long *best, hipStream_t st);
 
+// minibatch.hip -- mini-batch K-means (kmamd_minibatch_*, minibatch_job.cpp)
+// One step's update of the resident state, in place and in one launch, over the CSR launch_inverse_assignments leaves
+// for the batch (inv, offsets: K + 1 entries): for every centroid c with members, n_c = the fp64 sum of their weights
+// (weights == nullptr: their number), S_c = the fp64 sum of w * x over them in list_sum.hpp's association,
+// W' = W + n_c, C' = (float)((C W + S_c) / W') (L2) or (float)((C W + S_c) / |C W + S_c|) (angular).  A centroid
+// without members keeps C and W bit for bit.  rows: n x D fp32; weights: n, finite and > 0.
+hipError_t launch_minibatch_update(int metric, const float *rows, const float *weights, const uint32_t *inv,
+                                   const uint32_t *offsets, uint32_t K, uint32_t D, float *centroids,
+                                   double *cluster_weights, hipStream_t st);
+// out row j = corpus row floor(h(seed, step, j) N / 2^64) for j < batch (hash_draw.hpp), copied as it is -- D floats,
+// or D halves (fp16) --, and weights_out[j] = that row's weight (weights != nullptr)
+hipError_t launch_minibatch_draw_gather(const void *corpus, uint64_t N, uint32_t D, bool fp16, const float *weights,
+                                        uint32_t seed, uint32_t step, uint32_t batch, void *out, float *weights_out,
+                                        hipStream_t st);
+
 // assign_top.hip -- the m nearest centroids of every row (kmamd_kmeans_assign_top, assign_top_job.cpp)
 // top[s * m + j] = the j-th centroid of row s by (key, index), K where fewer qualify; *evaluated += the exact keys
 // computed.  The exhaustive kernel: every row of [0, N) (rows == nullptr) or rows[0 .. *nrows), N then bounding the grid
