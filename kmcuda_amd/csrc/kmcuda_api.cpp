@@ -229,20 +229,35 @@ struct Shard {
   float *gdrifts = nullptr;        // G per-group max drifts
   uint32_t *passed = nullptr;      // length
   hipEvent_t ev_filled = nullptr;  // several shards on one device: this shard's reduce buffer is written
-  std::vector<void *> owned;
   ~Shard() {
     (void)hipSetDevice(dev);
     if (ev_filled) (void)hipEventDestroy(ev_filled);
-    for (void *p : owned) (void)hipFree(p);
   }
+  // device memory of the job's lifetime: the engine's (small buffers share its slabs, a large one is its own hipMalloc)
   template <typename T>
-  int alloc(T **p, size_t count) {   // (through the engine once it exists: small buffers share its slabs)
-    if (eng) return eng->alloc(p, count);
-    void *q = nullptr;
-    if (hipMalloc(&q, count ? count * sizeof(T) : sizeof(T)) != hipSuccess) return kmcudaMemoryAllocationFailure;
-    owned.push_back(q);
-    *p = static_cast<T *>(q);
-    return 0;
+  int alloc(T **p, size_t count) { return eng->alloc(p, count); }
+  // enqueues the copy of `count` elements of a caller buffer -- host memory (device_ptrs < 0) or device device_ptrs'
+  // -- into dst, on this shard's stream
+  template <typename T>
+  int copy_in(T *dst, const T *src, size_t count, int32_t device_ptrs) {
+    const hipError_t e = device_ptrs < 0
+                             ? hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, eng->stream_)
+                             : hipMemcpyPeerAsync(dst, dev, src, device_ptrs, count * sizeof(T), eng->stream_);
+    return e == hipSuccess ? 0 : kmcudaMemoryCopyError;
+  }
+  // The one rule for a caller's read-only buffer (DeviceArena::stage_in's, host_job.hpp): used in place where it lies
+  // on this shard's device, otherwise copied into a buffer of alloc()
+  template <typename T>
+  int stage_in(const T *src, size_t count, int32_t device_ptrs, const T **dst) {
+    if (device_ptrs >= 0 && device_ptrs == dev) {
+      *dst = src;
+      return 0;
+    }
+    T *buf = nullptr;
+    int rc = alloc(&buf, count);
+    if (rc == 0) rc = copy_in(buf, src, count, device_ptrs);
+    *dst = buf;
+    return rc;
   }
 };
 
@@ -423,42 +438,22 @@ class Job {
       int rc = sh->eng->init(sh->dev, sh->length, D, K, metric, 0, shard_devs.size() == 1 ? on_stream : nullptr);
       if (rc) return rc;
       sh->eng->strict_h2_ = strict_h2;
-      const float *src = samples + (size_t)sh->offset * D;
+      const size_t n = (size_t)sh->length * D;
       if (fp16) {
-        // `samples` holds halves: stage the raw halves on the device, widen into the fp32 working copy
-        const uint16_t *hsrc = reinterpret_cast<const uint16_t *>(samples) + (size_t)sh->offset * D;
-        const size_t n = (size_t)sh->length * D;
+        // `samples` holds halves: the raw halves on the device (kept: the f16 matrix-core filter reads the rows as
+        // halves), widened into the fp32 working copy
         float *buf = nullptr;
         if ((rc = sh->alloc(&buf, n))) return rc;
-        const uint16_t *dev_half = hsrc;
-        uint16_t *tmp = nullptr;
-        if (!(device_ptrs >= 0 && device_ptrs == sh->dev)) {
-          if (hipMalloc((void **)&tmp, (n ? n : 1) * sizeof(uint16_t)) != hipSuccess) return kmcudaMemoryAllocationFailure;
-          hipError_t e = device_ptrs < 0
-                             ? hipMemcpyAsync(tmp, hsrc, n * sizeof(uint16_t), hipMemcpyHostToDevice, sh->eng->stream_)
-                             : hipMemcpyPeerAsync(tmp, sh->dev, hsrc, device_ptrs, n * sizeof(uint16_t), sh->eng->stream_);
-          if (e != hipSuccess) { (void)hipFree(tmp); return kmcudaMemoryCopyError; }
-          dev_half = tmp;
-        }
-        hipError_t e = launch_half_to_float(dev_half, n, buf, sh->eng->stream_);
-        if (e == hipSuccess) e = hipStreamSynchronize(sh->eng->stream_);
-        if (tmp) sh->owned.push_back(tmp);  // kept: the f16 matrix-core filter reads the rows as halves
-        if (e != hipSuccess) return kmcudaRuntimeError;
+        const uint16_t *dev_half = nullptr;
+        if ((rc = sh->stage_in(reinterpret_cast<const uint16_t *>(samples) + (size_t)sh->offset * D, n, device_ptrs, &dev_half)))
+          return rc;
+        if (launch_half_to_float(dev_half, n, buf, sh->eng->stream_) != hipSuccess ||
+            hipStreamSynchronize(sh->eng->stream_) != hipSuccess)
+          return kmcudaRuntimeError;
         sh->samples = buf;
         sh->eng->half_rows_ = dev_half;
-      } else if (device_ptrs >= 0 && device_ptrs == sh->dev) {
-        sh->samples = src;  // already resident, used in place and never modified
-      } else {
-        float *buf = nullptr;
-        if ((rc = sh->alloc(&buf, (size_t)sh->length * D))) return rc;
-        hipError_t e;
-        if (device_ptrs < 0)
-          e = hipMemcpyAsync(buf, src, (size_t)sh->length * D * sizeof(float), hipMemcpyHostToDevice, sh->eng->stream_);
-        else
-          e = hipMemcpyPeerAsync(buf, sh->dev, src, device_ptrs, (size_t)sh->length * D * sizeof(float),
-                                 sh->eng->stream_);
-        if (e != hipSuccess) return kmcudaMemoryCopyError;
-        sh->samples = buf;
+      } else if ((rc = sh->stage_in(samples + (size_t)sh->offset * D, n, device_ptrs, &sh->samples))) {
+        return rc;   // (resident rows are used in place and never modified)
       }
       if ((rc = sh->alloc(&sh->centroids, (size_t)K * D))) return rc;
       if ((rc = sh->alloc(&sh->assignments, sh->length))) return rc;
@@ -466,21 +461,7 @@ class Job {
       if ((rc = sh->alloc(&sh->ccounts, K))) return rc;
       if ((rc = sh->alloc(&sh->reduce, reduce_len()))) return rc;
       if ((rc = sh->alloc(&sh->dists, sh->length))) return rc;
-      if (weighted) {
-        const float *wsrc = sample_weights + sh->offset;
-        if (device_ptrs >= 0 && device_ptrs == sh->dev) {
-          sh->weights = wsrc;   // already resident, used in place and never modified
-        } else {
-          float *wbuf = nullptr;
-          if ((rc = sh->alloc(&wbuf, sh->length))) return rc;
-          const hipError_t e =
-              device_ptrs < 0
-                  ? hipMemcpyAsync(wbuf, wsrc, (size_t)sh->length * sizeof(float), hipMemcpyHostToDevice, sh->eng->stream_)
-                  : hipMemcpyPeerAsync(wbuf, sh->dev, wsrc, device_ptrs, (size_t)sh->length * sizeof(float), sh->eng->stream_);
-          if (e != hipSuccess) return kmcudaMemoryCopyError;
-          sh->weights = wbuf;
-        }
-      }
+      if (weighted && (rc = sh->stage_in(sample_weights + sh->offset, sh->length, device_ptrs, &sh->weights))) return rc;
       shards.push_back(std::move(sh));
     }
     bool distinct = shards.size() > 1;
@@ -532,21 +513,16 @@ class Job {
   }
 
   // ---- replicated-state helpers ----
-  int broadcast_centroids_from_host(const float *host) {
-    for (auto &s : shards) {
-      (void)hipSetDevice(s->dev);
-      if (hipMemcpyAsync(s->centroids, host, (size_t)K * D * sizeof(float), hipMemcpyHostToDevice, s->eng->stream_) !=
-          hipSuccess)
-        return kmcudaMemoryCopyError;
-    }
-    return sync_all();
+  // the shard that holds sample row `index` (global numbering)
+  Shard *owner_of(uint32_t index) {
+    for (auto &s : shards)
+      if (index >= s->offset && index < s->offset + s->length) return s.get();
+    return nullptr;
   }
 
   // copies sample row `index` (global numbering) into centroid slot `slot` on every shard
   int copy_sample_to_centroid(uint32_t index, uint32_t slot) {
-    Shard *owner = nullptr;
-    for (auto &s : shards)
-      if (index >= s->offset && index < s->offset + s->length) owner = s.get();
+    Shard *owner = owner_of(index);
     if (!owner) return kmcudaRuntimeError;
     const float *src = owner->samples + (size_t)(index - owner->offset) * D;
     for (auto &s : shards) {
@@ -564,518 +540,542 @@ class Job {
     return 0;
   }
 
-  int read_sample_value(uint32_t index, uint32_t feature, float *out) {
-    for (auto &s : shards)
-      if (index >= s->offset && index < s->offset + s->length) {
-        (void)hipSetDevice(s->dev);
-        RETERR(s->eng->sync());
-        if (hipMemcpy(out, s->samples + (size_t)(index - s->offset) * D + feature, sizeof(float),
-                      hipMemcpyDeviceToHost) != hipSuccess)
-          return kmcudaMemoryCopyError;
-        return 0;
-      }
-    return kmcudaRuntimeError;
-  }
-
-  int read_sample_row(uint32_t index, float *out) {
-    for (auto &s : shards)
-      if (index >= s->offset && index < s->offset + s->length) {
-        (void)hipSetDevice(s->dev);
-        RETERR(s->eng->sync());
-        if (hipMemcpy(out, s->samples + (size_t)(index - s->offset) * D, D * sizeof(float), hipMemcpyDeviceToHost) !=
-            hipSuccess)
-          return kmcudaMemoryCopyError;
-        return 0;
-      }
-    return kmcudaRuntimeError;
+  // `count` features of sample row `index` from feature `first` on, once its shard's stream has run dry
+  int read_sample(uint32_t index, uint32_t first, uint32_t count, float *out) {
+    Shard *s = owner_of(index);
+    if (!s) return kmcudaRuntimeError;
+    (void)hipSetDevice(s->dev);
+    RETERR(s->eng->sync());
+    if (hipMemcpy(out, s->samples + (size_t)(index - s->offset) * D + first, count * sizeof(float),
+                  hipMemcpyDeviceToHost) != hipSuccess)
+      return kmcudaMemoryCopyError;
+    return 0;
   }
 
   // ---- seeding (reference: kmeans_init_centroids, kmcuda.cc:189-400) ----
   int init_centroids(KMCUDAInitMethod method, uint32_t seed, const float *host_centroids, int32_t device_ptrs,
                      uint32_t afk_m = 0) {
-    if (metric == kmcudaDistanceMetricCosine && !fp16) {  // kmcuda.cc:195-220: three unit-norm probes, fp32 only
-      std::vector<float> probe(D);
-      for (uint32_t s : {0u, N / 2, N - 1}) {
-        RETERR(read_sample_row(s, probe.data()));
-        double norm = 0;
-        for (uint32_t i = 0; i < D; i++) norm += probe[i] * probe[i];
-        const float high = 1.00001, low = 0.99999;
-        if (norm > high || norm < low) {
-          INFO("error: angular distance: samples[%u] has L2 norm = %f which is outside [%f, %f]\n", s, norm, low, high);
-          return kmcudaInvalidArguments;
-        }
-      }
-    }
+    if (metric == kmcudaDistanceMetricCosine && !fp16) RETERR(check_unit_norms());  // (fp32 only)
     srand(seed);  // kmcuda.cc:222
     switch (method) {
-      case kmcudaInitMethodImport: {
-        if (fp16) {  // K x D halves -> fp32 replicas
-          const size_t n = (size_t)K * D;
-          for (auto &s : shards) {
-            (void)hipSetDevice(s->dev);
-            uint16_t *tmp = nullptr;
-            if (hipMalloc((void **)&tmp, n * sizeof(uint16_t)) != hipSuccess) return kmcudaMemoryAllocationFailure;
-            hipError_t e = device_ptrs < 0
-                               ? hipMemcpy(tmp, host_centroids, n * sizeof(uint16_t), hipMemcpyHostToDevice)
-                               : hipMemcpyPeer(tmp, s->dev, host_centroids, device_ptrs, n * sizeof(uint16_t));
-            if (e == hipSuccess) e = launch_half_to_float(tmp, n, s->centroids, s->eng->stream_);
-            if (e == hipSuccess) e = hipStreamSynchronize(s->eng->stream_);
-            (void)hipFree(tmp);
-            if (e != hipSuccess) return kmcudaMemoryCopyError;
-          }
-          return 0;
-        }
-        if (device_ptrs < 0) return broadcast_centroids_from_host(host_centroids);
-        for (auto &s : shards) {
-          (void)hipSetDevice(s->dev);
-          hipError_t e = hipMemcpyPeerAsync(s->centroids, s->dev, host_centroids, device_ptrs,
-                                            (size_t)K * D * sizeof(float), s->eng->stream_);
-          if (e != hipSuccess) return kmcudaMemoryCopyError;
-        }
-        return sync_all();
-      }
-      case kmcudaInitMethodRandom: {
-        INFO("randomly picking initial centroids...\n");
-        // The reference shuffles ALL N indices with libstdc++'s std::random_shuffle over rand() and takes the first K
-        // (kmcuda.cc:245-253): for i = 1 .. N-1: swap(a[i], a[rand() % (i + 1)]).  Position i is untouched before its
-        // own step and a value that leaves the first K never returns, so the first K entries follow from a K-entry
-        // array: steps i < K swap inside it, a step i >= K whose draw j falls below K puts i at j.  Same draws, same
-        // rows, no N-entry array; with glibc's generator restated (GlibcRand: a rand() call is 10-20 ns behind its
-        // lock -- 45 ms of a 4M-row call, 90 ms at 8M rows) the N - 1 draws take a few ms, and rand()'s own state is
-        // set to what N - 1 calls would have left.
-        std::vector<uint32_t> chosen(K);
-        for (uint32_t c = 0; c < K; c++) chosen[c] = c;
-        GlibcRand fast;
-        if (fast.attach(seed)) {
-          for (uint32_t i = 1; i < N && i < K; i++) std::swap(chosen[i], chosen[fast.next() % (i + 1)]);
-          for (uint32_t i = K; i < N; i++) {
-            const uint32_t j = fast.next() % (i + 1);
-            if (j < K) chosen[j] = i;
-          }
-          fast.detach();
-        } else {   // another C library: its rand(), call by call
-          for (uint32_t i = 1; i < N && i < K; i++) std::swap(chosen[i], chosen[rand() % (i + 1)]);
-          for (uint32_t i = K; i < N; i++) {
-            const uint32_t j = rand() % (i + 1);
-            if (j < K) chosen[j] = i;
-          }
-        }
-        DEBUG("shuffle complete, copying to device(s)...\n");
-        if (shards.size() == 1) {   // one gather launch (the index list rides in the dists buffer: N >= K floats)
-          Shard &s = *shards[0];
-          (void)hipSetDevice(s.dev);
-          uint32_t *idx = reinterpret_cast<uint32_t *>(s.dists);
-          if (hipMemcpyAsync(idx, chosen.data(), K * sizeof(uint32_t), hipMemcpyHostToDevice, s.eng->stream_) != hipSuccess)
-            return kmcudaMemoryCopyError;
-          if (launch_gather_rows(s.samples, idx, K, D, s.centroids, s.eng->stream_) != hipSuccess) return kmcudaRuntimeError;
-          return sync_all();   // (chosen[] must outlive the copy)
-        }
-        for (uint32_t c = 0; c < K; c++) RETERR(copy_sample_to_centroid(chosen[c], c));
-        return sync_all();
-      }
-      case kmcudaInitMethodPlusPlus: {
-        float smoke = NAN;
-        uint32_t first_index = 0;
-        while (smoke != smoke) {  // kmcuda.cc:265-270
-          first_index = rand() % N;
-          RETERR(read_sample_value(first_index, 0, &smoke));
-        }
-        RETERR(copy_sample_to_centroid(first_index, 0));
-        INFO("performing kmeans++...\n");
-        // Two ways to the reference's choice (kmcuda.cc:286-326).  HOST: all N distances come back
-        // (pinned, 4 N bytes per step), butterfly sum and sequential double prefix sums as the
-        // reference.  DEVICE (one shard; seeding.hip): sums of floats in double are exact -- order free
-        // -- while the distances' exponent range is narrow enough, so the step kernel's exact block
-        // sums give the same choice from 32 bytes per step; a step whose range is too wide (or that
-        // holds a NaN / inf distance) takes the host way.
-        if (weighted)
-          for (auto &s : shards) {
-            int rc;
-            if (!s->wterms && (rc = s->alloc(&s->wterms, s->length))) return rc;
-          }
-        float *host_dists = nullptr;
-        struct HostFree { float **p; ~HostFree() { if (*p) (void)hipHostFree(*p); } } host_dists_guard{&host_dists};
-        // Several row shards (round 5): every shard runs the step on its rows and leaves its own exact block sums; ONE
-        // chooser kernel on the first shard's device reads them where they lie (peer access) as the concatenation
-        // they are and copies the seed's row into every replica (seeding.hip: kmpp_choose_kernel) -- no N-sized
-        // transfer, no host in the loop.  Needs whole 256-row blocks on every shard but the last (row_plan()) and
-        // peer access from the first shard's device to the others'; otherwise the host chooser below.
-        bool device_chooser = !strict_h2 && getenv("KMCUDA_AMD_KMPP_HOST") == nullptr && shards.size() <= (size_t)kKmppMaxShards;
-        for (auto &s : shards) {
-          device_chooser = device_chooser && kmpp_blocks(s->length) <= (1u << 20) &&   // (two-level prefix: 1024 x 1024 blocks of 256 rows)
-                           (s->offset % 256u == 0u) && s->length != 0;
-          if (device_chooser && s->dev != shards[0]->dev) {
-            int can = 0;
-            (void)hipSetDevice(shards[0]->dev);
-            if (hipDeviceCanAccessPeer(&can, shards[0]->dev, s->dev) != hipSuccess || !can) {
-              device_chooser = false;
-            } else {
-              const hipError_t pe = hipDeviceEnablePeerAccess(s->dev, 0);
-              if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) device_chooser = false;
-            }
-            (void)hipGetLastError();
-          }
-        }
-        struct Totals { double sum_g, sum_d; uint32_t emin, emax, bad, chosen; };
-        Totals *totals_host = nullptr;
-        struct TotalsFree { Totals **p; ~TotalsFree() { if (*p) (void)hipHostFree(*p); } } totals_guard{&totals_host};
-        // Per shard: block statistics, local prefixes, totals, the fail flag, an event behind its step -- and for the
-        // filtered steps (seeding.hip) a centred byte copy of its rows (xs8; n2c: 4 floats per row): a step's first kernel
-        // drops every row that provably is no closer to the new seed than to an earlier one, the exact chains run for
-        // the rest.  Needs DP + 20 bytes per row beside the rows; without that memory (or KMCUDA_AMD_KMPP_FILTER=0) every
-        // step is the plain one.  Same dists[] after every step either way, hence the same seeds.
-        struct KppShard {
-          int dev = 0;
-          void *block_stats = nullptr, *totals = nullptr;
-          double *bpre = nullptr;
-          uint32_t *fail = nullptr;
-          KmppOutlierBuf out;   // the step's exponent cut, the distances below it (seeding.hip: KmppOutlier)
-          hipEvent_t ev_step = nullptr;
-          void *xs8 = nullptr;
-          float *n2c = nullptr, *mu = nullptr;
-          uint32_t *stats = nullptr, *list = nullptr;
-          double *part = nullptr;
-          void release() {
-            (void)hipSetDevice(dev);
-            if (ev_step) (void)hipEventDestroy(ev_step);
-            for (void *q : {xs8, (void *)n2c, (void *)mu, (void *)stats, (void *)list, (void *)part})
-              if (q) (void)hipFree(q);
-            ev_step = nullptr; xs8 = nullptr; n2c = nullptr; mu = nullptr; stats = nullptr; list = nullptr; part = nullptr;
-          }
-        };
-        std::vector<KppShard> kpp(shards.size());
-        struct KppFree { std::vector<KppShard> *v; ~KppFree() { for (auto &k : *v) k.release(); } } kpp_guard{&kpp};
-        hipEvent_t ev_chosen = nullptr;
-        struct EvFree { hipEvent_t *e; int dev; ~EvFree() { if (*e) { (void)hipSetDevice(dev); (void)hipEventDestroy(*e); } } } ev_guard{&ev_chosen, shards[0]->dev};
-        if (device_chooser) {
-          for (size_t q = 0; q < shards.size(); q++) {
-            Shard &s = *shards[q];
-            KppShard &k = kpp[q];
-            k.dev = s.dev;
-            (void)hipSetDevice(s.dev);
-            unsigned char *bs = nullptr, *td = nullptr;
-            int rc;
-            if ((rc = s.alloc(&bs, kmpp_block_stat_bytes(s.length)))) return rc;
-            if ((rc = s.alloc(&td, kmpp_totals_bytes()))) return rc;
-            if ((rc = s.alloc(&k.bpre, kmpp_prefix_doubles(s.length)))) return rc;
-            if ((rc = s.alloc(&k.fail, 4))) return rc;   // [0] the flag, [1] the exponent cut, [2] the listed values' number
-            unsigned char *ob = nullptr;
-            if ((rc = s.alloc(&ob, kmpp_outlier_bytes()))) return rc;
-            k.block_stats = bs;
-            k.totals = td;
-            k.out.ecut = k.fail + 1;
-            k.out.outl_count = k.fail + 2;
-            k.out.outl = ob;
-            if (hipMemsetAsync(k.fail, 0, 4 * sizeof(uint32_t), s.eng->stream_) != hipSuccess) return kmcudaRuntimeError;
-            if (hipMemsetAsync(td, 0, kmpp_totals_bytes(), s.eng->stream_) != hipSuccess) return kmcudaRuntimeError;
-            if (shards.size() > 1 && hipEventCreateWithFlags(&k.ev_step, hipEventDisableTiming) != hipSuccess) return kmcudaRuntimeError;
-          }
-          (void)hipSetDevice(shards[0]->dev);
-          if (shards.size() > 1 && hipEventCreateWithFlags(&ev_chosen, hipEventDisableTiming) != hipSuccess) return kmcudaRuntimeError;
-          if (hipHostMalloc(reinterpret_cast<void **>(&totals_host), sizeof(Totals), hipHostMallocDefault) != hipSuccess)
-            return kmcudaMemoryAllocationFailure;
-        }
-        const uint32_t kpp_dp = ((uint32_t)D + 127u) / 128u * 128u;
-        // (small jobs: the plain step is a few launches of nothing; KMCUDA_AMD_KMPP_FILTER=2 filters them too: tests)
-        bool kpp_filter = device_chooser && K >= 8 && N >= 65536u && kpp_dp <= 8192u;
-        if (const char *v = getenv("KMCUDA_AMD_KMPP_FILTER")) {
-          const int f = atoi(v);
-          kpp_filter = f >= 2 ? (device_chooser && K >= 3 && kpp_dp <= 8192u) : (kpp_filter && f != 0);
-        }
-        if (kpp_filter) {
-          bool ok = true;
-          for (size_t q = 0; q < shards.size() && ok; q++) {
-            Shard &s = *shards[q];
-            KppShard &k = kpp[q];
-            (void)hipSetDevice(s.dev);
-            ok = hipMalloc(&k.xs8, (size_t)s.length * kpp_dp) == hipSuccess &&   // (bytes)
-                 hipMalloc(reinterpret_cast<void **>(&k.n2c), (size_t)s.length * 4 * sizeof(float)) == hipSuccess &&
-                 hipMalloc(reinterpret_cast<void **>(&k.mu), (size_t)kpp_dp * sizeof(float)) == hipSuccess &&
-                 hipMalloc(reinterpret_cast<void **>(&k.stats), 4 * sizeof(uint32_t)) == hipSuccess &&
-                 hipMalloc(reinterpret_cast<void **>(&k.list), (size_t)s.length * sizeof(uint32_t)) == hipSuccess &&
-                 hipMalloc(reinterpret_cast<void **>(&k.part), (size_t)64 * D * sizeof(double)) == hipSuccess;
-          }
-          if (!ok) {
-            (void)hipGetLastError();
-            kpp_filter = false;
-            for (auto &k : kpp) {   // (the events stay: release() is the end of the seeding)
-              (void)hipSetDevice(k.dev);
-              for (void *q : {k.xs8, (void *)k.n2c, (void *)k.mu, (void *)k.stats, (void *)k.list, (void *)k.part})
-                if (q) (void)hipFree(q);
-              k.xs8 = nullptr; k.n2c = nullptr; k.mu = nullptr; k.stats = nullptr; k.list = nullptr; k.part = nullptr;
-            }
-            DEBUG("k-means++: no memory for the byte copy of the rows, plain steps\n");
-          } else {
-            for (size_t q = 0; q < shards.size(); q++) {
-              Shard &s = *shards[q];
-              KppShard &k = kpp[q];
-              (void)hipSetDevice(s.dev);
-              if (launch_kmpp_cache(s.samples, s.length, D, kpp_dp, k.part, k.mu, k.xs8, k.n2c, k.stats, s.eng->stream_) != hipSuccess)
-                return kmcudaRuntimeError;
-            }
-          }
-        }
-        uint32_t log2n = 0;
-        while ((1ull << log2n) < (uint64_t)N) log2n++;
-        uint32_t host_steps = 0;
-        auto progress = [&](uint32_t i) {
-          if (verbosity > 1 || (verbosity > 0 && (K < 100 || i % (K / 100) == 0))) {
-            printf("\rstep %d", i);
-            fflush(stdout);
-          }
-        };
-        // the reference's chooser on the host (kmcuda.cc:286-326) for step i with random number `choice`: all N
-        // distances come back, butterfly sum, sequential double prefix sums; copies the seed
-        auto host_choose = [&](uint32_t i, double choice) -> int {
-          host_steps++;
-          if (!host_dists &&
-              hipHostMalloc(reinterpret_cast<void **>(&host_dists), (size_t)N * sizeof(float), hipHostMallocDefault) != hipSuccess)
-            return kmcudaMemoryAllocationFailure;
-          for (auto &s : shards) {
-            (void)hipSetDevice(s->dev);
-            // (weighted: the terms w * d where the reference sums d)
-            if (weighted && launch_kmpp_weigh(s->dists, s->weights, s->length, s->wterms, nullptr, s->eng->stream_) != hipSuccess)
-              return kmcudaRuntimeError;
-            if (hipMemcpyAsync(host_dists + s->offset, weighted ? s->wterms : s->dists, (size_t)s->length * sizeof(float),
-                               hipMemcpyDeviceToHost, s->eng->stream_) != hipSuccess)
-              return kmcudaMemoryCopyError;
-          }
-          RETERR(sync_all());
-          const double dist_sum = butterfly_sum(host_dists, N);
-          const uint32_t choice_approx = choice * N;
-          const double choice_sum = choice * dist_sum;
-          uint32_t j = 0;
-          if (choice_approx < 100) {
-            double dist_sum2 = 0;
-            for (j = 0; j < N && dist_sum2 < choice_sum; j++) dist_sum2 += host_dists[j];
-          } else {
-            double dist_sum2 = 0;
-            for (uint32_t t = 0; t < choice_approx; t++) dist_sum2 += host_dists[t];
-            if (dist_sum2 < choice_sum) {
-              for (j = choice_approx; j < N && dist_sum2 < choice_sum; j++) dist_sum2 += host_dists[j];
-            } else {
-              for (j = choice_approx; j > 1 && dist_sum2 >= choice_sum; j--) dist_sum2 -= host_dists[j];
-              j++;
-            }
-          }
-          if (j == 0 || j > N) {
-            INFO("\ninternal bug in kmeans_init_centroids: j = %u\n", j);
-            return kmcudaRuntimeError;
-          }
-          return copy_sample_to_centroid(j - 1, i);
-        };
-        if (device_chooser) {
-          // The host only draws the random numbers (one rand() per step, in order, as the reference) and enqueues:
-          // distances, statistics, prefix sums, the chooser and the copy of the chosen row all run on the device
-          // (seeding.hip).  A step the device cannot decide raises a flag that turns the rest of the enqueued
-          // kernels into no-ops; the host looks after every batch of steps, chooses that seed the reference's way from the
-          // distances as that step left them, lowers the flag and goes on behind it.
-          // Several shards: one host thread enqueues every shard's step, the chooser on the first shard's stream behind
-          // events of the others' steps, and the others' next steps behind an event of the chooser (the events must be
-          // RECORDED before they are waited for: one thread, in order).
-          Shard &lead = *shards[0];
-          const bool many = shards.size() > 1;
-          std::vector<KmppShardPtrs> views(shards.size());
-          for (size_t q = 0; q < shards.size(); q++) {
-            Shard &s = *shards[q];
-            views[q].dists = weighted ? s.wterms : s.dists; views[q].bpre = kpp[q].bpre; views[q].totals = kpp[q].totals;
-            views[q].samples = s.samples; views[q].centroids = s.centroids; views[q].fail = kpp[q].fail;
-            views[q].offset = s.offset; views[q].length = s.length;
-            views[q].out = kpp[q].out;
-          }
-          if (many) RETERR(sync_all());   // (the first seed's peer copies and the flags' memsets have landed everywhere)
-          std::vector<double> choices(K, 0.0);
-          // (steps enqueued behind an undecided one are wasted launches: the batch starts small, doubles while the
-          //  device decides, and falls back to one step after a hand-over -- a data set whose distances span too many
-          //  binades hands over every step)
-          constexpr uint32_t kBatchMax = 256;
-          uint32_t batch = 8;
-          uint32_t drawn = 1;   // choices[1 .. drawn) are drawn
-          uint32_t i = 1;
-          while (i < K) {
-            const uint32_t end = i + batch < K ? i + batch : K;
-            for (uint32_t t = i; t < end; t++) {
-              progress(t);
-              if (t >= drawn) {
-                choices[t] = ((rand() + .0) / RAND_MAX);   // kmcuda.cc:300
-                drawn = t + 1;
-              }
-              for (size_t q = 0; q < shards.size(); q++) {
-                Shard &s = *shards[q];
-                KppShard &k = kpp[q];
-                (void)hipSetDevice(s.dev);
-                hipStream_t st = s.eng->stream_;
-                const float *newest = s.centroids + (size_t)(t - 1) * D;
-                const hipError_t se =
-                    (kpp_filter && t >= 2)
-                        ? launch_kmpp_step_filtered(metric, s.samples, s.length, D, kpp_dp, k.xs8, k.n2c, k.mu, k.stats, k.list,
-                                                    newest, t, s.dists, k.block_stats, k.bpre, k.totals, k.fail, k.out, st,
-                                                    s.weights, s.wterms)
-                        : launch_kmpp_step2(metric, s.samples, s.length, D, newest, t, s.dists, k.block_stats, k.bpre, k.totals,
-                                            k.fail, k.out, st, s.weights, s.wterms);
-                if (se != hipSuccess) return kmcudaRuntimeError;
-                if (many && q != 0 && hipEventRecord(k.ev_step, st) != hipSuccess) return kmcudaRuntimeError;
-              }
-              (void)hipSetDevice(lead.dev);
-              for (size_t q = 1; q < shards.size(); q++)
-                if (hipStreamWaitEvent(lead.eng->stream_, kpp[q].ev_step, 0) != hipSuccess) return kmcudaRuntimeError;
-              if (launch_kmpp_choose(views.data(), (uint32_t)views.size(), N, choices[t], log2n, t, D, lead.eng->stream_) != hipSuccess)
-                return kmcudaRuntimeError;
-              if (many) {
-                if (hipEventRecord(ev_chosen, lead.eng->stream_) != hipSuccess) return kmcudaRuntimeError;
-                for (size_t q = 1; q < shards.size(); q++) {
-                  (void)hipSetDevice(shards[q]->dev);
-                  if (hipStreamWaitEvent(shards[q]->eng->stream_, ev_chosen, 0) != hipSuccess) return kmcudaRuntimeError;
-                }
-              }
-            }
-            uint32_t failed = 0;
-            (void)hipSetDevice(lead.dev);
-            if (hipMemcpyAsync(totals_host, kpp[0].fail, sizeof(uint32_t), hipMemcpyDeviceToHost, lead.eng->stream_) != hipSuccess ||
-                hipStreamSynchronize(lead.eng->stream_) != hipSuccess)
-              return kmcudaMemoryCopyError;
-            memcpy(&failed, totals_host, sizeof(uint32_t));
-            if (failed == 0) {
-              i = end;
-              batch = batch * 2 < kBatchMax ? batch * 2 : kBatchMax;
-              continue;
-            }
-            batch = 1;
-            if (failed < i || failed >= end) return kmcudaRuntimeError;
-            RETERR(host_choose(failed, choices[failed]));   // (waits for every shard: sync_all)
-            for (size_t q = 0; q < shards.size(); q++) {
-              (void)hipSetDevice(shards[q]->dev);
-              if (hipMemsetAsync(kpp[q].fail, 0, sizeof(uint32_t), shards[q]->eng->stream_) != hipSuccess) return kmcudaRuntimeError;
-            }
-            if (many) RETERR(sync_all());   // (the seed's peer copies and the lowered flags, before the chooser reads across shards)
-            i = failed + 1;
-          }
-        } else {
-          for (uint32_t i = 1; i < K; i++) {
-            progress(i);
-            for (auto &s : shards) {
-              (void)hipSetDevice(s->dev);
-              const hipError_t ke = strict_h2
-                  ? launch_h2_to_row(metric, s->samples, s->length, D, s->centroids + (size_t)(i - 1) * D, i, 0, s->dists,
-                                     s->eng->stream_)
-                  : launch_kmpp_step(metric, s->samples, s->length, D, s->centroids + (size_t)(i - 1) * D, i, s->dists,
-                                     s->eng->stream_);
-              if (ke != hipSuccess) return kmcudaRuntimeError;
-            }
-            RETERR(host_choose(i, ((rand() + .0) / RAND_MAX)));
-          }
-        }
-        if (device_chooser) DEBUG("k-means++: %u of %u steps took the host chooser\n", host_steps, K - 1);
-        RETERR(sync_all());
-        if (kpp_filter) {
-          unsigned long long chains = 0;
-          bool read = true;
-          for (auto &k : kpp) {
-            unsigned long long v = 0;
-            (void)hipSetDevice(k.dev);
-            read = read && hipMemcpy(&v, k.stats + 2, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess;
-            chains += v;
-          }
-          if (read)
-            DEBUG("k-means++: the filtered steps ran %llu exact chains for %llu (row, step) pairs\n", chains,
-                  (unsigned long long)N * (K - 2));
-        }
+      case kmcudaInitMethodImport:
+        return seed_import(host_centroids, device_ptrs);
+      case kmcudaInitMethodRandom:
+        return seed_random(seed);
+      case kmcudaInitMethodPlusPlus:
+        RETERR(seed_plusplus());
         break;
-      }
-      case kmcudaInitMethodAFKMC2: {   // kmcuda.cc:337-396
-        uint32_t m = afk_m;
-        if (m == 0) {
-          m = 200;
-        } else if (m > N / 2) {
-          INFO("afkmc2: m > %u is not supported (got %u)\n", N / 2, m);
-          return kmcudaInvalidArguments;
-        }
-        float smoke = NAN;
-        uint32_t first_index = 0;
-        while (smoke != smoke) {
-          first_index = rand() % N;
-          RETERR(read_sample_value(first_index, 0, &smoke));
-        }
-        INFO("afkmc2: calculating q (c0 = %u)... ", first_index / D);
-        RETERR(copy_sample_to_centroid(first_index, 0));
-        // the candidate kernels index rows globally: with several shards the rows are gathered on the first
-        Shard &s0 = *shards[0];
-        (void)hipSetDevice(s0.dev);
-        hipStream_t st = s0.eng->stream_;
-        const float *all = s0.samples;
-        if (shards.size() > 1) {
-          float *gathered = nullptr;
-          int rc = s0.alloc(&gathered, (size_t)N * D);
-          if (rc) return rc;
-          RETERR(sync_all());
-          for (auto &s : shards) {
-            const hipError_t e = s->dev == s0.dev
-                ? hipMemcpy(gathered + (size_t)s->offset * D, s->samples, (size_t)s->length * D * sizeof(float), hipMemcpyDeviceToDevice)
-                : hipMemcpyPeer(gathered + (size_t)s->offset * D, s0.dev, s->samples, s->dev, (size_t)s->length * D * sizeof(float));
-            if (e != hipSuccess) return kmcudaMemoryCopyError;
-          }
-          all = gathered;
-        }
-        float *qdev = nullptr, *rand_dev = nullptr, *mind_dev = nullptr;
-        uint32_t *choice_dev = nullptr;
-        {
-          int rc;
-          if ((rc = s0.alloc(&qdev, N))) return rc;
-          if ((rc = s0.alloc(&rand_dev, m))) return rc;
-          if ((rc = s0.alloc(&mind_dev, m))) return rc;
-          if ((rc = s0.alloc(&choice_dev, m))) return rc;
-        }
-        if (hipMemsetAsync(choice_dev, 0, m * sizeof(uint32_t), st) != hipSuccess) return kmcudaRuntimeError;
-        std::vector<float> q(N), rand_a(m), p_cand(m);
-        std::vector<uint32_t> cand_ind(m);
-        // q(x) = 1 / 2N + d(x, c1)^2 / (2 sum d^2), with c1 = sample (first_index / D): the reference
-        // seeds q from THAT sample while centroid 0 is sample first_index (kmcuda.cc:356-362)
-        if ((strict_h2 ? launch_h2_to_row(metric, all, N, D, all + (size_t)(first_index / D) * D, 0, 1, qdev, st)
-                       : launch_afk_qdist(metric, all, N, D, all + (size_t)(first_index / D) * D, qdev, st)) != hipSuccess)
-          return kmcudaRuntimeError;
-        if (hipMemcpyAsync(q.data(), qdev, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-          return kmcudaMemoryCopyError;
-        const double dsum = butterfly_sum(q.data(), N);   // kmeans.cu:92-95 (warp sums, double accumulation)
-        if (launch_afk_q(qdev, N, (float)dsum, st) != hipSuccess) return kmcudaRuntimeError;
-        if (hipMemcpyAsync(q.data(), qdev, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-          return kmcudaMemoryCopyError;
-        INFO("done\n");
-        for (uint32_t k = 1; k < K; k++) {
-          if (verbosity > 1 || (verbosity > 0 && (K < 100 || k % (K / 100) == 0))) {
-            printf("\rstep %d", k);
-            fflush(stdout);
-          }
-          (void)hipSetDevice(s0.dev);
-          if (launch_afk_random_step(m, seed, k, qdev, N, choice_dev, rand_dev, st) != hipSuccess ||
-              (strict_h2 ? launch_h2_afk_min_dist(metric, m, k, all, D, choice_dev, s0.centroids, mind_dev, st)
-                         : launch_afk_min_dist(metric, m, k, all, D, choice_dev, s0.centroids, mind_dev, st)) != hipSuccess)
-            return kmcudaRuntimeError;
-          if (hipMemcpyAsync(cand_ind.data(), choice_dev, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-              hipMemcpyAsync(rand_a.data(), rand_dev, m * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
-              hipMemcpyAsync(p_cand.data(), mind_dev, m * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
-              hipStreamSynchronize(st) != hipSuccess)
-            return kmcudaMemoryCopyError;
-          float curr_prob = 0;   // the Metropolis-Hastings chain, kmcuda.cc:381-388
-          uint32_t curr_ind = 0;
-          for (uint32_t j = 0; j < m; j++) {
-            const float cand_prob = p_cand[j] / q[cand_ind[j]];
-            if (curr_prob == 0 || cand_prob / curr_prob > rand_a[j]) {
-              curr_ind = j;
-              curr_prob = cand_prob;
-            }
-          }
-          RETERR(copy_sample_to_centroid(cand_ind[curr_ind], k));
-        }
-        RETERR(sync_all());
+      case kmcudaInitMethodAFKMC2:
+        RETERR(seed_afkmc2(seed, afk_m));
         break;
-      }
       case kmcudaInitMethodParallel:   // (runs at the entry of kmamd_kmeans_weighted and arrives here as Import)
         return kmcudaInvalidArguments;
     }
     INFO("\rdone            \n");
     return 0;
+  }
+
+  int check_unit_norms() {  // kmcuda.cc:195-220: three unit-norm probes
+    std::vector<float> probe(D);
+    for (uint32_t s : {0u, N / 2, N - 1}) {
+      RETERR(read_sample(s, 0, D, probe.data()));
+      double norm = 0;
+      for (uint32_t i = 0; i < D; i++) norm += probe[i] * probe[i];
+      const float high = 1.00001, low = 0.99999;
+      if (norm > high || norm < low) {
+        INFO("error: angular distance: samples[%u] has L2 norm = %f which is outside [%f, %f]\n", s, norm, low, high);
+        return kmcudaInvalidArguments;
+      }
+    }
+    return 0;
+  }
+
+  // the first seed of k-means++ and AFK-MC2: random rows until one's first feature is not NaN (kmcuda.cc:265-270)
+  int draw_first_seed(uint32_t *index) {
+    float smoke = NAN;
+    while (smoke != smoke) {
+      *index = rand() % N;
+      RETERR(read_sample(*index, 0, 1, &smoke));
+    }
+    return 0;
+  }
+
+  void seeding_progress(uint32_t step) const {
+    if (verbosity > 1 || (verbosity > 0 && (K < 100 || step % (K / 100) == 0))) {
+      printf("\rstep %d", step);
+      fflush(stdout);
+    }
+  }
+
+  // K x D centroids of the caller (host memory, or device device_ptrs') into every replica
+  int seed_import(const float *host_centroids, int32_t device_ptrs) {
+    const size_t n = (size_t)K * D;
+    for (auto &s : shards) {
+      (void)hipSetDevice(s->dev);
+      if (!fp16) {
+        RETERR(s->copy_in(s->centroids, host_centroids, n, device_ptrs));
+        continue;
+      }
+      // halves -> the fp32 replica (halves that had to be copied stay in the shard's memory: K x D of them)
+      const uint16_t *halves = nullptr;
+      RETERR(s->stage_in(reinterpret_cast<const uint16_t *>(host_centroids), n, device_ptrs, &halves));
+      if (launch_half_to_float(halves, n, s->centroids, s->eng->stream_) != hipSuccess ||
+          hipStreamSynchronize(s->eng->stream_) != hipSuccess)
+        return kmcudaMemoryCopyError;   // (the code this step has always failed with)
+    }
+    return sync_all();
+  }
+
+  int seed_random(uint32_t seed) {
+    INFO("randomly picking initial centroids...\n");
+    // The reference shuffles ALL N indices with libstdc++'s std::random_shuffle over rand() and takes the first K
+    // (kmcuda.cc:245-253): for i = 1 .. N-1: swap(a[i], a[rand() % (i + 1)]).  Position i is untouched before its
+    // own step and a value that leaves the first K never returns, so the first K entries follow from a K-entry
+    // array: steps i < K swap inside it, a step i >= K whose draw j falls below K puts i at j.  Same draws, same
+    // rows, no N-entry array; with glibc's generator restated (GlibcRand: a rand() call is 10-20 ns behind its
+    // lock -- 45 ms of a 4M-row call, 90 ms at 8M rows) the N - 1 draws take a few ms, and rand()'s own state is
+    // set to what N - 1 calls would have left.
+    std::vector<uint32_t> chosen(K);
+    for (uint32_t c = 0; c < K; c++) chosen[c] = c;
+    GlibcRand fast;
+    if (fast.attach(seed)) {
+      for (uint32_t i = 1; i < N && i < K; i++) std::swap(chosen[i], chosen[fast.next() % (i + 1)]);
+      for (uint32_t i = K; i < N; i++) {
+        const uint32_t j = fast.next() % (i + 1);
+        if (j < K) chosen[j] = i;
+      }
+      fast.detach();
+    } else {   // another C library: its rand(), call by call
+      for (uint32_t i = 1; i < N && i < K; i++) std::swap(chosen[i], chosen[rand() % (i + 1)]);
+      for (uint32_t i = K; i < N; i++) {
+        const uint32_t j = rand() % (i + 1);
+        if (j < K) chosen[j] = i;
+      }
+    }
+    DEBUG("shuffle complete, copying to device(s)...\n");
+    if (shards.size() == 1) {   // one gather launch (the index list rides in the dists buffer: N >= K floats)
+      Shard &s = *shards[0];
+      (void)hipSetDevice(s.dev);
+      uint32_t *idx = reinterpret_cast<uint32_t *>(s.dists);
+      if (hipMemcpyAsync(idx, chosen.data(), K * sizeof(uint32_t), hipMemcpyHostToDevice, s.eng->stream_) != hipSuccess)
+        return kmcudaMemoryCopyError;
+      if (launch_gather_rows(s.samples, idx, K, D, s.centroids, s.eng->stream_) != hipSuccess) return kmcudaRuntimeError;
+    } else {
+      for (uint32_t c = 0; c < K; c++) RETERR(copy_sample_to_centroid(chosen[c], c));
+    }
+    return sync_all();   // (chosen[] must outlive the copy)
+  }
+
+  // k-means++ (kmcuda.cc:262-335): the scratch memory and the state of one seeding, from the second seed on.
+  // Two ways to the reference's choice (kmcuda.cc:286-326).  HOST: all N distances come back (pinned, 4 N bytes per
+  // step), butterfly sum and sequential double prefix sums as the reference.  DEVICE (seeding.hip): sums of floats in
+  // double are exact -- order free -- while the distances' exponent range is narrow enough, so the step kernel's
+  // exact block sums give the same choice from 4 bytes per batch of steps; a step whose range is too wide (or that
+  // holds a NaN / inf distance) takes the host way.
+  // Several row shards (round 5): every shard runs the step on its rows and leaves its own exact block sums; ONE
+  // chooser kernel on the first shard's device reads them where they lie (peer access) as the concatenation they are
+  // and copies the seed's row into every replica (seeding.hip: kmpp_choose_kernel) -- no N-sized transfer, no host in
+  // the loop.
+  struct KmppSeeding {
+    // Per shard: block statistics, local prefixes, totals, the fail flag and the outlier list (the shard's own memory,
+    // Shard::alloc), an event behind its step -- and for the filtered steps (seeding.hip) a centred byte copy of its
+    // rows (xs8; n2c: 4 floats per row) with what goes with it, in an arena of plain hipMallocs that ends with the
+    // seeding: a step's first kernel drops every row that provably is no closer to the new seed than to an earlier
+    // one, the exact chains run for the rest.  Same dists[] after every step either way, hence the same seeds.
+    struct PerShard {
+      unsigned char *block_stats = nullptr, *totals = nullptr, *outliers = nullptr;
+      double *bpre = nullptr;
+      uint32_t *fail = nullptr;   // [0] the flag, [1] the exponent cut, [2] the listed values' number
+      KmppOutlierBuf out;         // the step's exponent cut, the distances below it (seeding.hip: KmppOutlier)
+      hipEvent_t ev_step = nullptr;
+      std::unique_ptr<DeviceArena> filter_mem;
+      unsigned char *xs8 = nullptr;
+      float *n2c = nullptr, *mu = nullptr;
+      uint32_t *stats = nullptr, *list = nullptr;
+      double *part = nullptr;
+    };
+    Job &job;
+    const std::vector<std::unique_ptr<Shard>> &shards;
+    const int verbosity;
+    const uint32_t dp;                  // D rounded up to 128: the byte copy's row pitch
+    uint32_t log2n = 0;
+    std::vector<PerShard> kpp;
+    std::vector<KmppShardPtrs> views;   // what the chooser kernel reads of every shard
+    hipEvent_t ev_chosen = nullptr;
+    uint32_t *fail_host = nullptr;      // pinned: the first shard's fail flag after a batch of steps
+    float *host_dists = nullptr;        // pinned, N floats: allocated by the first step the host chooses
+    bool filter = false;
+    uint32_t host_steps = 0;
+
+    explicit KmppSeeding(Job &j)
+        : job(j), shards(j.shards), verbosity(j.verbosity), dp((j.D + 127u) / 128u * 128u), kpp(j.shards.size()) {
+      while ((1ull << log2n) < (uint64_t)job.N) log2n++;
+    }
+    ~KmppSeeding() {
+      (void)hipSetDevice(shards[0]->dev);
+      if (ev_chosen) (void)hipEventDestroy(ev_chosen);
+      for (size_t q = 0; q < kpp.size(); q++) {
+        (void)hipSetDevice(shards[q]->dev);
+        if (kpp[q].ev_step) (void)hipEventDestroy(kpp[q].ev_step);
+        kpp[q].filter_mem.reset();
+      }
+      if (fail_host) (void)hipHostFree(fail_host);
+      if (host_dists) (void)hipHostFree(host_dists);
+    }
+
+    int run() {
+      const bool device_chooser = device_chooser_possible();
+      if (device_chooser) RETERR(alloc_chooser());
+      RETERR(prepare_filter(device_chooser));
+      RETERR(device_chooser ? run_device() : run_host());
+      RETERR(job.sync_all());
+      if (filter) report_chains();
+      return 0;
+    }
+
+    // The device chooser needs whole 256-row blocks on every shard but the last (row_plan()) and peer access from the
+    // first shard's device to the others'; otherwise the host chooser.
+    bool device_chooser_possible() const {
+      bool can_choose = !job.strict_h2 && getenv("KMCUDA_AMD_KMPP_HOST") == nullptr && shards.size() <= (size_t)kKmppMaxShards;
+      for (auto &s : shards) {
+        can_choose = can_choose && kmpp_blocks(s->length) <= (1u << 20) &&   // (two-level prefix: 1024 x 1024 blocks of 256 rows)
+                     (s->offset % 256u == 0u) && s->length != 0;
+        if (can_choose && s->dev != shards[0]->dev) {
+          int can = 0;
+          (void)hipSetDevice(shards[0]->dev);
+          if (hipDeviceCanAccessPeer(&can, shards[0]->dev, s->dev) != hipSuccess || !can) {
+            can_choose = false;
+          } else {
+            const hipError_t pe = hipDeviceEnablePeerAccess(s->dev, 0);
+            if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) can_choose = false;
+          }
+          (void)hipGetLastError();
+        }
+      }
+      return can_choose;
+    }
+
+    // the chooser's buffers on every shard (small: the shard's slabs, alive until the job ends), the events that order
+    // the shards' steps around the chooser, the pinned word the fail flag comes back in
+    int alloc_chooser() {
+      const bool many = shards.size() > 1;
+      views.resize(shards.size());
+      for (size_t q = 0; q < shards.size(); q++) {
+        Shard &s = *shards[q];
+        PerShard &k = kpp[q];
+        (void)hipSetDevice(s.dev);
+        RETERR(s.alloc(&k.block_stats, kmpp_block_stat_bytes(s.length)));
+        RETERR(s.alloc(&k.totals, kmpp_totals_bytes()));
+        RETERR(s.alloc(&k.bpre, kmpp_prefix_doubles(s.length)));
+        RETERR(s.alloc(&k.fail, 4));
+        RETERR(s.alloc(&k.outliers, kmpp_outlier_bytes()));
+        k.out.ecut = k.fail + 1;
+        k.out.outl_count = k.fail + 2;
+        k.out.outl = k.outliers;
+        if (hipMemsetAsync(k.fail, 0, 4 * sizeof(uint32_t), s.eng->stream_) != hipSuccess) return kmcudaRuntimeError;
+        if (hipMemsetAsync(k.totals, 0, kmpp_totals_bytes(), s.eng->stream_) != hipSuccess) return kmcudaRuntimeError;
+        if (many && hipEventCreateWithFlags(&k.ev_step, hipEventDisableTiming) != hipSuccess) return kmcudaRuntimeError;
+        KmppShardPtrs &v = views[q];
+        v.dists = job.weighted ? s.wterms : s.dists; v.bpre = k.bpre; v.totals = k.totals;
+        v.samples = s.samples; v.centroids = s.centroids; v.fail = k.fail;
+        v.offset = s.offset; v.length = s.length;
+        v.out = k.out;
+      }
+      (void)hipSetDevice(shards[0]->dev);
+      if (many && hipEventCreateWithFlags(&ev_chosen, hipEventDisableTiming) != hipSuccess) return kmcudaRuntimeError;
+      if (hipHostMalloc(reinterpret_cast<void **>(&fail_host), sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+        return kmcudaMemoryAllocationFailure;
+      return 0;
+    }
+
+    // Whether the steps are the filtered ones, and if so the byte copy of every shard's rows.  Needs DP + 20 bytes per
+    // row beside the rows; without that memory on ANY shard (or KMCUDA_AMD_KMPP_FILTER=0) every step on every shard
+    // is the plain one, and what was allocated is freed here and now.
+    int prepare_filter(bool device_chooser) {
+      // (small jobs: the plain step is a few launches of nothing; KMCUDA_AMD_KMPP_FILTER=2 filters them too: tests)
+      filter = device_chooser && job.K >= 8 && job.N >= 65536u && dp <= 8192u;
+      if (const char *v = getenv("KMCUDA_AMD_KMPP_FILTER")) {
+        const int f = atoi(v);
+        filter = f >= 2 ? (device_chooser && job.K >= 3 && dp <= 8192u) : (filter && f != 0);
+      }
+      if (!filter) return 0;
+      bool ok = true;
+      for (size_t q = 0; q < shards.size() && ok; q++) {
+        Shard &s = *shards[q];
+        PerShard &k = kpp[q];
+        (void)hipSetDevice(s.dev);
+        k.filter_mem.reset(new DeviceArena{s.dev});
+        DeviceArena &mem = *k.filter_mem;
+        ok = mem.alloc(&k.xs8, (size_t)s.length * dp) == 0 && mem.alloc(&k.n2c, (size_t)s.length * 4) == 0 &&
+             mem.alloc(&k.mu, dp) == 0 && mem.alloc(&k.stats, 4) == 0 && mem.alloc(&k.list, s.length) == 0 &&
+             mem.alloc(&k.part, (size_t)64 * job.D) == 0;
+      }
+      if (!ok) {
+        (void)hipGetLastError();
+        filter = false;
+        for (auto &k : kpp) k.filter_mem.reset();   // (the events stay: they end with the seeding)
+        DEBUG("k-means++: no memory for the byte copy of the rows, plain steps\n");
+        return 0;
+      }
+      for (size_t q = 0; q < shards.size(); q++) {
+        Shard &s = *shards[q];
+        PerShard &k = kpp[q];
+        (void)hipSetDevice(s.dev);
+        if (launch_kmpp_cache(s.samples, s.length, job.D, dp, k.part, k.mu, k.xs8, k.n2c, k.stats, s.eng->stream_) != hipSuccess)
+          return kmcudaRuntimeError;
+      }
+      return 0;
+    }
+
+    // Enqueues step t for the random number `choice`: every shard's distances to seed t - 1 with their statistics,
+    // the chooser on the first shard's stream behind events of the others' steps, and the others' next steps behind
+    // an event of the chooser (the events must be RECORDED before they are waited for: one thread, in order).
+    int enqueue_step(uint32_t t, double choice) {
+      Shard &lead = *shards[0];
+      const bool many = shards.size() > 1;
+      for (size_t q = 0; q < shards.size(); q++) {
+        Shard &s = *shards[q];
+        PerShard &k = kpp[q];
+        (void)hipSetDevice(s.dev);
+        hipStream_t st = s.eng->stream_;
+        const float *newest = s.centroids + (size_t)(t - 1) * job.D;
+        const hipError_t se =
+            (filter && t >= 2)
+                ? launch_kmpp_step_filtered(job.metric, s.samples, s.length, job.D, dp, k.xs8, k.n2c, k.mu, k.stats, k.list,
+                                            newest, t, s.dists, k.block_stats, k.bpre, k.totals, k.fail, k.out, st,
+                                            s.weights, s.wterms)
+                : launch_kmpp_step2(job.metric, s.samples, s.length, job.D, newest, t, s.dists, k.block_stats, k.bpre,
+                                    k.totals, k.fail, k.out, st, s.weights, s.wterms);
+        if (se != hipSuccess) return kmcudaRuntimeError;
+        if (many && q != 0 && hipEventRecord(k.ev_step, st) != hipSuccess) return kmcudaRuntimeError;
+      }
+      (void)hipSetDevice(lead.dev);
+      for (size_t q = 1; q < shards.size(); q++)
+        if (hipStreamWaitEvent(lead.eng->stream_, kpp[q].ev_step, 0) != hipSuccess) return kmcudaRuntimeError;
+      if (launch_kmpp_choose(views.data(), (uint32_t)views.size(), job.N, choice, log2n, t, job.D, lead.eng->stream_) != hipSuccess)
+        return kmcudaRuntimeError;
+      if (many) {
+        if (hipEventRecord(ev_chosen, lead.eng->stream_) != hipSuccess) return kmcudaRuntimeError;
+        for (size_t q = 1; q < shards.size(); q++) {
+          (void)hipSetDevice(shards[q]->dev);
+          if (hipStreamWaitEvent(shards[q]->eng->stream_, ev_chosen, 0) != hipSuccess) return kmcudaRuntimeError;
+        }
+      }
+      return 0;
+    }
+
+    // the reference's chooser on the host (kmcuda.cc:286-326) for step i with random number `choice`: all N
+    // distances come back, butterfly sum, sequential double prefix sums; copies the seed
+    int host_choose(uint32_t i, double choice) {
+      const uint32_t N = job.N;
+      host_steps++;
+      if (!host_dists &&
+          hipHostMalloc(reinterpret_cast<void **>(&host_dists), (size_t)N * sizeof(float), hipHostMallocDefault) != hipSuccess)
+        return kmcudaMemoryAllocationFailure;
+      for (auto &s : shards) {
+        (void)hipSetDevice(s->dev);
+        // (weighted: the terms w * d where the reference sums d)
+        if (job.weighted && launch_kmpp_weigh(s->dists, s->weights, s->length, s->wterms, nullptr, s->eng->stream_) != hipSuccess)
+          return kmcudaRuntimeError;
+        if (hipMemcpyAsync(host_dists + s->offset, job.weighted ? s->wterms : s->dists, (size_t)s->length * sizeof(float),
+                           hipMemcpyDeviceToHost, s->eng->stream_) != hipSuccess)
+          return kmcudaMemoryCopyError;
+      }
+      RETERR(job.sync_all());
+      const double dist_sum = butterfly_sum(host_dists, N);
+      const uint32_t choice_approx = choice * N;
+      const double choice_sum = choice * dist_sum;
+      uint32_t j = 0;
+      if (choice_approx < 100) {
+        double dist_sum2 = 0;
+        for (j = 0; j < N && dist_sum2 < choice_sum; j++) dist_sum2 += host_dists[j];
+      } else {
+        double dist_sum2 = 0;
+        for (uint32_t t = 0; t < choice_approx; t++) dist_sum2 += host_dists[t];
+        if (dist_sum2 < choice_sum) {
+          for (j = choice_approx; j < N && dist_sum2 < choice_sum; j++) dist_sum2 += host_dists[j];
+        } else {
+          for (j = choice_approx; j > 1 && dist_sum2 >= choice_sum; j--) dist_sum2 -= host_dists[j];
+          j++;
+        }
+      }
+      if (j == 0 || j > N) {
+        INFO("\ninternal bug in kmeans_init_centroids: j = %u\n", j);
+        return kmcudaRuntimeError;
+      }
+      return job.copy_sample_to_centroid(j - 1, i);
+    }
+
+    // The host only draws the random numbers (one rand() per step, in order, as the reference) and enqueues:
+    // distances, statistics, prefix sums, the chooser and the copy of the chosen row all run on the device
+    // (seeding.hip).  A step the device cannot decide raises a flag that turns the rest of the enqueued kernels into
+    // no-ops; the host looks after every batch of steps, chooses that seed the reference's way from the distances as
+    // that step left them, lowers the flag and goes on behind it.
+    int run_device() {
+      Shard &lead = *shards[0];
+      const bool many = shards.size() > 1;
+      if (many) RETERR(job.sync_all());   // (the first seed's peer copies and the flags' memsets have landed everywhere)
+      std::vector<double> choices(job.K, 0.0);
+      // (steps enqueued behind an undecided one are wasted launches: the batch starts small, doubles while the
+      //  device decides, and falls back to one step after a hand-over -- a data set whose distances span too many
+      //  binades hands over every step)
+      constexpr uint32_t kBatchMax = 256;
+      uint32_t batch = 8, i = 1;
+      uint32_t drawn = 1;   // choices[1 .. drawn) are drawn
+      while (i < job.K) {
+        const uint32_t end = i + batch < job.K ? i + batch : job.K;
+        for (uint32_t t = i; t < end; t++) {
+          job.seeding_progress(t);
+          if (t >= drawn) {
+            choices[t] = ((rand() + .0) / RAND_MAX);   // kmcuda.cc:300
+            drawn = t + 1;
+          }
+          RETERR(enqueue_step(t, choices[t]));
+        }
+        (void)hipSetDevice(lead.dev);
+        if (hipMemcpyAsync(fail_host, kpp[0].fail, sizeof(uint32_t), hipMemcpyDeviceToHost, lead.eng->stream_) != hipSuccess ||
+            hipStreamSynchronize(lead.eng->stream_) != hipSuccess)
+          return kmcudaMemoryCopyError;
+        const uint32_t failed = *fail_host;
+        if (failed == 0) {
+          i = end;
+          batch = batch * 2 < kBatchMax ? batch * 2 : kBatchMax;
+          continue;
+        }
+        batch = 1;
+        if (failed < i || failed >= end) return kmcudaRuntimeError;
+        RETERR(host_choose(failed, choices[failed]));   // (waits for every shard: sync_all)
+        for (size_t q = 0; q < shards.size(); q++) {
+          (void)hipSetDevice(shards[q]->dev);
+          if (hipMemsetAsync(kpp[q].fail, 0, sizeof(uint32_t), shards[q]->eng->stream_) != hipSuccess) return kmcudaRuntimeError;
+        }
+        if (many) RETERR(job.sync_all());   // (the seed's peer copies and the lowered flags, before the chooser reads across shards)
+        i = failed + 1;
+      }
+      DEBUG("k-means++: %u of %u steps took the host chooser\n", host_steps, job.K - 1);
+      return 0;
+    }
+
+    // every step: the plain distances on every shard, then the host chooser
+    int run_host() {
+      for (uint32_t i = 1; i < job.K; i++) {
+        job.seeding_progress(i);
+        for (auto &s : shards) {
+          (void)hipSetDevice(s->dev);
+          const float *newest = s->centroids + (size_t)(i - 1) * job.D;
+          const hipError_t ke =
+              job.strict_h2 ? launch_h2_to_row(job.metric, s->samples, s->length, job.D, newest, i, 0, s->dists, s->eng->stream_)
+                            : launch_kmpp_step(job.metric, s->samples, s->length, job.D, newest, i, s->dists, s->eng->stream_);
+          if (ke != hipSuccess) return kmcudaRuntimeError;
+        }
+        RETERR(host_choose(i, ((rand() + .0) / RAND_MAX)));
+      }
+      return 0;
+    }
+
+    void report_chains() {
+      unsigned long long chains = 0;
+      bool read = true;
+      for (size_t q = 0; q < kpp.size(); q++) {
+        unsigned long long v = 0;
+        (void)hipSetDevice(shards[q]->dev);
+        read = read && hipMemcpy(&v, kpp[q].stats + 2, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess;
+        chains += v;
+      }
+      if (read)
+        DEBUG("k-means++: the filtered steps ran %llu exact chains for %llu (row, step) pairs\n", chains,
+              (unsigned long long)job.N * (job.K - 2));
+    }
+  };
+
+  int seed_plusplus() {
+    uint32_t first_index = 0;
+    RETERR(draw_first_seed(&first_index));
+    RETERR(copy_sample_to_centroid(first_index, 0));
+    INFO("performing kmeans++...\n");
+    if (weighted)
+      for (auto &s : shards)
+        if (!s->wterms) RETERR(s->alloc(&s->wterms, s->length));
+    KmppSeeding kpp(*this);
+    return kpp.run();
+  }
+
+  int seed_afkmc2(uint32_t seed, uint32_t afk_m) {   // kmcuda.cc:337-396
+    uint32_t m = afk_m;
+    if (m == 0) {
+      m = 200;
+    } else if (m > N / 2) {
+      INFO("afkmc2: m > %u is not supported (got %u)\n", N / 2, m);
+      return kmcudaInvalidArguments;
+    }
+    uint32_t first_index = 0;
+    RETERR(draw_first_seed(&first_index));
+    INFO("afkmc2: calculating q (c0 = %u)... ", first_index / D);
+    RETERR(copy_sample_to_centroid(first_index, 0));
+    // the candidate kernels index rows globally: with several shards the rows are gathered on the first
+    Shard &s0 = *shards[0];
+    (void)hipSetDevice(s0.dev);
+    hipStream_t st = s0.eng->stream_;
+    const float *all = s0.samples;
+    if (shards.size() > 1) {
+      float *gathered = nullptr;
+      RETERR(s0.alloc(&gathered, (size_t)N * D));
+      RETERR(sync_all());
+      for (auto &s : shards) {
+        const hipError_t e = s->dev == s0.dev
+            ? hipMemcpy(gathered + (size_t)s->offset * D, s->samples, (size_t)s->length * D * sizeof(float), hipMemcpyDeviceToDevice)
+            : hipMemcpyPeer(gathered + (size_t)s->offset * D, s0.dev, s->samples, s->dev, (size_t)s->length * D * sizeof(float));
+        if (e != hipSuccess) return kmcudaMemoryCopyError;
+      }
+      all = gathered;
+    }
+    float *qdev = nullptr, *rand_dev = nullptr, *mind_dev = nullptr;
+    uint32_t *choice_dev = nullptr;
+    RETERR(s0.alloc(&qdev, N));
+    RETERR(s0.alloc(&rand_dev, m));
+    RETERR(s0.alloc(&mind_dev, m));
+    RETERR(s0.alloc(&choice_dev, m));
+    if (hipMemsetAsync(choice_dev, 0, m * sizeof(uint32_t), st) != hipSuccess) return kmcudaRuntimeError;
+    std::vector<float> q(N), rand_a(m), p_cand(m);
+    std::vector<uint32_t> cand_ind(m);
+    // q(x) = 1 / 2N + d(x, c1)^2 / (2 sum d^2), with c1 = sample (first_index / D): the reference
+    // seeds q from THAT sample while centroid 0 is sample first_index (kmcuda.cc:356-362)
+    if ((strict_h2 ? launch_h2_to_row(metric, all, N, D, all + (size_t)(first_index / D) * D, 0, 1, qdev, st)
+                   : launch_afk_qdist(metric, all, N, D, all + (size_t)(first_index / D) * D, qdev, st)) != hipSuccess)
+      return kmcudaRuntimeError;
+    if (hipMemcpyAsync(q.data(), qdev, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return kmcudaMemoryCopyError;
+    const double dsum = butterfly_sum(q.data(), N);   // kmeans.cu:92-95 (warp sums, double accumulation)
+    if (launch_afk_q(qdev, N, (float)dsum, st) != hipSuccess) return kmcudaRuntimeError;
+    if (hipMemcpyAsync(q.data(), qdev, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return kmcudaMemoryCopyError;
+    INFO("done\n");
+    for (uint32_t k = 1; k < K; k++) {
+      seeding_progress(k);
+      (void)hipSetDevice(s0.dev);
+      if (launch_afk_random_step(m, seed, k, qdev, N, choice_dev, rand_dev, st) != hipSuccess ||
+          (strict_h2 ? launch_h2_afk_min_dist(metric, m, k, all, D, choice_dev, s0.centroids, mind_dev, st)
+                     : launch_afk_min_dist(metric, m, k, all, D, choice_dev, s0.centroids, mind_dev, st)) != hipSuccess)
+        return kmcudaRuntimeError;
+      if (hipMemcpyAsync(cand_ind.data(), choice_dev, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipMemcpyAsync(rand_a.data(), rand_dev, m * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipMemcpyAsync(p_cand.data(), mind_dev, m * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess)
+        return kmcudaMemoryCopyError;
+      float curr_prob = 0;   // the Metropolis-Hastings chain, kmcuda.cc:381-388
+      uint32_t curr_ind = 0;
+      for (uint32_t j = 0; j < m; j++) {
+        const float cand_prob = p_cand[j] / q[cand_ind[j]];
+        if (curr_prob == 0 || cand_prob / curr_prob > rand_a[j]) {
+          curr_ind = j;
+          curr_prob = cand_prob;
+        }
+      }
+      RETERR(copy_sample_to_centroid(cand_ind[curr_ind], k));
+    }
+    return sync_all();
   }
 
   // runs fn(shard) for every shard -- on one host thread per shard when there are several, so that a

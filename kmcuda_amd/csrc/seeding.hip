@@ -545,7 +545,7 @@ hipError_t launch_gather_rows(const float *samples, const uint32_t *idx, uint32_
   return hipGetLastError();
 }
 
-struct KmppTotals {   // device memory, one per shard (kmcuda_api.cpp mirrors the size)
+struct KmppTotals {   // device memory, one per shard (the host allocates kmpp_totals_bytes() and never reads it)
   double sum_g, sum_d;
   uint32_t emin, emax, bad, chosen;
   uint32_t grange, pad;   // exponent range of the non-zero butterfly sums ((max << 16) | min)
