@@ -462,32 +462,35 @@ int Engine::yy_filters(const float *samples, const float *centroids, const float
   return kSuccess;
 }
 
-int Engine::lloyd_assign(const float *samples, const float *centroids, uint32_t *assignments,
-                         uint32_t *assignments_prev, bool exact_only) {
-  KMX_HIP(hipSetDevice(device_), kNoSuchDevice);
-  // carried bounds describe the assignments of the LAST pass: whatever this pass turns out to be, they hold afterwards
-  // only if it was a carried pass itself (set at its end) -- an exact pass, the f32 filter, a rebuilt panel void them
-  const bool carry_was_valid = carry_valid_;
-  carry_valid_ = false;
-  if (strict_h2_) {
-    if (!h2_sq_) {
-      int rc = alloc(&h2_sq_, 2 * (size_t)K_);
-      if (rc) return rc;
-    }
-    span_begin(1);
-    KMX_HIP(launch_h2_csqr(metric_, centroids, K_, D_, h2_sq_, stream_), kRuntimeError);
-    KMX_HIP(launch_h2_assign(metric_, samples, N_, D_, centroids, K_, h2_sq_, assignments, assignments_prev, counters_,
-                             stream_),
-            kRuntimeError);
-    span_end();
-    return kSuccess;
+// ---------------------------------------------------------------------------------------
+// A Lloyd pass, stage by stage ("the host sequence of a pass"): lloyd_assign() below picks the kind of
+// pass and calls these in order.
+// ---------------------------------------------------------------------------------------
+namespace {
+// KMCUDA_AMD_CARRY_TRACE: what the carried-bounds passes decide, on stderr (read per pass: a caller may set it late)
+bool carry_trace() { return getenv("KMCUDA_AMD_CARRY_TRACE") != nullptr; }
+}  // namespace
+
+// KMCUDA_AMD_FP16_STRICT: the reference's half2 arithmetic, one kernel for the norms and one for the rows
+int Engine::assign_strict_h2(const float *samples, const float *centroids, uint32_t *assignments,
+                             uint32_t *assignments_prev) {
+  if (!h2_sq_) {
+    int rc = alloc(&h2_sq_, 2 * (size_t)K_);
+    if (rc) return rc;
   }
-  // row cache (two-stage f16 filter only): x - mu as halves in operand order, built on the first pass
-  // after set_row_cache(1); mu is frozen from then on, so the copy stays valid for every later pass
-  const bool two_stage = !exact_only && DP_ != 0 && filter_mode_ == 0 && lloyd_filter_f16_supported(D_, DP_);
-  const bool want_cache = row_cache_on_ && two_stage && N_ != 0;
-  const bool build_cache = want_cache && !row_cache_valid_;
-  if (build_cache) mu_frozen_ = false;  // take the mean of THESE centroids
+  span_begin(1);
+  KMX_HIP(launch_h2_csqr(metric_, centroids, K_, D_, h2_sq_, stream_), kRuntimeError);
+  KMX_HIP(launch_h2_assign(metric_, samples, N_, D_, centroids, K_, h2_sq_, assignments, assignments_prev, counters_,
+                           stream_),
+          kRuntimeError);
+  span_end();
+  return kSuccess;
+}
+
+// What every pass but the strict one needs before it enqueues anything: the side stream with its fork / join events
+// and, for the two-stage filter, the hi panel and the undecided list.  The duo list is an optimisation: without
+// memory for it stage 2 sweeps for every listed row.
+int Engine::ensure_pass_resources(bool two_stage) {
   if (!side_stream_) {
     // (non-blocking even beside a blocking main stream: fork / join events order it completely)
     side_stream_ = pooled_stream_acquire(device_);
@@ -503,202 +506,222 @@ int Engine::lloyd_assign(const float *samples, const float *centroids, uint32_t 
     int rc = alloc(&phi, (size_t)((K_pad_ + 63u) / 64u * 64u) * (DP_ + 2));  // whole 64-row super-tiles + their biases
     if (rc) return rc;
     if (!undecided_ && ((rc = alloc(&undecided_, N_)) || (rc = alloc(&und_thr_, N_)))) return rc;
-    if (duo_on_ && !duo_ && alloc(&duo_, 4 * (size_t)N_) != kSuccess) {   // (an optimisation: without it stage 2 sweeps for every listed row)
+    if (duo_on_ && !duo_ && alloc(&duo_, 4 * (size_t)N_) != kSuccess) {
       (void)hipGetLastError();
       duo_ = nullptr;
       duo_on_ = false;
     }
     panelhi_ = phi;
   }
-  // Steady state of the two-stage filter (mean frozen, cache valid): ONE preparation kernel in front of
-  // stage 1; the reference's serial sum_squares chain and the transposed panel, which only the pair /
-  // exact kernels read, are computed beside stage 1 on the side stream.
-  const bool steady = steady_state(exact_only);
-  // (the streamed filter's steady state: the same ONE preparation kernel, operands padded to wide_dp_)
-  const bool wide_sel = !exact_only && DP_ == 0 && wide_dp_ != 0 && !wide_failed_;
-  const bool wide_steady = wide_sel && mu_frozen_ && row_cache_on_ && row_cache_valid_ && N_ != 0 && panelhi_ != nullptr &&
-                           wide_rows16_ != nullptr && !strict_h2_;
+  return kSuccess;
+}
+
+// What the two frozen-mean preparations (launch_centroid_prep_frozen here, launch_apply_prep_frozen in
+// apply_prepare) share: the statistics' double buffer flips to the half the last preparation left zero, and a
+// carrying engine gets the centroids' drifts and its list cursor zeroed.
+Engine::FrozenPrep Engine::frozen_prep_flip() {
+  FrozenPrep p;
+  p.stats_next = stats_;
+  stats_ = stats_ == stats_base_ ? stats_base_ + 8 : stats_base_;
+  p.stats = stats_;
+  p.drift = carry_on_ ? drift_ : nullptr;
+  p.zero_d = carry_on_ && drift_ ? counters_ + kCarryCursor : nullptr;
+  return p;
+}
+
+// The centroids' preparation.  Steady state of either filter (mean frozen, row copy valid): ONE preparation kernel
+// in front of stage 1 -- unless apply_prepare() has run it behind the update --; the reference's serial sum_squares
+// chain and the transposed panel, which only the pair / exact kernels read, are computed beside stage 1 on the side
+// stream (*rows_on_side: their readers wait for ev_rows_).  Any other pass: prepare_centroids().
+int Engine::prepare_pass(const float *centroids, bool steady, bool wide_steady, bool *rows_on_side) {
   const bool prepared = steady && prepared_for_ == centroids;   // apply_prepare() has done this pass's preparation
   prepared_for_ = nullptr;
-  bool rows_on_side = false;
-  if (steady || wide_steady) {
-    KMX_HIP(hipEventRecord(ev_fork_, stream_), kRuntimeError);   // the centroids are final here
-    KMX_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0), kRuntimeError);
-    KMX_HIP(launch_centroid_rows(metric_, centroids, K_, D_, Kt_, csqr_, ct_, side_stream_), kRuntimeError);
-    KMX_HIP(hipEventRecord(ev_rows_, side_stream_), kRuntimeError);
-    rows_on_side = true;
-    if (!prepared) {
-      uint32_t *next = stats_;
-      stats_ = stats_ == stats_base_ ? stats_base_ + 8 : stats_base_;
-      KMX_HIP(launch_centroid_prep_frozen(metric_, centroids, K_, D_, K_pad_, DP_ ? DP_ : wide_dp_, mu_, finite_, bias_,
-                                          bias2_, cfil_, panelhi_, stats_, next, counters_ + 1, counters_ + 3, counters_ + 4,
-                                          carry_on_ ? drift_ : nullptr, carry_on_ && drift_ ? counters_ + kCarryCursor : nullptr,
-                                          stream_),
-              kRuntimeError);
-      carry_preps_++;
+  *rows_on_side = steady || wide_steady;
+  if (!*rows_on_side) return prepare_centroids(centroids);
+  KMX_HIP(hipEventRecord(ev_fork_, stream_), kRuntimeError);   // the centroids are final here
+  KMX_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0), kRuntimeError);
+  KMX_HIP(launch_centroid_rows(metric_, centroids, K_, D_, Kt_, csqr_, ct_, side_stream_), kRuntimeError);
+  KMX_HIP(hipEventRecord(ev_rows_, side_stream_), kRuntimeError);
+  if (!prepared) {
+    const FrozenPrep p = frozen_prep_flip();
+    KMX_HIP(launch_centroid_prep_frozen(metric_, centroids, K_, D_, K_pad_, DP_ ? DP_ : wide_dp_, mu_, finite_, bias_,
+                                        bias2_, cfil_, panelhi_, p.stats, p.stats_next, counters_ + 1, counters_ + 3,
+                                        counters_ + 4, p.drift, p.zero_d, stream_),
+            kRuntimeError);
+    carry_preps_++;
+  }
+  return kSuccess;
+}
+
+// The exact kernel over every row: exact_only passes, shapes without a filter
+int Engine::assign_exact(const LloydArgs &a) {
+  span_begin(1);
+  const uint32_t grid = N_ < 8192u ? N_ : 8192u;
+  KMX_HIP(launch_lloyd_exact(metric_, a, nullptr, nullptr, grid, stream_), kRuntimeError);
+  span_end();
+  return kSuccess;
+}
+
+// Row cache (two-stage f16 filter): x - mu as halves in operand order, built on the first pass after
+// set_row_cache(1); mu is frozen from then on, so the copy stays valid for every later pass.
+// No memory for the copy: not an error, the operands are converted from the rows every pass.
+int Engine::build_row_cache(const void *rows, bool half) {
+  if (!xcache_) {
+    const size_t npad = ((size_t)N_ + 255) / 256 * 256;
+    uint16_t *xc = nullptr;
+    float *xm = nullptr;
+    if (alloc(&xc, npad * DP_) == kSuccess && alloc(&xm, npad * 3 + 2) == kSuccess) {
+      xcache_ = xc;
+      xmeta_ = xm;
+    } else {
+      (void)hipGetLastError();
+      row_cache_on_ = false;
+      return kSuccess;
     }
-  } else {
-    int rc = prepare_centroids(centroids);
-    if (rc) return rc;
   }
-  LloydArgs a;
-  a.samples = samples; a.N = N_; a.D = D_; a.K = K_; a.K_pad = K_pad_; a.DP = DP_; a.Kt = Kt_;
-  a.cfil = cfil_; a.bias = bias_; a.mu = mu_; a.ct = ct_; a.csqr = csqr_; a.stats = stats_;
-  a.eps = eps_; a.tie_slack = tie_slack_;
-  a.assignments = assignments; a.assignments_prev = assignments_prev;
-  a.flagged = flagged_; a.pairs = pairs_; a.counters = counters_;
-  a.coarse_mfma = coarse_mfma_;
-  if (N_ == 0) return kSuccess;
-  if (wide_sel) {
-    const int rc = lloyd_assign_wide(a, centroids, wide_steady, rows_on_side, carry_was_valid);
-    if (rc != kNoSuchDevice + 100) return rc;   // (that code: no memory for its buffers -- the exact kernel below serves the shape)
-  }
-  if (exact_only || DP_ == 0 || (DP_ > 256 && filter_mode_ != 0)) {
-    span_begin(1);
-    const uint32_t grid = N_ < 8192u ? N_ : 8192u;
-    KMX_HIP(launch_lloyd_exact(metric_, a, nullptr, nullptr, grid, stream_), kRuntimeError);
-    span_end();
+  KMX_HIP(launch_row_cache(rows, half, N_, D_, DP_, mu_, xcache_, xmeta_, stream_), kRuntimeError);
+  row_cache_valid_ = true;
+  mu_frozen_ = true;
+  return kSuccess;
+}
+
+// The duo list pays when it takes whole ROUNDS of blocks off stage 2's sweep: a list that fits one round of its
+// 128-row blocks (two per CU) is one sweep long either way, and the second kernel only adds its launch.  By an
+// earlier pass's list lengths (whatever the update's report has delivered), the row count before any report.
+bool Engine::duo_pays() const {
+  if (!(duo_on_ && duo_)) return false;
+  if (duo_always_) return true;
+  const uint32_t und_prev = host_move_count_[2], duo_prev = host_move_count_[4];
+  const uint64_t listed_rows = (und_prev != 0xFFFFFFFFu && duo_prev != 0xFFFFFFFFu) ? (uint64_t)und_prev + duo_prev
+                                                                                      : (uint64_t)N_ / 16u;
+  return listed_rows > 512u * 128u;
+}
+
+// Carried bounds (lloyd_carry.hip), the set-up of both filters' carried passes: in the steady state a pass can leave
+// per-row distance bounds behind and the next one only looks at the rows they do not decide.  The drift of this
+// pass's centroids against the last pass's is the preparation kernel's (exactly one preparation since: anything
+// else voids the bounds).  `eligible` is the caller's (its steady state); wide_dg != 0: the streamed filter, whose
+// rows' records are wide_meta_ and which has no pair certificates (a row the later stages settle is listed again;
+// the drift bound's rounding allowance covers fp32 sums of up to ~6000 terms).  Leaves cp->on false for a plain
+// pass: not eligible, paused by the policy, or no memory for the bounds (not an error: carrying is switched off).
+// Otherwise cp->cy is filled and, when the bounds are valid and moved once, the skip kernel is enqueued.
+int Engine::carry_begin(bool eligible, bool carry_was_valid, const LloydArgs &a, uint32_t wide_dg, CarryPass *cp) {
+  const bool streamed = wide_dg != 0;
+  if (!eligible) return kSuccess;
+  const bool trace = carry_trace();
+  if (carry_policy_.paused()) {   // the bounds decided next to nothing lately: plain passes for a while
+    if (trace) fprintf(stderr, "[carry] paused (%u more)\n", carry_policy_.pause);
     return kSuccess;
   }
-  // counters_[1] / [3] / [4] (the filter's list lengths) were zeroed by the preparation
-  span_begin(0);
-  if (two_stage) {
-    const void *rows = half_rows_ ? half_rows_ : (const void *)samples;
-    const bool half = half_rows_ != nullptr;
-    bool duo_listed = false;   // stage 1 wrote a duo list (plain passes)
-    if (!steady)
-      KMX_HIP(launch_centroid_panelhi(centroids, K_, D_, K_pad_, DP_, finite_, mu_, bias_, panelhi_, stats_, stream_),
-              kRuntimeError);
-    if (build_cache) {
-      const size_t npad = ((size_t)N_ + 255) / 256 * 256;
-      if (!xcache_) {
-        uint16_t *xc = nullptr;
-        float *xm = nullptr;
-        // no memory for the copy: not an error, the operands are converted from the rows every pass
-        if (alloc(&xc, npad * DP_) == kSuccess && alloc(&xm, npad * 3 + 2) == kSuccess) {
-          xcache_ = xc;
-          xmeta_ = xm;
-        } else {
-          (void)hipGetLastError();
-          row_cache_on_ = false;
-        }
-      }
-      if (xcache_) {
-        KMX_HIP(launch_row_cache(rows, half, N_, D_, DP_, mu_, xcache_, xmeta_, stream_), kRuntimeError);
-        row_cache_valid_ = true;
-        mu_frozen_ = true;
-      }
+  if (!ub_) {
+    const bool pairs = !streamed && carry_pairs_;   // (the pair certificates)
+    if (alloc(&ub_, N_) != kSuccess || alloc(&lb_, N_) != kSuccess ||
+        alloc(&drift_, 2 * (size_t)K_) != kSuccess ||   // (+ K bias changes: the angular metric)
+        (pairs && (alloc(&l3_, N_) != kSuccess || alloc(&p1_, N_) != kSuccess || alloc(&p2_, N_) != kSuccess)) ||
+        alloc(&carry_list_, N_) != kSuccess || !(host_carry_ = pinned_words(2, &host_carry_dev_))) {
+      (void)hipGetLastError();
+      carry_on_ = false;
+      ub_ = nullptr;
+      l3_ = nullptr;
+      return kSuccess;
     }
-    const bool cached = row_cache_on_ && row_cache_valid_;
-    // Carried bounds (lloyd_carry.hip): in the steady state the pass can leave per-row distance bounds behind and the
-    // next one only looks at the rows they do not decide.  The drift of this pass's centroids against the last pass's
-    // is the preparation kernel's (exactly one preparation since: anything else voids the bounds).
-    bool carry = carry_on_ && steady && cached;
-    if (carry && carry_policy_.paused()) {   // the bounds decided next to nothing lately: plain passes for a while
-      carry = false;
-      if (getenv("KMCUDA_AMD_CARRY_TRACE")) fprintf(stderr, "[carry] paused (%u more)\n", carry_policy_.pause);
-    }
-    if (carry && !ub_) {
-      // (no memory: not an error, plain passes)
-      const bool pairs = carry_pairs_;   // (the pair certificates)
-      if (alloc(&ub_, N_) != kSuccess || alloc(&lb_, N_) != kSuccess ||
-          alloc(&drift_, 2 * (size_t)K_) != kSuccess ||   // (+ K bias changes: the angular metric)
-          (pairs && (alloc(&l3_, N_) != kSuccess || alloc(&p1_, N_) != kSuccess || alloc(&p2_, N_) != kSuccess)) ||
-          alloc(&carry_list_, N_) != kSuccess || !(host_carry_ = pinned_words(2, &host_carry_dev_))) {
-        (void)hipGetLastError();
-        carry_on_ = false;
-        ub_ = nullptr;
-        l3_ = nullptr;
-      } else {
-        host_carry_[0] = 0xFFFFFFFFu;
-        host_carry_[1] = 0;
-        if (const char *v = getenv("KMCUDA_AMD_CARRY_MAX")) carry_policy_.list_max = (float)atof(v);
-      }
-    }
-    span_begin(3);  // the dominant kernel on its own, inside the filter span
-    // The duo list pays when it takes whole ROUNDS of blocks off stage 2's sweep: a list that fits one round of its
-    // 128-row blocks (two per CU) is one sweep long either way, and the second kernel only adds its launch.  By an
-    // earlier pass's list lengths (whatever the update's report has delivered), the row count before any report.
-    duo_listed = duo_on_ && duo_;
-    if (duo_listed && !duo_always_) {
-      const uint32_t und_prev = host_move_count_[2], duo_prev = host_move_count_[4];
-      const uint64_t listed_rows = (und_prev != 0xFFFFFFFFu && duo_prev != 0xFFFFFFFFu) ? (uint64_t)und_prev + duo_prev
-                                                                                          : (uint64_t)N_ / 16u;
-      duo_listed = listed_rows > 512u * 128u;
-    }
-    CarryArgs cy_refine;   // (stage 2 leaves bounds only in a carried pass)
-    if (carry && carry_on_) {
-      CarryArgs cy;
-      cy.ub = ub_; cy.lb = lb_; cy.host_report = host_carry_dev_; cy.seq = ++carry_seq_;
-      cy.angular = metric_ != 0;
-      cy.l3 = l3_; cy.p1 = p1_; cy.p2 = p2_;
-      cy_refine = cy;
-      const bool moved = carry_was_valid && carry_preps_ == 1;   // drift_ / stats_[6] belong to the bounds
-      uint32_t hint = 0xFFFFFFFFu;
-      bool listed = false;
-      if (moved) {
-        // what the host knows of an EARLIER pass's list (a pinned word the coarse kernel writes; only speed depends
-        // on it): a short list -> the listed pass; else every row from the row cache, the list only counted
-        const uint32_t last = host_carry_[0], last_seq = host_carry_[1];
-        listed = carry_policy_.decide(last, last_seq, carry_seq_, N_);
-        if (listed) hint = last;
-        KMX_HIP(launch_carry_skip(N_, K_, assignments, assignments_prev, cy, xmeta_, drift_, stats_, tie_slack_,
-                                  carry_list_, finite_, pairs_, counters_, !listed, stream_),
-                kRuntimeError);
-        cy.n_list = counters_ + kCarryCursor;
-      }
-      if (listed) cy.row_list = carry_list_;
-      static const bool trace = getenv("KMCUDA_AMD_CARRY_TRACE") != nullptr;
-      if (trace) {   // (debugging aid: synchronises)
-        uint32_t w[8] = {0};
-        (void)hipStreamSynchronize(stream_);
-        (void)hipMemcpy(w, stats_, sizeof(w), hipMemcpyDeviceToHost);
-        float f[8];
-        memcpy(f, w, sizeof(f));
-        fprintf(stderr, "[carry] stats: max ||c'||^2 %g, max |bias| %g, max ||c||^2 %g, max residual^2 %g, max drift %g, max bias change %g; "
-                "stage 2 took %u rows of an earlier pass\n", f[0], f[1], f[2], f[5], f[6], f[7], host_move_count_[2]);
-      }
-      if (trace)
-        fprintf(stderr, "[carry] pass %u: bounds %s, %u preparation(s) since, last reported list %u (pass %u), %s\n",
-                carry_seq_, carry_was_valid ? "valid" : "void", carry_preps_, host_carry_[0], host_carry_[1],
-                listed ? "listed pass" : (moved ? "whole pass, list counted" : "whole pass"));
-      KMX_HIP(launch_lloyd_coarse_carry(a, rows, half, xcache_, xmeta_, panelhi_, undecided_, und_thr_, cy, hint,
-                                        duo_listed ? duo_ : nullptr, stream_),
-              kRuntimeError);
-      carry_valid_ = true;
-    } else {
-      KMX_HIP(launch_lloyd_coarse(a, rows, half, cached ? xcache_ : nullptr, xmeta_, panelhi_, undecided_, und_thr_,
-                                  duo_listed ? duo_ : nullptr, stream_),
-              kRuntimeError);
-    }
-    // the rows stage 1 listed with their two contenders (lloyd_duo.hip): stage 2's decision without its sweep, beside
-    // stage 2's sweep over the rest (a round of 67-KB blocks that leaves most of the chip's waves free)
-    if (duo_listed) {
-      KMX_HIP(hipEventRecord(ev_fork_, stream_), kRuntimeError);
-      KMX_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0), kRuntimeError);
-      KMX_HIP(launch_lloyd_duo(a, duo_, side_stream_, cy_refine.l3 ? &cy_refine : nullptr), kRuntimeError);
-      KMX_HIP(hipEventRecord(ev_join_, side_stream_), kRuntimeError);
-    }
-    carry_preps_ = 0;
-    span_end();
-    // stage 2's grid follows an EARLIER pass's list length (whatever the update's async copy has
-    // delivered to the pinned word; the kernel strides over the device-side count, so only speed
-    // depends on it)
-    last_undecided_ = host_move_count_[2];
-    if (cy_refine.l3) {
-      KMX_HIP(launch_lloyd_refine_carry(a, rows, half, panelhi_, undecided_, und_thr_, counters_ + 4, last_undecided_,
-                                        cy_refine, stream_),
-              kRuntimeError);
-    } else {
-      KMX_HIP(launch_lloyd_refine(a, rows, half, panelhi_, undecided_, und_thr_, counters_ + 4, last_undecided_,
-                                  stream_),
-              kRuntimeError);
-    }
-    if (duo_listed) KMX_HIP(hipStreamWaitEvent(stream_, ev_join_, 0), kRuntimeError);
-  } else {
-    KMX_HIP(launch_lloyd_filter(a, stream_), kRuntimeError);
+    host_carry_[0] = 0xFFFFFFFFu;
+    host_carry_[1] = 0;
+    if (const char *v = getenv("KMCUDA_AMD_CARRY_MAX")) carry_policy_.list_max = (float)atof(v);
   }
+  CarryArgs &cy = cp->cy;
+  cy.ub = ub_; cy.lb = lb_; cy.host_report = host_carry_dev_; cy.seq = ++carry_seq_;
+  cy.angular = metric_ != 0;
+  if (!streamed) { cy.l3 = l3_; cy.p1 = p1_; cy.p2 = p2_; }
+  cp->moved = carry_was_valid && carry_preps_ == 1;   // drift_ / stats_[6] belong to the bounds
+  if (cp->moved) {
+    // what the host knows of an EARLIER pass's list (a pinned word the filter kernel writes; only speed depends
+    // on it): a short list -> the listed pass; else every row from the row copy, the list only counted
+    const uint32_t last = host_carry_[0], last_seq = host_carry_[1];
+    cp->listed = carry_policy_.decide(last, last_seq, carry_seq_, N_);
+    if (cp->listed) cp->hint = last;
+    KMX_HIP(launch_carry_skip(N_, K_, a.assignments, a.assignments_prev, cy, streamed ? wide_meta_ : xmeta_, drift_,
+                              stats_, tie_slack_, carry_list_, finite_, pairs_, counters_, !cp->listed, stream_, wide_dg),
+            kRuntimeError);
+    cy.n_list = counters_ + kCarryCursor;
+  }
+  if (cp->listed) cy.row_list = carry_list_;
+  if (trace && !streamed) {   // (debugging aid: synchronises)
+    uint32_t w[8] = {0};
+    (void)hipStreamSynchronize(stream_);
+    (void)hipMemcpy(w, stats_, sizeof(w), hipMemcpyDeviceToHost);
+    float f[8];
+    memcpy(f, w, sizeof(f));
+    fprintf(stderr, "[carry] stats: max ||c'||^2 %g, max |bias| %g, max ||c||^2 %g, max residual^2 %g, max drift %g, max bias change %g; "
+            "stage 2 took %u rows of an earlier pass\n", f[0], f[1], f[2], f[5], f[6], f[7], host_move_count_[2]);
+  }
+  if (trace)
+    fprintf(stderr, "[carry] %spass %u: bounds %s, %u preparation(s) since, last reported list %u (pass %u), %s\n",
+            streamed ? "streamed " : "", carry_seq_, carry_was_valid ? "valid" : "void", carry_preps_, host_carry_[0],
+            host_carry_[1], cp->listed ? "listed pass" : (cp->moved ? "whole pass, list counted" : "whole pass"));
+  cp->on = true;
+  return kSuccess;
+}
+
+// The two-stage f16 filter: stage 1 (hi.hi products; a carried pass over the rows its bounds do not decide), the
+// rows it lists with two contenders beside stage 2 on the side stream, stage 2 over the rest.
+// counters_[1] / [3] / [4] (the filter's list lengths) were zeroed by the preparation.
+int Engine::filter_two_stage(const LloydArgs &a, const float *centroids, bool steady, bool carry_was_valid) {
+  const void *rows = half_rows_ ? half_rows_ : (const void *)a.samples;
+  const bool half = half_rows_ != nullptr;
+  int rc;
+  if (!steady)
+    KMX_HIP(launch_centroid_panelhi(centroids, K_, D_, K_pad_, DP_, finite_, mu_, bias_, panelhi_, stats_, stream_),
+            kRuntimeError);
+  if (row_cache_on_ && !row_cache_valid_ && (rc = build_row_cache(rows, half))) return rc;
+  const bool cached = row_cache_on_ && row_cache_valid_;
+  span_begin(3);  // the dominant kernel on its own, inside the filter span
+  const bool duo_listed = duo_pays();   // stage 1 writes a duo list
+  CarryPass cp;
+  if ((rc = carry_begin(carry_on_ && steady && cached, carry_was_valid, a, 0, &cp))) return rc;
+  CarryArgs cy_refine;   // (stage 2 leaves bounds only in a carried pass: the pair certificates, for every row it takes)
+  if (cp.on) {
+    cy_refine = cp.cy;
+    cy_refine.n_list = nullptr;
+    cy_refine.row_list = nullptr;
+    KMX_HIP(launch_lloyd_coarse_carry(a, rows, half, xcache_, xmeta_, panelhi_, undecided_, und_thr_, cp.cy, cp.hint,
+                                      duo_listed ? duo_ : nullptr, stream_),
+            kRuntimeError);
+    carry_valid_ = true;
+  } else {
+    KMX_HIP(launch_lloyd_coarse(a, rows, half, cached ? xcache_ : nullptr, xmeta_, panelhi_, undecided_, und_thr_,
+                                duo_listed ? duo_ : nullptr, stream_),
+            kRuntimeError);
+  }
+  // the rows stage 1 listed with their two contenders (lloyd_duo.hip): stage 2's decision without its sweep, beside
+  // stage 2's sweep over the rest (a round of 67-KB blocks that leaves most of the chip's waves free)
+  if (duo_listed) {
+    KMX_HIP(hipEventRecord(ev_fork_, stream_), kRuntimeError);
+    KMX_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0), kRuntimeError);
+    KMX_HIP(launch_lloyd_duo(a, duo_, side_stream_, cy_refine.l3 ? &cy_refine : nullptr), kRuntimeError);
+    KMX_HIP(hipEventRecord(ev_join_, side_stream_), kRuntimeError);
+  }
+  carry_preps_ = 0;
   span_end();
+  // stage 2's grid follows an EARLIER pass's list length (whatever the update's async copy has
+  // delivered to the pinned word; the kernel strides over the device-side count, so only speed
+  // depends on it)
+  last_undecided_ = host_move_count_[2];
+  if (cy_refine.l3) {
+    KMX_HIP(launch_lloyd_refine_carry(a, rows, half, panelhi_, undecided_, und_thr_, counters_ + 4, last_undecided_,
+                                      cy_refine, stream_),
+            kRuntimeError);
+  } else {
+    KMX_HIP(launch_lloyd_refine(a, rows, half, panelhi_, undecided_, und_thr_, counters_ + 4, last_undecided_,
+                                stream_),
+            kRuntimeError);
+  }
+  if (duo_listed) KMX_HIP(hipStreamWaitEvent(stream_, ev_join_, 0), kRuntimeError);
+  return kSuccess;
+}
+
+// The exact kernels over the lists a register-resident filter left: contender pairs and flagged rows.
+int Engine::settle_lists(const LloydArgs &a, const float *centroids, bool rows_on_side) {
   span_begin(1);
   if (settle_ && lloyd_settle_supported(a, centroids)) {
     // both lists in one launch (KMCUDA_AMD_SETTLE=0: the two older kernels below, the cross-check)
@@ -722,25 +745,63 @@ int Engine::lloyd_assign(const float *samples, const float *centroids, uint32_t 
   return kSuccess;
 }
 
-// D beyond the register-resident filters: lloyd_wide.hip.  prepare_centroids() has run (csqr, ct, mean -- frozen
-// while a row copy is alive --, centred fp32 panel, biases, statistics, list counters zeroed).
-int Engine::lloyd_assign_wide(const LloydArgs &a0, const float *centroids, bool steady, bool rows_on_side,
-                              bool carry_was_valid) {
-  constexpr int kNoFilter = kNoSuchDevice + 100;
-  LloydArgs a = a0;
+int Engine::lloyd_assign(const float *samples, const float *centroids, uint32_t *assignments,
+                         uint32_t *assignments_prev, bool exact_only) {
+  KMX_HIP(hipSetDevice(device_), kNoSuchDevice);
+  // carried bounds describe the assignments of the LAST pass: whatever this pass turns out to be, they hold afterwards
+  // only if it was a carried pass itself (set at its end) -- an exact pass, the f32 filter, a rebuilt panel void them
+  const bool carry_was_valid = carry_valid_;
+  carry_valid_ = false;
+  if (strict_h2_) return assign_strict_h2(samples, centroids, assignments, assignments_prev);
+  const bool two_stage = !exact_only && DP_ != 0 && filter_mode_ == 0 && lloyd_filter_f16_supported(D_, DP_);
+  // a row cache to build in this pass: take the mean of THESE centroids
+  if (row_cache_on_ && two_stage && N_ != 0 && !row_cache_valid_) mu_frozen_ = false;
+  int rc = ensure_pass_resources(two_stage);
+  if (rc) return rc;
+  // the steady states (mean frozen, row copy valid, panel allocated) of the two-stage filter and of the streamed one
+  const bool steady = steady_state(exact_only);
+  const bool wide_sel = !exact_only && DP_ == 0 && wide_dp_ != 0 && !wide_failed_;
+  const bool wide_steady = wide_sel && mu_frozen_ && row_cache_on_ && row_cache_valid_ && N_ != 0 && panelhi_ != nullptr &&
+                           wide_rows16_ != nullptr;
+  bool rows_on_side = false;
+  if ((rc = prepare_pass(centroids, steady, wide_steady, &rows_on_side))) return rc;
+  LloydArgs a;
+  a.samples = samples; a.N = N_; a.D = D_; a.K = K_; a.K_pad = K_pad_; a.DP = DP_; a.Kt = Kt_;
+  a.cfil = cfil_; a.bias = bias_; a.mu = mu_; a.ct = ct_; a.csqr = csqr_; a.stats = stats_;
+  a.eps = eps_; a.tie_slack = tie_slack_;
+  a.assignments = assignments; a.assignments_prev = assignments_prev;
+  a.flagged = flagged_; a.pairs = pairs_; a.counters = counters_;
+  a.coarse_mfma = coarse_mfma_;
+  if (N_ == 0) return kSuccess;
+  if (wide_sel) {
+    rc = lloyd_assign_wide(a, centroids, wide_steady, rows_on_side, carry_was_valid);
+    if (rc != kNoFilter) return rc;   // (no memory for its buffers: the exact kernel below serves the shape)
+  }
+  if (exact_only || DP_ == 0 || (DP_ > 256 && filter_mode_ != 0)) return assign_exact(a);
+  span_begin(0);
+  if (two_stage) {
+    if ((rc = filter_two_stage(a, centroids, steady, carry_was_valid))) return rc;
+  } else {
+    KMX_HIP(launch_lloyd_filter(a, stream_), kRuntimeError);
+  }
+  span_end();
+  return settle_lists(a, centroids, rows_on_side);
+}
+
+// The streamed filter's own memory (the hi panel at its width, the listed rows' contender table, the half copy of
+// the rows) is an optimisation: a job whose rows fit but whose copies do not runs on the exact kernels, as it did
+// before this path existed.  kNoFilter then, for good (wide_dp_ stays: the preparation's buffers are sized by it).
+int Engine::ensure_wide_buffers() {
   const uint32_t DG = wide_dp_;
-  const uint32_t k_pad64 = (K_pad_ + 63u) / 64u * 64u;
-  // This path's own memory (half copy of the rows, the listed rows' contender table) is an optimisation: a job whose
-  // rows fit but whose copies do not runs on the exact kernels, as it did before this path existed
   auto no_memory = [&]() {
     (void)hipGetLastError();
     if (g_verbosity > 0) printf("rows wider than 256 features: no memory for the streamed filter's buffers -- exact kernels\n");
-    wide_failed_ = true;   // (wide_dp_ stays: the preparation's buffers are sized by it)
+    wide_failed_ = true;
     return kNoFilter;
   };
   if (!panelhi_) {
     uint16_t *phi = nullptr;
-    if (alloc(&phi, (size_t)k_pad64 * (DG + 2))) return no_memory();
+    if (alloc(&phi, (size_t)((K_pad_ + 63u) / 64u * 64u) * (DG + 2))) return no_memory();
     panelhi_ = phi;
   }
   if (!wide_cont_) {
@@ -754,6 +815,17 @@ int Engine::lloyd_assign_wide(const LloydArgs &a0, const float *centroids, bool 
     if (alloc(&xg, (size_t)N_ * DG) || alloc(&wide_meta_, ((size_t)N_ + 1) * 4)) return no_memory();
     wide_rows16_ = xg;
   }
+  return kSuccess;
+}
+
+// D beyond the register-resident filters: lloyd_wide.hip.  prepare_pass() has run (csqr, ct, mean -- frozen
+// while a row copy is alive --, centred fp32 panel, biases, statistics, list counters zeroed).  Everything on the
+// main stream; the exact chains wait for the side stream's csqr / ct in front of the contender kernel.
+int Engine::lloyd_assign_wide(const LloydArgs &a, const float *centroids, bool steady, bool rows_on_side,
+                              bool carry_was_valid) {
+  const uint32_t DG = wide_dp_;
+  int rc = ensure_wide_buffers();
+  if (rc) return rc;
   span_begin(0);
   // hi halves of the centred centroids (+ their residual maximum, stats[5]); the steady state's one preparation
   // kernel has written them
@@ -770,52 +842,13 @@ int Engine::lloyd_assign_wide(const LloydArgs &a0, const float *centroids, bool 
       mu_frozen_ = true;
     }
   }
-  // Carried bounds, as in the register-resident filter's steady state (lloyd_assign): the pass leaves per-row bounds,
-  // the next one only looks at the rows they do not decide.  No pair certificates here: a row the later stages settle
-  // is listed again.  (The drift bound's rounding allowance covers fp32 sums of up to ~6000 terms.)
-  bool carry = carry_on_ && steady && DG <= 4096u;
-  if (carry && carry_policy_.paused()) {
-    carry = false;
-    if (getenv("KMCUDA_AMD_CARRY_TRACE")) fprintf(stderr, "[carry] paused (%u more)\n", carry_policy_.pause);
-  }
-  if (carry && !ub_) {
-    if (alloc(&ub_, N_) != kSuccess || alloc(&lb_, N_) != kSuccess || alloc(&drift_, 2 * (size_t)K_) != kSuccess ||
-        alloc(&carry_list_, N_) != kSuccess || !(host_carry_ = pinned_words(2, &host_carry_dev_))) {
-      (void)hipGetLastError();   // (no memory: not an error, plain passes)
-      carry_on_ = false;
-      ub_ = nullptr;
-    } else {
-      host_carry_[0] = 0xFFFFFFFFu;
-      host_carry_[1] = 0;
-      if (const char *v = getenv("KMCUDA_AMD_CARRY_MAX")) carry_policy_.list_max = (float)atof(v);
-    }
-  }
   span_begin(3);   // the dominant kernels on their own, inside the filter span
-  if (carry && carry_on_) {
-    CarryArgs cy;
-    cy.ub = ub_; cy.lb = lb_; cy.host_report = host_carry_dev_; cy.seq = ++carry_seq_;
-    cy.angular = metric_ != 0;
-    const bool moved = carry_was_valid && carry_preps_ == 1;   // drift_ / stats_[6] belong to the bounds
-    bool listed = false;
-    if (moved) {
-      const uint32_t last = host_carry_[0], last_seq = host_carry_[1];
-      listed = carry_policy_.decide(last, last_seq, carry_seq_, N_);
-      KMX_HIP(launch_carry_skip(N_, K_, a.assignments, a.assignments_prev, cy, wide_meta_, drift_, stats_, tie_slack_,
-                                carry_list_, finite_, pairs_, counters_, !listed, stream_, DG),
-              kRuntimeError);
-      cy.n_list = counters_ + kCarryCursor;
-    }
-    if (listed) cy.row_list = carry_list_;
-    if (getenv("KMCUDA_AMD_CARRY_TRACE"))
-      fprintf(stderr, "[carry] streamed pass %u: bounds %s, %u preparation(s) since, last reported list %u (pass %u), %s\n",
-              carry_seq_, carry_was_valid ? "valid" : "void", carry_preps_, host_carry_[0], host_carry_[1],
-              listed ? "listed pass" : (moved ? "whole pass, list counted" : "whole pass"));
-    KMX_HIP(launch_lloyd_wide(a, wide_rows16_, wide_meta_, DG, panelhi_, undecided_, und_thr_, wide_cont_, stream_, &cy),
-            kRuntimeError);
-    carry_valid_ = true;
-  } else {
-    KMX_HIP(launch_lloyd_wide(a, wide_rows16_, wide_meta_, DG, panelhi_, undecided_, und_thr_, wide_cont_, stream_), kRuntimeError);
-  }
+  CarryPass cp;
+  if ((rc = carry_begin(carry_on_ && steady && DG <= 4096u, carry_was_valid, a, DG, &cp))) return rc;
+  KMX_HIP(launch_lloyd_wide(a, wide_rows16_, wide_meta_, DG, panelhi_, undecided_, und_thr_, wide_cont_, stream_,
+                            cp.on ? &cp.cy : nullptr),
+          kRuntimeError);
+  if (cp.on) carry_valid_ = true;
   carry_preps_ = 0;
   span_end();
   if (rows_on_side) KMX_HIP(hipStreamWaitEvent(stream_, ev_rows_, 0), kRuntimeError);   // csqr / ct: the exact chains
@@ -918,13 +951,11 @@ int Engine::apply_prepare(const double *delta, const double *dcount_d, float *ce
     int rc = stop_ctl(stop_threshold, report, seq, &ctl);
     if (rc) return rc;
   }
-  uint32_t *next = stats_;
-  stats_ = stats_ == stats_base_ ? stats_base_ + 8 : stats_base_;
+  const FrozenPrep p = frozen_prep_flip();
   span_begin(2);
   KMX_HIP(launch_apply_prep_frozen(delta, dcount_d, centroids, ccounts, ctl, K_, D_, K_pad_, DP_, mu_, finite_, bias_,
-                                   bias2_, cfil_, panelhi_, stats_, next, counters_ + 1, counters_ + 3, counters_ + 4,
-                                   carry_on_ ? drift_ : nullptr, carry_on_ && drift_ ? counters_ + kCarryCursor : nullptr,
-                                   stream_),
+                                   bias2_, cfil_, panelhi_, p.stats, p.stats_next, counters_ + 1, counters_ + 3,
+                                   counters_ + 4, p.drift, p.zero_d, stream_),
           kRuntimeError);
   carry_preps_++;
   span_end();

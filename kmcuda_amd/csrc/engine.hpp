@@ -210,7 +210,6 @@ class Engine {
   void *wide_rows16_ = nullptr;          // N x wide_dp_ halves: x - mu, row-major (this path's row cache)
   float *wide_meta_ = nullptr;       // 4 floats per row
   uint32_t *wide_cont_ = nullptr; // per listed row: the number of its contenders, then up to 16 of them
-  int lloyd_assign_wide(const LloydArgs &a, const float *centroids, bool steady, bool rows_on_side, bool carry_was_valid);
   // row cache of the coarse filter stage (lloyd_f16.hip: row_cache_kernel); set_row_cache()
   bool row_cache_allowed_ = true;   // KMCUDA_AMD_ROW_CACHE=0 vetoes it
   bool row_cache_on_ = false, row_cache_valid_ = false, mu_frozen_ = false;
@@ -232,7 +231,6 @@ class Engine {
   uint32_t *p1_ = nullptr, *p2_ = nullptr;
   uint32_t *carry_list_ = nullptr;
   uint32_t *host_carry_ = nullptr, *host_carry_dev_ = nullptr;   // 2 pinned words: [0] the last list's length, [1] seq
-  bool carry_usable() const;     // the state in which a pass can carry bounds
   int carry_stats(unsigned long long *rows_spared, uint32_t *last_list);
   int carry_pair_stats(unsigned long long *rows_paired);
   int duo_rows(uint32_t *rows);   // the last assignment pass's duo list (lloyd_duo.hip)
@@ -278,6 +276,29 @@ class Engine {
   void profile_reset();
 
  private:
+  // The stages of a Lloyd pass, in the order lloyd_assign() calls them (engine.cpp; DESIGN.md has the order per path)
+  static constexpr int kNoFilter = kNoSuchDevice + 100;   // lloyd_assign_wide: no memory for its buffers, the exact kernel serves the shape
+  struct FrozenPrep { uint32_t *stats, *stats_next; float *drift; uint32_t *zero_d; };
+  struct CarryPass {   // what carry_begin() decided for a pass
+    bool on = false;                  // the pass carries bounds: cy is filled (false: a plain pass)
+    bool moved = false;               // the bounds were valid and moved once: the skip kernel is enqueued
+    bool listed = false;              // ... and the pass takes its rows from the skip kernel's list
+    uint32_t hint = 0xFFFFFFFFu;      // a listed pass: the last list length the host has seen (sizes stage 1's grid)
+    CarryArgs cy;
+  };
+  int assign_strict_h2(const float *samples, const float *centroids, uint32_t *assignments, uint32_t *assignments_prev);
+  int ensure_pass_resources(bool two_stage);
+  FrozenPrep frozen_prep_flip();
+  int prepare_pass(const float *centroids, bool steady, bool wide_steady, bool *rows_on_side);
+  int assign_exact(const LloydArgs &a);
+  int build_row_cache(const void *rows, bool half);
+  bool duo_pays() const;
+  int carry_begin(bool eligible, bool carry_was_valid, const LloydArgs &a, uint32_t wide_dg, CarryPass *cp);
+  int filter_two_stage(const LloydArgs &a, const float *centroids, bool steady, bool carry_was_valid);
+  int settle_lists(const LloydArgs &a, const float *centroids, bool rows_on_side);
+  int ensure_wide_buffers();
+  int lloyd_assign_wide(const LloydArgs &a, const float *centroids, bool steady, bool rows_on_side, bool carry_was_valid);
+
   std::vector<void *> owned_;
   static constexpr size_t kSlabBytes = 4u << 20, kSlabMaxItem = 512u << 10;
   char *slab_ = nullptr;

@@ -819,12 +819,10 @@ bool lloyd_settle_supported(const LloydArgs &a, const float *centroids) {
 }
 
 hipError_t launch_lloyd_settle(int metric, const LloydArgs &a, const float *centroids, hipStream_t st) {
-  static bool attr_set[2] = {false, false};
   const void *fn = metric == 0 ? (const void *)lloyd_settle_kernel<0> : (const void *)lloyd_settle_kernel<1>;
   // (per device: the attribute belongs to the current device's copy of the kernel; setting it again is cheap)
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSettleLds);
   if (e != hipSuccess) return e;
-  (void)attr_set;
   const dim3 grid(kSettlePairBlocks + kSettleScanBlocks);
   if (metric == 0)
     hipLaunchKernelGGL((lloyd_settle_kernel<0>), grid, dim3(256), kSettleLds, st, a.samples, a.N, a.D, centroids, a.ct,

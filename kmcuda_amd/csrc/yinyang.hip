@@ -333,13 +333,11 @@ hipError_t launch_yy_global_filter(int metric, const float *samples, uint32_t le
                                    const uint32_t *assignments, uint32_t *assignments_prev, float *bounds,
                                    uint32_t *passed, uint32_t *counters, hipStream_t st) {
   if (len == 0) return hipSuccess;
-  const size_t lds = (2 * 256 * 36 + 256) * sizeof(float);
-  static bool attr_set = false;   // > 64 KB of dynamic LDS
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void *)yy_global_filter_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void *)yy_global_filter_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  const size_t lds = (2 * 256 * 36 + 256) * sizeof(float);   // > 64 KB of dynamic LDS
+  const void *fn = metric == 0 ? (const void *)yy_global_filter_kernel<0> : (const void *)yy_global_filter_kernel<1>;
+  // (per device: the attribute belongs to the current device's copy of the kernel; setting it again is cheap)
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
   if (metric == 0)
     hipLaunchKernelGGL((yy_global_filter_kernel<0>), dim3((len + 255) / 256), dim3(256), lds, st, samples, len, D, K, G,
                        centroids, drifts, gdrifts, assignments, assignments_prev, bounds, passed, counters);
