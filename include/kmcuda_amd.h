@@ -352,6 +352,40 @@ int kmamd_knn_index_radius_fill(kmamd_knn_index *ix, float radius, uint32_t n_qu
                                 const uint32_t *query_assignments, const uint64_t *offsets /* n_queries + 1 */,
                                 uint32_t *neighbors, float *distances /* optional */, int32_t device_ptrs);
 
+/* More rows for an index, in place.  After add the index is observably the index that
+ * kmamd_knn_index_create builds from the concatenation of its rows so far and the new ones, with the same centroids:
+ * the new rows get the ids n_rows_so_far, n_rows_so_far + 1, ... in the order given, and query, query_probe and both
+ * radius calls return what they return on that fresh index, bit for bit in indices and distances, on every search path
+ * (nothing the searches read depends on how the corpus arrived).
+ *   rows             n_rows x features in the index's dtype (fp32, or halves for an fp16x2 index)
+ *   assignments      (optional, in) n_rows cluster ids by create's rule: an id >= clusters means "no cluster" -- the row
+ *                    is never returned, but it takes an id and counts in n_rows.  NULL: the rows' clusters are
+ *                    kmamd_kmeans_assign(rows, the index's centroids)'s assignments (the engine's filtered bit-exact
+ *                    pass, as a query chunk runs it; `clusters` for a row that pass gives no cluster), written to
+ *                    assignments_out if given.  So add(B) is exactly add(B, kmeans_predict(B, centroids)).
+ *   assignments_out  (optional) n_rows: the clusters used
+ *   first_row        (optional, host) the id of rows[0]
+ *   device_ptrs      -1 host buffers, else the index's device (all of the call's buffers but first_row)
+ * Synchronous.  n_rows == 0 succeeds and changes nothing.  NOT safe against a concurrent call on the same index.
+ * InvalidArguments, before any device work and with the index untouched: a null handle, null rows with n_rows > 0,
+ * device_ptrs naming another device, more than 0xFFFFFFFE rows in all (0xFFFFFFFF is the "no neighbour" marker), and
+ * assignments == NULL where the index runs the half2 arithmetic (KMCUDA_AMD_FP16_STRICT has no assignment pass, as
+ * query_probe refuses its ranking; a caller's assignments work there).  If an allocation fails the call returns
+ * kmcudaMemoryAllocationFailure and the index is exactly what it was, still usable: the new sorted copies are built
+ * beside the old ones (peak: both, about 2 x (6 DP + 24) bytes per row, DP the padded row width) and swapped in at the
+ * end.  Afterwards k <= the new n_rows is accepted by the queries.  A centred new row outside the half range makes the
+ * index leave the f16 filter for good, as create on the concatenation would (the f32 filter up to 256 features, the
+ * exact search beyond); verbosity > 0 says so once.  Env KMCUDA_AMD_KNN_ADD_CHUNK=<rows> (tests): rows per chunk -- each
+ * chunk is one merge -- (default: a chunk's staged and sorted copies within 4 GiB); the result does not depend on it.
+ *   info   n_rows, n_clustered (the rows that have a cluster) and filter (2: the f16 matrix-core filter, 1: the f32
+ *          one, 0: every candidate evaluated exactly); any of the three may be NULL. */
+int kmamd_knn_index_add(kmamd_knn_index *ix, uint32_t n_rows, const void *rows,
+                        const uint32_t *assignments /* optional in, n_rows */,
+                        uint32_t *assignments_out /* optional, n_rows */,
+                        uint32_t *first_row /* optional out, host: the id of rows[0] */, int32_t device_ptrs);
+int kmamd_knn_index_info(kmamd_knn_index *ix, uint32_t *n_rows, uint32_t *n_clustered,
+                         int *filter /* 2: f16, 1: f32, 0: exact; any may be NULL */);
+
 /* Assigns rows to GIVEN centroids -- the "predict" of a trained K-means (no counterpart in the reference, whose
  * kmeans_cuda returns the assignments of the rows it was trained on only) -- with, as asked, the distance of every row
  * to its centroid and per-cluster statistics.  Stateless and synchronous; the caller owns all memory.

@@ -24,7 +24,7 @@ EXPORTS = [
     "kmamd_move_deltas", "kmamd_apply_delta", "kmamd_transpose", "kmamd_afkmc2_draws", "kmamd_reduce_len", "kmamd_reduce_fill",
     "kmamd_reduce_apply", "kmamd_reduce_apply_stop", "kmamd_reduce_apply_prepare", "kmamd_stop_report", "kmamd_stop_clear", "kmamd_centroids_written", "kmamd_set_carry", "kmamd_carry_stats", "kmamd_carry_pair_stats", "kmamd_duo_rows", "kmamd_carry_policy_sim", "kmamd_set_update_mode", "kmamd_last_run_stats", "kmamd_last_run_collective", "kmamd_adjust_exact", "kmamd_yy_configure", "kmamd_yy_init", "kmamd_yy_drifts", "kmamd_yy_filters",
     "kmamd_knn_index_create", "kmamd_knn_index_query", "kmamd_knn_index_query_probe", "kmamd_knn_index_destroy",
-    "kmamd_knn_index_radius_count", "kmamd_knn_index_radius_fill",
+    "kmamd_knn_index_radius_count", "kmamd_knn_index_radius_fill", "kmamd_knn_index_add", "kmamd_knn_index_info",
     "kmamd_kmeans_assign", "kmamd_assigned_distances",
     "kmamd_kmeans_assign_top", "kmamd_assign_top_stats",
     "kmamd_kmeans_seed_parallel",
@@ -151,6 +151,10 @@ def lib():
     L.kmamd_knn_index_radius_count.argtypes = [vp, f32, u32, vp, vp, vp, vp, i32]
     L.kmamd_knn_index_radius_fill.restype = i32
     L.kmamd_knn_index_radius_fill.argtypes = [vp, f32, u32, vp, vp, vp, vp, vp, i32]
+    L.kmamd_knn_index_add.restype = i32
+    L.kmamd_knn_index_add.argtypes = [vp, u32, vp, vp, vp, ctypes.POINTER(u32), i32]
+    L.kmamd_knn_index_info.restype = i32
+    L.kmamd_knn_index_info.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_int)]
     L.kmamd_knn_index_destroy.restype = None
     L.kmamd_knn_index_destroy.argtypes = [vp]
     L.kmamd_kmeans_assign.restype = i32

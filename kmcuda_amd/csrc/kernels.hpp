@@ -565,6 +565,29 @@ hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks,
 hipError_t launch_knn_scatter(const uint32_t *sorted_out, const uint32_t *inv, uint32_t p_base, uint32_t p_end,
                               uint32_t k, uint32_t *neighbors, hipStream_t st);
 
+// knn_merge.hip -- rows added to an index (kmamd_knn_index_add).  What an index keeps per sorted row;
+// xs16 / n2c / mux / kbias only while it runs the f16 filter (null otherwise, on all three sides of a merge)
+struct KnnSortedRows {
+  float *xs, *n2s, *mydist, *n2c, *mux, *kbias;
+  uint16_t *xs16;
+  uint32_t *inv;
+};
+// One merge: destination position p of cluster c (K: no cluster) at rank j = p - off_new[c] takes the index's row
+// off_old[c] + j while j is below the cluster's old size, else the chunk's row boffs[c] + j - that size, whose inv is
+// the chunk's row number: N_old is added.  off_old / off_new / boffs: K + 1 entries on the device.
+struct KnnMergeArgs {
+  KnnSortedRows old_rows, chunk, out;
+  const uint32_t *off_old, *boffs, *off_new;
+  uint32_t N_old, n, K, DP;
+};
+hipError_t launch_knn_merge_rows(const KnnMergeArgs &a, hipStream_t st);
+// R_new[c] = max(R_old[c], the chunk's largest rdist in c), NaN only while c stays empty; the statistics: stats_new[0]
+// / stats_c_new[0] (null: none) = the larger of the old maximum and the chunk's (bstats[0] plain, bstats[2] centred),
+// stats_new[1] = the old half-range flag | bstats[1]
+hipError_t launch_knn_merge_radii(const float *R_old, const float *rdist, const uint32_t *boffs, uint32_t K, float *R_new,
+                                  const uint32_t *stats_old, const uint32_t *stats_c_old, const uint32_t *bstats,
+                                  uint32_t *stats_new, uint32_t *stats_c_new, hipStream_t st);
+
 // knn_radius.hip -- radius search of a query batch (kmamd_knn_index_radius_*).  `a` is the query mode's
 // KnnArgs (heaps / out / outd / k unread).  Query i of the chunk (caller's order; qinv: sorted query position -> i)
 // gets counts[i], or its hits at [offsets[i], offsets[i + 1]) of neighbors / distances, both addressed relative to

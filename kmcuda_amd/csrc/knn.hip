@@ -79,16 +79,6 @@ __global__ __launch_bounds__(256) void knn_gather_kernel(const float *__restrict
   }
 }
 
-__device__ __forceinline__ uint32_t cluster_of(const uint32_t *__restrict__ offsets, uint32_t K, uint32_t p) {
-  // largest c with offsets[c] <= p, c in [0, K]; K means "no cluster" (p >= offsets[K])
-  uint32_t lo = 0, hi = K + 1;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) / 2;
-    if (offsets[mid] <= p) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // metric_abstraction.h:103-118 partial (L2: Kahan sum of squared differences; angular: Kahan dot)
 // H2 (KMCUDA_AMD_FP16_STRICT): the same with F = half2 (half2_ops.hpp; the rows hold half values, n is even)
 template <int METRIC, bool H2 = false>

@@ -1,8 +1,19 @@
-// knn_heap.hpp -- the k-NN heap step, ONE copy for every search kernel (knn.hip, knn_f16.hip).
+// knn_heap.hpp -- the k-NN heap step, ONE copy for every search kernel (knn.hip, knn_f16.hip), and the cluster of a
+// sorted position (knn.hip, knn_merge.hip).
 #pragma once
 #include <stdint.h>
 
 namespace kmx {
+
+__device__ __forceinline__ uint32_t cluster_of(const uint32_t *__restrict__ offsets, uint32_t K, uint32_t p) {
+  // largest c with offsets[c] <= p, c in [0, K]; K means "no cluster" (p >= offsets[K])
+  uint32_t lo = 0, hi = K + 1;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (offsets[mid] <= p) lo = mid; else hi = mid;
+  }
+  return lo;
+}
 
 // push_sample (knn.cu:133-175): replace-root + sift-down on a max-heap of interleaved (distance, index)
 // pairs.  Which child moves up on equal distances decides the order of tied neighbours in the output, so the

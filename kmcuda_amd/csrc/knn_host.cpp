@@ -33,6 +33,11 @@ KnnSwitches knn_switches() {
     const long v = atol(chunk);
     if (v > 0) sw.query_chunk = (size_t)v;
   }
+  if (const char *chunk = getenv("KMCUDA_AMD_KNN_ADD_CHUNK")) {
+    const long v = atol(chunk);
+    if (v > 0) sw.add_chunk = (size_t)v;
+  }
+  sw.add_time = on(getenv("KMCUDA_AMD_KNN_ADD_TIME"));
   return sw;
 }
 

@@ -54,6 +54,8 @@ struct KnnSwitches {
   bool stats = false;        // KMCUDA_AMD_KNN_STATS: the f16 search's counters at any verbosity
   unsigned shard_i = 0, shard_n = 0;  // KMCUDA_AMD_KNN_SHARD="i/n" (shard_n = 0: unset)
   size_t query_chunk = 0;    // KMCUDA_AMD_KNN_QUERY_CHUNK: queries per chunk of an index query (0: unset)
+  size_t add_chunk = 0;      // KMCUDA_AMD_KNN_ADD_CHUNK: rows per chunk (one merge each) of an index add (0: unset)
+  bool add_time = false;     // KMCUDA_AMD_KNN_ADD_TIME: an index add prints the device time of its three stages
 };
 KnnSwitches knn_switches();
 

@@ -14,6 +14,10 @@
 // query_probe() is the approximate mode: the same procedure with one more skip rule -- a cluster that
 // is not in the query's probe list is never visited.  The lists are the caller's, or the ranking of
 // kmamd_kmeans_assign_top run here on the index's own centroids (AssignTopRanker, assign_top_job.cpp).
+//
+// add() takes more rows into the index: the new rows are prepared chunk by chunk with the launches a
+// fresh index's rows go through and merged into new cluster-sorted copies (knn_merge.hip); the index's own buffers stay
+// as they are until the whole batch has been enqueued without error.
 #include <math.h>
 #include <stdio.h>
 
@@ -21,6 +25,7 @@
 
 #include "../../include/kmcuda_amd.h"
 #include "knn_host.hpp"
+#include "knn_merge_host.hpp"
 
 using namespace kmx;
 
@@ -29,9 +34,22 @@ namespace {
 // lb (K floats per query) and the heaps (2k floats per query) of one chunk of queries stay within this budget
 constexpr size_t kQueryChunkBytes = (size_t)4 << 30;
 
+// What an add replaces: the per-row copies of the index (the f16 filter's only while it runs), its CSR offsets (on the
+// device and on the host: K + 2 entries, [K] the rows that have a cluster, [K + 1] all of them), radii and statistics.
+struct IndexState {
+  KnnSortedRows rows{};
+  uint32_t *offsets = nullptr, *stats = nullptr, *stats_c = nullptr;
+  float *R = nullptr;
+  uint32_t N = 0;
+  std::vector<uint32_t> off_host;
+};
+
+struct AddChunk;
+
 class KnnIndex {
  public:
   KnnShard s;   // the prepared corpus (its buffers and stream); plain and centred norms both kept
+  std::vector<uint32_t> off_host;   // IndexState::off_host of `s`
   KnnPath path;
   int verbosity = 0;
   bool fp16 = false;
@@ -44,7 +62,8 @@ class KnnIndex {
     s.dev = device;
     KnnShard *one = &s;
     bool left_half_range = false;
-    KNN_TRY(knn_prepare_corpus(&one, 1, c, true, &path, &left_half_range, nullptr));
+    off_host.assign((size_t)c.K + 2, c.N);
+    KNN_TRY(knn_prepare_corpus(&one, 1, c, true, &path, &left_half_range, off_host.data()));
     if (left_half_range && verbosity > 0)   // no f16 filter for this index
       printf("k-NN index: a centred row leaves the half range, %s\n",
              path.dp_filter ? "the f32 matrix-core filter instead of the f16 one" : "every candidate is evaluated exactly");
@@ -79,7 +98,86 @@ class KnnIndex {
                   uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs);
   int radius(bool fill, float r, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *counts,
              uint32_t *qassign_out, const uint64_t *offsets, uint32_t *neighbors, float *distances, int32_t device_ptrs);
+
+  // ---- add ----
+  int add(uint32_t n_rows, const void *rows, const uint32_t *assign_in, uint32_t *assign_out, int32_t device_ptrs);
+  IndexState state() const {
+    IndexState t;
+    t.rows.xs = s.xs; t.rows.n2s = s.n2s; t.rows.mydist = s.mydist; t.rows.inv = s.inv;
+    t.rows.xs16 = s.xs16; t.rows.n2c = s.n2c; t.rows.mux = s.mux; t.rows.kbias = s.kbias;
+    t.offsets = s.offsets; t.stats = s.stats; t.stats_c = s.stats_c; t.R = s.R; t.N = s.N;
+    t.off_host = off_host;
+    return t;
+  }
+  void adopt(IndexState &t) {
+    s.xs = t.rows.xs; s.n2s = t.rows.n2s; s.mydist = t.rows.mydist; s.inv = t.rows.inv;
+    s.xs16 = t.rows.xs16; s.n2c = t.rows.n2c; s.mux = t.rows.mux; s.kbias = t.rows.kbias;
+    s.offsets = t.offsets; s.stats = t.stats; s.stats_c = t.stats_c; s.R = t.R; s.N = t.N;
+    off_host.swap(t.off_host);
+  }
+  // buffers for N rows (f16: the filter's too), owned by the shard's arena; whatever was allocated is released again
+  // if one allocation fails
+  int alloc_state(IndexState *t, uint32_t N, bool f16) {
+    const uint32_t DP = s.DP, K = s.K;
+    KnnSortedRows &r = t->rows;
+    int rc = 0;
+    auto get = [&](auto **p, size_t count) { if (!rc) rc = s.alloc(p, count); };
+    get(&r.xs, (size_t)N * DP);
+    get(&r.n2s, N);
+    get(&r.mydist, N);
+    get(&r.inv, N);
+    get(&t->offsets, (size_t)K + 2);
+    get(&t->stats, 4);
+    get(&t->R, K);
+    if (f16) {
+      get(&r.xs16, ((size_t)N + KNN16_PAD_ROWS) * DP);
+      get(&r.kbias, (size_t)N + KNN16_PAD_ROWS);
+      get(&r.n2c, N);
+      get(&r.mux, N);
+      get(&t->stats_c, 4);
+    }
+    t->N = N;
+    if (rc) {
+      (void)hipGetLastError();
+      release_state(*t);
+    }
+    return rc;
+  }
+  void release_f16(IndexState &t) {
+    s.release(t.rows.xs16); s.release(t.rows.kbias); s.release(t.rows.n2c); s.release(t.rows.mux); s.release(t.stats_c);
+    t.rows.xs16 = nullptr; t.rows.kbias = t.rows.n2c = t.rows.mux = nullptr; t.stats_c = nullptr;
+  }
+  void release_state(IndexState &t) {
+    release_f16(t);
+    s.release(t.rows.xs); s.release(t.rows.n2s); s.release(t.rows.mydist); s.release(t.rows.inv);
+    s.release(t.offsets); s.release(t.stats); s.release(t.R);
+    t = IndexState();
+  }
+  int merge(const IndexState &cur, const AddChunk &c, uint32_t n, IndexState *next);
 };
+
+// rows [r0, r0 + n) of a caller's row matrix, fp32 in `rows` on this device (halves by way of `half`)
+int upload_rows(bool fp16, const void *src, size_t r0, size_t n, uint32_t D, bool host, uint16_t *half, float *rows,
+                hipStream_t st) {
+  const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  if (fp16) {
+    KMX_HIPCP(hipMemcpyAsync(half, static_cast<const uint16_t *>(src) + r0 * D, n * D * sizeof(uint16_t), kind, st));
+    KMX_HIPRT(launch_half_to_float(half, n * D, rows, st));
+  } else {
+    KMX_HIPCP(hipMemcpyAsync(rows, static_cast<const float *>(src) + r0 * D, n * D * sizeof(float), kind, st));
+  }
+  return 0;
+}
+
+// n rows in cluster-sorted order by their CSR (inv, offsets): the DP-padded copy, plain norms, their maximum and the
+// half-range flag (stats[0], stats[1]; mu: the f16 filter's centre or null), distances to the own centroid
+int sorted_rows(const KnnIndex &ix, const float *rows, uint32_t n, const uint32_t *inv, const uint32_t *offsets, float *xs,
+                float *n2s, uint32_t *stats, float *mydist, float *rdist) {
+  const KnnShard &s = ix.s;
+  KMX_HIPRT(launch_knn_gather(rows, n, s.D, s.DP, inv, xs, n2s, stats, ix.path.use_f16 ? s.mu : nullptr, offsets, s.K, s.stream));
+  KMX_HIPRT(launch_knn_member(s.metric, xs, n, s.D, s.DP, offsets, s.K, s.centroids, mydist, rdist, ix.path.strict_h2, s.stream));
+  return 0;
+}
 
 // The per-call buffers of a query batch (sized for one chunk of at most Qc queries, reused by every chunk) and the
 // preparation of a chunk, shared by query() and the radius calls: upload and half widening, the queries' clusters,
@@ -162,14 +260,7 @@ struct QueryChunk {
     const uint32_t D = s.D, DP = s.DP, K = s.K;
     const hipStream_t st = s.stream;
     // ---- the chunk's rows, fp32 on this device ----
-    if (ix.fp16) {
-      const uint16_t *src = static_cast<const uint16_t *>(queries) + (size_t)q0 * D;
-      KMX_HIPCP(hipMemcpyAsync(qhalf, src, (size_t)n * D * sizeof(uint16_t), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
-      KMX_HIPRT(launch_half_to_float(qhalf, (size_t)n * D, qrows, st));
-    } else {
-      const float *src = static_cast<const float *>(queries) + (size_t)q0 * D;
-      KMX_HIPCP(hipMemcpyAsync(qrows, src, (size_t)n * D * sizeof(float), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
-    }
+    KNN_TRY(upload_rows(ix.fp16, queries, q0, n, D, host, qhalf, qrows, st));
     // ---- their clusters ----
     if (pr) {
       const size_t cnt = (size_t)n * pr->pw;
@@ -202,8 +293,7 @@ struct QueryChunk {
                                          scratch.sort_bytes, st));
     if (pr) KMX_HIPRT(launch_knn_probe_lists(pr->raw, pr->pw, n, qinv, K, pr->lists, qstats + 2, st));
     // (with mu: the queries raise the half-range flag qstats[1] as the corpus rows do)
-    KMX_HIPRT(launch_knn_gather(qrows, n, D, DP, qinv, qxs, qn2p, qstats, ix.path.use_f16 ? s.mu : nullptr, qoffsets, K, st));
-    KMX_HIPRT(launch_knn_member(s.metric, qxs, n, D, DP, qoffsets, K, s.centroids, qmydist, qrdist, ix.path.strict_h2, st));
+    KNN_TRY(sorted_rows(ix, qrows, n, qinv, qoffsets, qxs, qn2p, qstats, qmydist, qrdist));
     uint32_t flags[4] = {0, 0, 0, 0};
     KMX_HIPCP(hipMemcpyAsync(offs.data(), qoffsets, (K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KMX_HIPCP(hipMemcpyAsync(flags, qstats, sizeof(flags), hipMemcpyDeviceToHost, st));
@@ -230,6 +320,121 @@ struct QueryChunk {
     a->blocks = blocks;
     a->p_base = 0;
     a->qxs = qxs; a->qn2s = cp.use_f16 ? qn2c : qn2p; a->qmux = qmux; a->qmydist = qmydist; a->qxs16 = qxs16; a->qoffsets = qoffsets;
+  }
+};
+
+// KMCUDA_AMD_KNN_ADD_TIME: HIP events on the index's stream around the three stages of every chunk of an add -- the
+// rows' clusters (upload and assignment pass), the chunk's preparation (CSR, gather, member distances, split), the merge
+// --, summed over the chunks and printed at the end of the call (scripts/knn_add_bench.py reads the line)
+struct AddTimer {
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // (2 -> 3: the host's wait and allocations)
+  bool on = false;
+  float ms[3] = {0.f, 0.f, 0.f};
+  unsigned long long merged_bytes = 0;
+  ~AddTimer() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  void start(bool on_) {
+    on = on_;
+    for (hipEvent_t &e : ev)
+      if (on && hipEventCreate(&e) != hipSuccess) on = false;
+  }
+  void mark(int i, hipStream_t st) const {
+    if (on) (void)hipEventRecord(ev[i], st);
+  }
+  void fold() {   // (after a wait for the stream)
+    float t = 0.f;
+    for (int i = 0; on && i < 3; i++)
+      if (hipEventElapsedTime(&t, ev[i == 2 ? 3 : i], ev[i == 2 ? 4 : i + 1]) == hipSuccess) ms[i] += t;
+  }
+};
+
+// The buffers of one chunk of an add (at most Cn rows, reused by every chunk) and its preparation: what
+// knn_prepare_corpus makes of a corpus's rows, by the same launches, with the index's centroids, mu and path.
+struct AddChunk {
+  DeviceArena w;   // owns the buffers; enqueues on the index's stream (nothing to release)
+  KnnScratch scratch;
+  uint32_t Cn = 0;
+  float *rows = nullptr, *rdist = nullptr;
+  uint16_t *half = nullptr;
+  uint32_t *asg = nullptr, *prev = nullptr, *boffs = nullptr, *bstats = nullptr;
+  KnnSortedRows b{};   // the chunk in cluster-sorted order (inv: sorted position -> row of the chunk)
+  EngineSlot slot;     // (after `w`: the engine goes first)
+  std::vector<uint32_t> offs;   // boffs on the host (K + 1)
+
+  int init(const KnnIndex &ix, uint32_t Cn_, bool assign) {
+    const KnnShard &s = ix.s;
+    const uint32_t D = s.D, DP = s.DP, K = s.K;
+    Cn = Cn_;
+    w.dev = s.dev;
+    w.stream = nullptr;
+    KNN_TRY(w.alloc(&rows, (size_t)Cn * D));
+    if (ix.fp16) KNN_TRY(w.alloc(&half, (size_t)Cn * D));
+    KNN_TRY(w.alloc(&asg, Cn));
+    if (assign) KNN_TRY(w.alloc(&prev, Cn));
+    KNN_TRY(w.alloc(&b.inv, Cn));
+    KNN_TRY(w.alloc(&boffs, (size_t)K + 2));
+    KNN_TRY(w.alloc(&scratch.keys_tmp, Cn));
+    KNN_TRY(w.alloc(&scratch.vals_tmp, Cn));
+    KNN_TRY(w.alloc(&scratch.keys_sorted, Cn));
+    KNN_TRY(w.alloc(&bstats, 4));
+    KNN_TRY(w.alloc(&b.xs, (size_t)Cn * DP));
+    KNN_TRY(w.alloc(&b.n2s, Cn));
+    KNN_TRY(w.alloc(&b.mydist, Cn));
+    KNN_TRY(w.alloc(&rdist, Cn));
+    if (ix.path.use_f16) {
+      KNN_TRY(w.alloc(&b.xs16, ((size_t)Cn + KNN16_PAD_ROWS) * DP));
+      KNN_TRY(w.alloc(&b.n2c, Cn));
+      KNN_TRY(w.alloc(&b.mux, Cn));
+      KNN_TRY(w.alloc(&b.kbias, (size_t)Cn + KNN16_PAD_ROWS));
+    }
+    scratch.rows = Cn;
+    scratch.sort_bytes = sort_temp_bytes(Cn, K);
+    char *sort_temp = nullptr;
+    KNN_TRY(w.alloc(&sort_temp, scratch.sort_bytes + 16));
+    scratch.sort_temp = sort_temp;
+    offs.resize((size_t)K + 1);
+    return 0;
+  }
+
+  // rows [r0, r0 + n) of the batch; waits for the stream once (the chunk's offsets reach the host).  bstats: [0] the
+  // largest plain norm, [1] the half-range flag, [2] the largest centred norm
+  int prepare(const KnnIndex &ix, uint32_t r0, uint32_t n, const void *src, const uint32_t *assign_in,
+              uint32_t *assign_out, bool host, const AddTimer &tm) {
+    const KnnShard &s = ix.s;
+    const uint32_t D = s.D, DP = s.DP, K = s.K;
+    const hipStream_t st = s.stream;
+    const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    tm.mark(0, st);
+    KNN_TRY(upload_rows(ix.fp16, src, r0, n, D, host, half, rows, st));
+    // ---- their clusters: the caller's (>= K: none, as create takes them), or kmamd_kmeans_assign's ----
+    if (assign_in) {
+      KMX_HIPCP(hipMemcpyAsync(asg, assign_in + r0, (size_t)n * sizeof(uint32_t), in, st));
+    } else if (K == 1) {   // (the engine needs two centroids: a row of finite features has cluster 0)
+      KMX_HIPRT(hipMemsetAsync(prev, 0, (size_t)n * sizeof(uint32_t), st));
+      KMX_HIPRT(launch_knn_query_clusters(rows, n, D, prev, K, s.centroids, asg, bstats + 3, st));
+    } else {
+      // assignments <- K ("no cluster"), then one pass of an engine sized for the chunk (assign_job.cpp)
+      Engine *eng = nullptr;
+      KNN_TRY(slot.get(s.dev, n, D, K, s.metric, st, half, &eng));
+      KMX_HIPRT(hipMemsetD32Async((hipDeviceptr_t)asg, (int)K, n, st));
+      KNN_TRY(eng->lloyd_assign(rows, s.centroids, asg, prev, false));
+    }
+    if (assign_out)
+      KMX_HIPCP(hipMemcpyAsync(assign_out + r0, asg, (size_t)n * sizeof(uint32_t),
+                               host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    tm.mark(1, st);
+    // ---- the chunk in cluster-sorted order, with everything an index keeps per row ----
+    KMX_HIPRT(launch_inverse_assignments(asg, n, K, scratch.keys_tmp, scratch.vals_tmp, scratch.keys_sorted, b.inv, boffs,
+                                         scratch.sort_temp, scratch.sort_bytes, st));
+    KNN_TRY(sorted_rows(ix, rows, n, b.inv, boffs, b.xs, b.n2s, bstats, b.mydist, rdist));
+    if (ix.path.use_f16)
+      KMX_HIPRT(launch_knn_split(s.metric, b.xs, n, D, DP, s.mu, b.xs16, b.n2c, b.mux, b.kbias, bstats + 2, st));
+    tm.mark(2, st);
+    KMX_HIPCP(hipMemcpyAsync(offs.data(), boffs, ((size_t)K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KMX_HIPRT(hipStreamSynchronize(st));
+    return 0;
   }
 };
 
@@ -559,6 +764,97 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
   return raised ? kmcudaInvalidArguments : 0;   // a query's hit count differs from its range
 }
 
+// One merge (knn_merge.hip): `cur` and the prepared chunk into the buffers of `next`, whose host offsets are made.
+int KnnIndex::merge(const IndexState &cur, const AddChunk &c, uint32_t n, IndexState *next) {
+  const uint32_t DP = s.DP, K = s.K;
+  const hipStream_t st = s.stream;
+  const bool f16 = path.use_f16;
+  KMX_HIPCP(hipMemcpyAsync(next->offsets, next->off_host.data(), ((size_t)K + 2) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  KMX_HIPRT(hipMemsetAsync(next->stats, 0, 4 * sizeof(uint32_t), st));
+  KnnMergeArgs a;
+  a.old_rows = cur.rows; a.chunk = c.b; a.out = next->rows;
+  a.off_old = cur.offsets; a.boffs = c.boffs; a.off_new = next->offsets;
+  a.N_old = cur.N; a.n = n; a.K = K; a.DP = DP;
+  KMX_HIPRT(launch_knn_merge_rows(a, st));
+  if (f16) {   // the filter's tile DMA reads whole tiles: zeros past the last row, as launch_knn_split leaves them
+    KMX_HIPRT(hipMemsetAsync(next->rows.xs16 + (size_t)next->N * DP, 0, (size_t)KNN16_PAD_ROWS * DP * sizeof(uint16_t), st));
+    KMX_HIPRT(hipMemsetAsync(next->rows.kbias + next->N, 0, (size_t)KNN16_PAD_ROWS * sizeof(float), st));
+    KMX_HIPRT(hipMemsetAsync(next->stats_c, 0, 4 * sizeof(uint32_t), st));
+  }
+  KMX_HIPRT(launch_knn_merge_radii(cur.R, c.rdist, c.boffs, K, next->R, cur.stats, f16 ? cur.stats_c : nullptr, c.bstats,
+                                   next->stats, f16 ? next->stats_c : nullptr, st));
+  return 0;
+}
+
+// n_rows more rows, in chunks of one merge each.  Every merge writes a whole new state; the index's
+// own buffers are read only, and replaced once the last chunk has been enqueued and the stream has drained without error.
+int KnnIndex::add(uint32_t n_rows, const void *rows, const uint32_t *assign_in, uint32_t *assign_out, int32_t device_ptrs) {
+  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
+  const hipStream_t st = s.stream;
+  const bool host = device_ptrs < 0, f16 = path.use_f16;
+  const uint32_t Cn = knn_add_chunk_rows(n_rows, s.D, s.DP, kQueryChunkBytes, knn_switches().add_chunk);
+  IndexState cur = state();   // the index's own until the first merge, then this call's
+  bool mine = false;
+  int rc = 0;
+  {
+    AddTimer tm;
+    tm.start(knn_switches().add_time);
+    AddChunk c;
+    rc = c.init(*this, Cn, !assign_in);
+    for (uint32_t r0 = 0; rc == 0 && r0 < n_rows; r0 += Cn) {
+      const uint32_t n = n_rows - r0 < Cn ? n_rows - r0 : Cn;
+      IndexState next;
+      if (r0 != 0 && tm.on && hipStreamSynchronize(st) == hipSuccess) tm.fold();   // (the chunk before: its events are reused)
+      rc = c.prepare(*this, r0, n, rows, assign_in, assign_out, host, tm);
+      if (rc == 0) rc = alloc_state(&next, cur.N + n, f16);
+      if (rc == 0 && !knn_merge_offsets(cur.off_host, c.offs.data(), s.K, n, &next.off_host)) rc = kmcudaRuntimeError;
+      tm.mark(3, st);
+      if (rc == 0) rc = merge(cur, c, n, &next);
+      tm.mark(4, st);
+      // (read and written once: the fp32 rows, the halves and six words per row)
+      tm.merged_bytes += 2ull * ((unsigned long long)cur.N + n) * ((f16 ? 6ull : 4ull) * s.DP + (f16 ? 24ull : 12ull));
+      if (rc == 0 && mine && hipStreamSynchronize(st) != hipSuccess) rc = kmcudaRuntimeError;   // (the merge reads `cur`)
+      if (rc != 0) {
+        (void)hipStreamSynchronize(st);
+        release_state(next);
+        break;
+      }
+      if (mine) release_state(cur);
+      cur = std::move(next);
+      mine = true;
+    }
+    // the half-range flag, once per add (create waits for it too); the chunk's buffers go behind this wait
+    uint32_t flag = 0;
+    if (rc == 0 && f16 && hipMemcpyAsync(&flag, cur.stats + 1, sizeof(flag), hipMemcpyDeviceToHost, st) != hipSuccess)
+      rc = kmcudaMemoryCopyError;
+    if (hipStreamSynchronize(st) != hipSuccess && rc == 0) rc = kmcudaRuntimeError;
+    if (rc != 0) {
+      if (verbosity > 0) printf("k-NN index add failed: %s\n", hipGetErrorString(hipGetLastError()));
+      if (mine) release_state(cur);
+      return rc;
+    }
+    if (tm.on) {
+      tm.fold();
+      printf("k-NN index add: %u rows in chunks of %u: clusters %.3f ms, preparation %.3f ms, merge %.3f ms (%.3f GB moved, "
+             "%.3f TB/s)\n", n_rows, Cn, tm.ms[0], tm.ms[1], tm.ms[2], 1e-9 * (double)tm.merged_bytes,
+             tm.ms[2] > 0.f ? 1e-9 * (double)tm.merged_bytes / (double)tm.ms[2] : 0.0);
+      fflush(stdout);
+    }
+    IndexState old = state();
+    adopt(cur);
+    release_state(old);
+    if (knn_leaves_half_range(&path.use_f16, &path.dp_filter, s.D, flag)) {   // no f16 filter for this index any more
+      if (verbosity > 0)
+        printf("k-NN index: a centred row leaves the half range, %s\n",
+               path.dp_filter ? "the f32 matrix-core filter instead of the f16 one" : "every candidate is evaluated exactly");
+      IndexState now = state();
+      release_f16(now);
+      adopt(now);
+    }
+  }
+  return 0;
+}
+
 }  // namespace
 
 struct kmamd_knn_index {
@@ -649,6 +945,33 @@ int kmamd_knn_index_radius_fill(kmamd_knn_index *h, float radius, uint32_t n_que
   if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
   return h->ix.radius(true, radius, n_queries, queries, query_assignments, nullptr, nullptr, offsets, neighbors,
                       distances, device_ptrs);
+}
+
+int kmamd_knn_index_add(kmamd_knn_index *h, uint32_t n_rows, const void *rows, const uint32_t *assignments,
+                        uint32_t *assignments_out, uint32_t *first_row, int32_t device_ptrs) {
+  if (!h) return kmcudaInvalidArguments;
+  KnnIndex &ix = h->ix;
+  if (n_rows > 0 && !rows) return kmcudaInvalidArguments;
+  if (device_ptrs >= 0 && device_ptrs != ix.s.dev) return kmcudaInvalidArguments;
+  if (!knn_add_fits(ix.s.N, n_rows)) return kmcudaInvalidArguments;
+  // the reference's half2 arithmetic has no assignment pass (query_probe refuses its ranking likewise): the caller's only
+  if (!assignments && ix.fp16 && (ix.path.strict_h2 || knn_switches().fp16_strict)) return kmcudaInvalidArguments;
+  const uint32_t first = ix.s.N;
+  if (n_rows != 0) {
+    if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
+    KNN_TRY(ix.add(n_rows, rows, assignments, assignments_out, device_ptrs));
+  }
+  if (first_row) *first_row = first;
+  return kmcudaSuccess;
+}
+
+int kmamd_knn_index_info(kmamd_knn_index *h, uint32_t *n_rows, uint32_t *n_clustered, int *filter) {
+  if (!h) return kmcudaInvalidArguments;
+  const KnnIndex &ix = h->ix;
+  if (n_rows) *n_rows = ix.s.N;
+  if (n_clustered) *n_clustered = ix.off_host[ix.s.K];
+  if (filter) *filter = ix.path.use_f16 ? 2 : (ix.path.dp_filter ? 1 : 0);
+  return kmcudaSuccess;
 }
 
 void kmamd_knn_index_destroy(kmamd_knn_index *h) { delete h; }

@@ -20,6 +20,11 @@ the caller names (Q x p; column 0 is the query's own cluster, K is a filler).  T
 above yields when a cluster outside the probe set is never visited: reproducible, and equal to the exact list at p = K.
 return_probes appends the lists used.
 
+Rows can be added in place, DESIGN.md 4.15: index.add(rows) (clusters by kmeans_predict on the index's centroids) or
+index.add(rows, assignments) returns the id of rows[0]; the new rows take the ids n_rows, n_rows + 1, ... and the index
+then answers every query exactly -- indices and distance bits -- as KnnIndex(old rows + new rows, centroids, ...) would.
+index.info() is (n_rows, n_clustered, filter): filter 2 the f16 matrix-core filter, 1 the f32 one, 0 the exact search.
+
 numpy in, numpy out (neighbors uint32, distances float32, assignments uint32).  torch tensors on the index's device
 in, torch tensors on that device out (neighbors / assignments int32: 0xFFFFFFFF reads -1), with no host round trip;
 the call orders with torch's work on the device (it waits for the device first and its outputs are complete when
@@ -31,6 +36,7 @@ import os
 import numpy
 
 from . import _lib
+from ._lib import u32
 from .api import _get_metric, _raise_for
 
 
@@ -365,6 +371,55 @@ class KnnIndex:
         if sort:
             nb, dist = _sort_slices(offsets, nb, dist)
         return (offsets, nb, dist) if return_distances else (offsets, nb)
+
+    def add(self, rows, assignments=None, return_assignments=False):
+        """Adds `rows` (n x features, the kind and dtype rules of query()) to the index in place and returns the id of
+        rows[0] -- the rows get the ids n_rows, n_rows + 1, ... -- or (that id, the rows' clusters) with
+        return_assignments.  assignments: one cluster id per row (an id >= the number of clusters: the row has no
+        cluster and is never returned, but takes an id); None: kmeans_predict(rows, the index's centroids).  The
+        index then equals KnnIndex(old rows + rows, ...) bit for bit in every query.  Not safe against
+        a concurrent call on the same index."""
+        if not getattr(self, "h", None):
+            raise ValueError("the index is closed")
+        r, fp16, n, d, on_dev = _rows(rows, "rows", self.device)
+        if fp16 != self.fp16:
+            raise TypeError("\"rows\" must have the dtype of \"samples\"")
+        if d != self.features:
+            raise ValueError("\"rows\" must have same number of features as \"samples\" (shape[-1])")
+        a = None
+        if assignments is not None:
+            if _is_torch(assignments) != on_dev:
+                raise TypeError("\"assignments\" must be of the same kind as \"rows\" (numpy array or torch tensor)")
+            a, _ = _labels(assignments, n, "assignments", None, self.device)
+        elif self.fp16 and _fp16_strict():
+            raise ValueError("KMCUDA_AMD_FP16_STRICT=1: the reference's half2 arithmetic has no assignment pass "
+                             "(kmeans_predict refuses it too): pass \"assignments\"")
+        if self.n_rows + n > 0xFFFFFFFE:
+            raise ValueError("an index holds at most 0xFFFFFFFE rows")
+        out = None
+        if return_assignments:
+            if on_dev:
+                import torch
+                out = torch.empty((n,), dtype=torch.int32, device=torch.device("cuda", self.device))
+            else:
+                out = numpy.empty((n,), numpy.uint32)
+        first = u32(self.n_rows)
+        rc = self.lib.kmamd_knn_index_add(self.h, n, _ptr(r), _ptr(a) if a is not None else None,
+                                          _ptr(out) if out is not None else None, ctypes.byref(first),
+                                          self.device if on_dev else -1)
+        _raise_for(rc, "kmamd_knn_index_add")
+        self.n_rows += n
+        return (int(first.value), out) if return_assignments else int(first.value)
+
+    def info(self):
+        """(n_rows, n_clustered, filter): the rows of the index, those of them that have a cluster, and the search it
+        runs -- 2: the f16 matrix-core filter, 1: the f32 one, 0: every candidate evaluated exactly."""
+        if not getattr(self, "h", None):
+            raise ValueError("the index is closed")
+        n, nc, f = u32(0), u32(0), ctypes.c_int(0)
+        rc = self.lib.kmamd_knn_index_info(self.h, ctypes.byref(n), ctypes.byref(nc), ctypes.byref(f))
+        _raise_for(rc, "kmamd_knn_index_info")
+        return int(n.value), int(nc.value), int(f.value)
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,0 +1,124 @@
+// knn_merge_host_check.cpp -- drives the host arithmetic of kmamd_knn_index_add (kmcuda_amd/csrc/knn_merge_host.hpp:
+// the merged CSR offsets, the row limit, the chunk loop) on the CPU against a plain recount, and replays the merge
+// kernel's source rule on the host to check that every destination position gets exactly one source row in the order a
+// fresh index has.  No device call: meant for a build with the host sanitizers,
+//   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I kmcuda_amd/csrc \
+//       scripts/knn_merge_host_check.cpp -o knn_merge_host_check && ./knn_merge_host_check
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <numeric>
+#include <random>
+
+#include "knn_merge_host.hpp"
+
+using namespace kmx;
+
+static int failures = 0;
+#define CHECK(cond)                                                     \
+  do {                                                                  \
+    if (!(cond)) {                                                      \
+      printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);          \
+      failures++;                                                       \
+    }                                                                   \
+  } while (0)
+
+// what launch_inverse_assignments leaves for assignments (ids >= K: no cluster): inv (stable by cluster) and K + 1
+// offsets; all: K + 2 entries, the last one the row count (an index's host copy)
+static void csr(const std::vector<uint32_t> &asg, uint32_t K, std::vector<uint32_t> *inv, std::vector<uint32_t> *offs,
+                bool all) {
+  std::vector<uint32_t> key(asg.size());
+  for (size_t i = 0; i < asg.size(); i++) key[i] = asg[i] < K ? asg[i] : K;
+  inv->resize(asg.size());
+  std::iota(inv->begin(), inv->end(), 0u);
+  std::stable_sort(inv->begin(), inv->end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+  offs->assign((size_t)K + (all ? 2 : 1), 0);
+  for (uint32_t c = 0; c <= K; c++)
+    (*offs)[c] = (uint32_t)std::count_if(key.begin(), key.end(), [&](uint32_t v) { return v < c; });
+  if (all) (*offs)[(size_t)K + 1] = (uint32_t)asg.size();
+}
+
+// knn_merge_rows_kernel's rule for destination position p: which row id lands there
+static uint32_t merged_row(uint32_t p, uint32_t K, const std::vector<uint32_t> &off_old, const std::vector<uint32_t> &inv_old,
+                           const std::vector<uint32_t> &boffs, const std::vector<uint32_t> &binv,
+                           const std::vector<uint32_t> &off_new) {
+  uint32_t lo = 0, hi = K + 1;   // cluster_of
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (off_new[mid] <= p) lo = mid; else hi = mid;
+  }
+  const uint32_t c = lo, j = p - off_new[c], N_old = off_old[(size_t)K + 1];
+  const uint32_t cnt_old = (c < K ? off_old[c + 1] : N_old) - off_old[c];
+  return j < cnt_old ? inv_old.at((size_t)off_old[c] + j) : N_old + binv.at((size_t)boffs[c] + (j - cnt_old));
+}
+
+static void one_case(uint32_t K, uint32_t n_old, uint32_t n_add, size_t chunk, unsigned seed, bool skewed) {
+  std::mt19937 rng(seed);
+  auto draw = [&](uint32_t n, uint32_t lo_c, uint32_t hi_c) {   // ids in [lo_c, hi_c], hi_c may be K and above
+    std::vector<uint32_t> a(n);
+    for (auto &v : a) v = lo_c + rng() % (hi_c - lo_c + 1);
+    return a;
+  };
+  // skewed: the old rows leave the upper clusters empty, the new rows sit in few clusters, some rows have none
+  std::vector<uint32_t> a_old = skewed ? draw(n_old, 0, K / 2) : draw(n_old, 0, K + 1);
+  std::vector<uint32_t> a_add = skewed ? draw(n_add, K / 2, K + 2) : draw(n_add, 0, K);
+  std::vector<uint32_t> inv, off, binv, boffs, next;
+  csr(a_old, K, &inv, &off, true);
+  std::vector<uint32_t> all = a_old;
+  uint32_t done = 0;
+  while (done < n_add) {   // the chunk loop of KnnIndex::add
+    const uint32_t n = knn_add_chunk_rows(n_add - done, 64, 64, (size_t)4 << 30, chunk);
+    CHECK(n >= 1 && n <= n_add - done);
+    std::vector<uint32_t> piece(a_add.begin() + done, a_add.begin() + done + n);
+    csr(piece, K, &binv, &boffs, false);
+    CHECK(knn_merge_offsets(off, boffs.data(), K, n, &next));
+    std::vector<uint32_t> inv_next((size_t)off[(size_t)K + 1] + n);
+    for (uint32_t p = 0; p < inv_next.size(); p++) inv_next[p] = merged_row(p, K, off, inv, boffs, binv, next);
+    inv.swap(inv_next);
+    off.swap(next);
+    all.insert(all.end(), piece.begin(), piece.end());
+    done += n;
+  }
+  // the index a fresh build makes of all rows
+  std::vector<uint32_t> want_inv, want_off;
+  csr(all, K, &want_inv, &want_off, true);
+  CHECK(off == want_off);
+  CHECK(inv == want_inv);
+}
+
+int main() {
+  for (uint32_t K : {1u, 2u, 7u, 64u})
+    for (uint32_t n_old : {1u, 63u, 200u})
+      for (uint32_t n_add : {1u, 5u, 64u, 333u})
+        for (size_t chunk : {(size_t)0, (size_t)1, (size_t)5, (size_t)1000})
+          for (int skewed = 0; skewed < 2; skewed++)
+            one_case(K, n_old, n_add, chunk, 17u * K + n_old + n_add + (unsigned)chunk, skewed != 0);
+  // the row limit: 0xFFFFFFFF is the searches' "no neighbour" marker
+  CHECK(knn_add_fits(0xFFFFFFFDu, 1));
+  CHECK(!knn_add_fits(0xFFFFFFFDu, 2));
+  CHECK(!knn_add_fits(0xFFFFFFFEu, 1));
+  CHECK(knn_add_fits(0xFFFFFFFEu, 0));
+  CHECK(!knn_add_fits(0x80000000u, 0x80000000u));
+  // refusals of knn_merge_offsets leave the output alone
+  {
+    std::vector<uint32_t> off = {0, 2, 5, 5}, out = {9};   // K = 2: [0,2) [2,5), no unclustered rows, 5 rows
+    const uint32_t good[3] = {0, 1, 3}, bad_order[3] = {0, 3, 1}, bad_start[3] = {1, 1, 3}, too_many[3] = {0, 1, 9};
+    CHECK(knn_merge_offsets(off, good, 2, 4, &out) && out == std::vector<uint32_t>({0, 3, 8, 9}));
+    out = {9};
+    CHECK(!knn_merge_offsets(off, bad_order, 2, 4, &out) && out == std::vector<uint32_t>({9}));
+    CHECK(!knn_merge_offsets(off, bad_start, 2, 4, &out) && out == std::vector<uint32_t>({9}));
+    CHECK(!knn_merge_offsets(off, too_many, 2, 4, &out) && out == std::vector<uint32_t>({9}));
+    std::vector<uint32_t> short_off = {0, 2, 5};
+    CHECK(!knn_merge_offsets(short_off, good, 2, 4, &out) && out == std::vector<uint32_t>({9}));
+    std::vector<uint32_t> full = {0, 0, 0, 0xFFFFFFFEu};
+    CHECK(!knn_merge_offsets(full, good, 2, 4, &out) && out == std::vector<uint32_t>({9}));
+  }
+  // the default chunk: within the budget, at least one row, never more than asked
+  CHECK(knn_add_chunk_rows(1048576, 256, 256, (size_t)4 << 30, 0) == 1048576);
+  CHECK(knn_add_chunk_rows(0xFFFFFFFEu, 256, 256, (size_t)4 << 30, 0) == ((size_t)4 << 30) / (256 * 10 + 48));
+  CHECK(knn_add_chunk_rows(10, 1u << 30, 1u << 30, 1024, 0) == 1);
+  CHECK(knn_add_chunk_rows(10, 64, 64, (size_t)4 << 30, 3) == 3);
+  printf(failures ? "%d checks FAILED\n" : "knn_merge_host_check: all checks passed\n", failures);
+  return failures ? 1 : 0;
+}
