@@ -386,6 +386,35 @@ int kmamd_knn_index_add(kmamd_knn_index *ix, uint32_t n_rows, const void *rows,
 int kmamd_knn_index_info(kmamd_knn_index *ix, uint32_t *n_rows, uint32_t *n_clustered,
                          int *filter /* 2: f16, 1: f32, 0: exact; any may be NULL */);
 
+/* Rows out of an index, in place.  After remove the index is observably the index that
+ * kmamd_knn_index_create builds from the same rows and centroids with the assignments of the listed ids set to
+ * `clusters` ("no cluster"): the rows are never returned again by query, query_probe or either radius call, and those
+ * calls return what they return on that fresh index, bit for bit in indices and distances, on every search path.  Ids
+ * are stable: n_rows does not change, every other row keeps its id, and a later add hands out n_rows, n_rows + 1, ...
+ * as before.  n_clustered drops by the rows that lost a cluster; k up to n_rows stays valid (slots nothing fills hold
+ * what the fresh index puts there).
+ *   ids          n_ids row ids, each below n_rows, in any order.  An id whose row has no cluster (removed before, or
+ *                given as >= clusters at create / add) is allowed and changes nothing; a repeated id counts once.
+ *   n_removed    (optional, host) the rows that actually lost a cluster.  If that is 0 -- n_ids == 0 included -- the
+ *                index's buffers are not touched at all.
+ *   device_ptrs  -1: ids is a host buffer, else the index's device
+ * Synchronous.  NOT safe against a concurrent call on the same index.  InvalidArguments, before any device work that
+ * changes the index and with the index and *n_removed untouched: a null handle, null ids with n_ids > 0, device_ptrs
+ * naming another device, an id >= n_rows.  If an allocation fails the call returns kmcudaMemoryAllocationFailure and
+ * the index is exactly what it was, still usable: the new sorted copies are built beside the old ones (peak: both, and
+ * about 7 words per row of scratch) and swapped in at the end.  The cost is that of one pass over the whole index,
+ * whatever the length of the list.  Memory is NOT reclaimed: a removed row moves to the no-cluster tail of the sorted
+ * copies, where a fresh index keeps such rows; there is no compaction and no reuse of ids.  The index never returns to
+ * a filter it has left: one that left the f16 filter (a centred row outside the half range) stays where it is even if
+ * that row is removed -- the results are the same bits either way, info's `filter` is the one difference from the
+ * fresh index.  Env KMCUDA_AMD_KNN_REMOVE_TIME=1 prints the device time of the call's stages.
+ *   radii   the clusters' radii as the searches' prune reads them (clusters floats, host; NaN: an empty cluster), after a
+ *           wait for the index's stream.  A window for tests: a stale radius would only loosen the prune without
+ *           changing any result, so nothing else shows it. */
+int kmamd_knn_index_remove(kmamd_knn_index *ix, uint32_t n_ids, const uint32_t *ids,
+                           uint32_t *n_removed /* optional out, host */, int32_t device_ptrs);
+int kmamd_knn_index_radii(kmamd_knn_index *ix, float *radii /* host, clusters floats */);
+
 /* Assigns rows to GIVEN centroids -- the "predict" of a trained K-means (no counterpart in the reference, whose
  * kmeans_cuda returns the assignments of the rows it was trained on only) -- with, as asked, the distance of every row
  * to its centroid and per-cluster statistics.  Stateless and synchronous; the caller owns all memory.

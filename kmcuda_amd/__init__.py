@@ -7,6 +7,8 @@ kmcuda_amd.distributed.
 k-NN of new rows against a clustered corpus (beyond the reference): KnnIndex, knn_query; radius search on
 the same index: KnnIndex.query_radius, knn_query_radius; multi-probe (approximate) search, only the nprobe nearest
 clusters of every query or the clusters the caller lists: KnnIndex.query / knn_query with nprobe= or probes=.
+A live index: KnnIndex.add takes more rows in place, KnnIndex.remove takes rows out of every later search (ids stay
+stable, memory is not reclaimed); after either the index answers bit for bit as a freshly built one.
 New rows assigned to given centroids, with distances and cluster statistics (beyond the reference): kmeans_predict;
 the m nearest centroids of every row, in the order an assignment pass would find them: kmeans_predict_top.
 k-means|| seeding (beyond the reference), stand-alone -- kmeans_seed_parallel -- and as kmeans_cuda(init="k-means||").

@@ -25,6 +25,7 @@ EXPORTS = [
     "kmamd_reduce_apply", "kmamd_reduce_apply_stop", "kmamd_reduce_apply_prepare", "kmamd_stop_report", "kmamd_stop_clear", "kmamd_centroids_written", "kmamd_set_carry", "kmamd_carry_stats", "kmamd_carry_pair_stats", "kmamd_duo_rows", "kmamd_carry_policy_sim", "kmamd_set_update_mode", "kmamd_last_run_stats", "kmamd_last_run_collective", "kmamd_adjust_exact", "kmamd_yy_configure", "kmamd_yy_init", "kmamd_yy_drifts", "kmamd_yy_filters",
     "kmamd_knn_index_create", "kmamd_knn_index_query", "kmamd_knn_index_query_probe", "kmamd_knn_index_destroy",
     "kmamd_knn_index_radius_count", "kmamd_knn_index_radius_fill", "kmamd_knn_index_add", "kmamd_knn_index_info",
+    "kmamd_knn_index_remove", "kmamd_knn_index_radii",
     "kmamd_kmeans_assign", "kmamd_assigned_distances",
     "kmamd_kmeans_assign_top", "kmamd_assign_top_stats",
     "kmamd_kmeans_seed_parallel",
@@ -155,6 +156,10 @@ def lib():
     L.kmamd_knn_index_add.argtypes = [vp, u32, vp, vp, vp, ctypes.POINTER(u32), i32]
     L.kmamd_knn_index_info.restype = i32
     L.kmamd_knn_index_info.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_int)]
+    L.kmamd_knn_index_remove.restype = i32
+    L.kmamd_knn_index_remove.argtypes = [vp, u32, vp, ctypes.POINTER(u32), i32]
+    L.kmamd_knn_index_radii.restype = i32
+    L.kmamd_knn_index_radii.argtypes = [vp, vp]
     L.kmamd_knn_index_destroy.restype = None
     L.kmamd_knn_index_destroy.argtypes = [vp]
     L.kmamd_kmeans_assign.restype = i32

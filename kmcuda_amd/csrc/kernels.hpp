@@ -588,6 +588,27 @@ hipError_t launch_knn_merge_radii(const float *R_old, const float *rdist, const 
                                   const uint32_t *stats_old, const uint32_t *stats_c_old, const uint32_t *bstats,
                                   uint32_t *stats_new, uint32_t *stats_c_new, hipStream_t st);
 
+// knn_remove.hip -- rows removed from an index (kmamd_knn_index_remove).
+// *flag |= 1 if one of ids[0 .. n) (device) is >= N
+hipError_t launch_knn_remove_ids_check(const uint32_t *ids, uint32_t n, uint32_t N, uint32_t *flag, hipStream_t st);
+// the index's CSR (offsets: K + 1 entries, inv: sorted position -> row) back by row id: asg[row] = its cluster (K:
+// none), pos[row] = its sorted position
+hipError_t launch_knn_remove_scatter(const uint32_t *offsets, uint32_t K, const uint32_t *inv, uint32_t N, uint32_t *asg,
+                                     uint32_t *pos, hipStream_t st);
+// asg[ids[i]] = K for every i < n (ids < N); *count += the distinct ids whose entry was below K
+hipError_t launch_knn_remove_mark(const uint32_t *ids, uint32_t n, uint32_t K, uint32_t *asg, uint32_t *count,
+                                  hipStream_t st);
+// The gather: destination position p takes the values of the index's position pos[out.inv[p]] -- xs, n2s and, where
+// out.xs16 is set, xs16 / n2c / mux / kbias.  out.inv holds the new order already; out.mydist is left alone.
+struct KnnRemoveArgs {
+  KnnSortedRows old_rows, out;
+  const uint32_t *pos;
+  uint32_t N, DP;
+};
+hipError_t launch_knn_remove_rows(const KnnRemoveArgs &a, hipStream_t st);
+// knn.hip: R[c] = the largest rdist of cluster c's sorted positions, NaN for an empty cluster (launch_knn_prep's last step)
+hipError_t launch_knn_radii(const float *rdist, const uint32_t *offsets, uint32_t K, float *R, hipStream_t st);
+
 // knn_radius.hip -- radius search of a query batch (kmamd_knn_index_radius_*).  `a` is the query mode's
 // KnnArgs (heaps / out / outd / k unread).  Query i of the chunk (caller's order; qinv: sorted query position -> i)
 // gets counts[i], or its hits at [offsets[i], offsets[i + 1]) of neighbors / distances, both addressed relative to

@@ -680,6 +680,10 @@ hipError_t launch_knn_prep(int metric, const float *xs, uint32_t N, uint32_t D, 
     if (strict_h2) hipLaunchKernelGGL((knn_cdist_kernel<1, true>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
     else hipLaunchKernelGGL((knn_cdist_kernel<1, false>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
   }
+  return launch_knn_radii(rdist, offsets, K, R, st);
+}
+
+hipError_t launch_knn_radii(const float *rdist, const uint32_t *offsets, uint32_t K, float *R, hipStream_t st) {
   hipLaunchKernelGGL(knn_radii_kernel, dim3(K), dim3(64), 0, st, rdist, offsets, K, R);
   return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 // knn_heap.hpp -- the k-NN heap step, ONE copy for every search kernel (knn.hip, knn_f16.hip), and the cluster of a
-// sorted position (knn.hip, knn_merge.hip).
+// sorted position (knn.hip, knn_merge.hip, knn_remove.hip).
 #pragma once
 #include <stdint.h>
 

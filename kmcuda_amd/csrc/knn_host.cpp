@@ -38,6 +38,7 @@ KnnSwitches knn_switches() {
     if (v > 0) sw.add_chunk = (size_t)v;
   }
   sw.add_time = on(getenv("KMCUDA_AMD_KNN_ADD_TIME"));
+  sw.remove_time = on(getenv("KMCUDA_AMD_KNN_REMOVE_TIME"));
   return sw;
 }
 

@@ -56,6 +56,7 @@ struct KnnSwitches {
   size_t query_chunk = 0;    // KMCUDA_AMD_KNN_QUERY_CHUNK: queries per chunk of an index query (0: unset)
   size_t add_chunk = 0;      // KMCUDA_AMD_KNN_ADD_CHUNK: rows per chunk (one merge each) of an index add (0: unset)
   bool add_time = false;     // KMCUDA_AMD_KNN_ADD_TIME: an index add prints the device time of its three stages
+  bool remove_time = false;  // KMCUDA_AMD_KNN_REMOVE_TIME: an index remove prints the device time of its four stages
 };
 KnnSwitches knn_switches();
 

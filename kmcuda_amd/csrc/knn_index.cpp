@@ -18,6 +18,10 @@
 // add() takes more rows into the index: the new rows are prepared chunk by chunk with the launches a
 // fresh index's rows go through and merged into new cluster-sorted copies (knn_merge.hip); the index's own buffers stay
 // as they are until the whole batch has been enqueued without error.
+//
+// remove() takes rows out of every later search: their assignments become K ("no cluster"), the order a
+// fresh index would give the patched assignments is made by its own sort, and one gather (knn_remove.hip) moves every
+// row's values into a new state, whose member distances and radii the fresh index's kernels make again.
 #include <math.h>
 #include <stdio.h>
 
@@ -154,6 +158,10 @@ class KnnIndex {
     t = IndexState();
   }
   int merge(const IndexState &cur, const AddChunk &c, uint32_t n, IndexState *next);
+
+  // ---- remove ----
+  int remove(uint32_t n_ids, const uint32_t *ids, uint32_t *n_removed, int32_t device_ptrs);
+  int radii(float *out);
 };
 
 // rows [r0, r0 + n) of a caller's row matrix, fp32 in `rows` on this device (halves by way of `half`)
@@ -323,15 +331,12 @@ struct QueryChunk {
   }
 };
 
-// KMCUDA_AMD_KNN_ADD_TIME: HIP events on the index's stream around the three stages of every chunk of an add -- the
-// rows' clusters (upload and assignment pass), the chunk's preparation (CSR, gather, member distances, split), the merge
-// --, summed over the chunks and printed at the end of the call (scripts/knn_add_bench.py reads the line)
-struct AddTimer {
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // (2 -> 3: the host's wait and allocations)
+// HIP events on the index's stream at the stage boundaries of a call, where a switch asks for them
+template <int N>
+struct StageEvents {
+  hipEvent_t ev[N] = {};
   bool on = false;
-  float ms[3] = {0.f, 0.f, 0.f};
-  unsigned long long merged_bytes = 0;
-  ~AddTimer() {
+  ~StageEvents() {
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -343,10 +348,20 @@ struct AddTimer {
   void mark(int i, hipStream_t st) const {
     if (on) (void)hipEventRecord(ev[i], st);
   }
-  void fold() {   // (after a wait for the stream)
+  float elapsed(int from, int to) const {   // (after a wait for the stream)
     float t = 0.f;
-    for (int i = 0; on && i < 3; i++)
-      if (hipEventElapsedTime(&t, ev[i == 2 ? 3 : i], ev[i == 2 ? 4 : i + 1]) == hipSuccess) ms[i] += t;
+    return on && hipEventElapsedTime(&t, ev[from], ev[to]) == hipSuccess ? t : 0.f;
+  }
+};
+
+// KMCUDA_AMD_KNN_ADD_TIME: the three stages of every chunk of an add -- the rows' clusters (upload and assignment pass),
+// the chunk's preparation (CSR, gather, member distances, split), the merge --, summed over the chunks and printed at
+// the end of the call (scripts/knn_add_bench.py reads the line)
+struct AddTimer : StageEvents<5> {   // (2 -> 3: the host's wait and allocations)
+  float ms[3] = {0.f, 0.f, 0.f};
+  unsigned long long merged_bytes = 0;
+  void fold() {   // (after a wait for the stream)
+    for (int i = 0; i < 3; i++) ms[i] += elapsed(i == 2 ? 3 : i, i == 2 ? 4 : i + 1);
   }
 };
 
@@ -855,6 +870,154 @@ int KnnIndex::add(uint32_t n_rows, const void *rows, const uint32_t *assign_in, 
   return 0;
 }
 
+// The scratch of one call, taken from the index's arena and given back when the call ends, whichever way it ends
+// (behind a wait for the stream: kernels may still read it)
+struct ArenaScratch {
+  DeviceArena &a;
+  std::vector<void *> mine;
+  explicit ArenaScratch(DeviceArena &a_) : a(a_) {}
+  ~ArenaScratch() {
+    (void)hipStreamSynchronize(a.stream);
+    for (void *p : mine) a.release(p);
+  }
+  template <typename T>
+  int get(T **p, size_t count) {
+    const int rc = a.alloc(p, count);
+    if (rc == 0) mine.push_back(*p);
+    else (void)hipGetLastError();
+    return rc;
+  }
+};
+
+// A state under construction: released with the call unless the index has adopted it
+struct PendingState {
+  KnnIndex &ix;
+  IndexState t;
+  bool adopted = false;
+  explicit PendingState(KnnIndex &ix_) : ix(ix_) {}
+  ~PendingState() {
+    if (adopted) return;
+    (void)hipStreamSynchronize(ix.s.stream);
+    ix.release_state(t);
+  }
+};
+
+// KMCUDA_AMD_KNN_REMOVE_TIME: the four stages of a remove -- the assignments (scatter and mark), the sort, the copy, the
+// member distances and radii --, printed at the end of the call (scripts/knn_remove_bench.py reads the line)
+using RemoveTimer = StageEvents<6>;   // (1 -> 2: the host's wait and allocations)
+
+// The listed rows lose their cluster.  A whole new state is built beside the index's own, which is
+// read only and replaced once everything has been enqueued and the stream has drained without error.
+int KnnIndex::remove(uint32_t n_ids, const uint32_t *ids, uint32_t *n_removed, int32_t device_ptrs) {
+  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
+  const hipStream_t st = s.stream;
+  const bool host = device_ptrs < 0, f16 = path.use_f16;
+  const uint32_t N = s.N, K = s.K, DP = s.DP;
+  if (host)
+    for (uint32_t i = 0; i < n_ids; i++)
+      if (ids[i] >= N) return kmcudaInvalidArguments;
+  if (n_ids == 0) {
+    if (n_removed) *n_removed = 0;
+    return 0;
+  }
+  RemoveTimer tm;
+  tm.start(knn_switches().remove_time);
+  ArenaScratch x(s);
+  // ---- the ids on the device, every one a row of the index ----
+  uint32_t *words = nullptr, *ids_up = nullptr;   // words: [0] the flag of the check, [1] the rows that lose a cluster
+  KNN_TRY(x.get(&words, 2));
+  KMX_HIPRT(hipMemsetAsync(words, 0, 2 * sizeof(uint32_t), st));
+  uint32_t seen[2] = {0, 0};
+  if (host) {
+    KNN_TRY(x.get(&ids_up, n_ids));
+    KMX_HIPCP(hipMemcpyAsync(ids_up, ids, (size_t)n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    ids = ids_up;
+  } else {
+    KMX_HIPRT(launch_knn_remove_ids_check(ids, n_ids, N, words, st));
+    KMX_HIPCP(hipMemcpyAsync(seen, words, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KMX_HIPRT(hipStreamSynchronize(st));
+    if (seen[0]) return kmcudaInvalidArguments;
+  }
+  // ---- the assignments the index stands for, the listed rows' set to K ----
+  uint32_t *asg = nullptr, *pos = nullptr;
+  KNN_TRY(x.get(&asg, N));
+  KNN_TRY(x.get(&pos, N));
+  tm.mark(0, st);
+  KMX_HIPRT(launch_knn_remove_scatter(s.offsets, K, s.inv, N, asg, pos, st));
+  KMX_HIPRT(launch_knn_remove_mark(ids, n_ids, K, asg, words + 1, st));
+  tm.mark(1, st);
+  KMX_HIPCP(hipMemcpyAsync(seen + 1, words + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  KMX_HIPRT(hipStreamSynchronize(st));
+  const uint32_t lost = seen[1];
+  if (lost == 0) {   // nothing listed had a cluster: the index's buffers have not been touched
+    if (n_removed) *n_removed = 0;
+    return 0;
+  }
+  // ---- the new order: the stable sort a fresh index runs over the patched assignments ----
+  PendingState next(*this);
+  KNN_TRY(alloc_state(&next.t, N, f16));
+  uint32_t *keys_tmp = nullptr, *vals_tmp = nullptr, *keys_sorted = nullptr;
+  char *sort_temp = nullptr;
+  float *rdist = nullptr;
+  const size_t sort_bytes = sort_temp_bytes(N, K);
+  KNN_TRY(x.get(&keys_tmp, N));
+  KNN_TRY(x.get(&vals_tmp, N));
+  KNN_TRY(x.get(&keys_sorted, N));
+  KNN_TRY(x.get(&sort_temp, sort_bytes + 16));
+  KNN_TRY(x.get(&rdist, N));
+  KnnSortedRows &out = next.t.rows;
+  tm.mark(2, st);
+  KMX_HIPRT(launch_inverse_assignments(asg, N, K, keys_tmp, vals_tmp, keys_sorted, out.inv, next.t.offsets, sort_temp,
+                                       sort_bytes, st));
+  KMX_HIPRT(hipMemsetD32Async((hipDeviceptr_t)(next.t.offsets + K + 1), (int)N, 1, st));
+  tm.mark(3, st);
+  // ---- every row's own values into their new places ----
+  KnnRemoveArgs a;
+  a.old_rows = state().rows; a.out = out; a.pos = pos; a.N = N; a.DP = DP;
+  KMX_HIPRT(launch_knn_remove_rows(a, st));
+  if (f16) {   // the filter's tile DMA reads whole tiles: zeros past the last row, as launch_knn_split leaves them
+    KMX_HIPRT(hipMemsetAsync(out.xs16 + (size_t)N * DP, 0, (size_t)KNN16_PAD_ROWS * DP * sizeof(uint16_t), st));
+    KMX_HIPRT(hipMemsetAsync(out.kbias + N, 0, (size_t)KNN16_PAD_ROWS * sizeof(float), st));
+    KMX_HIPCP(hipMemcpyAsync(next.t.stats_c, s.stats_c, 4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  }
+  // (maxima over all rows, and every row stays; the half-range flag cannot rise)
+  KMX_HIPCP(hipMemcpyAsync(next.t.stats, s.stats, 4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  tm.mark(4, st);
+  // ---- what depends on membership, by the kernels of a fresh index ----
+  KMX_HIPRT(launch_knn_member(s.metric, out.xs, N, s.D, DP, next.t.offsets, K, s.centroids, out.mydist, rdist, path.strict_h2, st));
+  KMX_HIPRT(launch_knn_radii(rdist, next.t.offsets, K, next.t.R, st));
+  tm.mark(5, st);
+  next.t.off_host.assign((size_t)K + 2, N);
+  KMX_HIPCP(hipMemcpyAsync(next.t.off_host.data(), next.t.offsets, ((size_t)K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    if (verbosity > 0) printf("k-NN index remove failed: %s\n", hipGetErrorString(hipGetLastError()));
+    return kmcudaRuntimeError;
+  }
+  if (tm.on) {
+    // (read and written once: the fp32 rows, the halves and one or four words per row)
+    const double bytes = 2.0 * (double)N * ((f16 ? 6.0 : 4.0) * DP + (f16 ? 16.0 : 4.0));
+    const float copy_ms = tm.elapsed(3, 4);
+    printf("k-NN index remove: %u ids, %u rows lost a cluster of %u: assignments %.3f ms, sort %.3f ms, copy %.3f ms "
+           "(%.3f GB moved, %.3f TB/s), member distances and radii %.3f ms\n", n_ids, lost, N, tm.elapsed(0, 1),
+           tm.elapsed(2, 3), copy_ms, 1e-9 * bytes, copy_ms > 0.f ? 1e-9 * bytes / (double)copy_ms : 0.0, tm.elapsed(4, 5));
+    fflush(stdout);
+  }
+  IndexState old = state();
+  adopt(next.t);
+  next.adopted = true;
+  release_state(old);
+  if (n_removed) *n_removed = lost;
+  return 0;
+}
+
+// R on the host (a window for tests: the radii are otherwise invisible)
+int KnnIndex::radii(float *out) {
+  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
+  KMX_HIPRT(hipStreamSynchronize(s.stream));
+  KMX_HIPCP(hipMemcpy(out, s.R, (size_t)s.K * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 }  // namespace
 
 struct kmamd_knn_index {
@@ -963,6 +1126,21 @@ int kmamd_knn_index_add(kmamd_knn_index *h, uint32_t n_rows, const void *rows, c
   }
   if (first_row) *first_row = first;
   return kmcudaSuccess;
+}
+
+int kmamd_knn_index_remove(kmamd_knn_index *h, uint32_t n_ids, const uint32_t *ids, uint32_t *n_removed,
+                           int32_t device_ptrs) {
+  if (!h) return kmcudaInvalidArguments;
+  KnnIndex &ix = h->ix;
+  if (n_ids > 0 && !ids) return kmcudaInvalidArguments;
+  if (device_ptrs >= 0 && device_ptrs != ix.s.dev) return kmcudaInvalidArguments;
+  if (n_ids != 0 && device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
+  return ix.remove(n_ids, ids, n_removed, device_ptrs);
+}
+
+int kmamd_knn_index_radii(kmamd_knn_index *h, float *radii) {
+  if (!h || !radii) return kmcudaInvalidArguments;
+  return h->ix.radii(radii);
 }
 
 int kmamd_knn_index_info(kmamd_knn_index *h, uint32_t *n_rows, uint32_t *n_clustered, int *filter) {

@@ -5,6 +5,7 @@
 // was made per row by the kernels that make it for a fresh index (knn_gather / knn_member / knn_split), so the merged
 // index holds the bits the fresh one would.
 #include "kernels.hpp"
+#include "knn_copy_tile.hpp"
 #include "knn_heap.hpp"
 
 namespace kmx {
@@ -12,31 +13,6 @@ namespace kmx {
 namespace {
 
 constexpr uint32_t kMergeTile = 64;   // destination rows per wave and step: one per lane
-// `rows` rows of `nvec` pieces each, consecutive at dst; row r comes from position src_q (of lane r) of the index's
-// buffer (src_old of lane r) or the chunk's.  The pieces of the tile are dealt to the lanes as one flat range, so a row
-// narrower than the wave leaves no lane idle, and every lane has four loads under way before its first store (two
-// and eight, and non-temporal accesses, measured the same within the run-to-run spread: DESIGN_LOG 29).  Four named
-// values, not an array: the compiler kept an array in LDS and scratch.
-template <typename T>
-__device__ __forceinline__ void copy_tile(const T *__restrict__ from_old, const T *__restrict__ from_chunk, T *__restrict__ dst,
-                                          uint32_t nvec, uint32_t rows, uint32_t src_q, bool src_old, uint32_t lane) {
-  const uint32_t total = rows * nvec;
-  auto fetch = [&](uint32_t idx) -> T {
-    const uint32_t r = idx < total ? idx / nvec : 0;   // (every lane takes part in the shuffles)
-    const uint32_t q = __shfl(src_q, r);
-    const bool old = __shfl((int)src_old, r) != 0;
-    if (idx >= total) return T();
-    return (old ? from_old : from_chunk)[(size_t)q * nvec + (idx - r * nvec)];
-  };
-  for (uint32_t base = lane; base < total + lane; base += 256) {   // (the bound is the same for every lane)
-    const T v0 = fetch(base), v1 = fetch(base + 64), v2 = fetch(base + 128), v3 = fetch(base + 192);
-    if (base < total) dst[base] = v0;
-    if (base + 64 < total) dst[base + 64] = v1;
-    if (base + 128 < total) dst[base + 128] = v2;
-    if (base + 192 < total) dst[base + 192] = v3;
-  }
-}
-
 // One wave per tile of kMergeTile consecutive destination positions (a bounded grid strides over the tiles,
 // kernels.hpp: wave_row_grid).  Lane l resolves position p = tile + l: it lies in cluster c (K: the rows without a
 // cluster) at rank j; ranks below the cluster's old size come from the index, the others from the chunk.  The lane

@@ -25,6 +25,12 @@ index.add(rows, assignments) returns the id of rows[0]; the new rows take the id
 then answers every query exactly -- indices and distance bits -- as KnnIndex(old rows + new rows, centroids, ...) would.
 index.info() is (n_rows, n_clustered, filter): filter 2 the f16 matrix-core filter, 1 the f32 one, 0 the exact search.
 
+Rows can be removed in place, DESIGN.md 4.16: index.remove(ids) returns how many rows lost their cluster; they are never
+returned again and the index then answers every query exactly -- indices and distance bits -- as KnnIndex(rows,
+centroids, assignments with assignments[ids] = K) would.  Ids are stable: n_rows does not change, memory is not reclaimed
+(the rows move to the no-cluster tail; no compaction, no reuse of ids), and an index that has left the f16 filter stays
+where it is.  index.radii() reads the clusters' radii (a window for tests).
+
 numpy in, numpy out (neighbors uint32, distances float32, assignments uint32).  torch tensors on the index's device
 in, torch tensors on that device out (neighbors / assignments int32: 0xFFFFFFFF reads -1), with no host round trip;
 the call orders with torch's work on the device (it waits for the device first and its outputs are complete when
@@ -410,6 +416,56 @@ class KnnIndex:
         _raise_for(rc, "kmamd_knn_index_add")
         self.n_rows += n
         return (int(first.value), out) if return_assignments else int(first.value)
+
+    def remove(self, ids):
+        """Removes the rows `ids` (a 1-D integer numpy array or sequence, or an integer tensor on the index's device;
+        independent of how the corpus was passed) from every later search and returns how many rows lost their cluster:
+        an id without a cluster (removed before, or given as >= the number of clusters) is allowed and changes nothing, a
+        repeated id counts once.  The rows keep their ids and n_rows does not change; memory is not reclaimed.  The
+        index then equals KnnIndex(rows, centroids, assignments with those ids set to the number of clusters) bit for
+        bit in every query.  One pass over the whole index, whatever len(ids).  Not safe against a
+        concurrent call on the same index."""
+        if not getattr(self, "h", None):
+            raise ValueError("the index is closed")
+        if _is_torch(ids):
+            import torch
+            if ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+                raise TypeError("\"ids\" must be a 1D integer tensor")
+            if ids.dim() != 1:
+                raise ValueError("\"ids\" must be a 1D tensor")
+            if not ids.is_cuda or ids.device.index != self.device:
+                raise ValueError("\"ids\" must be on the index's device (or be a numpy array)")
+            n = int(ids.shape[0])
+            if n and bool(((ids < 0) | (ids >= self.n_rows)).any()):
+                raise ValueError("\"ids\" must hold row ids in [0, %d)" % self.n_rows)
+            arr, on_dev = ids.to(torch.int32).contiguous(), True   # (an id from 2^31 on keeps its 32 bits)
+        else:
+            arr = ids if isinstance(ids, numpy.ndarray) else numpy.asarray(ids)
+            if arr.size == 0 and not isinstance(ids, numpy.ndarray):
+                arr = arr.astype(numpy.uint32)   # (an empty list has no dtype of its own)
+            if arr.dtype.kind not in "iu":
+                raise TypeError("\"ids\" must be a 1D integer numpy array or sequence")
+            if arr.ndim != 1:
+                raise ValueError("\"ids\" must be a 1D numpy array or sequence")
+            n = int(arr.shape[0])
+            if n and (arr.min() < 0 or arr.max() >= self.n_rows):
+                raise ValueError("\"ids\" must hold row ids in [0, %d)" % self.n_rows)
+            arr, on_dev = numpy.ascontiguousarray(arr, dtype=numpy.uint32), False
+        lost = u32(0)
+        rc = self.lib.kmamd_knn_index_remove(self.h, n, _ptr(arr) if n else None, ctypes.byref(lost),
+                                             self.device if on_dev else -1)
+        _raise_for(rc, "kmamd_knn_index_remove")
+        return int(lost.value)
+
+    def radii(self):
+        """The clusters' radii as the searches' prune reads them: numpy float32 (clusters,), NaN for a cluster without
+        rows.  A window for tests (a stale radius would only loosen the prune, never change a result)."""
+        if not getattr(self, "h", None):
+            raise ValueError("the index is closed")
+        out = numpy.empty((self.clusters,), numpy.float32)
+        rc = self.lib.kmamd_knn_index_radii(self.h, _ptr(out))
+        _raise_for(rc, "kmamd_knn_index_radii")
+        return out
 
     def info(self):
         """(n_rows, n_clustered, filter): the rows of the index, those of them that have a cluster, and the search it
