@@ -1,7 +1,7 @@
 // host_job.hpp -- the host plumbing the chunked row calls share: kmamd_kmeans_assign (assign_job.cpp),
 // kmamd_kmeans_assign_top (assign_top_job.cpp), kmamd_kmeans_seed_parallel (seed_par_job.cpp) and, for the arena alone,
-// the k-NN files (knn_host.hpp).  The queries of the k-NN index stay off RowStage: QueryChunk::prepare (knn_index.cpp)
-// always copies, device to device too, into buffers its init() sizes together with everything else.
+// the k-NN files (knn_host.hpp).  The queries and added rows of the k-NN index stay off RowStage: SortedChunk::upload
+// (knn_index.cpp) always copies, device to device too, into buffers its init() sizes together with everything else.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>

@@ -38,6 +38,20 @@ namespace {
 // lb (K floats per query) and the heaps (2k floats per query) of one chunk of queries stay within this budget
 constexpr size_t kQueryChunkBytes = (size_t)4 << 30;
 
+// The centred half copy of a state or chunk of N rows ends in KNN16_PAD_ROWS rows / biases of zeros (the filter's tile
+// DMA reads whole tiles), as launch_knn_split leaves them
+int zero_f16_pad(const KnnSortedRows &r, uint32_t N, uint32_t DP, hipStream_t st) {
+  KMX_HIPRT(hipMemsetAsync(r.xs16 + (size_t)N * DP, 0, (size_t)KNN16_PAD_ROWS * DP * sizeof(uint16_t), st));
+  KMX_HIPRT(hipMemsetAsync(r.kbias + N, 0, (size_t)KNN16_PAD_ROWS * sizeof(float), st));
+  return 0;
+}
+
+// (`path`: what the index runs from now on)
+void say_left_half_range(const KnnPath &path) {
+  printf("k-NN index: a centred row leaves the half range, %s\n",
+         path.dp_filter ? "the f32 matrix-core filter instead of the f16 one" : "every candidate is evaluated exactly");
+}
+
 // What an add replaces: the per-row copies of the index (the f16 filter's only while it runs), its CSR offsets (on the
 // device and on the host: K + 2 entries, [K] the rows that have a cluster, [K + 1] all of them), radii and statistics.
 struct IndexState {
@@ -68,9 +82,7 @@ class KnnIndex {
     bool left_half_range = false;
     off_host.assign((size_t)c.K + 2, c.N);
     KNN_TRY(knn_prepare_corpus(&one, 1, c, true, &path, &left_half_range, off_host.data()));
-    if (left_half_range && verbosity > 0)   // no f16 filter for this index
-      printf("k-NN index: a centred row leaves the half range, %s\n",
-             path.dp_filter ? "the f32 matrix-core filter instead of the f16 one" : "every candidate is evaluated exactly");
+    if (left_half_range && verbosity > 0) say_left_half_range(path);   // no f16 filter for this index
     if (s.centroids == c.centroids) {   // the caller's centroids may change after this call: the index keeps a copy
       float *cen = nullptr;
       KNN_TRY(s.alloc(&cen, (size_t)c.K * c.D));
@@ -105,6 +117,7 @@ class KnnIndex {
 
   // ---- add ----
   int add(uint32_t n_rows, const void *rows, const uint32_t *assign_in, uint32_t *assign_out, int32_t device_ptrs);
+  int add_chunks(uint32_t n_rows, const void *rows, const uint32_t *assign_in, uint32_t *assign_out, bool host);
   IndexState state() const {
     IndexState t;
     t.rows.xs = s.xs; t.rows.n2s = s.n2s; t.rows.mydist = s.mydist; t.rows.inv = s.inv;
@@ -164,32 +177,100 @@ class KnnIndex {
   int radii(float *out);
 };
 
-// rows [r0, r0 + n) of a caller's row matrix, fp32 in `rows` on this device (halves by way of `half`)
-int upload_rows(bool fp16, const void *src, size_t r0, size_t n, uint32_t D, bool host, uint16_t *half, float *rows,
-                hipStream_t st) {
-  const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  if (fp16) {
-    KMX_HIPCP(hipMemcpyAsync(half, static_cast<const uint16_t *>(src) + r0 * D, n * D * sizeof(uint16_t), kind, st));
-    KMX_HIPRT(launch_half_to_float(half, n * D, rows, st));
-  } else {
-    KMX_HIPCP(hipMemcpyAsync(rows, static_cast<const float *>(src) + r0 * D, n * D * sizeof(float), kind, st));
+// n caller rows made cluster-sorted against this index: the buffers of one chunk of a query batch or of an add (sized
+// for at most `cap` rows, reused by every chunk) and the steps both take on them.  Between upload() and sort() lies
+// what differs: the rows' clusters (QueryChunk, AddChunk).
+// stats: [0] the largest plain norm, [1] the half-range flag (both the gather's), [2] the largest centred norm (the
+// split's; launch_knn_merge_radii reads it), [3] a flag of the cluster step
+struct SortedChunk {
+  DeviceArena w;   // owns the buffers; enqueues on the index's stream (nothing to release)
+  KnnScratch scratch;   // the sort scratch (w's) and the optional buffers of knn_search
+  uint32_t cap = 0;
+  float *rows = nullptr, *rdist = nullptr;
+  uint16_t *half = nullptr;
+  uint32_t *asg = nullptr, *prev = nullptr, *offsets = nullptr, *stats = nullptr;
+  KnnSortedRows b{};   // the chunk in cluster-sorted order (inv: sorted position -> row of the chunk)
+  std::vector<uint32_t> offs;   // `offsets` on the host (K + 1)
+
+  // sort_max_key: the largest key sort() or a search's query order will see; want_prev: an engine's assignment pass runs
+  int init(const KnnIndex &ix, uint32_t cap_, uint32_t sort_max_key, bool want_prev) {
+    const KnnShard &s = ix.s;
+    const uint32_t D = s.D, DP = s.DP, K = s.K;
+    cap = cap_;
+    w.dev = s.dev;
+    w.stream = nullptr;
+    KNN_TRY(w.alloc(&rows, (size_t)cap * D));
+    if (ix.fp16) KNN_TRY(w.alloc(&half, (size_t)cap * D));
+    KNN_TRY(w.alloc(&asg, cap));
+    if (want_prev) KNN_TRY(w.alloc(&prev, cap));
+    KNN_TRY(w.alloc(&b.inv, cap));
+    KNN_TRY(w.alloc(&offsets, (size_t)K + 2));
+    KNN_TRY(w.alloc(&scratch.keys_tmp, cap));
+    KNN_TRY(w.alloc(&scratch.vals_tmp, cap));
+    KNN_TRY(w.alloc(&scratch.keys_sorted, cap));
+    KNN_TRY(w.alloc(&stats, 4));
+    KNN_TRY(w.alloc(&b.xs, (size_t)cap * DP));
+    KNN_TRY(w.alloc(&b.n2s, cap));
+    KNN_TRY(w.alloc(&b.mydist, cap));
+    KNN_TRY(w.alloc(&rdist, cap));
+    if (ix.path.use_f16) {
+      KNN_TRY(w.alloc(&b.xs16, ((size_t)cap + KNN16_PAD_ROWS) * DP));
+      KNN_TRY(w.alloc(&b.n2c, cap));
+      KNN_TRY(w.alloc(&b.mux, cap));
+      KNN_TRY(w.alloc(&b.kbias, (size_t)cap + KNN16_PAD_ROWS));
+    }
+    scratch.rows = cap;
+    scratch.sort_bytes = sort_temp_bytes(cap, sort_max_key);
+    char *sort_temp = nullptr;
+    KNN_TRY(w.alloc(&sort_temp, scratch.sort_bytes + 16));
+    scratch.sort_temp = sort_temp;
+    offs.resize((size_t)K + 1);
+    return 0;
   }
-  return 0;
-}
 
-// n rows in cluster-sorted order by their CSR (inv, offsets): the DP-padded copy, plain norms, their maximum and the
-// half-range flag (stats[0], stats[1]; mu: the f16 filter's centre or null), distances to the own centroid
-int sorted_rows(const KnnIndex &ix, const float *rows, uint32_t n, const uint32_t *inv, const uint32_t *offsets, float *xs,
-                float *n2s, uint32_t *stats, float *mydist, float *rdist) {
-  const KnnShard &s = ix.s;
-  KMX_HIPRT(launch_knn_gather(rows, n, s.D, s.DP, inv, xs, n2s, stats, ix.path.use_f16 ? s.mu : nullptr, offsets, s.K, s.stream));
-  KMX_HIPRT(launch_knn_member(s.metric, xs, n, s.D, s.DP, offsets, s.K, s.centroids, mydist, rdist, ix.path.strict_h2, s.stream));
-  return 0;
-}
+  // rows [r0, r0 + n) of the caller's row matrix, fp32 in `rows` (halves by way of `half`)
+  int upload(const KnnIndex &ix, const void *src, size_t r0, size_t n, bool host) {
+    const hipStream_t st = ix.s.stream;
+    const uint32_t D = ix.s.D;
+    const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    if (ix.fp16) {
+      KMX_HIPCP(hipMemcpyAsync(half, static_cast<const uint16_t *>(src) + r0 * D, n * D * sizeof(uint16_t), kind, st));
+      KMX_HIPRT(launch_half_to_float(half, n * D, rows, st));
+    } else {
+      KMX_HIPCP(hipMemcpyAsync(rows, static_cast<const float *>(src) + r0 * D, n * D * sizeof(float), kind, st));
+    }
+    return 0;
+  }
+  // the CSR of the chunk (b.inv, offsets) by a key per row (>= K: no cluster)
+  int sort(const KnnIndex &ix, const uint32_t *keys, uint32_t n) {
+    KMX_HIPRT(launch_inverse_assignments(keys, n, ix.s.K, scratch.keys_tmp, scratch.vals_tmp, scratch.keys_sorted, b.inv, offsets,
+                                         scratch.sort_temp, scratch.sort_bytes, ix.s.stream));
+    return 0;
+  }
+  // the rows in that order: the DP-padded copy, plain norms, their maximum and -- with mu, the f16 filter's centre --
+  // the half-range flag, which the chunk's rows raise as the corpus rows do; distances to the own centroid
+  int gather(const KnnIndex &ix, uint32_t n) {
+    const KnnShard &s = ix.s;
+    KMX_HIPRT(launch_knn_gather(rows, n, s.D, s.DP, b.inv, b.xs, b.n2s, stats, ix.path.use_f16 ? s.mu : nullptr, offsets, s.K, s.stream));
+    KMX_HIPRT(launch_knn_member(s.metric, b.xs, n, s.D, s.DP, offsets, s.K, s.centroids, b.mydist, rdist, ix.path.strict_h2, s.stream));
+    return 0;
+  }
+  // the f16 filter's side of the sorted rows
+  int split(const KnnIndex &ix, uint32_t n) {
+    const KnnShard &s = ix.s;
+    KMX_HIPRT(launch_knn_split(s.metric, b.xs, n, s.D, s.DP, s.mu, b.xs16, b.n2c, b.mux, b.kbias, stats + 2, s.stream));
+    return 0;
+  }
+  // the offsets and, where asked for, the four stat words on the host: the chunk's one wait for the stream
+  int fetch(const KnnIndex &ix, uint32_t *stats_host) {
+    const hipStream_t st = ix.s.stream;
+    KMX_HIPCP(hipMemcpyAsync(offs.data(), offsets, ((size_t)ix.s.K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (stats_host) KMX_HIPCP(hipMemcpyAsync(stats_host, stats, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KMX_HIPRT(hipStreamSynchronize(st));
+    return 0;
+  }
+};
 
-// The per-call buffers of a query batch (sized for one chunk of at most Qc queries, reused by every chunk) and the
-// preparation of a chunk, shared by query() and the radius calls: upload and half widening, the queries' clusters,
-// the CSR of the chunk, the cluster-sorted rows with their norms and member distances, the f16 split and the block plan.
 // The probe side of a chunk: raw = the chunk's n x pw lists in query order (the caller's slice, or the
 // ranking's), lists = what the PROBE kernels read, per sorted query position (launch_knn_probe_lists)
 struct ProbeSide {
@@ -201,62 +282,28 @@ struct ProbeSide {
   uint32_t *raw = nullptr, *lists = nullptr;
 };
 
-struct QueryChunk {
-  DeviceArena w;   // owns the buffers; enqueues on the index's stream (nothing to release)
-  KnnScratch scratch;   // the sort scratch (w's) and the optional buffers of knn_search
-  uint32_t Qc = 0;
-  float *qrows = nullptr, *qxs = nullptr, *qn2p = nullptr, *qn2c = nullptr, *qmydist = nullptr, *qrdist = nullptr,
-        *qmux = nullptr, *qkbias = nullptr;
-  uint16_t *qhalf = nullptr, *qxs16 = nullptr;
-  uint32_t *qassign = nullptr, *qprev = nullptr, *qeff = nullptr, *qinv = nullptr, *qoffsets = nullptr,
-           *qstats = nullptr, *blocks = nullptr;
-  std::unique_ptr<Engine> eng;
-  std::vector<uint32_t> offs, plan;
+// A chunk of queries, shared by query(), query_probe() and the radius calls: the queries' clusters, the sorted chunk
+// and the block plan of its search.
+struct QueryChunk : SortedChunk {
+  uint32_t *qeff = nullptr, *blocks = nullptr;
+  std::unique_ptr<Engine> eng;   // (a member of the derived type: it goes before the arena whose stream it uses)
+  std::vector<uint32_t> plan;
   // what prepare() found out about the chunk
   KnnPath cp;
   uint32_t assigned = 0;   // sorted positions >= assigned: queries without a cluster (NaN / inf features)
 
-  int init(const KnnIndex &ix, uint32_t Qc_, bool assign) {
+  int init(const KnnIndex &ix, uint32_t Qc, bool assign) {
     const KnnShard &s = ix.s;
-    const uint32_t D = s.D, DP = s.DP, K = s.K;
-    Qc = Qc_;
-    w.dev = s.dev;
-    w.stream = nullptr;
-    KNN_TRY(w.alloc(&qrows, (size_t)Qc * D));
-    if (ix.fp16) KNN_TRY(w.alloc(&qhalf, (size_t)Qc * D));
-    KNN_TRY(w.alloc(&qassign, Qc));
-    KNN_TRY(w.alloc(&qprev, Qc));
-    KNN_TRY(w.alloc(&qeff, Qc));
-    KNN_TRY(w.alloc(&qinv, Qc));
-    KNN_TRY(w.alloc(&qoffsets, (size_t)K + 2));
-    KNN_TRY(w.alloc(&scratch.keys_tmp, Qc));
-    KNN_TRY(w.alloc(&scratch.vals_tmp, Qc));
-    KNN_TRY(w.alloc(&scratch.keys_sorted, Qc));
-    KNN_TRY(w.alloc(&qstats, 4));
-    KNN_TRY(w.alloc(&qxs, (size_t)Qc * DP));
-    KNN_TRY(w.alloc(&qn2p, Qc));
-    KNN_TRY(w.alloc(&qmydist, Qc));
-    KNN_TRY(w.alloc(&qrdist, Qc));
-    if (ix.path.use_f16) {
-      KNN_TRY(w.alloc(&qxs16, ((size_t)Qc + KNN16_PAD_ROWS) * DP));
-      KNN_TRY(w.alloc(&qn2c, Qc));
-      KNN_TRY(w.alloc(&qmux, Qc));
-      KNN_TRY(w.alloc(&qkbias, (size_t)Qc + KNN16_PAD_ROWS));
-    }
-    const size_t max_blocks = (size_t)Qc / 32 + K + 1;   // (every plan packs >= 32 queries per block but one per cluster)
-    KNN_TRY(w.alloc(&blocks, 2 * max_blocks));
     // radix sorts: the CSR of the chunk (keys <= K) and the query order (keys of up to 32 bits)
-    scratch.rows = Qc;
-    scratch.sort_bytes = sort_temp_bytes(Qc, 0xFFFFFFFFu);
-    char *sort_temp = nullptr;
-    KNN_TRY(w.alloc(&sort_temp, scratch.sort_bytes + 16));
-    scratch.sort_temp = sort_temp;
+    KNN_TRY(SortedChunk::init(ix, Qc, 0xFFFFFFFFu, true));
+    KNN_TRY(w.alloc(&qeff, Qc));
+    const size_t max_blocks = (size_t)Qc / 32 + s.K + 1;   // (every plan packs >= 32 queries per block but one per cluster)
+    KNN_TRY(w.alloc(&blocks, 2 * max_blocks));
     // the queries' clusters: the engine's assignment pass (kmamd_lloyd_assign; D > 256 through lloyd_wide), on fp32 rows
     if (assign) {
       eng.reset(new Engine());
-      KNN_TRY(eng->init(s.dev, Qc, D, K, s.metric, 0, s.stream));
+      KNN_TRY(eng->init(s.dev, Qc, s.D, s.K, s.metric, 0, s.stream));
     }
-    offs.resize((size_t)K + 1);
     return 0;
   }
 
@@ -265,10 +312,9 @@ struct QueryChunk {
   int prepare(const KnnIndex &ix, uint32_t q0, uint32_t n, const void *queries, const uint32_t *qassign_in,
               uint32_t *qassign_out, bool host, ProbeSide *pr = nullptr) {
     const KnnShard &s = ix.s;
-    const uint32_t D = s.D, DP = s.DP, K = s.K;
+    const uint32_t D = s.D, K = s.K;
     const hipStream_t st = s.stream;
-    // ---- the chunk's rows, fp32 on this device ----
-    KNN_TRY(upload_rows(ix.fp16, queries, q0, n, D, host, qhalf, qrows, st));
+    KNN_TRY(upload(ix, queries, q0, n, host));
     // ---- their clusters ----
     if (pr) {
       const size_t cnt = (size_t)n * pr->pw;
@@ -278,46 +324,42 @@ struct QueryChunk {
       else if (K == 1)   // (the ranking kernels need two centroids: P = {0})
         KMX_HIPRT(hipMemsetAsync(pr->raw, 0, cnt * sizeof(uint32_t), st));
       else
-        KNN_TRY(pr->ranker.rank(qrows, n, pr->pw, pr->raw, pr->rank_exact, st));
+        KNN_TRY(pr->ranker.rank(rows, n, pr->pw, pr->raw, pr->rank_exact, st));
       if (pr->probes_out)
         KMX_HIPCP(hipMemcpyAsync(pr->probes_out + (size_t)q0 * pr->pw, pr->raw, cnt * sizeof(uint32_t),
                                  host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
-      KMX_HIPRT(launch_knn_probe_column0(pr->raw, pr->pw, n, qassign, st));
+      KMX_HIPRT(launch_knn_probe_column0(pr->raw, pr->pw, n, asg, st));
     } else if (qassign_in) {
-      KMX_HIPCP(hipMemcpyAsync(qassign, qassign_in + q0, (size_t)n * sizeof(uint32_t),
+      KMX_HIPCP(hipMemcpyAsync(asg, qassign_in + q0, (size_t)n * sizeof(uint32_t),
                                host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
     } else {
-      // (rows [n, Qc) of a shorter chunk hold an earlier chunk's rows, or radius()'s zeros: assigned and ignored)
-      KMX_HIPRT(hipMemsetAsync(qassign, 0, (size_t)Qc * sizeof(uint32_t), st));
-      KNN_TRY(eng->lloyd_assign(qrows, s.centroids, qassign, qprev, false));
+      // (rows [n, cap) of a shorter chunk hold an earlier chunk's rows, or radius()'s zeros: assigned and ignored)
+      KMX_HIPRT(hipMemsetAsync(asg, 0, (size_t)cap * sizeof(uint32_t), st));
+      KNN_TRY(eng->lloyd_assign(rows, s.centroids, asg, prev, false));
     }
     if (qassign_out)
-      KMX_HIPCP(hipMemcpyAsync(qassign_out + q0, qassign, (size_t)n * sizeof(uint32_t),
+      KMX_HIPCP(hipMemcpyAsync(qassign_out + q0, asg, (size_t)n * sizeof(uint32_t),
                                host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     // ---- the chunk in cluster-sorted order: rows, norms, distances to the own centroid ----
-    KMX_HIPRT(hipMemsetAsync(qstats, 0, 4 * sizeof(uint32_t), st));
-    KMX_HIPRT(launch_knn_query_clusters(qrows, n, D, qassign, K, s.centroids, qeff, qstats + 2, st));
-    KMX_HIPRT(launch_inverse_assignments(qeff, n, K, scratch.keys_tmp, scratch.vals_tmp, scratch.keys_sorted, qinv, qoffsets, scratch.sort_temp,
-                                         scratch.sort_bytes, st));
-    if (pr) KMX_HIPRT(launch_knn_probe_lists(pr->raw, pr->pw, n, qinv, K, pr->lists, qstats + 2, st));
-    // (with mu: the queries raise the half-range flag qstats[1] as the corpus rows do)
-    KNN_TRY(sorted_rows(ix, qrows, n, qinv, qoffsets, qxs, qn2p, qstats, qmydist, qrdist));
+    KMX_HIPRT(hipMemsetAsync(stats, 0, 4 * sizeof(uint32_t), st));
+    KMX_HIPRT(launch_knn_query_clusters(rows, n, D, asg, K, s.centroids, qeff, stats + 3, st));
+    KNN_TRY(sort(ix, qeff, n));
+    if (pr) KMX_HIPRT(launch_knn_probe_lists(pr->raw, pr->pw, n, b.inv, K, pr->lists, stats + 3, st));
+    KNN_TRY(gather(ix, n));
     uint32_t flags[4] = {0, 0, 0, 0};
-    KMX_HIPCP(hipMemcpyAsync(offs.data(), qoffsets, (K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    KMX_HIPCP(hipMemcpyAsync(flags, qstats, sizeof(flags), hipMemcpyDeviceToHost, st));
-    KMX_HIPRT(hipStreamSynchronize(st));
+    KNN_TRY(fetch(ix, flags));
     // a caller-supplied cluster id >= K or with a non-finite centroid, or an entry > K in a caller's probe list (a row
     // the ranking fills with K has no cluster: no error)
-    if (flags[2] && !(pr && !pr->probes_in)) return kmcudaInvalidArguments;
+    if (flags[3] && !(pr && !pr->probes_in)) return kmcudaInvalidArguments;
     // which search this chunk takes: a query that leaves the half range sends it from the f16 filter to the f32 one
     // (D <= 256) or to the exact search, as a corpus row sends knn_cuda()
     cp = ix.path;
     if (knn_leaves_half_range(&cp.use_f16, &cp.dp_filter, D, flags[1]) && ix.verbosity > 0)
       printf("k-NN query: a centred query leaves the half range, %s\n",
              cp.dp_filter && !pr ? "the f32 matrix-core filter" : "the exact search");
-    if (cp.use_f16) KMX_HIPRT(launch_knn_split(s.metric, qxs, n, D, DP, s.mu, qxs16, qn2c, qmux, qkbias, qstats + 3, st));
+    if (cp.use_f16) KNN_TRY(split(ix, n));
     assigned = offs[K];
-    knn_block_plan(offs.data(), K, knn_qpb(cp.use_f16, DP), &plan);
+    knn_block_plan(offs.data(), K, knn_qpb(cp.use_f16, s.DP), &plan);
     if (!plan.empty())
       KMX_HIPCP(hipMemcpyAsync(blocks, plan.data(), plan.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     return 0;
@@ -327,7 +369,7 @@ struct QueryChunk {
   void fill_args(KnnArgs *a) const {
     a->blocks = blocks;
     a->p_base = 0;
-    a->qxs = qxs; a->qn2s = cp.use_f16 ? qn2c : qn2p; a->qmux = qmux; a->qmydist = qmydist; a->qxs16 = qxs16; a->qoffsets = qoffsets;
+    a->qxs = b.xs; a->qn2s = cp.use_f16 ? b.n2c : b.n2s; a->qmux = b.mux; a->qmydist = b.mydist; a->qxs16 = b.xs16; a->qoffsets = offsets;
   }
 };
 
@@ -365,70 +407,28 @@ struct AddTimer : StageEvents<5> {   // (2 -> 3: the host's wait and allocations
   }
 };
 
-// The buffers of one chunk of an add (at most Cn rows, reused by every chunk) and its preparation: what
-// knn_prepare_corpus makes of a corpus's rows, by the same launches, with the index's centroids, mu and path.
-struct AddChunk {
-  DeviceArena w;   // owns the buffers; enqueues on the index's stream (nothing to release)
-  KnnScratch scratch;
-  uint32_t Cn = 0;
-  float *rows = nullptr, *rdist = nullptr;
-  uint16_t *half = nullptr;
-  uint32_t *asg = nullptr, *prev = nullptr, *boffs = nullptr, *bstats = nullptr;
-  KnnSortedRows b{};   // the chunk in cluster-sorted order (inv: sorted position -> row of the chunk)
-  EngineSlot slot;     // (after `w`: the engine goes first)
-  std::vector<uint32_t> offs;   // boffs on the host (K + 1)
+// A chunk of an add: what knn_prepare_corpus makes of a corpus's rows, by the same launches, with the index's
+// centroids, mu and path.
+struct AddChunk : SortedChunk {
+  EngineSlot slot;   // (a member of the derived type: the engine goes before the arena whose stream it uses)
 
-  int init(const KnnIndex &ix, uint32_t Cn_, bool assign) {
-    const KnnShard &s = ix.s;
-    const uint32_t D = s.D, DP = s.DP, K = s.K;
-    Cn = Cn_;
-    w.dev = s.dev;
-    w.stream = nullptr;
-    KNN_TRY(w.alloc(&rows, (size_t)Cn * D));
-    if (ix.fp16) KNN_TRY(w.alloc(&half, (size_t)Cn * D));
-    KNN_TRY(w.alloc(&asg, Cn));
-    if (assign) KNN_TRY(w.alloc(&prev, Cn));
-    KNN_TRY(w.alloc(&b.inv, Cn));
-    KNN_TRY(w.alloc(&boffs, (size_t)K + 2));
-    KNN_TRY(w.alloc(&scratch.keys_tmp, Cn));
-    KNN_TRY(w.alloc(&scratch.vals_tmp, Cn));
-    KNN_TRY(w.alloc(&scratch.keys_sorted, Cn));
-    KNN_TRY(w.alloc(&bstats, 4));
-    KNN_TRY(w.alloc(&b.xs, (size_t)Cn * DP));
-    KNN_TRY(w.alloc(&b.n2s, Cn));
-    KNN_TRY(w.alloc(&b.mydist, Cn));
-    KNN_TRY(w.alloc(&rdist, Cn));
-    if (ix.path.use_f16) {
-      KNN_TRY(w.alloc(&b.xs16, ((size_t)Cn + KNN16_PAD_ROWS) * DP));
-      KNN_TRY(w.alloc(&b.n2c, Cn));
-      KNN_TRY(w.alloc(&b.mux, Cn));
-      KNN_TRY(w.alloc(&b.kbias, (size_t)Cn + KNN16_PAD_ROWS));
-    }
-    scratch.rows = Cn;
-    scratch.sort_bytes = sort_temp_bytes(Cn, K);
-    char *sort_temp = nullptr;
-    KNN_TRY(w.alloc(&sort_temp, scratch.sort_bytes + 16));
-    scratch.sort_temp = sort_temp;
-    offs.resize((size_t)K + 1);
-    return 0;
-  }
+  int init(const KnnIndex &ix, uint32_t Cn, bool assign) { return SortedChunk::init(ix, Cn, ix.s.K, assign); }
 
-  // rows [r0, r0 + n) of the batch; waits for the stream once (the chunk's offsets reach the host).  bstats: [0] the
-  // largest plain norm, [1] the half-range flag, [2] the largest centred norm
+  // rows [r0, r0 + n) of the batch; waits for the stream once (the chunk's offsets reach the host)
   int prepare(const KnnIndex &ix, uint32_t r0, uint32_t n, const void *src, const uint32_t *assign_in,
               uint32_t *assign_out, bool host, const AddTimer &tm) {
     const KnnShard &s = ix.s;
-    const uint32_t D = s.D, DP = s.DP, K = s.K;
+    const uint32_t D = s.D, K = s.K;
     const hipStream_t st = s.stream;
-    const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     tm.mark(0, st);
-    KNN_TRY(upload_rows(ix.fp16, src, r0, n, D, host, half, rows, st));
+    KNN_TRY(upload(ix, src, r0, n, host));
     // ---- their clusters: the caller's (>= K: none, as create takes them), or kmamd_kmeans_assign's ----
     if (assign_in) {
-      KMX_HIPCP(hipMemcpyAsync(asg, assign_in + r0, (size_t)n * sizeof(uint32_t), in, st));
+      KMX_HIPCP(hipMemcpyAsync(asg, assign_in + r0, (size_t)n * sizeof(uint32_t),
+                               host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
     } else if (K == 1) {   // (the engine needs two centroids: a row of finite features has cluster 0)
       KMX_HIPRT(hipMemsetAsync(prev, 0, (size_t)n * sizeof(uint32_t), st));
-      KMX_HIPRT(launch_knn_query_clusters(rows, n, D, prev, K, s.centroids, asg, bstats + 3, st));
+      KMX_HIPRT(launch_knn_query_clusters(rows, n, D, prev, K, s.centroids, asg, stats + 3, st));
     } else {
       // assignments <- K ("no cluster"), then one pass of an engine sized for the chunk (assign_job.cpp)
       Engine *eng = nullptr;
@@ -441,15 +441,11 @@ struct AddChunk {
                                host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     tm.mark(1, st);
     // ---- the chunk in cluster-sorted order, with everything an index keeps per row ----
-    KMX_HIPRT(launch_inverse_assignments(asg, n, K, scratch.keys_tmp, scratch.vals_tmp, scratch.keys_sorted, b.inv, boffs,
-                                         scratch.sort_temp, scratch.sort_bytes, st));
-    KNN_TRY(sorted_rows(ix, rows, n, b.inv, boffs, b.xs, b.n2s, bstats, b.mydist, rdist));
-    if (ix.path.use_f16)
-      KMX_HIPRT(launch_knn_split(s.metric, b.xs, n, D, DP, s.mu, b.xs16, b.n2c, b.mux, b.kbias, bstats + 2, st));
+    KNN_TRY(sort(ix, asg, n));
+    KNN_TRY(gather(ix, n));
+    if (ix.path.use_f16) KNN_TRY(split(ix, n));
     tm.mark(2, st);
-    KMX_HIPCP(hipMemcpyAsync(offs.data(), boffs, ((size_t)K + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    KMX_HIPRT(hipStreamSynchronize(st));
-    return 0;
+    return fetch(ix, nullptr);
   }
 };
 
@@ -465,63 +461,82 @@ int report_stats(const KnnIndex &ix, const char *what) {
   return 0;
 }
 
-// One query batch, in chunks of at most `chunk` queries; every buffer is sized for one chunk and reused.
+// The top-k lists of a query batch on their way to the caller: the search's buffers for one chunk of at most Qc queries
+// (heaps, and out / outd in sorted-position order) and, for a caller on the host, the chunk in query order
+struct TopkResult {
+  uint32_t k = 0;
+  bool host = false;
+  float *heaps = nullptr, *outd = nullptr, *dist_dev = nullptr;
+  uint32_t *out = nullptr, *nb_dev = nullptr;
+
+  int init(DeviceArena &w, uint32_t Qc, uint32_t k_, bool host_, bool want_distances) {
+    k = k_; host = host_;
+    KNN_TRY(w.alloc(&heaps, (size_t)Qc * 2 * k));
+    KNN_TRY(w.alloc(&out, (size_t)Qc * k));
+    KNN_TRY(w.alloc(&outd, (size_t)Qc * k));
+    if (host) {
+      KNN_TRY(w.alloc(&nb_dev, (size_t)Qc * k));
+      if (want_distances) KNN_TRY(w.alloc(&dist_dev, (size_t)Qc * k));
+    }
+    return 0;
+  }
+  // unassigned queries: indices 0xFFFFFFFF, distances NaN (the filters leave their slots alone)
+  int clear(uint32_t n, hipStream_t st) {
+    KMX_HIPRT(hipMemsetAsync(out, 0xFF, (size_t)n * k * sizeof(uint32_t), st));
+    KMX_HIPRT(hipMemsetAsync(outd, 0xFF, (size_t)n * k * sizeof(float), st));
+    return 0;
+  }
+  void fill_args(KnnArgs *a) const { a->k = k; a->heaps = heaps; a->out = out; a->outd = outd; }
+  // the chunk of n queries from q0 on, back in query order (qinv: sorted position -> query) and to the caller.  (The
+  // next chunk overwrites these buffers: the stream orders it behind this one's scatter and copies.)
+  int deliver(uint32_t q0, uint32_t n, const uint32_t *qinv, uint32_t *neighbors, float *distances, hipStream_t st) {
+    const size_t at = (size_t)q0 * k, count = (size_t)n * k;
+    KMX_HIPRT(launch_knn_scatter(out, qinv, 0, n, k, host ? nb_dev : neighbors + at, st));
+    if (distances)
+      KMX_HIPRT(launch_knn_scatter(reinterpret_cast<const uint32_t *>(outd), qinv, 0, n, k,
+                                   reinterpret_cast<uint32_t *>(host ? dist_dev : distances + at), st));
+    if (host) {
+      KMX_HIPCP(hipMemcpyAsync(neighbors + at, nb_dev, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      if (distances) KMX_HIPCP(hipMemcpyAsync(distances + at, dist_dev, count * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    return 0;
+  }
+};
+
+// the last wait of a query call (`what`: its name)
+int finish_query(const KnnIndex &ix, const char *what) {
+  if (hipStreamSynchronize(ix.s.stream) == hipSuccess) return 0;
+  if (ix.verbosity > 0) printf("k-NN %s failed: %s\n", what, hipGetErrorString(hipGetLastError()));
+  return kmcudaRuntimeError;
+}
+
+// One query batch, in chunks of at most Qc queries; every buffer is sized for one chunk and reused.
 int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
                     float *distances, uint32_t *qassign_out, int32_t device_ptrs) {
   if (Q == 0) return 0;
   if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
-  const uint32_t K = s.K;
   const hipStream_t st = s.stream;
   const KnnSwitches sw = knn_switches();
-  size_t chunk = kQueryChunkBytes / (4 * ((size_t)K + 2 * (size_t)k));
-  if (sw.query_chunk) chunk = sw.query_chunk;   // test hook: queries per chunk
-  if (chunk < 1) chunk = 1;
-  const uint32_t Qc = (uint32_t)(chunk < Q ? chunk : Q);
+  const uint32_t Qc = knn_chunk_rows(kQueryChunkBytes, 4 * ((size_t)s.K + 2 * (size_t)k), sw.query_chunk, Q);
   const bool host = device_ptrs < 0;
 
   // per-call buffers (freed with `c`), among them the sort scratch and the optional buffers of knn_search
   QueryChunk c;
   KNN_TRY(c.init(*this, Qc, !qassign_in));
-  DeviceArena &w = c.w;
-  float *heaps = nullptr, *outd = nullptr, *dist_dev = nullptr;
-  uint32_t *out = nullptr, *nb_dev = nullptr;
-  KNN_TRY(w.alloc(&heaps, (size_t)Qc * 2 * k));
-  KNN_TRY(w.alloc(&out, (size_t)Qc * k));
-  KNN_TRY(w.alloc(&outd, (size_t)Qc * k));
-  if (host) {
-    KNN_TRY(w.alloc(&nb_dev, (size_t)Qc * k));
-    if (distances) KNN_TRY(w.alloc(&dist_dev, (size_t)Qc * k));
-  }
+  TopkResult res;
+  KNN_TRY(res.init(c.w, Qc, k, host, distances != nullptr));
   for (uint32_t q0 = 0; q0 < Q; q0 += Qc) {
     const uint32_t n = Q - q0 < Qc ? Q - q0 : Qc;
     KNN_TRY(c.prepare(*this, q0, n, queries, qassign_in, qassign_out, host));
-    // unassigned queries: indices 0xFFFFFFFF, distances NaN (the filters leave their slots alone)
-    KMX_HIPRT(hipMemsetAsync(out, 0xFF, (size_t)n * k * sizeof(uint32_t), st));
-    KMX_HIPRT(hipMemsetAsync(outd, 0xFF, (size_t)n * k * sizeof(float), st));
+    KNN_TRY(res.clear(n, st));
     KnnArgs a;
     c.fill_args(&a);
-    a.k = k; a.heaps = heaps; a.out = out; a.outd = outd;
+    res.fill_args(&a);
     a.p_end = c.cp.dp_filter ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
     KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity));
-    // ---- back in query order ----
-    uint32_t *nb = host ? nb_dev : neighbors + (size_t)q0 * k;
-    KMX_HIPRT(launch_knn_scatter(out, c.qinv, 0, n, k, nb, st));
-    if (distances) {
-      float *dd = host ? dist_dev : distances + (size_t)q0 * k;
-      KMX_HIPRT(launch_knn_scatter(reinterpret_cast<const uint32_t *>(outd), c.qinv, 0, n, k, reinterpret_cast<uint32_t *>(dd), st));
-    }
-    if (host) {
-      KMX_HIPCP(hipMemcpyAsync(neighbors + (size_t)q0 * k, nb_dev, (size_t)n * k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      if (distances)
-        KMX_HIPCP(hipMemcpyAsync(distances + (size_t)q0 * k, dist_dev, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, st));
-    }
-    // (the next chunk overwrites these buffers: the stream orders it behind this one's scatter and copies)
+    KNN_TRY(res.deliver(q0, n, c.b.inv, neighbors, distances, st));
   }
-  if (hipStreamSynchronize(st) != hipSuccess) {
-    if (verbosity > 0) printf("k-NN query failed: %s\n", hipGetErrorString(hipGetLastError()));
-    return kmcudaRuntimeError;
-  }
-  return 0;
+  return finish_query(*this, "query");
 }
 
 // One probed query batch: query() with the cluster loop driven by every query's probe list.
@@ -533,10 +548,7 @@ int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queri
   const hipStream_t st = s.stream;
   const KnnSwitches sw = knn_switches();
   // (no lb table here: the heaps and the lists of a chunk within the budget)
-  size_t chunk = kQueryChunkBytes / (4 * ((size_t)pw + 2 * (size_t)k));
-  if (sw.query_chunk) chunk = sw.query_chunk;
-  if (chunk < 1) chunk = 1;
-  const uint32_t Qc = (uint32_t)(chunk < Q ? chunk : Q);
+  const uint32_t Qc = knn_chunk_rows(kQueryChunkBytes, 4 * ((size_t)pw + 2 * (size_t)k), sw.query_chunk, Q);
   const bool host = device_ptrs < 0;
 
   QueryChunk c;
@@ -555,15 +567,8 @@ int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queri
     pr.rank_exact = assign_top_exact_only();
     KNN_TRY(pr.ranker.reserve(w, Qc));
   }
-  float *heaps = nullptr, *outd = nullptr, *dist_dev = nullptr;
-  uint32_t *out = nullptr, *nb_dev = nullptr;
-  KNN_TRY(w.alloc(&heaps, (size_t)Qc * 2 * k));
-  KNN_TRY(w.alloc(&out, (size_t)Qc * k));
-  KNN_TRY(w.alloc(&outd, (size_t)Qc * k));
-  if (host) {
-    KNN_TRY(w.alloc(&nb_dev, (size_t)Qc * k));
-    if (distances) KNN_TRY(w.alloc(&dist_dev, (size_t)Qc * k));
-  }
+  TopkResult res;
+  KNN_TRY(res.init(w, Qc, k, host, distances != nullptr));
   if (sw.stats) KMX_HIPRT(hipMemsetAsync(s.calced, 0, KNN_STATS * sizeof(unsigned long long), st));
   bool said = said_exact || verbosity <= 0;
   for (uint32_t q0 = 0; q0 < Q; q0 += Qc) {
@@ -577,32 +582,16 @@ int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queri
       printf("k-NN probe query: every candidate is evaluated with the exact arithmetic (no f32-filtered probe search)\n");
       said = true;
     }
-    KMX_HIPRT(hipMemsetAsync(out, 0xFF, (size_t)n * k * sizeof(uint32_t), st));
-    KMX_HIPRT(hipMemsetAsync(outd, 0xFF, (size_t)n * k * sizeof(float), st));
+    KNN_TRY(res.clear(n, st));
     KnnArgs a;
     c.fill_args(&a);
-    a.k = k; a.heaps = heaps; a.out = out; a.outd = outd;
+    res.fill_args(&a);
     a.p_end = c.cp.use_f16 ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
     a.plist = pr.lists; a.pw = pw;
-    KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity, pr.raw, c.qinv));
-    // ---- back in query order ----
-    uint32_t *nb = host ? nb_dev : neighbors + (size_t)q0 * k;
-    KMX_HIPRT(launch_knn_scatter(out, c.qinv, 0, n, k, nb, st));
-    if (distances) {
-      float *dd = host ? dist_dev : distances + (size_t)q0 * k;
-      KMX_HIPRT(launch_knn_scatter(reinterpret_cast<const uint32_t *>(outd), c.qinv, 0, n, k, reinterpret_cast<uint32_t *>(dd), st));
-    }
-    if (host) {
-      KMX_HIPCP(hipMemcpyAsync(neighbors + (size_t)q0 * k, nb_dev, (size_t)n * k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      if (distances)
-        KMX_HIPCP(hipMemcpyAsync(distances + (size_t)q0 * k, dist_dev, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, st));
-    }
-    // (the next chunk overwrites these buffers: the stream orders it behind this one's scatter and copies)
+    KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity, pr.raw, c.b.inv));
+    KNN_TRY(res.deliver(q0, n, c.b.inv, neighbors, distances, st));
   }
-  if (hipStreamSynchronize(st) != hipSuccess) {
-    if (verbosity > 0) printf("k-NN probe query failed: %s\n", hipGetErrorString(hipGetLastError()));
-    return kmcudaRuntimeError;
-  }
+  KNN_TRY(finish_query(*this, "probe query"));
   if (sw.stats) KNN_TRY(report_stats(*this, "probe query"));
   return 0;
 }
@@ -618,10 +607,7 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
   const hipStream_t st = s.stream;
   const KnnSwitches sw = knn_switches();
   const bool host = device_ptrs < 0;
-  size_t chunk = kQueryChunkBytes / (4 * (size_t)K);
-  if (sw.query_chunk) chunk = sw.query_chunk;
-  if (chunk < 1) chunk = 1;
-  const uint32_t Qc = (uint32_t)(chunk < Q ? chunk : Q);
+  const uint32_t Qc = knn_chunk_rows(kQueryChunkBytes, 4 * (size_t)K, sw.query_chunk, Q);
 
   DeviceArena own;   // this call's own device buffers (nothing to release: the index's stream)
   own.dev = s.dev;
@@ -663,7 +649,7 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
   QueryChunk c;
   KNN_TRY(c.init(*this, Qc, !qassign_in));
   // (a fill's first chunk may be shorter than Qc, and the assignment pass reads Qc rows: defined values for them)
-  if (fill && host && !qassign_in) KMX_HIPRT(hipMemsetAsync(c.qrows, 0, (size_t)Qc * D * sizeof(float), st));
+  if (fill && host && !qassign_in) KMX_HIPRT(hipMemsetAsync(c.rows, 0, (size_t)Qc * D * sizeof(float), st));
   // the cluster prune: the lb table (L2, D <= 1024, rows the bounds kernel can read four features at a time), else
   // the triangle test with a margin for the rounding of its computed terms; the half2 arithmetic's
   // distances carry half-precision errors no such margin covers: nothing is pruned there
@@ -723,21 +709,21 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
     a.calced = s.calced;
     a.xs16 = s.xs16; a.mux = s.mux; a.kbias = s.kbias; a.mu2 = s.mu2;
     if (use_lb && c.assigned) {
-      KMX_HIPRT(launch_knn_centroid_bounds(c.qxs, D, DP, 0, c.assigned, s.centroids, K, s.R, c.scratch.lb, c.assigned, st));
+      KMX_HIPRT(launch_knn_centroid_bounds(c.b.xs, D, DP, 0, c.assigned, s.centroids, K, s.R, c.scratch.lb, c.assigned, st));
       a.lb = c.scratch.lb;
       a.lb_stride = c.assigned;
       // queries that want the same clusters into the same waves, as knn_search orders them
       if (f16 && c.scratch.qperm) {
         KnnScratch &x = c.scratch;
-        if (launch_knn_query_order(x.lb, c.assigned, c.qoffsets, K, 0, c.assigned, x.keys_tmp, x.vals_tmp, x.keys_sorted,
-                                   x.qperm, x.sort_temp, x.sort_bytes, st, sw.order, c.qmydist, s.R))
+        if (launch_knn_query_order(x.lb, c.assigned, c.offsets, K, 0, c.assigned, x.keys_tmp, x.vals_tmp, x.keys_sorted,
+                                   x.qperm, x.sort_temp, x.sort_bytes, st, sw.order, c.b.mydist, s.R))
           a.qperm = x.qperm;
         else
           (void)hipGetLastError();
       }
     }
     ra.radius = r; ra.prune_abs = prune_abs; ra.prune_rel = prune_rel;
-    ra.qinv = c.qinv;
+    ra.qinv = c.b.inv;
     ra.counts = host ? counts_dev : (counts ? counts + q0 : nullptr);
     ra.offsets = nullptr; ra.out_base = 0; ra.neighbors = nullptr; ra.distances = nullptr; ra.flag = flag;
     if (fill) {
@@ -779,97 +765,6 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
   return raised ? kmcudaInvalidArguments : 0;   // a query's hit count differs from its range
 }
 
-// One merge (knn_merge.hip): `cur` and the prepared chunk into the buffers of `next`, whose host offsets are made.
-int KnnIndex::merge(const IndexState &cur, const AddChunk &c, uint32_t n, IndexState *next) {
-  const uint32_t DP = s.DP, K = s.K;
-  const hipStream_t st = s.stream;
-  const bool f16 = path.use_f16;
-  KMX_HIPCP(hipMemcpyAsync(next->offsets, next->off_host.data(), ((size_t)K + 2) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  KMX_HIPRT(hipMemsetAsync(next->stats, 0, 4 * sizeof(uint32_t), st));
-  KnnMergeArgs a;
-  a.old_rows = cur.rows; a.chunk = c.b; a.out = next->rows;
-  a.off_old = cur.offsets; a.boffs = c.boffs; a.off_new = next->offsets;
-  a.N_old = cur.N; a.n = n; a.K = K; a.DP = DP;
-  KMX_HIPRT(launch_knn_merge_rows(a, st));
-  if (f16) {   // the filter's tile DMA reads whole tiles: zeros past the last row, as launch_knn_split leaves them
-    KMX_HIPRT(hipMemsetAsync(next->rows.xs16 + (size_t)next->N * DP, 0, (size_t)KNN16_PAD_ROWS * DP * sizeof(uint16_t), st));
-    KMX_HIPRT(hipMemsetAsync(next->rows.kbias + next->N, 0, (size_t)KNN16_PAD_ROWS * sizeof(float), st));
-    KMX_HIPRT(hipMemsetAsync(next->stats_c, 0, 4 * sizeof(uint32_t), st));
-  }
-  KMX_HIPRT(launch_knn_merge_radii(cur.R, c.rdist, c.boffs, K, next->R, cur.stats, f16 ? cur.stats_c : nullptr, c.bstats,
-                                   next->stats, f16 ? next->stats_c : nullptr, st));
-  return 0;
-}
-
-// n_rows more rows (DESIGN.md 4.15), in chunks of one merge each.  Every merge writes a whole new state; the index's
-// own buffers are read only, and replaced once the last chunk has been enqueued and the stream has drained without error.
-int KnnIndex::add(uint32_t n_rows, const void *rows, const uint32_t *assign_in, uint32_t *assign_out, int32_t device_ptrs) {
-  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
-  const hipStream_t st = s.stream;
-  const bool host = device_ptrs < 0, f16 = path.use_f16;
-  const uint32_t Cn = knn_add_chunk_rows(n_rows, s.D, s.DP, kQueryChunkBytes, knn_switches().add_chunk);
-  IndexState cur = state();   // the index's own until the first merge, then this call's
-  bool mine = false;
-  int rc = 0;
-  {
-    AddTimer tm;
-    tm.start(knn_switches().add_time);
-    AddChunk c;
-    rc = c.init(*this, Cn, !assign_in);
-    for (uint32_t r0 = 0; rc == 0 && r0 < n_rows; r0 += Cn) {
-      const uint32_t n = n_rows - r0 < Cn ? n_rows - r0 : Cn;
-      IndexState next;
-      if (r0 != 0 && tm.on && hipStreamSynchronize(st) == hipSuccess) tm.fold();   // (the chunk before: its events are reused)
-      rc = c.prepare(*this, r0, n, rows, assign_in, assign_out, host, tm);
-      if (rc == 0) rc = alloc_state(&next, cur.N + n, f16);
-      if (rc == 0 && !knn_merge_offsets(cur.off_host, c.offs.data(), s.K, n, &next.off_host)) rc = kmcudaRuntimeError;
-      tm.mark(3, st);
-      if (rc == 0) rc = merge(cur, c, n, &next);
-      tm.mark(4, st);
-      // (read and written once: the fp32 rows, the halves and six words per row)
-      tm.merged_bytes += 2ull * ((unsigned long long)cur.N + n) * ((f16 ? 6ull : 4ull) * s.DP + (f16 ? 24ull : 12ull));
-      if (rc == 0 && mine && hipStreamSynchronize(st) != hipSuccess) rc = kmcudaRuntimeError;   // (the merge reads `cur`)
-      if (rc != 0) {
-        (void)hipStreamSynchronize(st);
-        release_state(next);
-        break;
-      }
-      if (mine) release_state(cur);
-      cur = std::move(next);
-      mine = true;
-    }
-    // the half-range flag, once per add (create waits for it too); the chunk's buffers go behind this wait
-    uint32_t flag = 0;
-    if (rc == 0 && f16 && hipMemcpyAsync(&flag, cur.stats + 1, sizeof(flag), hipMemcpyDeviceToHost, st) != hipSuccess)
-      rc = kmcudaMemoryCopyError;
-    if (hipStreamSynchronize(st) != hipSuccess && rc == 0) rc = kmcudaRuntimeError;
-    if (rc != 0) {
-      if (verbosity > 0) printf("k-NN index add failed: %s\n", hipGetErrorString(hipGetLastError()));
-      if (mine) release_state(cur);
-      return rc;
-    }
-    if (tm.on) {
-      tm.fold();
-      printf("k-NN index add: %u rows in chunks of %u: clusters %.3f ms, preparation %.3f ms, merge %.3f ms (%.3f GB moved, "
-             "%.3f TB/s)\n", n_rows, Cn, tm.ms[0], tm.ms[1], tm.ms[2], 1e-9 * (double)tm.merged_bytes,
-             tm.ms[2] > 0.f ? 1e-9 * (double)tm.merged_bytes / (double)tm.ms[2] : 0.0);
-      fflush(stdout);
-    }
-    IndexState old = state();
-    adopt(cur);
-    release_state(old);
-    if (knn_leaves_half_range(&path.use_f16, &path.dp_filter, s.D, flag)) {   // no f16 filter for this index any more
-      if (verbosity > 0)
-        printf("k-NN index: a centred row leaves the half range, %s\n",
-               path.dp_filter ? "the f32 matrix-core filter instead of the f16 one" : "every candidate is evaluated exactly");
-      IndexState now = state();
-      release_f16(now);
-      adopt(now);
-    }
-  }
-  return 0;
-}
-
 // The scratch of one call, taken from the index's arena and given back when the call ends, whichever way it ends
 // (behind a wait for the stream: kernels may still read it)
 struct ArenaScratch {
@@ -889,18 +784,102 @@ struct ArenaScratch {
   }
 };
 
-// A state under construction: released with the call unless the index has adopted it
+// A state under construction (none yet: nothing to do): released with the call, behind a wait for the stream, unless
+// the index has adopted it
 struct PendingState {
   KnnIndex &ix;
   IndexState t;
   bool adopted = false;
   explicit PendingState(KnnIndex &ix_) : ix(ix_) {}
   ~PendingState() {
-    if (adopted) return;
+    if (adopted || !t.rows.xs) return;
     (void)hipStreamSynchronize(ix.s.stream);
     ix.release_state(t);
   }
 };
+
+// One merge (knn_merge.hip): `cur` and the prepared chunk into the buffers of `next`, whose host offsets are made.
+int KnnIndex::merge(const IndexState &cur, const AddChunk &c, uint32_t n, IndexState *next) {
+  const uint32_t DP = s.DP, K = s.K;
+  const hipStream_t st = s.stream;
+  const bool f16 = path.use_f16;
+  KMX_HIPCP(hipMemcpyAsync(next->offsets, next->off_host.data(), ((size_t)K + 2) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  KMX_HIPRT(hipMemsetAsync(next->stats, 0, 4 * sizeof(uint32_t), st));
+  KnnMergeArgs a;
+  a.old_rows = cur.rows; a.chunk = c.b; a.out = next->rows;
+  a.off_old = cur.offsets; a.boffs = c.offsets; a.off_new = next->offsets;
+  a.N_old = cur.N; a.n = n; a.K = K; a.DP = DP;
+  KMX_HIPRT(launch_knn_merge_rows(a, st));
+  if (f16) {
+    KNN_TRY(zero_f16_pad(next->rows, next->N, DP, st));
+    KMX_HIPRT(hipMemsetAsync(next->stats_c, 0, 4 * sizeof(uint32_t), st));
+  }
+  KMX_HIPRT(launch_knn_merge_radii(cur.R, c.rdist, c.offsets, K, next->R, cur.stats, f16 ? cur.stats_c : nullptr, c.stats,
+                                   next->stats, f16 ? next->stats_c : nullptr, st));
+  return 0;
+}
+
+// n_rows more rows (DESIGN.md 4.15), in chunks of one merge each.  Every merge writes a whole new state; the index's
+// own buffers are read only, and replaced once the last chunk has been enqueued and the stream has drained without error.
+int KnnIndex::add(uint32_t n_rows, const void *rows, const uint32_t *assign_in, uint32_t *assign_out, int32_t device_ptrs) {
+  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
+  const int rc = add_chunks(n_rows, rows, assign_in, assign_out, device_ptrs < 0);
+  if (rc != 0 && verbosity > 0) printf("k-NN index add failed: %s\n", hipGetErrorString(hipGetLastError()));
+  return rc;
+}
+
+// (Every return before the adoption leaves the index as it was: the guards wait for the stream, then release the states
+// under construction, then the chunk's buffers go.)
+int KnnIndex::add_chunks(uint32_t n_rows, const void *rows, const uint32_t *assign_in, uint32_t *assign_out, bool host) {
+  const hipStream_t st = s.stream;
+  const bool f16 = path.use_f16;
+  const uint32_t Cn = knn_add_chunk_rows(n_rows, s.D, s.DP, kQueryChunkBytes, knn_switches().add_chunk);
+  AddTimer tm;
+  tm.start(knn_switches().add_time);
+  AddChunk c;
+  KNN_TRY(c.init(*this, Cn, !assign_in));
+  const IndexState own = state();
+  PendingState cur(*this);   // what the merges so far have made (none before the first)
+  for (uint32_t r0 = 0; r0 < n_rows; r0 += Cn) {
+    const uint32_t n = n_rows - r0 < Cn ? n_rows - r0 : Cn;
+    const bool first = r0 == 0;
+    const IndexState &from = first ? own : cur.t;
+    PendingState next(*this);
+    if (!first && tm.on && hipStreamSynchronize(st) == hipSuccess) tm.fold();   // (the chunk before: its events are reused)
+    KNN_TRY(c.prepare(*this, r0, n, rows, assign_in, assign_out, host, tm));
+    KNN_TRY(alloc_state(&next.t, from.N + n, f16));
+    if (!knn_merge_offsets(from.off_host, c.offs.data(), s.K, n, &next.t.off_host)) return kmcudaRuntimeError;
+    tm.mark(3, st);
+    KNN_TRY(merge(from, c, n, &next.t));
+    tm.mark(4, st);
+    // (read and written once: the fp32 rows, the halves and six words per row)
+    tm.merged_bytes += 2ull * ((unsigned long long)from.N + n) * ((f16 ? 6ull : 4ull) * s.DP + (f16 ? 24ull : 12ull));
+    if (!first) KMX_HIPRT(hipStreamSynchronize(st));   // (the merge reads `cur`, which goes with `next`'s guard)
+    std::swap(cur.t, next.t);
+  }
+  // the half-range flag, once per add (create waits for it too); the chunk's buffers go behind this wait
+  uint32_t flag = 0;
+  if (f16) KMX_HIPCP(hipMemcpyAsync(&flag, cur.t.stats + 1, sizeof(flag), hipMemcpyDeviceToHost, st));
+  KMX_HIPRT(hipStreamSynchronize(st));
+  if (tm.on) {
+    tm.fold();
+    printf("k-NN index add: %u rows in chunks of %u: clusters %.3f ms, preparation %.3f ms, merge %.3f ms (%.3f GB moved, "
+           "%.3f TB/s)\n", n_rows, Cn, tm.ms[0], tm.ms[1], tm.ms[2], 1e-9 * (double)tm.merged_bytes,
+           tm.ms[2] > 0.f ? 1e-9 * (double)tm.merged_bytes / (double)tm.ms[2] : 0.0);
+    fflush(stdout);
+  }
+  IndexState old = state();
+  adopt(cur.t);
+  cur.adopted = true;
+  release_state(old);
+  if (knn_leaves_half_range(&path.use_f16, &path.dp_filter, s.D, flag)) {   // no f16 filter for this index any more
+    if (verbosity > 0) say_left_half_range(path);
+    IndexState now = state();
+    release_f16(now);
+    adopt(now);
+  }
+  return 0;
+}
 
 // KMCUDA_AMD_KNN_REMOVE_TIME: the four stages of a remove -- the assignments (scatter and mark), the sort, the copy, the
 // member distances and radii --, printed at the end of the call (scripts/knn_remove_bench.py reads the line)
@@ -975,9 +954,8 @@ int KnnIndex::remove(uint32_t n_ids, const uint32_t *ids, uint32_t *n_removed, i
   KnnRemoveArgs a;
   a.old_rows = state().rows; a.out = out; a.pos = pos; a.N = N; a.DP = DP;
   KMX_HIPRT(launch_knn_remove_rows(a, st));
-  if (f16) {   // the filter's tile DMA reads whole tiles: zeros past the last row, as launch_knn_split leaves them
-    KMX_HIPRT(hipMemsetAsync(out.xs16 + (size_t)N * DP, 0, (size_t)KNN16_PAD_ROWS * DP * sizeof(uint16_t), st));
-    KMX_HIPRT(hipMemsetAsync(out.kbias + N, 0, (size_t)KNN16_PAD_ROWS * sizeof(float), st));
+  if (f16) {
+    KNN_TRY(zero_f16_pad(out, N, DP, st));
     KMX_HIPCP(hipMemcpyAsync(next.t.stats_c, s.stats_c, 4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   }
   // (maxima over all rows, and every row stays; the half-range flag cannot rise)
@@ -1024,6 +1002,18 @@ struct kmamd_knn_index {
   KnnIndex ix;
 };
 
+// what the caller wrote on its device (device_ptrs >= 0) has to be there before the index's stream reads it
+static void sync_callers_writes(int32_t device_ptrs) {
+  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();
+}
+
+// the arguments query and query_probe share
+static bool query_call_ok(kmamd_knn_index *h, uint32_t k, int32_t device_ptrs) {
+  if (!h) return false;
+  if (k == 0 || k > 65535u || k > h->ix.s.N) return false;
+  return device_ptrs < 0 || device_ptrs == h->ix.s.dev;
+}
+
 extern "C" {
 
 int kmamd_knn_index_create(kmamd_knn_index **out, int device, int metric, int fp16x2, uint32_t n_rows,
@@ -1039,7 +1029,7 @@ int kmamd_knn_index_create(kmamd_knn_index **out, int device, int metric, int fp
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return kmcudaNoSuchDevice;
   if (device_ptrs >= 0 && device_ptrs != device) return kmcudaInvalidArguments;   // one device per index
   g_verbosity = verbosity;
-  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // as knn_cuda()
+  sync_callers_writes(device_ptrs);   // as knn_cuda()
   KnnCorpus c;
   c.metric = metric; c.fp16 = fp16x2 != 0; c.N = n_rows; c.D = features; c.K = clusters;
   c.samples = samples; c.centroids = centroids; c.assignments = assignments; c.device_ptrs = device_ptrs;
@@ -1056,29 +1046,24 @@ int kmamd_knn_index_create(kmamd_knn_index **out, int device, int metric, int fp
 int kmamd_knn_index_query(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, const void *queries,
                           const uint32_t *query_assignments, uint32_t *neighbors, float *distances,
                           uint32_t *query_assignments_out, int32_t device_ptrs) {
-  if (!h) return kmcudaInvalidArguments;
-  KnnIndex &ix = h->ix;
-  if (k == 0 || k > 65535u || k > ix.s.N) return kmcudaInvalidArguments;
-  if (device_ptrs >= 0 && device_ptrs != ix.s.dev) return kmcudaInvalidArguments;
+  if (!query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
   if (n_queries == 0) return kmcudaSuccess;
   if (!queries || !neighbors) return kmcudaInvalidArguments;
-  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
-  return ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs);
+  sync_callers_writes(device_ptrs);
+  return h->ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs);
 }
 
 int kmamd_knn_index_query_probe(kmamd_knn_index *h, uint32_t k, uint32_t nprobe, uint32_t n_queries,
                                 const void *queries, const uint32_t *probes, uint32_t *neighbors, float *distances,
                                 uint32_t *probes_out, int32_t device_ptrs) {
-  if (!h) return kmcudaInvalidArguments;
+  if (!query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
   KnnIndex &ix = h->ix;
-  if (k == 0 || k > 65535u || k > ix.s.N) return kmcudaInvalidArguments;
   if (nprobe < 1 || nprobe > KNN_PROBE_MAX || nprobe > ix.s.K) return kmcudaInvalidArguments;
-  if (device_ptrs >= 0 && device_ptrs != ix.s.dev) return kmcudaInvalidArguments;
   // the reference's half2 arithmetic has no ranking (kmamd_kmeans_assign_top refuses it likewise): the caller's lists only
   if (!probes && ix.fp16 && (ix.path.strict_h2 || knn_switches().fp16_strict)) return kmcudaInvalidArguments;
   if (n_queries == 0) return kmcudaSuccess;
   if (!queries || !neighbors) return kmcudaInvalidArguments;
-  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
+  sync_callers_writes(device_ptrs);
   return ix.query_probe(k, nprobe, n_queries, queries, probes, neighbors, distances, probes_out, device_ptrs);
 }
 
@@ -1094,7 +1079,7 @@ int kmamd_knn_index_radius_count(kmamd_knn_index *h, float radius, uint32_t n_qu
   if (!radius_call_ok(h, radius, device_ptrs)) return kmcudaInvalidArguments;
   if (n_queries == 0) return kmcudaSuccess;
   if (!queries || !counts) return kmcudaInvalidArguments;
-  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
+  sync_callers_writes(device_ptrs);
   return h->ix.radius(false, radius, n_queries, queries, query_assignments, counts, query_assignments_out, nullptr,
                       nullptr, nullptr, device_ptrs);
 }
@@ -1105,7 +1090,7 @@ int kmamd_knn_index_radius_fill(kmamd_knn_index *h, float radius, uint32_t n_que
   if (!radius_call_ok(h, radius, device_ptrs)) return kmcudaInvalidArguments;
   if (n_queries == 0) return kmcudaSuccess;
   if (!queries || !offsets || !neighbors) return kmcudaInvalidArguments;
-  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
+  sync_callers_writes(device_ptrs);
   return h->ix.radius(true, radius, n_queries, queries, query_assignments, nullptr, nullptr, offsets, neighbors,
                       distances, device_ptrs);
 }
@@ -1121,7 +1106,7 @@ int kmamd_knn_index_add(kmamd_knn_index *h, uint32_t n_rows, const void *rows, c
   if (!assignments && ix.fp16 && (ix.path.strict_h2 || knn_switches().fp16_strict)) return kmcudaInvalidArguments;
   const uint32_t first = ix.s.N;
   if (n_rows != 0) {
-    if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
+    sync_callers_writes(device_ptrs);
     KNN_TRY(ix.add(n_rows, rows, assignments, assignments_out, device_ptrs));
   }
   if (first_row) *first_row = first;
@@ -1134,7 +1119,7 @@ int kmamd_knn_index_remove(kmamd_knn_index *h, uint32_t n_ids, const uint32_t *i
   KnnIndex &ix = h->ix;
   if (n_ids > 0 && !ids) return kmcudaInvalidArguments;
   if (device_ptrs >= 0 && device_ptrs != ix.s.dev) return kmcudaInvalidArguments;
-  if (n_ids != 0 && device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // the caller's writes
+  if (n_ids != 0) sync_callers_writes(device_ptrs);
   return ix.remove(n_ids, ids, n_removed, device_ptrs);
 }
 

@@ -1,5 +1,6 @@
-// knn_merge_host.hpp -- the host arithmetic of kmamd_knn_index_add (knn_index.cpp), free of any device
-// call so that a stand-alone program can drive it (scripts/knn_merge_host_check.cpp).
+// knn_merge_host.hpp -- the host arithmetic of kmamd_knn_index_add (knn_index.cpp) and the rows per
+// chunk of every chunked index call, free of any device call so that a stand-alone program can drive it
+// (scripts/knn_merge_host_check.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -33,14 +34,19 @@ inline bool knn_merge_offsets(const std::vector<uint32_t> &off_old, const uint32
   return true;
 }
 
-// Rows per chunk of an add: a chunk's staged fp32 rows (D floats), its sorted fp32 copy (DP floats), the centred halves
-// (DP) and the per-row scalars and sort scratch (some 48 bytes) stay within `budget` bytes; `forced` (the test hook
-// KMCUDA_AMD_KNN_ADD_CHUNK) overrides; at least one row, never more than n
-inline uint32_t knn_add_chunk_rows(uint32_t n, uint32_t D, uint32_t DP, size_t budget, size_t forced) {
-  size_t rows = budget / ((size_t)D * 4 + (size_t)DP * 6 + 48);
-  if (forced) rows = forced;
+// Rows per chunk of a chunked index call over n rows: as many as `budget` bytes hold at row_bytes (> 0) each, or
+// `forced` where a test hook sets it (KMCUDA_AMD_KNN_QUERY_CHUNK, KMCUDA_AMD_KNN_ADD_CHUNK); at least one row, never
+// more than n
+inline uint32_t knn_chunk_rows(size_t budget, size_t row_bytes, size_t forced, uint32_t n) {
+  size_t rows = forced ? forced : budget / row_bytes;
   if (rows < 1) rows = 1;
   return rows < n ? (uint32_t)rows : n;
+}
+
+// ... of an add: a chunk's staged fp32 rows (D floats), its sorted fp32 copy (DP floats), the centred halves (DP) and
+// the per-row scalars and sort scratch (some 48 bytes)
+inline uint32_t knn_add_chunk_rows(uint32_t n, uint32_t D, uint32_t DP, size_t budget, size_t forced) {
+  return knn_chunk_rows(budget, (size_t)D * 4 + (size_t)DP * 6 + 48, forced, n);
 }
 
 }  // namespace kmx

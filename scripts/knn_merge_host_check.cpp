@@ -1,5 +1,6 @@
 // knn_merge_host_check.cpp -- drives the host arithmetic of kmamd_knn_index_add (kmcuda_amd/csrc/knn_merge_host.hpp:
-// the merged CSR offsets, the row limit, the chunk loop) on the CPU against a plain recount, and replays the merge
+// the merged CSR offsets, the row limit, the chunk loop, the rows per chunk of every chunked index call) on the CPU
+// against a plain recount, and replays the merge
 // kernel's source rule on the host to check that every destination position gets exactly one source row in the order a
 // fresh index has.  No device call: meant for a build with the host sanitizers,
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I kmcuda_amd/csrc \
@@ -119,6 +120,35 @@ int main() {
   CHECK(knn_add_chunk_rows(0xFFFFFFFEu, 256, 256, (size_t)4 << 30, 0) == ((size_t)4 << 30) / (256 * 10 + 48));
   CHECK(knn_add_chunk_rows(10, 1u << 30, 1u << 30, 1024, 0) == 1);
   CHECK(knn_add_chunk_rows(10, 64, 64, (size_t)4 << 30, 3) == 3);
+  // the helper under it, which the query, probe and radius calls size their chunks with
+  {
+    const size_t budget = (size_t)4 << 30;
+    CHECK(knn_chunk_rows(1024, 4096, 0, 10) == 1);    // a budget smaller than one row
+    CHECK(knn_chunk_rows(budget, 12, 1000, 37) == 37);   // a forced value above the row count
+    CHECK(knn_chunk_rows(budget, 12, 5, 37) == 5);
+    CHECK(knn_chunk_rows(budget, 12, 0, 0) == 0);     // no rows
+    CHECK(knn_chunk_rows(budget, 12, 7, 0) == 0);
+    CHECK(knn_chunk_rows(1024, 4096, 0, 0) == 0);
+    // bytes per query: K + 2k floats (query: lb and heaps), pw + 2k (probe: lists and heaps; pw <= min(K, 64)), K
+    // (radius: lb) -- against the arithmetic the three calls used to spell out
+    auto spelled_out = [&](size_t row_bytes, size_t forced, uint32_t Q) {
+      size_t chunk = budget / row_bytes;
+      if (forced) chunk = forced;
+      if (chunk < 1) chunk = 1;
+      return (uint32_t)(chunk < Q ? chunk : Q);
+    };
+    const size_t Ks[2] = {1, (size_t)1 << 20}, ks[2] = {1, 65535}, pws[2] = {1, 64};
+    const uint32_t want[2][3] = {{357913941u, 357913941u, 1073741824u}, {910u, 8188u, 1024u}};
+    for (int i = 0; i < 2; i++) {
+      const size_t terms[3] = {4 * (Ks[i] + 2 * ks[i]), 4 * (pws[i] + 2 * ks[i]), 4 * Ks[i]};
+      for (int t = 0; t < 3; t++)
+        for (uint32_t Q : {0u, 1u, 909u, 910u, 911u, 8188u, 8189u, 0xFFFFFFFEu})
+          for (size_t forced : {(size_t)0, (size_t)37}) {
+            CHECK(knn_chunk_rows(budget, terms[t], forced, Q) == spelled_out(terms[t], forced, Q));
+            if (!forced && Q == 0xFFFFFFFEu) CHECK(knn_chunk_rows(budget, terms[t], 0, Q) == want[i][t]);
+          }
+    }
+  }
   printf(failures ? "%d checks FAILED\n" : "knn_merge_host_check: all checks passed\n", failures);
   return failures ? 1 : 0;
 }

@@ -291,6 +291,32 @@ def test_small_chunks_equal_the_default(monkeypatch, computed):
     assert_equal(want, fresh_snapshot(x[:n], c, a2, q), "default chunk")
 
 
+@pytest.mark.parametrize("computed", [False, True])
+def test_small_chunks_leave_the_same_index(monkeypatch, computed):
+    """70 rows onto 30 in chunks of 5 on the f16 path -- 14 merges, each from the state the one before made, the row
+    count passing the 64 rows of the f16 tile padding --: info(), radii() and the lists of every row of the index are
+    those of the add in one chunk, bit for bit.  Two of the given assignments name no cluster."""
+    from kmcuda_amd import KnnIndex
+    x, c, a, _ = clustered(64, n=100, clusters=4)
+    given = a[30:].copy()
+    given[[11, 52]] = 4
+    seen = []
+    for chunk in ({}, {"KMCUDA_AMD_KNN_ADD_CHUNK": "5"}):
+        set_env(monkeypatch, chunk)
+        with KnnIndex(x[:30], c, a[:30]) as ix:
+            assert ix.info() == (30, 30, 2)
+            first, used = ix.add(x[30:], None if computed else given, return_assignments=True)
+            assert first == 30 and (computed or (used == given).all())
+            seen.append((ix.info(), ix.radii(), used) + tuple(ix.query(x, 7)))
+    (info1, radii1, used1, nb1, dist1), (info5, radii5, used5, nb5, dist5) = seen
+    assert info5 == info1 == (100, 100 if computed else 98, 2)
+    assert (bits(radii5) == bits(radii1)).all() and (used5 == used1).all()
+    assert (nb5 == nb1).all() and (bits(dist5) == bits(dist1)).all()
+    assert numpy.isin(numpy.arange(30, 100), nb1).sum() == (70 if computed else 68)   # (every added row is somebody's)
+    if not computed:
+        assert not numpy.isin(nb1, [30 + 11, 30 + 52]).any()                          # (but the two without a cluster)
+
+
 def test_across_the_f16_tile_padding(monkeypatch):
     """63 rows, then 64, then 65: the zeroed rows past the last one move with every add."""
     from kmcuda_amd import KnnIndex

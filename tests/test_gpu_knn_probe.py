@@ -365,6 +365,30 @@ def test_chunking_and_buffers(monkeypatch):
     assert (nb0 == ref_nb).all() and (bits(dist0) == bits(ref_dist)).all()
 
 
+@pytest.mark.parametrize("chunk", [None, 37])
+@pytest.mark.parametrize("ptr", ["host", "device"])
+def test_without_distances(ptr, chunk, monkeypatch):
+    """distances == nullptr in a probed query: the lists are those of the call that returns distances."""
+    from kmcuda_amd import KnnIndex
+    x, c, a = cached(("chunks",), lambda: corpus(2500, 64, 24, 1700))
+    q = fresh(c, 300, 15)
+    q[100, 3] = numpy.nan
+    if chunk is not None:
+        monkeypatch.setenv("KMCUDA_AMD_KNN_QUERY_CHUNK", str(chunk))
+    if ptr == "device":
+        dev = torch.device("cuda", 0)
+        x, c, q = (torch.from_numpy(v).to(dev) for v in (x, c, q))
+        a = torch.from_numpy(a.view(numpy.int32)).to(dev)
+    with KnnIndex(x, c, a) as ix:
+        nb, dist = ix.query(q, 10, nprobe=4)
+        only = ix.query(q, 10, nprobe=4, return_distances=False)
+    if ptr == "device":
+        nb, dist, only = (t.cpu().numpy() for t in (nb, dist, only))
+    assert only.shape == nb.shape == (300, 10) and (only == nb).all()
+    assert (nb.view(numpy.uint32)[100] == NONE).all() and numpy.isnan(dist[100]).all()
+    assert (nb.view(numpy.uint32)[numpy.arange(300) != 100, 0] != NONE).all()
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # 10. the counters: nothing outside the probes is looked at
 # ----------------------------------------------------------------------------------------------------------------
