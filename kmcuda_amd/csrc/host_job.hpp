@@ -5,9 +5,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
+#include <stdarg.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 
+#include <chrono>
+#include <functional>
 #include <memory>
 #include <vector>
 
@@ -20,6 +24,36 @@ namespace kmx {
 #define KNN_TRY(call) do { int rc__ = (call); if (rc__ != 0) return rc__; } while (false)
 #define KMX_HIPRT(call) do { if ((call) != hipSuccess) return kmcudaRuntimeError; } while (false)
 #define KMX_HIPCP(call) do { if ((call) != hipSuccess) return kmcudaMemoryCopyError; } while (false)
+
+// KMCUDA_AMD_FP16_STRICT "set and non-zero": the reference's half2 arithmetic is asked for.  The one place that parses
+// it -- the switch sets (kmeans_switches, knn_switches) and the calls that refuse it (rows_call_begin, the mini-batch
+// model) all ask here.
+inline bool fp16_strict_requested() {
+  const char *v = getenv("KMCUDA_AMD_FP16_STRICT");
+  return v && atoi(v) != 0;
+}
+
+// KMCUDA_AMD_TIMING: wall-clock laps of a call's phases on stderr (a measurement aid).  lap() first runs `wait` (what
+// the lap has to wait for so that it measures finished work: the job's GPUs, a stream, or nothing where the code around
+// it has waited already), then prints "[timing] <what>: <ms since the last lap> ms".  Switched off it does nothing.
+struct PhaseClock {
+  bool on = false;
+  std::function<void()> wait;
+  std::chrono::steady_clock::time_point t_lap = std::chrono::steady_clock::now();
+  explicit PhaseClock(bool on_, std::function<void()> wait_ = nullptr) : on(on_), wait(std::move(wait_)) {}
+  __attribute__((format(printf, 2, 3))) void lap(const char *fmt, ...) {
+    if (!on) return;
+    if (wait) wait();
+    const auto t1 = std::chrono::steady_clock::now();
+    char what[128];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(what, sizeof(what), fmt, ap);
+    va_end(ap);
+    fprintf(stderr, "[timing] %s: %.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t_lap).count());
+    t_lap = t1;
+  }
+};
 
 // The device buffers of one call (or of one prepared corpus: KnnShard) on one GPU and the pooled stream its work is
 // enqueued on: everything alloc() hands out is freed with the arena, and the stream goes back to its pool (a null
@@ -160,9 +194,7 @@ inline int rows_call_begin(int metric, uint32_t features_size, int32_t fp16x2, i
   if (features_size == 0 || (fp16x2 && (features_size & 1u))) return kmcudaInvalidArguments;
   if (device < 0 || device > max_device || (device_ptrs >= 0 && device_ptrs != device)) return kmcudaInvalidArguments;
   // the reference's half2 arithmetic has no predict form (sample weights refuse it for the same reason)
-  if (fp16x2)
-    if (const char *v = getenv("KMCUDA_AMD_FP16_STRICT"))
-      if (atoi(v) != 0) return kmcudaInvalidArguments;
+  if (fp16x2 && fp16_strict_requested()) return kmcudaInvalidArguments;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return kmcudaNoSuchDevice;
   if (hipSetDevice(device) != hipSuccess) return kmcudaNoSuchDevice;

@@ -334,10 +334,65 @@ struct RunStats {
 RunStats g_last_run;        // published once per kmeans_cuda() call, under g_last_run_mutex (the Python module
 std::mutex g_last_run_mutex;  // releases the GIL around the call: two threads may be inside the library)
 
+// The KMCUDA_AMD_* switches of kmeans_cuda(), read once when the call starts (tests change them between calls); the
+// job, its nested group-clustering job and the seeding take them from here.  The engines' own switches (engine.cpp,
+// seeding.hip, lloyd_carry.hip) are theirs.
+struct KmeansSwitches {
+  bool timing = false;           // KMCUDA_AMD_TIMING (set at all): laps and iteration stamps on stderr
+  bool exact_update = false;     // KMCUDA_AMD_EXACT_UPDATE: the reference's serial Kahan chain (single shard)
+  bool fp16_strict = false;      // KMCUDA_AMD_FP16_STRICT: the reference's half2 arithmetic (fp16x2 only)
+  enum class Yy { unset, reference, carry } yy = Yy::unset;   // KMCUDA_AMD_YY (anything else: unset)
+  double yy_switch = -1.0;       // KMCUDA_AMD_YY_SWITCH=<fraction> (tests; negative: unset)
+  enum class Carry { unset, off, on } carry = Carry::unset;   // KMCUDA_AMD_CARRY: 0 / non-zero
+  bool speculate = true;         // KMCUDA_AMD_SPECULATE=0: every iteration waits for its stop test before its update
+  bool time_collective = false;  // KMCUDA_AMD_TIME_COLLECTIVE
+  bool force_rccl = false;       // KMCUDA_AMD_FORCE_RCCL (test hook)
+  bool kmpp_host = false;        // KMCUDA_AMD_KMPP_HOST (set at all): k-means++ chooses on the host
+  int kmpp_filter = 1;           // KMCUDA_AMD_KMPP_FILTER: 0 plain steps, >= 2 filtered steps for small jobs too
+  bool update_trace = false;     // KMCUDA_AMD_UPDATE_TRACE (set at all)
+  bool preload = true;           // KMCUDA_AMD_PRELOAD=0: no helper thread loads the code objects
+  int virtual_shards = 0;        // KMCUDA_AMD_VIRTUAL_SHARDS: row shards on one GPU (test hook)
+  // KMCUDA_AMD_YY_SWITCH (tests): hand over to the reference's bounds once the reassigned fraction is at most that
+  bool hand_over_forced() const { return yy_switch >= 0; }
+  bool hand_over_now(uint32_t changed, uint32_t N) const { return hand_over_forced() && (double)changed <= yy_switch * (double)N; }
+};
+KmeansSwitches kmeans_switches() {
+  KmeansSwitches sw;
+  auto on = [](const char *v) { return v && atoi(v) != 0; };
+  sw.timing = getenv("KMCUDA_AMD_TIMING") != nullptr;
+  sw.exact_update = on(getenv("KMCUDA_AMD_EXACT_UPDATE"));
+  sw.fp16_strict = fp16_strict_requested();
+  if (const char *v = getenv("KMCUDA_AMD_YY"))
+    sw.yy = strcmp(v, "reference") == 0 ? KmeansSwitches::Yy::reference
+                                        : (strcmp(v, "carry") == 0 ? KmeansSwitches::Yy::carry : KmeansSwitches::Yy::unset);
+  if (const char *v = getenv("KMCUDA_AMD_YY_SWITCH")) sw.yy_switch = atof(v);
+  if (const char *v = getenv("KMCUDA_AMD_CARRY")) sw.carry = atoi(v) != 0 ? KmeansSwitches::Carry::on : KmeansSwitches::Carry::off;
+  if (const char *v = getenv("KMCUDA_AMD_SPECULATE")) sw.speculate = atoi(v) != 0;
+  sw.time_collective = on(getenv("KMCUDA_AMD_TIME_COLLECTIVE"));
+  sw.force_rccl = on(getenv("KMCUDA_AMD_FORCE_RCCL"));
+  sw.kmpp_host = getenv("KMCUDA_AMD_KMPP_HOST") != nullptr;
+  if (const char *v = getenv("KMCUDA_AMD_KMPP_FILTER")) sw.kmpp_filter = atoi(v);
+  sw.update_trace = getenv("KMCUDA_AMD_UPDATE_TRACE") != nullptr;
+  if (const char *v = getenv("KMCUDA_AMD_PRELOAD")) sw.preload = atoi(v) != 0;
+  if (const char *v = getenv("KMCUDA_AMD_VIRTUAL_SHARDS")) sw.virtual_shards = atoi(v);
+  return sw;
+}
+
+// What the schedule of one call is going to be (Job::plan_schedule)
+struct SchedulePlan {
+  // kmeans.cu:1037-1050: no Yinyang phase at all
+  enum class LloydOnly { no, too_few_clusters, tolerance_too_high } lloyd_only = LloydOnly::no;
+  bool adaptive = false;        // behind the hand-over point: Lloyd passes go on (else the reference's bounds)
+  bool carry = false;           // ... and may carry per-row bounds from pass to pass
+  bool carry_at_once = false;   // ... from the first pass on, not once the run has been seen to go on
+  bool cluster_groups_for_real = true;   // the groups are clustered (else only the draws of their seeding are replayed)
+};
+
 class Job {
  public:
   uint32_t N = 0, D = 0, K = 0;
   int metric = 0, verbosity = 0;
+  KmeansSwitches sw;  // the call's switches (setup(); a nested job gets its parent's)
   bool fp16 = false;  // fp16x2 boundary: half buffers outside, fp32 arithmetic on the half values inside
   // KMCUDA_AMD_FP16_STRICT=1 (fp16x2 jobs, one GPU): every step in the reference's half2 ARITHMETIC
   // (half2_strict.hip) -- the verification mode the oracle's half2 restatement is compared with
@@ -420,10 +475,12 @@ class Job {
 
   // on_stream: the (single) shard's engine works on this existing stream instead of creating one -- the nested job
   // that clusters the centroids into groups rides on its parent's: a stream's first launches cost milliseconds
-  int setup(const std::vector<int> &devs, int nvirtual, uint32_t N_, uint32_t D_, uint32_t K_, int metric_,
-            int verbosity_, const float *samples, int32_t device_ptrs, hipStream_t on_stream = nullptr,
+  int setup(const KmeansSwitches &sw_, const std::vector<int> &devs, int nvirtual, uint32_t N_, uint32_t D_, uint32_t K_,
+            int metric_, int verbosity_, const float *samples, int32_t device_ptrs, hipStream_t on_stream = nullptr,
             const float *sample_weights = nullptr) {
+    sw = sw_;
     N = N_; D = D_; K = K_; metric = metric_; verbosity = verbosity_;
+    exact_update = sw.exact_update || strict_h2;   // (strict: the reference's serial update, in half2 arithmetic)
     weighted = sample_weights != nullptr;
     std::vector<int> shard_devs = devs;
     if (nvirtual > 1 && devs.size() == 1) shard_devs.assign(nvirtual, devs[0]);  // test hook
@@ -471,7 +528,7 @@ class Job {
     // KMCUDA_AMD_FORCE_RCCL=1 (test hook): a ONE-shard job also creates its (one-rank) communicator and sends its
     // reduce buffer through ncclAllReduce every iteration -- the library loading, the entry points' signatures, the
     // enum values and the stream the collective is enqueued on get exercised on a box with a single GPU
-    const bool force_rccl = shards.size() == 1 && getenv("KMCUDA_AMD_FORCE_RCCL") && atoi(getenv("KMCUDA_AMD_FORCE_RCCL")) != 0;
+    const bool force_rccl = shards.size() == 1 && sw.force_rccl;
     if (distinct || force_rccl) {
       if (!rccl.load()) {
         INFO("failed to load librccl.so: multi-GPU operation is unavailable\n");
@@ -495,8 +552,8 @@ class Job {
         return kmcudaMemoryCopyError;
       if (hipEventCreateWithFlags(&ev_summed, hipEventDisableTiming) != hipSuccess) return kmcudaRuntimeError;
     }
-    if (const char *v = getenv("KMCUDA_AMD_SPECULATE")) speculate = atoi(v) != 0;
-    if (const char *v = getenv("KMCUDA_AMD_TIME_COLLECTIVE")) time_collective = atoi(v) != 0 && (shards.size() > 1 || !comms.empty());
+    speculate = sw.speculate;
+    time_collective = sw.time_collective && (shards.size() > 1 || !comms.empty());
     RETERR(sync_all());  // uploads complete: later cross-stream reads of the samples are safe
     for (auto &s : shards) {   // (every weight finite and > 0, or InvalidArguments before any clustering work)
       if (!weighted) break;
@@ -736,7 +793,7 @@ class Job {
     // The device chooser needs whole 256-row blocks on every shard but the last (row_plan()) and peer access from the
     // first shard's device to the others'; otherwise the host chooser.
     bool device_chooser_possible() const {
-      bool can_choose = !job.strict_h2 && getenv("KMCUDA_AMD_KMPP_HOST") == nullptr && shards.size() <= (size_t)kKmppMaxShards;
+      bool can_choose = !job.strict_h2 && !job.sw.kmpp_host && shards.size() <= (size_t)kKmppMaxShards;
       for (auto &s : shards) {
         can_choose = can_choose && kmpp_blocks(s->length) <= (1u << 20) &&   // (two-level prefix: 1024 x 1024 blocks of 256 rows)
                      (s->offset % 256u == 0u) && s->length != 0;
@@ -794,10 +851,8 @@ class Job {
     int prepare_filter(bool device_chooser) {
       // (small jobs: the plain step is a few launches of nothing; KMCUDA_AMD_KMPP_FILTER=2 filters them too: tests)
       filter = device_chooser && job.K >= 8 && job.N >= 65536u && dp <= 8192u;
-      if (const char *v = getenv("KMCUDA_AMD_KMPP_FILTER")) {
-        const int f = atoi(v);
-        filter = f >= 2 ? (device_chooser && job.K >= 3 && dp <= 8192u) : (filter && f != 0);
-      }
+      const int f = job.sw.kmpp_filter;
+      filter = f >= 2 ? (device_chooser && job.K >= 3 && dp <= 8192u) : (filter && f != 0);
       if (!filter) return 0;
       bool ok = true;
       for (size_t q = 0; q < shards.size() && ok; q++) {
@@ -1179,26 +1234,38 @@ class Job {
   }
 
   // KMCUDA_AMD_TIMING: when the host learned an iteration's outcome (ms since the job was made; a measurement aid)
-  const bool timing_ = getenv("KMCUDA_AMD_TIMING") != nullptr;
   const std::chrono::steady_clock::time_point born_ = std::chrono::steady_clock::now();
   void stamp(int iter) const {
-    if (timing_)
+    if (sw.timing)
       fprintf(stderr, "[timing]   iteration %d judged at %.3f ms\n", iter,
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - born_).count());
   }
-  bool exact_update = false;  // KMCUDA_AMD_EXACT_UPDATE=1: the reference's serial Kahan chain (single shard)
+  bool exact_update = false;  // KMCUDA_AMD_EXACT_UPDATE=1 or the strict half2 mode: the reference's serial Kahan chain (single shard)
 
+  // The stop test of iteration `iter`, from where its numbers lie: the shards' counters under the strict update (no
+  // reduce buffer) and for the unweighted test at the hand-over point (kmeans.cu:1058), otherwise the reduced buffer's
+  // tail (weighted: the reassigned weight is in the stop iteration's reduced buffer, not in the counters)
+  int judge(int iter, float tolerance, bool print, uint32_t *passed_total = nullptr, bool at_hand_over = false) {
+    const bool from_counters = exact_update || (at_hand_over && !weighted);
+    return from_counters ? check_changed(iter, tolerance, print, passed_total)
+                         : check_changed_reduced(iter, tolerance, print, passed_total);
+  }
+
+  // the engines' carried-bounds flag, as kmamd_set_carry (engine.cpp) sets it: bounds left by earlier passes are void
+  void set_carry(bool on) {
+    for (auto &s : shards) {
+      s->eng->carry_on_ = on;
+      s->eng->carry_valid_ = false;
+    }
+  }
   // Default schedule: iteration number from which on a judged "goes on" starts the carried bounds (0: no such
-  // start pending; kmeans_cuda sets it at the hand-over point)
+  // start pending; carried_phase sets it at the hand-over point)
   int carry_after = 0;
   void maybe_start_carry(int judged_iter) {
     if (carry_after == 0 || judged_iter < carry_after) return;
     carry_after = 0;
     INFO("carrying per-sample distance bounds from pass to pass\n");
-    for (auto &s : shards) {
-      s->eng->carry_on_ = true;
-      s->eng->carry_valid_ = false;
-    }
+    set_carry(true);
   }
 
   // the update in three stream-ordered phases (reference: kmeans_adjust launch + peer exchange,
@@ -1300,7 +1367,7 @@ class Job {
       for (int iter = after + 1;; iter++) {
         for (auto &s : shards)
           RETERR(s->eng->lloyd_assign(s->samples, s->centroids, s->assignments, s->prev, false));
-        const int status = check_changed(iter, tolerance, true);
+        const int status = judge(iter, tolerance, true);
         if (status < 0) return -status;
         stats.iterations++;
         if (status == 1) {
@@ -1344,7 +1411,7 @@ class Job {
         unjudged = iter;
         continue;
       }
-      const int status = check_changed_reduced(iter, tolerance, true);   // the host waits: one 32-byte read
+      const int status = judge(iter, tolerance, true);   // the host waits: one 32-byte read
       if (status < 0) return -status;
       stats.iterations++;
       if (status == 1 || leave_next) {
@@ -1380,28 +1447,20 @@ class Job {
   int cluster_groups(uint32_t G, std::vector<uint32_t> *groups) {
     Shard &first = *shards[0];
     RETERR(first.eng->sync());
-    const bool timing = getenv("KMCUDA_AMD_TIMING") != nullptr;
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-      if (!timing) return;
-      const auto t1 = std::chrono::steady_clock::now();
-      fprintf(stderr, "[timing] group clustering, %s: %.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-      t0 = t1;
-    };
+    PhaseClock clock(sw.timing);   // (its laps wait for nothing: the waits are the code's own)
     Job gjob;
-    gjob.strict_h2 = strict_h2;   // (before setup: the engines take the flag there)
+    gjob.strict_h2 = strict_h2;   // (before setup: the engines take the flag there, and the strict update follows it)
     std::vector<int> one{first.dev};
-    RETERR(gjob.setup(one, 0, K, D, G, metric, verbosity, first.centroids, first.dev, first.eng->stream_));  // fp32 replica in place
+    RETERR(gjob.setup(sw, one, 0, K, D, G, metric, verbosity, first.centroids, first.dev, first.eng->stream_));  // fp32 replica in place
     gjob.shards[0]->eng->side_stream_ = first.eng->side_stream_;   // (borrowed with the main one; may be null)
-    lap("setup");
-    gjob.exact_update = exact_update;
+    clock.lap("group clustering, setup");
     gjob.fp16 = fp16;  // centroids_yy is half2 in the reference too (kmeans.cu:1084-1091)
     RETERR(gjob.init_centroids(kmcudaInitMethodPlusPlus, 0, nullptr, first.dev));
-    if (timing) RETERR(gjob.sync_all());
-    lap("k-means++");
+    if (sw.timing) RETERR(gjob.sync_all());
+    clock.lap("group clustering, k-means++");
     RETERR(gjob.lloyd((float)kYinyangGroupTolerance, nullptr));
     RETERR(gjob.sync_all());
-    lap("Lloyd");
+    clock.lap("group clustering, Lloyd");
     groups->resize(K);
     (void)hipSetDevice(first.dev);
     if (hipMemcpy(groups->data(), gjob.shards[0]->assignments, K * sizeof(uint32_t), hipMemcpyDeviceToHost) !=
@@ -1455,8 +1514,7 @@ class Job {
       }
       if (!refresh) {
         uint32_t passed_total = 0;
-        const int status = exact_update ? check_changed(iter, tolerance, true, &passed_total)
-                                        : check_changed_reduced(iter, tolerance, true, &passed_total);
+        const int status = judge(iter, tolerance, true, &passed_total);
         if (status < 0) return -status;
         if (status == 1) {
           if (verbosity > 1) {
@@ -1496,6 +1554,113 @@ class Job {
       }));
       stats.iterations++;
     }
+  }
+
+  // ---- the schedule ----
+  // The reference hands over from Lloyd to its bounds at 11 % reassignments whatever the data; its bounds refresh
+  // (kmeans_yy_init: >= G exact chains per row) costs 38 assignment passes on this hardware and its filters more than a
+  // pass per row that passes them (profiles/r2n_*, r3y_*): measured on both benchmark data sets it never pays.  The
+  // default keeps the reference's sequence up to and including the hand-over point (group clustering, its progress
+  // lines, its srand(0)) and then goes on with assignment passes that CARRY per-row bounds from pass to pass at no
+  // refresh cost (lloyd_carry.hip).  Every pass either way is the reference's arithmetic.
+  SchedulePlan plan_schedule(float tolerance, uint32_t yy_groups) const {
+    using Yy = KmeansSwitches::Yy;
+    using Carry = KmeansSwitches::Carry;
+    SchedulePlan p;
+    if (yy_groups == 0) p.lloyd_only = SchedulePlan::LloydOnly::too_few_clusters;   // kmeans.cu:1037-1050
+    else if (kYinyangDraftReassignments <= tolerance) p.lloyd_only = SchedulePlan::LloydOnly::tolerance_too_high;
+    if (p.lloyd_only != SchedulePlan::LloydOnly::no) return p;
+    const Engine &e = *shards[0]->eng;
+    const bool wide = e.DP_ == 0 && e.wide_dp_ != 0;   // D > 256: lloyd_wide.hip
+    // KMCUDA_AMD_YY=reference: the reference's fixed schedule (Lloyd down to 11 % reassignments, then its bounds).
+    // The strict parity modes keep the reference's schedule -- but KMCUDA_AMD_YY=carry: the default schedule also under
+    // the strict update -- every pass is the reference's Lloyd arithmetic, so the whole call then equals the
+    // reference's kmeans_cuda_lloyd bit for bit: the parity test of the carried bounds against the oracle end to end,
+    // tests/test_gpu_carry.py.  The last term: the passes that carry bounds are the two-stage f16 filter's and the
+    // streamed filter's (engine.cpp: carry_begin); a job on another filter keeps the reference's schedule.
+    p.adaptive = sw.yy != Yy::reference && (!exact_update || (sw.yy == Yy::carry && !strict_h2)) &&
+                 ((e.DP_ != 0 && e.filter_mode_ == 0) || wide);
+    // (rows wider than 256 features: the streamed filter carries the bounds itself, up to 4096 features)
+    p.carry = p.adaptive && sw.carry != Carry::off && (!wide || e.wide_dp_ <= 4096u);
+    // The first carried pass only LEAVES bounds (and allocates them: 24 bytes per row); rows are spared from the
+    // second one on.  A run that stops within a pass or two of the hand-over point never earns that back (round 4:
+    // the 4M-row mixture at tolerance 0.01, one iteration after the hand-over, +12-16 %), and how long a run will
+    // last cannot be read off its first counts (they fall by a factor of 4-8 per iteration, the tail by 1.1: an
+    // extrapolation tried in round 5 switched the bounds off for the 37-iteration run,
+    // profiles/r5e_configs_carry_extrapolation_rule_misfires.log).  So the bounds start once the host has SEEN the
+    // run go on past an iteration after the hand-over (lloyd(), carry_after).  KMCUDA_AMD_CARRY=1: at once
+    // (tests: every pass after the hand-over is then a carried one).
+    p.carry_at_once = p.carry && sw.carry == Carry::on;
+    // The groups are only ever USED by the reference's bounds (KMCUDA_AMD_YY=reference / the forced switch).  What a
+    // caller can observe of their clustering besides -- its progress lines, and the C library's rand() state after
+    // its srand(0) and draws -- is kept either way: a silent call (verbosity 0) that will not use the groups only
+    // replays the draws (13 ms -> 0.05 ms at K = 1024, G = 102).
+    p.cluster_groups_for_real = !p.adaptive || sw.hand_over_forced() || verbosity > 0;
+    return p;
+  }
+
+  // Everything between seeding and the outputs.  `clock`: the entry point's laps.
+  int run(float tolerance, uint32_t yy_groups, PhaseClock &clock) {
+    const SchedulePlan plan = plan_schedule(tolerance, yy_groups);
+    if (plan.lloyd_only != SchedulePlan::LloydOnly::no) {
+      if (plan.lloyd_only == SchedulePlan::LloydOnly::too_few_clusters) INFO("too few clusters for this yinyang_t => Lloyd\n");
+      else INFO("tolerance is too high (>= %.2f) => Lloyd\n", kYinyangDraftReassignments);
+      return lloyd(tolerance, nullptr);
+    }
+    int iter = 0;
+    RETERR(draft_lloyd(&iter));
+    clock.lap("Lloyd down to 11 %% reassignments");
+    const int st = judge(iter, tolerance, false, nullptr, true);   // kmeans.cu:1058
+    if (st < 0) return -st;
+    if (st == 1) return 0;
+    // the reference's hand-over point: the K centroids are clustered into groups here (its progress lines are
+    // part of what a caller sees, its srand(0) of what a caller's rand() sees) -- whichever schedule follows
+    std::vector<uint32_t> groups;
+    RETERR(hand_over_groups(plan, yy_groups, &groups));
+    clock.lap("group clustering, whole");
+    bool bounds = !plan.adaptive;
+    if (plan.adaptive) {
+      RETERR(carried_phase(plan, tolerance, &iter, &bounds));
+      clock.lap("Lloyd after the hand-over point");
+    }
+    if (bounds) {
+      RETERR(yinyang(tolerance, yy_groups, iter, groups));
+      clock.lap("Yinyang");
+    }
+    return 0;
+  }
+
+  int draft_lloyd(int *iter) {
+    INFO("running Lloyd until reassignments drop below %u\n", (uint32_t)(kYinyangDraftReassignments * N));
+    return lloyd((float)kYinyangDraftReassignments, iter);
+  }
+
+  int hand_over_groups(const SchedulePlan &plan, uint32_t yy_groups, std::vector<uint32_t> *groups) {
+    return plan.cluster_groups_for_real ? cluster_groups(yy_groups, groups) : replay_group_seeding_draws(yy_groups);
+  }
+
+  // The default schedule behind the hand-over point: Lloyd goes on from iteration *iter, whose update is still due,
+  // with or without carried bounds.  *bounds: the run left for the reference's bounds (KMCUDA_AMD_YY_SWITCH), not
+  // for the stop rule.  The engines' carry flags and carry_after are this phase's: set here, cleared here.
+  int carried_phase(const SchedulePlan &plan, float tolerance, int *iter, bool *bounds) {
+    INFO(plan.carry_at_once ? "Lloyd goes on, carrying per-sample distance bounds from pass to pass\n" : "Lloyd goes on\n");
+    set_carry(plan.carry_at_once);
+    carry_after = (plan.carry && !plan.carry_at_once) ? *iter + 1 : 0;
+    const LeaveFn leave = [this](int, uint32_t changed) { return sw.hand_over_now(changed, N); };
+    RETERR(lloyd(tolerance, iter, sw.hand_over_forced() ? &leave : nullptr, bounds, *iter));
+    if (plan.carry && verbosity > 1) {
+      unsigned long long spared = 0, paired = 0;
+      for (auto &s : shards) {
+        unsigned long long v = 0;
+        if (s->eng->carry_stats(&v, nullptr) == 0) spared += v;
+        if (s->eng->carry_pair_stats(&v) == 0) paired += v;
+      }
+      printf("carried bounds: %llu sample passes decided without looking at the sample\n", spared);
+      if (paired) printf("carried pairs: %llu sample passes settled between two carried contenders\n", paired);
+    }
+    set_carry(false);
+    carry_after = 0;
+    return 0;
   }
 
   int gather_outputs(float *centroids, uint32_t *assignments, int32_t device_ptrs) {
@@ -1559,22 +1724,6 @@ class Job {
 };
 
 
-// The Yinyang phase of the default schedule.  The reference hands over from Lloyd to its bounds at 11 %
-// reassignments whatever the data; its bounds refresh (kmeans_yy_init: >= G exact chains per row) costs 38 assignment
-// passes on this hardware and its filters more than a pass per row that passes them (profiles/r2n_*, r3y_*): measured on
-// both benchmark data sets it never pays.  The default keeps the reference's sequence up to and including the hand-over
-// point (group clustering, its progress lines, its srand(0)) and then goes on with assignment passes that CARRY
-// per-row bounds from pass to pass at no refresh cost (lloyd_carry.hip).  Every pass either way is the reference's
-// arithmetic.  KMCUDA_AMD_YY=reference: the reference's own schedule and kernels.  KMCUDA_AMD_YY_SWITCH=<fraction>
-// (tests): hand over to the reference's bounds once the reassigned fraction is at most that.
-struct SwitchRule {
-  double N, force = -1.0;
-  explicit SwitchRule(uint32_t n) : N(n) {
-    if (const char *v = getenv("KMCUDA_AMD_YY_SWITCH")) force = atof(v);
-  }
-  bool now(uint32_t changed) const { return force >= 0 && (double)changed <= force * N; }
-};
-
 // Once per process and device: the iteration kernels' code objects are loaded by a helper thread while the calling
 // thread uploads the rows and seeds (they would otherwise load one by one in front of the first iteration: 24 ms of a
 // 45-ms call on 4M rows).  Fire and forget: a launch that needs a code object the helper is still loading waits for it
@@ -1587,7 +1736,7 @@ struct PreloadThreads {
       if (t.joinable()) t.join();
   }
 };
-void preload_code_objects(int dev, PreloadThreads *keep) {
+void preload_code_objects(int dev, PreloadThreads *keep, const KmeansSwitches &sw) {
   static std::mutex m;
   static std::vector<bool> done;
   {
@@ -1596,8 +1745,7 @@ void preload_code_objects(int dev, PreloadThreads *keep) {
     if (done[dev]) return;
     done[dev] = true;
   }
-  if (const char *v = getenv("KMCUDA_AMD_PRELOAD"))
-    if (atoi(v) == 0) return;
+  if (!sw.preload) return;
   keep->threads.emplace_back([dev] {
     if (hipSetDevice(dev) != hipSuccess) return;
     (void)preload_update_code();
@@ -1609,9 +1757,77 @@ void preload_code_objects(int dev, PreloadThreads *keep) {
   });
 }
 
-int virtual_shards() {
-  const char *v = getenv("KMCUDA_AMD_VIRTUAL_SHARDS");
-  return v ? atoi(v) : 0;
+int virtual_shards() { return kmeans_switches().virtual_shards; }   // (knn_cuda(): the one switch it shares)
+
+// the reference's device-mask test (kmcuda.cc:37-41, :553-557)
+bool device_mask_refused(uint32_t device) {
+  int ndev = 0;
+  (void)hipGetDeviceCount(&ndev);
+  return ndev < 32 && device > (1u << ndev);
+}
+
+// device-pointer inputs: whatever the caller still has in flight on that GPU (any stream) must have
+// landed before our own non-blocking streams read it -- the reference got this from the legacy
+// default stream's implicit synchronisation
+void sync_callers_device(int32_t device_ptrs) {
+  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();
+}
+
+// reference: check_kmeans_args, kmcuda.cc:19-61 (same order), then what sample weights refuse -- all of it before any
+// device is touched
+int check_kmeans_args(const KmeansSwitches &sw, KMCUDAInitMethod init, float tolerance, float yinyang_t,
+                      uint32_t samples_size, uint16_t features_size, uint32_t clusters_size, uint32_t device,
+                      int32_t fp16x2, int32_t verbosity, const float *samples, const float *centroids,
+                      const uint32_t *assignments, const float *sample_weights) {
+  if (clusters_size < 2 || clusters_size == UINT32_MAX) return kmcudaInvalidArguments;
+  if (features_size == 0) return kmcudaInvalidArguments;
+  if (samples_size < clusters_size) return kmcudaInvalidArguments;
+  if (device_mask_refused(device)) return kmcudaNoSuchDevice;
+  if (samples == nullptr || centroids == nullptr || assignments == nullptr) return kmcudaInvalidArguments;
+  if (tolerance < 0 || tolerance > 1) return kmcudaInvalidArguments;
+  if (yinyang_t < 0 || yinyang_t > 0.5) return kmcudaInvalidArguments;
+  if (!sample_weights) return kmcudaSuccess;
+  // what restates the reference's own arithmetic has no weighted counterpart
+  if (init == kmcudaInitMethodAFKMC2 || sw.exact_update || (fp16x2 && sw.fp16_strict)) {
+    INFO("sample weights are not supported with afkmc2, KMCUDA_AMD_EXACT_UPDATE=1 or KMCUDA_AMD_FP16_STRICT=1\n");
+    return kmcudaInvalidArguments;
+  }
+  if (init == kmcudaInitMethodParallel) {   // (weighted k-means|| does not exist: refused as afkmc2)
+    INFO("sample weights are not supported with k-means||\n");
+    return kmcudaInvalidArguments;
+  }
+  return kmcudaSuccess;
+}
+
+// init = k-means|| (seed_par_job.cpp): the stand-alone seeding writes `centroids` on the first device of the mask (the
+// rows' own device in device-pointer mode), and the call goes on exactly as with imported centroids: *init becomes
+// Import.  Host rows are uploaded twice, once by the seeding and once by the job.  Any other method: nothing happens.
+int seed_parallel_first(KMCUDAInitMethod *init, const void *init_params, KMCUDADistanceMetric metric,
+                        uint32_t samples_size, uint16_t features_size, uint32_t clusters_size, uint32_t seed,
+                        int first_device, int32_t device_ptrs, int32_t fp16x2, int32_t verbosity, const float *samples,
+                        float *centroids) {
+  if (*init != kmcudaInitMethodParallel) return kmcudaSuccess;
+  const auto *sp = static_cast<const kmamd_seed_parallel_params *>(init_params);
+  INFO("performing k-means||...\n");
+  RETERR(kmamd_kmeans_seed_parallel(metric, samples_size, fp16x2 ? (uint16_t)(2u * features_size) : features_size,
+                                    clusters_size, sp ? sp->rounds : 0u, sp ? sp->oversampling : 0.f, seed,
+                                    device_ptrs >= 0 ? device_ptrs : first_device, device_ptrs, fp16x2, verbosity, samples,
+                                    centroids, nullptr, nullptr, 0, nullptr, nullptr, nullptr));
+  kmx::g_verbosity = verbosity;
+  *init = kmcudaInitMethodImport;
+  return kmcudaSuccess;
+}
+
+// the run's statistics for kmamd_last_run_stats / kmamd_last_run_collective, once the loops are over
+void publish_run_stats(Job &job, std::chrono::steady_clock::time_point t_loop) {
+  job.stats.loop_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
+  job.collective_collect();
+  if (job.sw.update_trace)   // (a measurement aid: which way the updates went; nothing is printed inside the loop)
+    for (auto &s : job.shards)
+      fprintf(stderr, "[update] shard on device %d: %u radix, %u direct; loop %.4f s\n", s->dev, s->eng->ms_.n_radix, s->eng->ms_.n_direct,
+              job.stats.loop_seconds);
+  std::lock_guard<std::mutex> lock(g_last_run_mutex);
+  g_last_run = job.stats;
 }
 
 }  // namespace
@@ -1629,7 +1845,8 @@ KMCUDAResult kmeans_cuda(KMCUDAInitMethod init, const void *init_params, float t
                                                          nullptr));
 }
 
-// kmeans_cuda() with per-row sample weights (include/kmcuda_amd.h); sample_weights == nullptr: kmeans_cuda() itself
+// kmeans_cuda() with per-row sample weights (include/kmcuda_amd.h); sample_weights == nullptr: kmeans_cuda() itself.
+// The phases: arguments, devices, the k-means|| detour, set-up, seeding, the schedule (Job::run), statistics, outputs.
 int kmamd_kmeans_weighted(int init_, const void *init_params, float tolerance, float yinyang_t, int metric_,
                           uint32_t samples_size, uint16_t features_size, uint32_t clusters_size, uint32_t seed,
                           uint32_t device, int32_t device_ptrs, int32_t fp16x2, int32_t verbosity, const float *samples,
@@ -1641,74 +1858,31 @@ int kmamd_kmeans_weighted(int init_, const void *init_params, float tolerance, f
   DEBUG("arguments: %d %p %.3f %.2f %d %u %u %u %u %u %d %d %p %p %p %p\n", init, init_params, tolerance, yinyang_t,
         metric, samples_size, (unsigned)features_size, clusters_size, seed, device, fp16x2, verbosity,
         (const void *)samples, (void *)centroids, (void *)assignments, (void *)average_distance);
-  // reference: check_kmeans_args, kmcuda.cc:19-61 (same order)
-  if (clusters_size < 2 || clusters_size == UINT32_MAX) return kmcudaInvalidArguments;
-  if (features_size == 0) return kmcudaInvalidArguments;
-  if (samples_size < clusters_size) return kmcudaInvalidArguments;
-  int ndev = 0;
-  (void)hipGetDeviceCount(&ndev);
-  if (ndev < 32 && device > (1u << ndev)) return kmcudaNoSuchDevice;
-  if (samples == nullptr || centroids == nullptr || assignments == nullptr) return kmcudaInvalidArguments;
-  if (tolerance < 0 || tolerance > 1) return kmcudaInvalidArguments;
-  if (yinyang_t < 0 || yinyang_t > 0.5) return kmcudaInvalidArguments;
-  if (sample_weights) {
-    // what restates the reference's own arithmetic has no weighted counterpart (refused before any device is touched)
-    const char *xu = getenv("KMCUDA_AMD_EXACT_UPDATE"), *sh = getenv("KMCUDA_AMD_FP16_STRICT");
-    if (init == kmcudaInitMethodAFKMC2 || (xu && atoi(xu) != 0) || (fp16x2 && sh && atoi(sh) != 0)) {
-      INFO("sample weights are not supported with afkmc2, KMCUDA_AMD_EXACT_UPDATE=1 or KMCUDA_AMD_FP16_STRICT=1\n");
-      return kmcudaInvalidArguments;
-    }
-  }
-  if (init == kmcudaInitMethodParallel && sample_weights) {   // (weighted k-means|| does not exist: refused as afkmc2)
-    INFO("sample weights are not supported with k-means||\n");
-    return kmcudaInvalidArguments;
-  }
+  const KmeansSwitches sw = kmeans_switches();   // read here, once: nothing below looks at the environment
+  RETERR(check_kmeans_args(sw, init, tolerance, yinyang_t, samples_size, features_size, clusters_size, device, fp16x2,
+                           verbosity, samples, centroids, assignments, sample_weights));
   INFO("reassignments threshold: %u\n", uint32_t(tolerance * samples_size));
   const uint32_t yy_groups_size = yinyang_t * clusters_size;  // float product, truncated (kmcuda.cc:417)
   DEBUG("yinyang groups: %u\n", yy_groups_size);
   auto devs = setup_devices(device, verbosity);
   if (devs.empty()) return kmcudaNoSuchDevice;
-  if (init == kmcudaInitMethodParallel) {
-    // k-means|| (seed_par_job.cpp): the stand-alone seeding writes `centroids` on the first device of the mask (the
-    // rows' own device in device-pointer mode), and the call goes on exactly as with imported centroids.  Host rows
-    // are uploaded twice, once by the seeding and once below.
-    const auto *sp = static_cast<const kmamd_seed_parallel_params *>(init_params);
-    INFO("performing k-means||...\n");
-    RETERR(kmamd_kmeans_seed_parallel(metric, samples_size, fp16x2 ? (uint16_t)(2u * features_size) : features_size,
-                                      clusters_size, sp ? sp->rounds : 0u, sp ? sp->oversampling : 0.f, seed,
-                                      device_ptrs >= 0 ? device_ptrs : devs[0], device_ptrs, fp16x2, verbosity, samples,
-                                      centroids, nullptr, nullptr, 0, nullptr, nullptr, nullptr));
-    kmx::g_verbosity = verbosity;
-    init = kmcudaInitMethodImport;
-  }
-
-  // device-pointer inputs: whatever the caller still has in flight on that GPU (any stream) must have
-  // landed before our own non-blocking streams read it -- the reference got this from the legacy
-  // default stream's implicit synchronisation
-  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();
+  RETERR(seed_parallel_first(&init, init_params, metric, samples_size, features_size, clusters_size, seed, devs[0],
+                             device_ptrs, fp16x2, verbosity, samples, centroids));
+  sync_callers_device(device_ptrs);
   PreloadThreads preload;   // (joined when this call returns, whichever way)
-  for (int d : devs) preload_code_objects(d, &preload);
-  const auto t_begin = std::chrono::steady_clock::now();
+  for (int d : devs) preload_code_objects(d, &preload, sw);
   // KMCUDA_AMD_TIMING=1: wall-clock laps of the call's phases on stderr (a measurement aid; each lap waits for the GPUs)
-  const bool timing = getenv("KMCUDA_AMD_TIMING") != nullptr;
-  auto t_lap = t_begin;
+  PhaseClock clock(sw.timing);
+  const auto t_begin = clock.t_lap;
   Job job;
-  auto lap = [&](const char *what) {
-    if (!timing) return;
-    (void)job.sync_all();
-    const auto t1 = std::chrono::steady_clock::now();
-    fprintf(stderr, "[timing] %s: %.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t_lap).count());
-    t_lap = t1;
-  };
+  clock.wait = [&job] { (void)job.sync_all(); };
   job.fp16 = fp16x2 != 0;
-  if (const char *v = getenv("KMCUDA_AMD_FP16_STRICT")) job.strict_h2 = job.fp16 && atoi(v) != 0;
+  job.strict_h2 = job.fp16 && sw.fp16_strict;
   // fp16x2: features_size counts half2 pairs (kmcuda.h:107-108); internally one feature per half
   const uint32_t feats = fp16x2 ? 2u * features_size : features_size;
-  RETERR(job.setup(devs, virtual_shards(), samples_size, feats, clusters_size, metric, verbosity, samples,
+  RETERR(job.setup(sw, devs, sw.virtual_shards, samples_size, feats, clusters_size, metric, verbosity, samples,
                    device_ptrs, nullptr, sample_weights));
-  if (const char *v = getenv("KMCUDA_AMD_EXACT_UPDATE")) job.exact_update = atoi(v) != 0;
-  if (job.strict_h2) job.exact_update = true;   // the reference's serial update, in half2 arithmetic
-  lap("set-up (engines, uploads)");
+  clock.lap("set-up (engines, uploads)");
   if (job.exact_update && job.shards.size() > 1) {
     INFO("KMCUDA_AMD_EXACT_UPDATE needs all rows on one GPU (the reference's update order is global)\n");
     return kmcudaInvalidArguments;
@@ -1716,106 +1890,18 @@ int kmamd_kmeans_weighted(int init_, const void *init_params, float tolerance, f
   const uint32_t afk_m = (init == kmcudaInitMethodAFKMC2 && init_params) ? *reinterpret_cast<const uint32_t *>(init_params) : 0;
   RETERR(job.init_centroids(init, seed, centroids, device_ptrs, afk_m));
   RETERR(job.sync_all());
-  lap("seeding");
+  clock.lap("seeding");
   const auto t_loop = std::chrono::steady_clock::now();
   job.stats.setup_seconds = std::chrono::duration<double>(t_loop - t_begin).count();
   job.stats.shards = (uint32_t)job.shards.size();
   job.stats.rccl = job.comms.empty() ? 0u : (uint32_t)job.comms.size();
-
-  if (yy_groups_size == 0 || kYinyangDraftReassignments <= tolerance) {  // kmeans.cu:1037-1050
-    if (yy_groups_size == 0) INFO("too few clusters for this yinyang_t => Lloyd\n");
-    else INFO("tolerance is too high (>= %.2f) => Lloyd\n", kYinyangDraftReassignments);
-    RETERR(job.lloyd(tolerance, nullptr));
-  } else {
-    // KMCUDA_AMD_YY=reference: the reference's fixed schedule (Lloyd down to 11 % reassignments, then its bounds).
-    // Default: the same hand-over point, then assignment passes that carry per-sample bounds (SwitchRule above).
-    // The strict parity modes keep the reference's schedule.
-    const char *yym = getenv("KMCUDA_AMD_YY");
-    const bool wide = job.shards[0]->eng->DP_ == 0 && job.shards[0]->eng->wide_dp_ != 0;   // D > 256: lloyd_wide.hip
-    // (KMCUDA_AMD_YY=carry: the default schedule also under the strict update -- every pass is the reference's Lloyd
-    //  arithmetic, so the whole call then equals the reference's kmeans_cuda_lloyd bit for bit: the parity test of the
-    //  carried bounds against the oracle end to end, tests/test_gpu_carry.py)
-    const bool carry_asked = yym && strcmp(yym, "carry") == 0;
-    const bool adaptive = !(yym && strcmp(yym, "reference") == 0) && (!job.exact_update || (carry_asked && !job.strict_h2)) &&
-                          ((job.shards[0]->eng->DP_ != 0 && job.shards[0]->eng->filter_mode_ == 0) || wide);
-    INFO("running Lloyd until reassignments drop below %u\n", (uint32_t)(kYinyangDraftReassignments * samples_size));
-    const SwitchRule rule(samples_size);
-    int iter = 0;
-    RETERR(job.lloyd((float)kYinyangDraftReassignments, &iter));
-    lap("Lloyd down to 11 % reassignments");
-    // (weighted: the reassigned weight is in the stop iteration's reduced buffer, not in the counters)
-    const int st = job.weighted ? job.check_changed_reduced(iter, tolerance, false)
-                                : job.check_changed(iter, tolerance, false);  // kmeans.cu:1058
-    if (st < 0) return static_cast<KMCUDAResult>(-st);
-    if (st == 0) {
-      // the reference's hand-over point: the K centroids are clustered into groups here (its progress lines are
-      // part of what a caller sees, its srand(0) of what a caller's rand() sees) -- whichever schedule follows
-      std::vector<uint32_t> groups;
-      // The groups are only ever USED by the reference's bounds (KMCUDA_AMD_YY=reference / the forced switch).  What a
-      // caller can observe of their clustering besides -- its progress lines, and the C library's rand() state after
-      // its srand(0) and draws -- is kept either way: a silent call (verbosity 0) that will not use the groups only
-      // replays the draws (13 ms -> 0.05 ms at K = 1024, G = 102).
-      if (!adaptive || rule.force >= 0 || verbosity > 0) {
-        RETERR(job.cluster_groups(yy_groups_size, &groups));
-      } else {
-        RETERR(job.replay_group_seeding_draws(yy_groups_size));
-      }
-      lap("group clustering, whole");
-      bool bounds = !adaptive;
-      if (adaptive) {
-        const char *cv = getenv("KMCUDA_AMD_CARRY");
-        // (rows wider than 256 features: the streamed filter carries the bounds itself, up to 4096 features)
-        const bool carry = !(cv && atoi(cv) == 0) && (!wide || job.shards[0]->eng->wide_dp_ <= 4096u);
-        // The first carried pass only LEAVES bounds (and allocates them: 24 bytes per row); rows are spared from the
-        // second one on.  A run that stops within a pass or two of the hand-over point never earns that back (round 4:
-        // the 4M-row mixture at tolerance 0.01, one iteration after the hand-over, +12-16 %), and how long a run will
-        // last cannot be read off its first counts (they fall by a factor of 4-8 per iteration, the tail by 1.1: an
-        // extrapolation tried in round 5 switched the bounds off for the 37-iteration run,
-        // profiles/r5e_configs_carry_extrapolation_rule_misfires.log).  So the bounds start once the host has SEEN the
-        // run go on past an iteration after the hand-over (Job::lloyd, carry_after).  KMCUDA_AMD_CARRY=1: at once
-        // (tests: every pass after the hand-over is then a carried one).
-        const bool at_once = carry && cv && atoi(cv) != 0;
-        INFO(at_once ? "Lloyd goes on, carrying per-sample distance bounds from pass to pass\n" : "Lloyd goes on\n");
-        for (auto &s : job.shards) {
-          s->eng->carry_on_ = at_once;
-          s->eng->carry_valid_ = false;
-        }
-        job.carry_after = (carry && !at_once) ? iter + 1 : 0;
-        const Job::LeaveFn leave = [&rule](int, uint32_t changed) { return rule.now(changed); };
-        RETERR(job.lloyd(tolerance, &iter, rule.force >= 0 ? &leave : nullptr, &bounds, iter));
-        if (carry && verbosity > 1) {
-          unsigned long long spared = 0, paired = 0;
-          for (auto &s : job.shards) {
-            unsigned long long v = 0;
-            if (s->eng->carry_stats(&v, nullptr) == 0) spared += v;
-            if (s->eng->carry_pair_stats(&v) == 0) paired += v;
-          }
-          printf("carried bounds: %llu sample passes decided without looking at the sample\n", spared);
-          if (paired) printf("carried pairs: %llu sample passes settled between two carried contenders\n", paired);
-        }
-        for (auto &s : job.shards) s->eng->carry_on_ = false;
-        job.carry_after = 0;
-        lap("Lloyd after the hand-over point");
-      }
-      if (bounds) RETERR(job.yinyang(tolerance, yy_groups_size, iter, groups));
-      if (bounds) lap("Yinyang");
-    }
-  }
+  RETERR(job.run(tolerance, yy_groups_size, clock));
   RETERR(job.sync_all());
-  job.stats.loop_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
-  job.collective_collect();
-  if (getenv("KMCUDA_AMD_UPDATE_TRACE"))   // (a measurement aid: which way the updates went; nothing is printed inside the loop)
-    for (auto &s : job.shards)
-      fprintf(stderr, "[update] shard on device %d: %u radix, %u direct; loop %.4f s\n", s->dev, s->eng->ms_.n_radix, s->eng->ms_.n_direct,
-              job.stats.loop_seconds);
-  {
-    std::lock_guard<std::mutex> lock(g_last_run_mutex);
-    g_last_run = job.stats;
-  }
-  lap("loop end");
+  publish_run_stats(job, t_loop);
+  clock.lap("loop end");
   if (average_distance) RETERR(job.average_distance(average_distance));
   RETERR(job.gather_outputs(centroids, assignments, device_ptrs));
-  lap("outputs");
+  clock.lap("outputs");
   DEBUG("return kmcudaSuccess\n");
   return kmcudaSuccess;
 }
@@ -1832,13 +1918,11 @@ KMCUDAResult knn_cuda(uint16_t k, KMCUDADistanceMetric metric, uint32_t samples_
   if (clusters_size < 2 || clusters_size == UINT32_MAX) return kmcudaInvalidArguments;
   if (features_size == 0) return kmcudaInvalidArguments;
   if (samples_size < clusters_size) return kmcudaInvalidArguments;
-  int ndev = 0;
-  (void)hipGetDeviceCount(&ndev);
-  if (ndev < 32 && device > (1u << ndev)) return kmcudaNoSuchDevice;
+  if (device_mask_refused(device)) return kmcudaNoSuchDevice;
   if (!samples || !centroids || !assignments || !neighbors) return kmcudaInvalidArguments;
   auto devs = setup_devices(device, verbosity);
   if (devs.empty()) return kmcudaNoSuchDevice;
-  if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();  // as kmeans_cuda
+  sync_callers_device(device_ptrs);   // as kmeans_cuda
   KnnCorpus c;
   c.metric = metric; c.fp16 = fp16x2 != 0; c.N = samples_size; c.K = clusters_size;
   c.D = fp16x2 ? 2u * features_size : features_size;  // kmcuda.h:107-108

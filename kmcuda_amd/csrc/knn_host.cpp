@@ -14,7 +14,7 @@ KnnSwitches knn_switches() {
   KnnSwitches sw;
   auto on = [](const char *v) { return v && atoi(v) != 0; };
   sw.exact = on(getenv("KMCUDA_AMD_KNN_EXACT"));
-  sw.fp16_strict = on(getenv("KMCUDA_AMD_FP16_STRICT"));
+  sw.fp16_strict = fp16_strict_requested();
   const char *filter = getenv("KMCUDA_AMD_FILTER");
   sw.filter_f32 = filter && strcmp(filter, "f32") == 0;
   const char *tight = getenv("KMCUDA_AMD_KNN_TIGHT");

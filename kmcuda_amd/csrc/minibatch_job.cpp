@@ -233,16 +233,11 @@ struct kmamd_minibatch {
 
 namespace {
 
-bool fp16_strict() {
-  const char *v = getenv("KMCUDA_AMD_FP16_STRICT");
-  return v && atoi(v) != 0;
-}
-
 // what step and fit refuse about their rows, before any device work
 int rows_refused(const kmamd_minibatch *h, uint64_t n, int32_t fp16x2, int32_t device_ptrs) {
   if (!h) return kmcudaInvalidArguments;
   if (device_ptrs >= 0 && device_ptrs != h->device) return kmcudaInvalidArguments;
-  if (fp16x2 && ((h->D & 1u) || fp16_strict())) return kmcudaInvalidArguments;
+  if (fp16x2 && ((h->D & 1u) || fp16_strict_requested())) return kmcudaInvalidArguments;
   if (n > assign_chunk_rows(h->D)) return kmcudaInvalidArguments;
   return 0;
 }

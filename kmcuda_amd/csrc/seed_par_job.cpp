@@ -12,7 +12,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <chrono>
 #include <vector>
 
 #include "../../include/kmcuda_amd.h"
@@ -57,16 +56,7 @@ struct SeedParJob {
     if (!w.stream) return kmcudaRuntimeError;
     const hipStream_t st = w.stream;
     // KMCUDA_AMD_TIMING=1: wall-clock laps of the call's phases on stderr, as kmeans_cuda() (each lap waits for the GPU)
-    const bool timing = getenv("KMCUDA_AMD_TIMING") != nullptr;
-    auto t_lap = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what, uint32_t r) {
-      if (!timing) return;
-      (void)hipStreamSynchronize(st);
-      const auto t1 = std::chrono::steady_clock::now();
-      fprintf(stderr, "[timing] k-means|| round %u %s: %.3f ms\n", r, what,
-              std::chrono::duration<double, std::milli>(t1 - t_lap).count());
-      t_lap = t1;
-    };
+    PhaseClock clock(getenv("KMCUDA_AMD_TIMING") != nullptr, [st] { (void)hipStreamSynchronize(st); });
 
     // ---- the rows: fp32 on this device, and the halves they were widened from ----
     RowStage stage;
@@ -124,12 +114,12 @@ struct SeedParJob {
         KNN_TRY(slot.get(device, N, D, b.M, metric, st, rows16, &eng));
         KMX_HIPRT(hipMemsetD32Async((hipDeviceptr_t)asg, (int)b.M, N, st));
         KNN_TRY(eng->lloyd_assign(rows32, b.rows, asg, prev, false));
-        lap("assignment", r);
+        clock.lap("k-means|| round %u assignment", r);
       } else {
         KMX_HIPRT(hipMemsetD32Async((hipDeviceptr_t)asg, 0, N, st));
       }
       KMX_HIPRT(launch_assigned_distances(metric, rows32, N, D, b.rows, asg, b.M, dist, st));
-      lap("distance", r);
+      clock.lap("k-means|| round %u distance", r);
       KMX_HIPRT(launch_seed_par_update(term, dist, N, is_first ? rows32 : nullptr, D, bsum, phi, st));
       return 0;
     };
@@ -146,7 +136,7 @@ struct SeedParJob {
       batches.push_back(b);
       total = 1;
       ends.push_back(total);
-      lap("term update", 0);
+      clock.lap("k-means|| round %u term update", 0u);
     }
 
     // ---- rounds 1 .. R (phi == 0 draws nothing: the remaining rounds add no candidate) ----
@@ -162,9 +152,9 @@ struct SeedParJob {
         KNN_TRY(w.alloc(&b.ids, M));
         KNN_TRY(w.alloc(&b.rows, (size_t)M * D));
         KMX_HIPRT(launch_seed_par_fill(term, N, seed, r, phi, ell, boff, carry, M, rows32, D, b.ids, b.rows, st));
-        lap("draw (count, prefix, fill)", r);
+        clock.lap("k-means|| round %u draw (count, prefix, fill)", r);
         KNN_TRY(absorb(b, false, r));
-        lap("term update", r);
+        clock.lap("k-means|| round %u term update", r);
         batches.push_back(b);
         total += M;
       }
@@ -201,7 +191,7 @@ struct SeedParJob {
     KMX_HIPCP(hipMemcpyAsync(ids_host.data(), ids_all, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KMX_HIPRT(hipStreamSynchronize(st));
     slot.reset();
-    lap("weighting pass", rounds);
+    clock.lap("k-means|| round %u weighting pass", rounds);
 
     // ---- the live candidates, in order ----
     std::vector<uint32_t> live_rows;
@@ -258,7 +248,7 @@ struct SeedParJob {
       KMX_HIPCP(hipMemcpyAsync(centroids, cen_dev, (size_t)K * D * esz, hipMemcpyDeviceToHost, st));
       KMX_HIPRT(hipStreamSynchronize(st));
     }
-    lap(fall ? "k-means++ on the rows" : "recluster", rounds);
+    clock.lap("k-means|| round %u %s", rounds, fall ? "k-means++ on the rows" : "recluster");
 
     // ---- the optional reports (host memory, whatever device_ptrs says) ----
     const uint32_t ncopy = total < capacity ? total : capacity;
