@@ -110,11 +110,10 @@ hipError_t launch_assigned_distances(int metric, const float *samples, uint32_t 
                                      const uint32_t *assignments, uint32_t K, float *dists, hipStream_t st) {
   if (N == 0) return hipSuccess;
   const dim3 grid(assigned_distance_grid(N)), block(kAdBlock);
-  if (metric == 0)
-    hipLaunchKernelGGL((assigned_distance_kernel<0>), grid, block, 0, st, samples, N, D, centroids, assignments, K, dists);
-  else
-    hipLaunchKernelGGL((assigned_distance_kernel<1>), grid, block, 0, st, samples, N, D, centroids, assignments, K, dists);
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((assigned_distance_kernel<M()>), grid, block, 0, st, samples, N, D, centroids, assignments, K, dists);
+    return hipGetLastError();
+  });
 }
 
 // One wave per cluster over the chunk's CSR (launch_inverse_assignments: a stable sort, so a cluster's rows stand in

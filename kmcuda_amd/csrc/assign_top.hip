@@ -444,56 +444,35 @@ hipError_t launch_assign_top_exact(int metric, const float *samples, uint32_t N,
   if (N == 0) return hipSuccess;
   uint32_t grid = wave_row_grid(N);
   if (rows && grid > 4096u) grid = 4096u;   // a list: few rows as a rule, the grid strides over it
-  if (metric == 0)
-    hipLaunchKernelGGL((assign_top_exact_kernel<0>), dim3(grid), dim3(256), 0, st, samples, N, D, ct, csqr, K, Kt, m,
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((assign_top_exact_kernel<M()>), dim3(grid), dim3(256), 0, st, samples, N, D, ct, csqr, K, Kt, m,
                        rows, nrows, top, evaluated);
-  else
-    hipLaunchKernelGGL((assign_top_exact_kernel<1>), dim3(grid), dim3(256), 0, st, samples, N, D, ct, csqr, K, Kt, m,
-                       rows, nrows, top, evaluated);
-  return hipGetLastError();
-}
-
-template <int DP>
-static hipError_t launch_scores_dp(const AssignTopFilter &a, const float *samples, uint32_t n, hipStream_t st) {
-  const bool fast = a.D == (uint32_t)DP && (((uintptr_t)samples) & 15u) == 0;
-  const size_t lds_bytes = (2 * 32 * (DP + 4) + 64) * sizeof(float);
-  const void *fn = fast ? reinterpret_cast<const void *>(&assign_top_scores_kernel<DP, true>)
-                        : reinterpret_cast<const void *>(&assign_top_scores_kernel<DP, false>);
-  // (per launch: the attribute belongs to the current device's copy of the kernel)
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) return e;
-  const dim3 grid((n + 127u) / 128u), block(256);
-  if (fast)
-    hipLaunchKernelGGL((assign_top_scores_kernel<DP, true>), grid, block, lds_bytes, st, samples, n, a.D, a.cfil,
-                       a.bias, a.mu, a.K_pad, a.stats, a.eps, a.metric, a.scores, a.meta);
-  else
-    hipLaunchKernelGGL((assign_top_scores_kernel<DP, false>), grid, block, lds_bytes, st, samples, n, a.D, a.cfil,
-                       a.bias, a.mu, a.K_pad, a.stats, a.eps, a.metric, a.scores, a.meta);
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_assign_top_filter(const AssignTopFilter &a, const float *samples, uint32_t n, uint32_t row0,
                                     uint32_t *top, hipStream_t st) {
   if (n == 0) return hipSuccess;
-  hipError_t e;
-  switch (a.DP) {
-    case 8: e = launch_scores_dp<8>(a, samples, n, st); break;
-    case 16: e = launch_scores_dp<16>(a, samples, n, st); break;
-    case 32: e = launch_scores_dp<32>(a, samples, n, st); break;
-    case 64: e = launch_scores_dp<64>(a, samples, n, st); break;
-    case 128: e = launch_scores_dp<128>(a, samples, n, st); break;
-    case 256: e = launch_scores_dp<256>(a, samples, n, st); break;
-    default: e = hipErrorInvalidValue;
-  }
+  const hipError_t e = with_width<FilterWidths>(a.DP, [&](auto DP) {
+    return with_flag(a.D == (uint32_t)DP() && (((uintptr_t)samples) & 15u) == 0, [&](auto FAST) {
+      const size_t lds_bytes = (2 * 32 * (DP() + 4) + 64) * sizeof(float);
+      // (per launch: the attribute belongs to the current device's copy of the kernel)
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&assign_top_scores_kernel<DP(), FAST()>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((assign_top_scores_kernel<DP(), FAST()>), dim3((n + 127u) / 128u), dim3(256), lds_bytes, st,
+                         samples, n, a.D, a.cfil, a.bias, a.mu, a.K_pad, a.stats, a.eps, a.metric, a.scores, a.meta);
+      return hipGetLastError();
+    });
+  });
   if (e != hipSuccess) return e;
-  const dim3 grid(wave_row_grid(n)), block(256);
-  if (a.metric == 0)
-    hipLaunchKernelGGL((assign_top_select_kernel<0>), grid, block, 0, st, samples, n, a.D, a.centroids, a.csqr, a.K,
-                       a.K_pad, a.m, a.scores, a.meta, row0, top, a.fb_rows, a.fb_count, a.evaluated);
-  else
-    hipLaunchKernelGGL((assign_top_select_kernel<1>), grid, block, 0, st, samples, n, a.D, a.centroids, a.csqr, a.K,
-                       a.K_pad, a.m, a.scores, a.meta, row0, top, a.fb_rows, a.fb_count, a.evaluated);
-  return hipGetLastError();
+  return with_metric(a.metric, [&](auto M) {
+    hipLaunchKernelGGL((assign_top_select_kernel<M()>), dim3(wave_row_grid(n)), dim3(256), 0, st, samples, n, a.D,
+                       a.centroids, a.csqr, a.K, a.K_pad, a.m, a.scores, a.meta, row0, top, a.fb_rows, a.fb_count,
+                       a.evaluated);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_assign_top_distances(int metric, const float *samples, uint32_t N, uint32_t D,
@@ -502,11 +481,10 @@ hipError_t launch_assign_top_distances(int metric, const float *samples, uint32_
   if (N == 0) return hipSuccess;
   const uint64_t slots = (uint64_t)N * m, blocks = (slots + 255) / 256;
   const dim3 grid((uint32_t)(blocks < kWaveRowGridMax ? blocks : kWaveRowGridMax)), block(256);
-  if (metric == 0)
-    hipLaunchKernelGGL((assign_top_dist_kernel<0>), grid, block, 0, st, samples, slots, D, centroids, K, m, top, dists);
-  else
-    hipLaunchKernelGGL((assign_top_dist_kernel<1>), grid, block, 0, st, samples, slots, D, centroids, K, m, top, dists);
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((assign_top_dist_kernel<M()>), grid, block, 0, st, samples, slots, D, centroids, K, m, top, dists);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace kmx

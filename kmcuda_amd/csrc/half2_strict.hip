@@ -287,59 +287,84 @@ __global__ void h2_yy_local_kernel(const float *__restrict__ samples, uint32_t l
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-#define H2_LAUNCH(metric, kernel, n, st, ...)                                                                  \
-  do {                                                                                                         \
-    if ((n) == 0) return hipSuccess;                                                                           \
-    if ((metric) == 0) hipLaunchKernelGGL((kernel<0>), dim3(((n) + 127) / 128), dim3(128), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((kernel<1>), dim3(((n) + 127) / 128), dim3(128), 0, st, __VA_ARGS__);              \
-    return hipGetLastError();                                                                                  \
-  } while (0)
+// a thread per item, 128 per block: launch(M, grid, block) with the metric as a type; nothing to do for n == 0
+template <class F>
+static hipError_t h2_launch(int metric, uint32_t n, F &&launch) {
+  if (n == 0) return hipSuccess;
+  return with_metric(metric, [&](auto M) {
+    launch(M, dim3((n + 127) / 128), dim3(128));
+    return hipGetLastError();
+  });
+}
 
 hipError_t launch_h2_csqr(int metric, const float *centroids, uint32_t K, uint32_t D, float *sq2, hipStream_t st) {
-  H2_LAUNCH(metric, h2_csqr_kernel, K, st, centroids, K, D, sq2);
+  return h2_launch(metric, K, [&](auto M, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((h2_csqr_kernel<M()>), grid, block, 0, st, centroids, K, D, sq2);
+  });
 }
 hipError_t launch_h2_assign(int metric, const float *samples, uint32_t N, uint32_t D, const float *centroids, uint32_t K,
                             const float *sq2, uint32_t *assignments, uint32_t *assignments_prev, uint32_t *counters,
                             hipStream_t st) {
-  H2_LAUNCH(metric, h2_assign_kernel, N, st, samples, N, D, centroids, K, sq2, assignments, assignments_prev, counters);
+  return h2_launch(metric, N, [&](auto M, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((h2_assign_kernel<M()>), grid, block, 0, st, samples, N, D, centroids, K, sq2, assignments,
+                       assignments_prev, counters);
+  });
 }
 hipError_t launch_h2_adjust(int metric, const float *samples, uint32_t N, uint32_t D, uint32_t K, const uint32_t *prev,
                             const uint32_t *cur, float *centroids, uint32_t *ccounts, hipStream_t st) {
-  H2_LAUNCH(metric, h2_adjust_kernel, K, st, samples, N, D, K, prev, cur, centroids, ccounts);
+  return h2_launch(metric, K, [&](auto M, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((h2_adjust_kernel<M()>), grid, block, 0, st, samples, N, D, K, prev, cur, centroids, ccounts);
+  });
 }
 hipError_t launch_h2_to_row(int metric, const float *samples, uint32_t N, uint32_t D, const float *row, uint32_t cc,
                             int mode, float *dists, hipStream_t st) {
-  H2_LAUNCH(metric, h2_to_row_kernel, N, st, samples, N, D, row, cc, mode, dists);
+  return h2_launch(metric, N, [&](auto M, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((h2_to_row_kernel<M()>), grid, block, 0, st, samples, N, D, row, cc, mode, dists);
+  });
 }
 hipError_t launch_h2_member(int metric, const float *samples, uint32_t N, uint32_t D, const float *centroids,
                             const uint32_t *assignments, uint32_t K, float *dists, hipStream_t st) {
-  H2_LAUNCH(metric, h2_member_kernel, N, st, samples, N, D, centroids, assignments, K, dists);
+  return h2_launch(metric, N, [&](auto M, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((h2_member_kernel<M()>), grid, block, 0, st, samples, N, D, centroids, assignments, K, dists);
+  });
 }
 hipError_t launch_h2_afk_min_dist(int metric, uint32_t m, uint32_t k, const float *samples, uint32_t D,
                                   const uint32_t *choices, const float *centroids, float *min_dists, hipStream_t st) {
-  H2_LAUNCH(metric, h2_afk_min_dist_kernel, m, st, m, k, samples, D, choices, centroids, min_dists);
+  return h2_launch(metric, m, [&](auto M, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((h2_afk_min_dist_kernel<M()>), grid, block, 0, st, m, k, samples, D, choices, centroids,
+                       min_dists);
+  });
 }
 hipError_t launch_h2_yy_init(int metric, const float *samples, uint32_t len, uint32_t D, uint32_t K, uint32_t G,
                              const float *centroids, const uint32_t *assignments, const uint32_t *groups, float *bounds,
                              hipStream_t st) {
-  H2_LAUNCH(metric, h2_yy_init_kernel, len, st, samples, len, D, K, G, centroids, assignments, groups, bounds);
+  return h2_launch(metric, len, [&](auto M, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((h2_yy_init_kernel<M()>), grid, block, 0, st, samples, len, D, K, G, centroids, assignments,
+                       groups, bounds);
+  });
 }
 hipError_t launch_h2_yy_drifts(int metric, const float *centroids, uint32_t K, uint32_t D, float *drifts, hipStream_t st) {
-  H2_LAUNCH(metric, h2_yy_drifts_kernel, K, st, centroids, K, D, drifts);
+  return h2_launch(metric, K, [&](auto M, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((h2_yy_drifts_kernel<M()>), grid, block, 0, st, centroids, K, D, drifts);
+  });
 }
 hipError_t launch_h2_yy_global(int metric, const float *samples, uint32_t len, uint32_t D, uint32_t K, uint32_t G,
                                const float *centroids, const float *drifts, const float *gdrifts,
                                const uint32_t *assignments, uint32_t *assignments_prev, float *bounds, uint32_t *passed,
                                uint32_t *counters, hipStream_t st) {
-  H2_LAUNCH(metric, h2_yy_global_kernel, len, st, samples, len, D, K, G, centroids, drifts, gdrifts, assignments,
-            assignments_prev, bounds, passed, counters);
+  return h2_launch(metric, len, [&](auto M, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((h2_yy_global_kernel<M()>), grid, block, 0, st, samples, len, D, K, G, centroids, drifts,
+                       gdrifts, assignments, assignments_prev, bounds, passed, counters);
+  });
 }
 hipError_t launch_h2_yy_local(int metric, const float *samples, uint32_t len, uint32_t D, uint32_t K, uint32_t G,
                               const uint32_t *passed, const float *centroids, const uint32_t *groups, const float *drifts,
                               const float *gdrifts, uint32_t *assignments, float *bounds, uint32_t *counters,
                               hipStream_t st) {
-  H2_LAUNCH(metric, h2_yy_local_kernel, len, st, samples, len, D, K, G, passed, centroids, groups, drifts, gdrifts,
-            assignments, bounds, counters);
+  return h2_launch(metric, len, [&](auto M, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((h2_yy_local_kernel<M()>), grid, block, 0, st, samples, len, D, K, G, passed, centroids, groups,
+                       drifts, gdrifts, assignments, bounds, counters);
+  });
 }
 
 }  // namespace kmx

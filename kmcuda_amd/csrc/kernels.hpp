@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "launch_dispatch.hpp"
 
 namespace kmx {
 
@@ -74,8 +75,7 @@ struct StopCtl {
   uint32_t seq = 0;
 };
 
-uint32_t filter_dp_for(uint32_t D);
-uint32_t lloyd_dp_for(uint32_t D);   // + 512 for 256 < D <= 512: two-stage f16 Lloyd filter only
+// (filter_dp_for, lloyd_dp_for: launch_dispatch.hpp, next to the width ladders)
 hipError_t launch_centroid_prep(int metric, const float *centroids, uint32_t K, uint32_t D, uint32_t K_pad,
                                 uint32_t DP, uint32_t Kt, float *csqr, float *bias, float *bias2, float *cfil,
                                 float *ct, float *mu, bool freeze_mu, uint32_t *finite, uint32_t *stats, uint32_t *zero_a,

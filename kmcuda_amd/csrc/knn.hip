@@ -650,22 +650,18 @@ hipError_t launch_knn_member(int metric, const float *xs, uint32_t N, uint32_t D
   // (the tiled member kernel: whole 32-feature chunks, 16-byte aligned rows and centroids; else, and for the half2
   //  arithmetic, a thread per row)
   const bool tiled = !strict_h2 && D >= 32 && (D & 31u) == 0 && (DP & 3u) == 0 && (((uintptr_t)xs | (uintptr_t)centroids) & 15u) == 0;
-#define KMX_KNN_MEMBER(M, H)                                                                                        \
-  do {                                                                                                              \
-    if (tiled)                                                                                                      \
-      hipLaunchKernelGGL((knn_member_tiled_kernel<M>), dim3((N + kMemberBlock - 1) / kMemberBlock), dim3(kMemberBlock), 0, \
-                         st, xs, N, D, DP, offsets, K, centroids, mydist, rdist);                                   \
-    else                                                                                                            \
-      hipLaunchKernelGGL((knn_member_kernel<M, H>), dim3((N + 127) / 128), dim3(128), 0, st, xs, N, D, DP, offsets, K, \
-                         centroids, mydist, rdist);                                                                 \
-  } while (0)
-  if (metric == 0) {
-    if (strict_h2) KMX_KNN_MEMBER(0, true); else KMX_KNN_MEMBER(0, false);
-  } else {
-    if (strict_h2) KMX_KNN_MEMBER(1, true); else KMX_KNN_MEMBER(1, false);
-  }
-#undef KMX_KNN_MEMBER
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    if (tiled) {
+      hipLaunchKernelGGL((knn_member_tiled_kernel<M()>), dim3((N + kMemberBlock - 1) / kMemberBlock), dim3(kMemberBlock), 0,
+                         st, xs, N, D, DP, offsets, K, centroids, mydist, rdist);
+      return hipGetLastError();
+    }
+    return with_flag(strict_h2, [&](auto H) {
+      hipLaunchKernelGGL((knn_member_kernel<M(), H()>), dim3((N + 127) / 128), dim3(128), 0, st, xs, N, D, DP, offsets, K,
+                         centroids, mydist, rdist);
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t launch_knn_prep(int metric, const float *xs, uint32_t N, uint32_t D, uint32_t DP, const uint32_t *offsets,
@@ -673,13 +669,13 @@ hipError_t launch_knn_prep(int metric, const float *xs, uint32_t N, uint32_t D, 
                            bool strict_h2, hipStream_t st) {
   hipError_t e = launch_knn_member(metric, xs, N, D, DP, offsets, K, centroids, mydist, rdist, strict_h2, st);
   if (e != hipSuccess) return e;
-  if (metric == 0) {
-    if (strict_h2) hipLaunchKernelGGL((knn_cdist_kernel<0, true>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
-    else hipLaunchKernelGGL((knn_cdist_kernel<0, false>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
-  } else {
-    if (strict_h2) hipLaunchKernelGGL((knn_cdist_kernel<1, true>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
-    else hipLaunchKernelGGL((knn_cdist_kernel<1, false>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
-  }
+  e = with_metric(metric, [&](auto M) {
+    return with_flag(strict_h2, [&](auto H) {
+      hipLaunchKernelGGL((knn_cdist_kernel<M(), H()>), dim3(((K + 127) / 128) * K), dim3(128), 0, st, centroids, K, D, C);
+      return hipGetLastError();
+    });
+  });
+  if (e != hipSuccess) return e;
   return launch_knn_radii(rdist, offsets, K, R, st);
 }
 
@@ -777,59 +773,35 @@ hipError_t launch_knn_probe_lists(const uint32_t *probes, uint32_t pw, uint32_t 
   return hipGetLastError();
 }
 
-template <int DP, int METRIC>
-static hipError_t launch_knn_filter_t(const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self) {
-  const size_t lds_bytes = (2 * 32 * (DP + 4) + 64 + 8) * sizeof(float);
-  if (self) hipLaunchKernelGGL((knn_filter_kernel<DP, METRIC, true>), dim3(nblocks), dim3(256), lds_bytes, st, a);
-  else hipLaunchKernelGGL((knn_filter_kernel<DP, METRIC, false>), dim3(nblocks), dim3(256), lds_bytes, st, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_knn_filter(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self) {
   if (nblocks == 0) return hipSuccess;
-#define KMX_KNN_CASE(dp)                                                             \
-  case dp:                                                                           \
-    return metric == 0 ? launch_knn_filter_t<dp, 0>(a, nblocks, st, self) : launch_knn_filter_t<dp, 1>(a, nblocks, st, self)
-  switch (a.DP) {
-    KMX_KNN_CASE(8);
-    KMX_KNN_CASE(16);
-    KMX_KNN_CASE(32);
-    KMX_KNN_CASE(64);
-    KMX_KNN_CASE(128);
-    KMX_KNN_CASE(256);
-    default: return hipErrorInvalidValue;
-  }
-#undef KMX_KNN_CASE
-}
-
-template <bool SELF>
-static void launch_knn_exact_t(int metric, const KnnArgs &a, bool strict_h2, uint32_t grid, hipStream_t st) {
-  if (metric == 0) {
-    if (strict_h2) hipLaunchKernelGGL((knn_exact_kernel<0, true, SELF>), dim3(grid), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((knn_exact_kernel<0, false, SELF>), dim3(grid), dim3(64), 0, st, a);
-  } else {
-    if (strict_h2) hipLaunchKernelGGL((knn_exact_kernel<1, true, SELF>), dim3(grid), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((knn_exact_kernel<1, false, SELF>), dim3(grid), dim3(64), 0, st, a);
-  }
+  return with_width<FilterWidths>(a.DP, [&](auto DP) {
+    return with_metric(metric, [&](auto M) {
+      return with_flag(self, [&](auto SELF) {
+        const size_t lds_bytes = (2 * 32 * (DP() + 4) + 64 + 8) * sizeof(float);
+        hipLaunchKernelGGL((knn_filter_kernel<DP(), M(), SELF()>), dim3(nblocks), dim3(256), lds_bytes, st, a);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st, bool self, bool probe) {
   if (a.p_end <= a.p_base) return hipSuccess;
-  const uint32_t grid = (a.p_end - a.p_base + 63) / 64;
-  if (probe) {
-    if (self || !a.plist || a.pw == 0) return hipErrorInvalidValue;
-    if (metric == 0) {
-      if (strict_h2) hipLaunchKernelGGL((knn_exact_kernel<0, true, false, true>), dim3(grid), dim3(64), 0, st, a);
-      else hipLaunchKernelGGL((knn_exact_kernel<0, false, false, true>), dim3(grid), dim3(64), 0, st, a);
-    } else {
-      if (strict_h2) hipLaunchKernelGGL((knn_exact_kernel<1, true, false, true>), dim3(grid), dim3(64), 0, st, a);
-      else hipLaunchKernelGGL((knn_exact_kernel<1, false, false, true>), dim3(grid), dim3(64), 0, st, a);
-    }
-    return hipGetLastError();
-  }
-  if (self) launch_knn_exact_t<true>(metric, a, strict_h2, grid, st);
-  else launch_knn_exact_t<false>(metric, a, strict_h2, grid, st);
-  return hipGetLastError();
+  const dim3 grid((a.p_end - a.p_base + 63) / 64);
+  if (probe && (self || !a.plist || a.pw == 0)) return hipErrorInvalidValue;
+  return with_metric(metric, [&](auto M) {
+    return with_flag(strict_h2, [&](auto H) {
+      if (probe) {
+        hipLaunchKernelGGL((knn_exact_kernel<M(), H(), false, true>), grid, dim3(64), 0, st, a);
+        return hipGetLastError();
+      }
+      return with_flag(self, [&](auto SELF) {
+        hipLaunchKernelGGL((knn_exact_kernel<M(), H(), SELF()>), grid, dim3(64), 0, st, a);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t launch_knn_scatter(const uint32_t *sorted_out, const uint32_t *inv, uint32_t p_base, uint32_t p_end,

@@ -566,89 +566,38 @@ hipError_t launch_knn_split(int metric, const float *xs, uint32_t N, uint32_t D,
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(kbias + N, 0, (size_t)KNN16_PAD_ROWS * sizeof(float), st);
   if (e != hipSuccess) return e;
-  if (metric == 0)
-    hipLaunchKernelGGL((knn_split_kernel<0>), dim3(wave_row_grid(N)), dim3(256), 0, st, xs, N, D, DP, mu,
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((knn_split_kernel<M()>), dim3(wave_row_grid(N)), dim3(256), 0, st, xs, N, D, DP, mu,
                        reinterpret_cast<_Float16 *>(xs16), n2c, mux, kbias, stats);
-  else
-    hipLaunchKernelGGL((knn_split_kernel<1>), dim3(wave_row_grid(N)), dim3(256), 0, st, xs, N, D, DP, mu,
-                       reinterpret_cast<_Float16 *>(xs16), n2c, mux, kbias, stats);
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }
 
-template <int DP, int METRIC, bool SELF>
+// PROBE (query mode): the tile ring's LDS plus the K-bit visit map
+template <int DP, int METRIC, bool SELF, bool PROBE>
 static hipError_t launch_knn_f16_t(const KnnArgs &a, uint32_t nblocks, hipStream_t st) {
-  const size_t lds_bytes = (size_t)knn16_nbuf(DP) * (32 * knn16_sub(DP) * DP * 2) + knn16_nbuf(DP) * 256 + 2 * knn16_waves(DP) * 4;
-  if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, true, SELF>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, false, SELF>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  if (a.D == (uint32_t)DP)
-    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, true, SELF>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
-  else
-    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, false, SELF>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
-  return hipGetLastError();
-}
-
-// the PROBE instantiations (query mode): the tile ring's LDS plus the K-bit visit map
-template <int DP, int METRIC>
-static hipError_t launch_knn_f16_probe_t(const KnnArgs &a, uint32_t nblocks, hipStream_t st) {
   const size_t lds_bytes = (size_t)knn16_nbuf(DP) * (32 * knn16_sub(DP) * DP * 2) + knn16_nbuf(DP) * 256 + 2 * knn16_waves(DP) * 4 +
-                           (size_t)((a.K + 31u) / 32u) * 4;
-  if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, true, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, false, false, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  if (a.D == (uint32_t)DP)
-    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, true, false, true>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
-  else
-    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, false, false, true>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
-  return hipGetLastError();
+                           (PROBE ? (size_t)((a.K + 31u) / 32u) * 4 : 0);
+  return with_flag(a.D == (uint32_t)DP, [&](auto FAST) {
+    if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, FAST(), SELF, PROBE>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, FAST(), SELF, PROBE>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self, bool probe) {
   if (nblocks == 0) return hipSuccess;
-  if (probe) {
-    if (self || !a.plist || a.pw == 0 || a.K > KNN_PROBE_BITMAP_K) return hipErrorInvalidValue;
-#define KMX_KNN16_PROBE_CASE(dp) \
-  case dp:                       \
-    return metric == 0 ? launch_knn_f16_probe_t<dp, 0>(a, nblocks, st) : launch_knn_f16_probe_t<dp, 1>(a, nblocks, st)
-    switch (a.DP) {
-      KMX_KNN16_PROBE_CASE(16);
-      KMX_KNN16_PROBE_CASE(32);
-      KMX_KNN16_PROBE_CASE(64);
-      KMX_KNN16_PROBE_CASE(128);
-      KMX_KNN16_PROBE_CASE(256);
-      KMX_KNN16_PROBE_CASE(512);
-      KMX_KNN16_PROBE_CASE(768);
-      KMX_KNN16_PROBE_CASE(1024);
-      default: return hipErrorInvalidValue;
-    }
-#undef KMX_KNN16_PROBE_CASE
-  }
-#define KMX_KNN16_CASE(dp)                                                                                \
-  case dp:                                                                                                 \
-    return self ? (metric == 0 ? launch_knn_f16_t<dp, 0, true>(a, nblocks, st) : launch_knn_f16_t<dp, 1, true>(a, nblocks, st)) \
-                : (metric == 0 ? launch_knn_f16_t<dp, 0, false>(a, nblocks, st) : launch_knn_f16_t<dp, 1, false>(a, nblocks, st))
-  switch (a.DP) {
-    KMX_KNN16_CASE(16);
-    KMX_KNN16_CASE(32);
-    KMX_KNN16_CASE(64);
-    KMX_KNN16_CASE(128);
-    KMX_KNN16_CASE(256);
-    KMX_KNN16_CASE(512);
-    KMX_KNN16_CASE(768);
-    KMX_KNN16_CASE(1024);
-    default: return hipErrorInvalidValue;
-  }
-#undef KMX_KNN16_CASE
+  if (probe && (self || !a.plist || a.pw == 0 || a.K > KNN_PROBE_BITMAP_K)) return hipErrorInvalidValue;
+  return with_width<KnnF16Widths>(a.DP, [&](auto DP) {
+    return with_metric(metric, [&](auto M) {
+      if (probe) return launch_knn_f16_t<DP(), M(), false, true>(a, nblocks, st);
+      return with_flag(self, [&](auto SELF) { return launch_knn_f16_t<DP(), M(), SELF(), false>(a, nblocks, st); });
+    });
+  });
 }
 
 }  // namespace kmx

@@ -53,8 +53,7 @@ KnnPath knn_choose_path(uint32_t D, bool fp16, int verbosity, const KnnSwitches 
   p.dp_filter = exact ? 0 : filter_dp_for(D);
   // 256 < D <= 1024: the f16 filter's one-operand-set instantiations (knn_f16.hip: 512 with two blocks per CU;
   // 768 / 1024 with one -- the queries' operands alone are 192 / 256 registers; the f32 filter stops at 256)
-  if (!p.dp_filter && !exact && !sw.filter_f32 && D > 256 && D <= 1024)
-    p.dp_filter = D <= 512 ? 512u : (D <= 768 ? 768u : 1024u);
+  if (!p.dp_filter && !exact && !sw.filter_f32) p.dp_filter = KnnF16Widths::fit(D);
   p.DP = p.dp_filter ? p.dp_filter : D;
   if (!p.dp_filter && verbosity > 0) printf("k-NN: every candidate is evaluated with the exact arithmetic (no matrix-core filter)\n");
   // which matrix-core instruction filters the candidates: f16 on centred hi/lo-split rows (default,

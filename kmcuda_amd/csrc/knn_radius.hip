@@ -516,58 +516,37 @@ __global__ void knn_radius_offsets_kernel(const unsigned long long *__restrict__
 template <int DP, int METRIC, bool FILL>
 static hipError_t launch_knn_radius_f16_t(const KnnRadiusArgs &ra, uint32_t nblocks, hipStream_t st) {
   const size_t lds_bytes = (size_t)knn16_nbuf(DP) * (32 * knn16_sub(DP) * DP * 2) + knn16_nbuf(DP) * 256 + 2 * knn16_waves(DP) * 4;
-  const bool fast = ra.a.D == (uint32_t)DP;
-  if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
-    const hipError_t e = fast ? hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_radius_f16_kernel<DP, METRIC, true, FILL>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)
-                              : hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_radius_f16_kernel<DP, METRIC, false, FILL>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  if (fast)
-    hipLaunchKernelGGL((knn_radius_f16_kernel<DP, METRIC, true, FILL>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, ra);
-  else
-    hipLaunchKernelGGL((knn_radius_f16_kernel<DP, METRIC, false, FILL>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, ra);
-  return hipGetLastError();
+  return with_flag(ra.a.D == (uint32_t)DP, [&](auto FAST) {
+    if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_radius_f16_kernel<DP, METRIC, FAST(), FILL>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((knn_radius_f16_kernel<DP, METRIC, FAST(), FILL>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, ra);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_knn_radius_f16(int metric, const KnnRadiusArgs &ra, uint32_t nblocks, bool fill, hipStream_t st) {
   if (nblocks == 0) return hipSuccess;
-#define KMX_RAD16_CASE(dp)                                                                                               \
-  case dp:                                                                                                               \
-    return fill ? (metric == 0 ? launch_knn_radius_f16_t<dp, 0, true>(ra, nblocks, st) : launch_knn_radius_f16_t<dp, 1, true>(ra, nblocks, st)) \
-                : (metric == 0 ? launch_knn_radius_f16_t<dp, 0, false>(ra, nblocks, st) : launch_knn_radius_f16_t<dp, 1, false>(ra, nblocks, st))
-  switch (ra.a.DP) {
-    KMX_RAD16_CASE(16);
-    KMX_RAD16_CASE(32);
-    KMX_RAD16_CASE(64);
-    KMX_RAD16_CASE(128);
-    KMX_RAD16_CASE(256);
-    KMX_RAD16_CASE(512);
-    KMX_RAD16_CASE(768);
-    KMX_RAD16_CASE(1024);
-    default: return hipErrorInvalidValue;
-  }
-#undef KMX_RAD16_CASE
-}
-
-template <bool FILL>
-static void launch_knn_radius_exact_t(int metric, const KnnRadiusArgs &ra, bool strict_h2, uint32_t grid, hipStream_t st) {
-  if (metric == 0) {
-    if (strict_h2) hipLaunchKernelGGL((knn_radius_exact_kernel<0, true, FILL>), dim3(grid), dim3(64), 0, st, ra);
-    else hipLaunchKernelGGL((knn_radius_exact_kernel<0, false, FILL>), dim3(grid), dim3(64), 0, st, ra);
-  } else {
-    if (strict_h2) hipLaunchKernelGGL((knn_radius_exact_kernel<1, true, FILL>), dim3(grid), dim3(64), 0, st, ra);
-    else hipLaunchKernelGGL((knn_radius_exact_kernel<1, false, FILL>), dim3(grid), dim3(64), 0, st, ra);
-  }
+  return with_width<KnnF16Widths>(ra.a.DP, [&](auto DP) {
+    return with_metric(metric, [&](auto M) {
+      return with_flag(fill, [&](auto FILL) { return launch_knn_radius_f16_t<DP(), M(), FILL()>(ra, nblocks, st); });
+    });
+  });
 }
 
 hipError_t launch_knn_radius_exact(int metric, const KnnRadiusArgs &ra, bool strict_h2, bool fill, hipStream_t st) {
   if (ra.a.p_end <= ra.a.p_base) return hipSuccess;
-  const uint32_t grid = (ra.a.p_end - ra.a.p_base + 63) / 64;
-  if (fill) launch_knn_radius_exact_t<true>(metric, ra, strict_h2, grid, st);
-  else launch_knn_radius_exact_t<false>(metric, ra, strict_h2, grid, st);
-  return hipGetLastError();
+  const dim3 grid((ra.a.p_end - ra.a.p_base + 63) / 64);
+  return with_metric(metric, [&](auto M) {
+    return with_flag(strict_h2, [&](auto H) {
+      return with_flag(fill, [&](auto FILL) {
+        hipLaunchKernelGGL((knn_radius_exact_kernel<M(), H(), FILL()>), grid, dim3(64), 0, st, ra);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t launch_knn_radius_rest(const KnnRadiusArgs &ra, bool fill, hipStream_t st) {

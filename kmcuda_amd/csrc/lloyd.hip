@@ -819,63 +819,40 @@ bool lloyd_settle_supported(const LloydArgs &a, const float *centroids) {
 }
 
 hipError_t launch_lloyd_settle(int metric, const LloydArgs &a, const float *centroids, hipStream_t st) {
-  const void *fn = metric == 0 ? (const void *)lloyd_settle_kernel<0> : (const void *)lloyd_settle_kernel<1>;
-  // (per device: the attribute belongs to the current device's copy of the kernel; setting it again is cheap)
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSettleLds);
-  if (e != hipSuccess) return e;
-  const dim3 grid(kSettlePairBlocks + kSettleScanBlocks);
-  if (metric == 0)
-    hipLaunchKernelGGL((lloyd_settle_kernel<0>), grid, dim3(256), kSettleLds, st, a.samples, a.N, a.D, centroids, a.ct,
-                       a.csqr, a.K, a.Kt, a.pairs, a.counters + 3, a.flagged, a.counters + 1, a.assignments,
-                       a.assignments_prev, a.counters);
-  else
-    hipLaunchKernelGGL((lloyd_settle_kernel<1>), grid, dim3(256), kSettleLds, st, a.samples, a.N, a.D, centroids, a.ct,
-                       a.csqr, a.K, a.Kt, a.pairs, a.counters + 3, a.flagged, a.counters + 1, a.assignments,
-                       a.assignments_prev, a.counters);
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    // (per device: the attribute belongs to the current device's copy of the kernel; setting it again is cheap)
+    hipError_t e = hipFuncSetAttribute((const void *)lloyd_settle_kernel<M()>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)kSettleLds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((lloyd_settle_kernel<M()>), dim3(kSettlePairBlocks + kSettleScanBlocks), dim3(256), kSettleLds, st,
+                       a.samples, a.N, a.D, centroids, a.ct, a.csqr, a.K, a.Kt, a.pairs, a.counters + 3, a.flagged,
+                       a.counters + 1, a.assignments, a.assignments_prev, a.counters);
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------
-// the Lloyd two-stage f16 filter also has a 512-wide instantiation (one operand set per wave)
-uint32_t filter_dp_for(uint32_t D);
-uint32_t lloyd_dp_for(uint32_t D) { return (D > 256 && D <= 512) ? 512u : filter_dp_for(D); }
-
-uint32_t filter_dp_for(uint32_t D) {
-  static const uint32_t sizes[] = {8, 16, 32, 64, 128, 256};
-  for (uint32_t v : sizes)
-    if (D <= v) return v;
-  return 0;  // no MFMA filter instantiation: exact kernel handles everything
-}
-
-template <int DP>
-static hipError_t launch_filter_dp(const LloydArgs &a, hipStream_t st) {
-  const bool fast = (a.D == (uint32_t)DP);
-  const size_t lds_bytes = (2 * 32 * (DP + 4) + 64) * sizeof(float);
-  const uint32_t grid = (a.N + 127) / 128;
-  if (fast) {
-    hipLaunchKernelGGL((lloyd_filter_kernel<DP, true>), dim3(grid), dim3(256), lds_bytes, st, a.samples, a.N,
-                       a.D, a.cfil, a.bias, a.mu, a.K_pad, a.K, a.stats, a.eps, a.tie_slack, a.assignments,
-                       a.assignments_prev, a.flagged, a.pairs, a.counters);
-  } else {
-    hipLaunchKernelGGL((lloyd_filter_kernel<DP, false>), dim3(grid), dim3(256), lds_bytes, st, a.samples, a.N,
-                       a.D, a.cfil, a.bias, a.mu, a.K_pad, a.K, a.stats, a.eps, a.tie_slack, a.assignments,
-                       a.assignments_prev, a.flagged, a.pairs, a.counters);
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_lloyd_filter(const LloydArgs &a, hipStream_t st) {
-  switch (a.DP) {
-    case 8: return launch_filter_dp<8>(a, st);
-    case 16: return launch_filter_dp<16>(a, st);
-    case 32: return launch_filter_dp<32>(a, st);
-    case 64: return launch_filter_dp<64>(a, st);
-    case 128: return launch_filter_dp<128>(a, st);
-    case 256: return launch_filter_dp<256>(a, st);
-    default: return hipErrorInvalidValue;
-  }
+  return with_width<FilterWidths>(a.DP, [&](auto DP) {
+    return with_flag(a.D == (uint32_t)DP(), [&](auto FAST) {
+      const size_t lds_bytes = (2 * 32 * (DP() + 4) + 64) * sizeof(float);
+      hipLaunchKernelGGL((lloyd_filter_kernel<DP(), FAST()>), dim3((a.N + 127) / 128), dim3(256), lds_bytes, st, a.samples,
+                         a.N, a.D, a.cfil, a.bias, a.mu, a.K_pad, a.K, a.stats, a.eps, a.tie_slack, a.assignments,
+                         a.assignments_prev, a.flagged, a.pairs, a.counters);
+      return hipGetLastError();
+    });
+  });
+}
+
+static hipError_t launch_centroid_rows_stats(int metric, const float *centroids, uint32_t K, uint32_t D, uint32_t Kt,
+                                             float *csqr, float *ct, uint32_t *finite, uint32_t *stats, hipStream_t st) {
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((centroid_rows_kernel<M()>), dim3((Kt + 63) / 64), dim3(64), 0, st, centroids, K, D, Kt, csqr, ct,
+                       finite, stats);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_centroid_prep(int metric, const float *centroids, uint32_t K, uint32_t D, uint32_t K_pad,
@@ -883,56 +860,39 @@ hipError_t launch_centroid_prep(int metric, const float *centroids, uint32_t K, 
                                 float *ct, float *mu, bool freeze_mu, uint32_t *finite, uint32_t *stats,
                                 uint32_t *zero_a, uint32_t *zero_b, uint32_t *zero_c, hipStream_t st) {
   // (stats: zeroed by the caller)
-  const dim3 block(64);
-  if (metric == 0)
-    hipLaunchKernelGGL((centroid_rows_kernel<0>), dim3((Kt + 63) / 64), block, 0, st, centroids, K, D, Kt, csqr, ct,
-                       finite, stats);
-  else
-    hipLaunchKernelGGL((centroid_rows_kernel<1>), dim3((Kt + 63) / 64), block, 0, st, centroids, K, D, Kt, csqr, ct,
-                       finite, stats);
+  const hipError_t e = launch_centroid_rows_stats(metric, centroids, K, D, Kt, csqr, ct, finite, stats, st);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(centroid_mean_kernel, dim3((DP + 63) / 64), dim3(1024), 0, st, centroids, K, D, DP, finite, mu,
                      freeze_mu, zero_a, zero_b, zero_c);
-  if (metric == 0)
-    hipLaunchKernelGGL((centroid_panel_kernel<0>), dim3((K_pad + 15) / 16), dim3(256), 0, st, centroids, K, D, K_pad, DP,
-                       finite, mu, bias, bias2, cfil, stats);
-  else
-    hipLaunchKernelGGL((centroid_panel_kernel<1>), dim3((K_pad + 15) / 16), dim3(256), 0, st, centroids, K, D, K_pad, DP,
-                       finite, mu, bias, bias2, cfil, stats);
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((centroid_panel_kernel<M()>), dim3((K_pad + 15) / 16), dim3(256), 0, st, centroids, K, D, K_pad,
+                       DP, finite, mu, bias, bias2, cfil, stats);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_centroid_rows(int metric, const float *centroids, uint32_t K, uint32_t D, uint32_t Kt, float *csqr,
                                 float *ct, hipStream_t st) {
-  if (metric == 0)
-    hipLaunchKernelGGL((centroid_rows_kernel<0>), dim3((Kt + 63) / 64), dim3(64), 0, st, centroids, K, D, Kt, csqr, ct,
-                       (uint32_t *)nullptr, (uint32_t *)nullptr);
-  else
-    hipLaunchKernelGGL((centroid_rows_kernel<1>), dim3((Kt + 63) / 64), dim3(64), 0, st, centroids, K, D, Kt, csqr, ct,
-                       (uint32_t *)nullptr, (uint32_t *)nullptr);
-  return hipGetLastError();
+  return launch_centroid_rows_stats(metric, centroids, K, D, Kt, csqr, ct, nullptr, nullptr, st);
 }
 
 hipError_t launch_lloyd_pair(int metric, const LloydArgs &a, const float *centroids, uint32_t grid, hipStream_t st) {
   if (grid == 0) return hipSuccess;
-  if (metric == 0)
-    hipLaunchKernelGGL((lloyd_pair_kernel<0>), dim3(grid), dim3(128), 0, st, a.samples, a.D, centroids, a.csqr,
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((lloyd_pair_kernel<M()>), dim3(grid), dim3(128), 0, st, a.samples, a.D, centroids, a.csqr,
                        a.pairs, a.counters + 3, a.assignments, a.assignments_prev, a.counters);
-  else
-    hipLaunchKernelGGL((lloyd_pair_kernel<1>), dim3(grid), dim3(128), 0, st, a.samples, a.D, centroids, a.csqr,
-                       a.pairs, a.counters + 3, a.assignments, a.assignments_prev, a.counters);
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_lloyd_exact(int metric, const LloydArgs &a, const uint32_t *rows, const uint32_t *nrows,
                               uint32_t grid, hipStream_t st) {
   if (grid == 0) return hipSuccess;
-  if (metric == 0)
-    hipLaunchKernelGGL((lloyd_exact_kernel<0>), dim3(grid), dim3(256), 0, st, a.samples, a.N, a.D, a.ct, a.csqr,
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((lloyd_exact_kernel<M()>), dim3(grid), dim3(256), 0, st, a.samples, a.N, a.D, a.ct, a.csqr,
                        a.K, a.Kt, rows, nrows, a.assignments, a.assignments_prev, a.counters);
-  else
-    hipLaunchKernelGGL((lloyd_exact_kernel<1>), dim3(grid), dim3(256), 0, st, a.samples, a.N, a.D, a.ct, a.csqr,
-                       a.K, a.Kt, rows, nrows, a.assignments, a.assignments_prev, a.counters);
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }
 
 hipError_t preload_lloyd_code() {   // (kernels.hpp: preload_code_objects)

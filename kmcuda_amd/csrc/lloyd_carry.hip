@@ -208,76 +208,19 @@ hipError_t launch_carry_skip(uint32_t N, uint32_t K, const uint32_t *assignments
                              float tie_slack, uint32_t *row_list, const uint32_t *finite, uint32_t *pairs,
                              uint32_t *counters, bool probe, hipStream_t st, uint32_t wide_dg) {
   const uint32_t chunk = kSkipBlock * kSkipRowsPerThread;
-  if (wide_dg)
-    hipLaunchKernelGGL(carry_skip_kernel<true>, dim3((N + chunk - 1) / chunk), dim3(kSkipBlock), 0, st, N, K, assignments,
+  return with_flag(wide_dg != 0, [&](auto WIDE) {
+    hipLaunchKernelGGL(carry_skip_kernel<WIDE()>, dim3((N + chunk - 1) / chunk), dim3(kSkipBlock), 0, st, N, K, assignments,
                        assignments_prev, cy, reinterpret_cast<const float2 *>(xmeta), drift, stats, tie_slack, row_list,
-                       finite, pairs, counters, probe ? 1 : 0, (float)(wide_dg + 8u));
-  else
-    hipLaunchKernelGGL(carry_skip_kernel<false>, dim3((N + chunk - 1) / chunk), dim3(kSkipBlock), 0, st, N, K, assignments,
-                       assignments_prev, cy, reinterpret_cast<const float2 *>(xmeta), drift, stats, tie_slack, row_list,
-                       finite, pairs, counters, probe ? 1 : 0, 520.0f);
-  return hipGetLastError();
-}
-
-template <int DP>
-static hipError_t launch_coarse_carry_dp(const LloydArgs &a, const void *rows, bool half_rows, const void *xcache,
-                                         const float *xmeta, const void *panelhi, uint32_t *undecided, float *und_thr,
-                                         const CarryArgs &cy, uint32_t rows_hint, uint32_t *duo, hipStream_t st) {
-  constexpr int NSET = DP <= 256 ? 2 : 1;
-  const size_t lds_bytes = 2 * 64 * (size_t)(DP * 2) + 512 + 64 + (size_t)DP * 4;
-  const uint32_t rows_per_block = 128u * NSET;
-  uint32_t grid = (a.N + rows_per_block - 1) / rows_per_block;
-  const bool fast = a.D == (uint32_t)DP;
-  // (the shapes as in lloyd_f16.hip, launch_coarse2_dp; the listed pass at 256 features keeps 32x32x16: with the
-  //  gathered rows' conversion 16x16x32 spills there)
-  constexpr bool kS16 = NSET == 2 && DP >= 32;
-  const bool s16 = kS16 && a.coarse_mfma != 32;
-#define KMX_CARRY_LAUNCH_S(H, F, C, MODE, SRC, SHAPE)                                                                       \
-  hipLaunchKernelGGL((lloyd_coarse2_kernel<DP, H, F, C, NSET, MODE, SHAPE>), dim3(grid), dim3(256), lds_bytes, st, SRC,     \
-                     xmeta, a.N, a.D, reinterpret_cast<const float *>(panelhi), a.bias, a.mu, a.K_pad, a.K, a.stats,        \
-                     a.eps, a.tie_slack, a.assignments, a.assignments_prev, undecided, und_thr, a.counters, cy, duo)
-#define KMX_CARRY_LAUNCH(H, F, C, MODE, SRC)                           \
-  do {                                                                 \
-    if (s16) KMX_CARRY_LAUNCH_S(H, F, C, MODE, SRC, (kS16 && !(MODE == 2 && DP >= 256)) ? 16 : 32); \
-    else KMX_CARRY_LAUNCH_S(H, F, C, MODE, SRC, 32);                   \
-  } while (0)
-  if (!cy.row_list) {   // every row, streamed from the row cache
-    KMX_CARRY_LAUNCH(false, true, true, 1, xcache);
+                       finite, pairs, counters, probe ? 1 : 0, WIDE() ? (float)(wide_dg + 8u) : 520.0f);
     return hipGetLastError();
-  }
-  // the listed rows: blocks past the (device-side) end of the list leave at once; the grid follows the host's
-  // estimate of the list so that a short list does not dispatch N / 256 of them
-  // (the kernel strides: a list longer than the estimate costs time, never rows.  KMCUDA_AMD_CARRY_GRID caps the
-  // grid -- the tests' way of making every block take several trips)
-  if (rows_hint != 0xFFFFFFFFu) {
-    const uint32_t want = rows_hint / rows_per_block + rows_hint / (4 * rows_per_block) + 64;
-    if (want < grid) grid = want;
-  }
-  if (const char *v = getenv("KMCUDA_AMD_CARRY_GRID")) {
-    const long cap = atol(v);
-    if (cap > 0 && (uint32_t)cap < grid) grid = (uint32_t)cap;
-  }
-  if (half_rows) {
-    if (fast) KMX_CARRY_LAUNCH(true, true, false, 2, rows); else KMX_CARRY_LAUNCH(true, false, false, 2, rows);
-  } else {
-    if (fast) KMX_CARRY_LAUNCH(false, true, false, 2, rows); else KMX_CARRY_LAUNCH(false, false, false, 2, rows);
-  }
-#undef KMX_CARRY_LAUNCH
-#undef KMX_CARRY_LAUNCH_S
-  return hipGetLastError();
+  });
 }
 
 // cy.row_list == nullptr: a whole pass from the row cache (xcache) that leaves bounds; else the listed rows
 hipError_t launch_lloyd_coarse_carry(const LloydArgs &a, const void *rows, bool half_rows, const void *xcache,
                                      const float *xmeta, const void *panelhi, uint32_t *undecided, float *und_thr,
                                      const CarryArgs &cy, uint32_t rows_hint, uint32_t *duo, hipStream_t st) {
-  switch (a.DP) {
-#define KMX_CARRY_CASE(dp) \
-    case dp: return launch_coarse_carry_dp<dp>(a, rows, half_rows, xcache, xmeta, panelhi, undecided, und_thr, cy, rows_hint, duo, st)
-    KMX_CARRY_CASE(16); KMX_CARRY_CASE(32); KMX_CARRY_CASE(64); KMX_CARRY_CASE(128); KMX_CARRY_CASE(256); KMX_CARRY_CASE(512);
-#undef KMX_CARRY_CASE
-    default: return hipErrorInvalidValue;
-  }
+  return launch_lloyd_coarse_t<true>(a, rows, half_rows, xcache, xmeta, panelhi, undecided, und_thr, cy, rows_hint, duo, st);
 }
 
 // stage 2 of a carried L2 pass: as launch_lloyd_refine, and the rows leave with bounds / pair certificates (cy)

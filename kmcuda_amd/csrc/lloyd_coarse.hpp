@@ -1,8 +1,10 @@
 // lloyd_coarse.hpp -- stage 1 of the default Lloyd assignment filter (lloyd_f16.hip has the story; reference:
 // src/kmeans.cu:293-364), as a template shared by two translation units: lloyd_f16.hip instantiates the plain
-// pass, lloyd_carry.hip the passes that carry per-row distance bounds from one iteration to the next.
+// pass, lloyd_carry.hip the passes that carry per-row distance bounds from one iteration to the next -- both through
+// the one launcher at the end of this file (launch_lloyd_coarse_t).
 #pragma once
 #include <hip/hip_fp16.h>
+#include <stdlib.h>
 
 #include "exact.hpp"
 #include "filter_common.hpp"
@@ -720,6 +722,56 @@ __global__ __launch_bounds__(256, 2) void lloyd_coarse2_kernel(
     __syncthreads();   // the tiles, the mean and the block sums in LDS belong to the next trip from here on
   }
   }
+}
+
+// The launcher of lloyd_coarse2_kernel.  CARRY = false: the plain pass (MODE 0) over `rows`, or over the row cache
+// where there is one.  CARRY = true: a pass that leaves bounds in cy -- every row, streamed from the row cache (MODE 1,
+// cy.row_list == nullptr), or the listed rows, gathered from `rows` (MODE 2)
+template <bool CARRY>
+static hipError_t launch_lloyd_coarse_t(const LloydArgs &a, const void *rows, bool half_rows, const void *xcache,
+                                        const float *xmeta, const void *panelhi, uint32_t *undecided, float *und_thr,
+                                        const CarryArgs &cy, uint32_t rows_hint, uint32_t *duo, hipStream_t st) {
+  return with_width<LloydF16Widths>(a.DP, [&](auto W) {
+    constexpr int DP = W(), NSET = DP <= 256 ? 2 : 1;
+    const size_t lds_bytes = 2 * 64 * (size_t)(DP * 2) + 512 + 64 + (size_t)DP * 4;
+    const uint32_t rows_per_block = 128u * NSET;
+    uint32_t grid = (a.N + rows_per_block - 1) / rows_per_block;
+    const bool listed = CARRY && cy.row_list, cached = CARRY ? !listed : xcache != nullptr;
+    if (listed) {
+      // blocks past the (device-side) end of the list leave at once; the grid follows the host's estimate of the
+      // list so that a short list does not dispatch N / 256 of them (the kernel strides: a list longer than the
+      // estimate costs time, never rows.  KMCUDA_AMD_CARRY_GRID caps the grid -- the tests' way of making every
+      // block take several trips)
+      if (rows_hint != 0xFFFFFFFFu) {
+        const uint32_t want = rows_hint / rows_per_block + rows_hint / (4 * rows_per_block) + 64;
+        if (want < grid) grid = want;
+      }
+      if (const char *v = getenv("KMCUDA_AMD_CARRY_GRID")) {
+        const long cap = atol(v);
+        if (cap > 0 && (uint32_t)cap < grid) grid = (uint32_t)cap;
+      }
+    }
+    // 16x16x32 with two row sets (DP 32..256); DP 16 (one k-step of 32 features does not fit) and 512 keep 32x32x16,
+    // and so does the listed pass at 256 features: with the gathered rows' conversion 16x16x32 spills there
+    constexpr bool kS16 = NSET == 2 && DP >= 32;
+    auto launch = [&](auto MODE, auto H, auto F, auto C) {
+      return with_flag(kS16 && a.coarse_mfma != 32, [&](auto S16) {
+        constexpr int SHAPE = (S16() && kS16 && !(MODE() == 2 && DP >= 256)) ? 16 : 32;
+        hipLaunchKernelGGL((lloyd_coarse2_kernel<DP, H(), F(), C(), NSET, MODE(), SHAPE>), dim3(grid), dim3(256), lds_bytes,
+                           st, cached ? xcache : rows, xmeta, a.N, a.D, reinterpret_cast<const float *>(panelhi), a.bias,
+                           a.mu, a.K_pad, a.K, a.stats, a.eps, a.tie_slack, a.assignments, a.assignments_prev, undecided,
+                           und_thr, a.counters, cy, duo);
+        return hipGetLastError();
+      });
+    };
+    if (cached)
+      return launch(std::integral_constant<int, CARRY ? 1 : 0>{}, std::false_type{}, std::true_type{}, std::true_type{});
+    return with_flag(half_rows, [&](auto H) {
+      return with_flag(a.D == (uint32_t)DP, [&](auto F) {
+        return launch(std::integral_constant<int, CARRY ? 2 : 0>{}, H, F, std::false_type{});
+      });
+    });
+  });
 }
 
 }  // namespace kmx

@@ -256,17 +256,14 @@ static hipError_t launch_duo_ni(const LloydArgs &a, const uint32_t *duo, hipStre
   // strides over the device-side count
   const uint32_t want = (a.N + 31u) / 32u, full = NI >= 4 ? 512u : 1024u;
   const dim3 grid(want < full ? (want ? want : 1u) : full);
-#define KMX_DUO_LAUNCH(F, B, CY)                                                                                      \
-  hipLaunchKernelGGL((lloyd_duo_kernel<NI, F, B>), grid, dim3(256), 0, st, a.samples, a.D, a.DP, a.K, a.cfil, a.bias,    \
-                     a.mu, a.stats, a.eps, a.tie_slack, reinterpret_cast<const uint4 *>(duo), a.assignments,          \
-                     a.assignments_prev, a.flagged, a.pairs, a.counters, CY)
-  if (cy && cy->l3) {
-    if (fast) KMX_DUO_LAUNCH(true, true, *cy); else KMX_DUO_LAUNCH(false, true, *cy);
-  } else {
-    if (fast) KMX_DUO_LAUNCH(true, false, CarryArgs()); else KMX_DUO_LAUNCH(false, false, CarryArgs());
-  }
-#undef KMX_DUO_LAUNCH
-  return hipGetLastError();
+  return with_flag(fast, [&](auto F) {
+    return with_flag(cy && cy->l3, [&](auto B) {   // B: the rows leave with pair certificates
+      hipLaunchKernelGGL((lloyd_duo_kernel<NI, F(), B()>), grid, dim3(256), 0, st, a.samples, a.D, a.DP, a.K, a.cfil, a.bias,
+                         a.mu, a.stats, a.eps, a.tie_slack, reinterpret_cast<const uint4 *>(duo), a.assignments,
+                         a.assignments_prev, a.flagged, a.pairs, a.counters, B() ? *cy : CarryArgs());
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t launch_lloyd_duo(const LloydArgs &a, const uint32_t *duo, hipStream_t st, const CarryArgs *cy) {

@@ -212,17 +212,13 @@ hipError_t launch_centroid_prep_frozen(int metric, const float *centroids, uint3
                                        uint32_t *zero_d, hipStream_t st) {
   const uint32_t K_pad64 = (K_pad + 63u) / 64u * 64u;
   float *cen = const_cast<float *>(centroids);   // (only the APPLY instantiation writes)
-  if (metric == 0)
-    hipLaunchKernelGGL((centroid_prep_frozen_kernel<0, false>), dim3(K_pad64 / 16), dim3(256), 0, st, cen, K, D, K_pad,
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((centroid_prep_frozen_kernel<M(), false>), dim3(K_pad64 / 16), dim3(256), 0, st, cen, K, D, K_pad,
                        DP, K_pad64, mu, finite, bias, bias2, cfil, reinterpret_cast<_Float16 *>(panelhi), stats,
                        stats_next, zero_a, zero_b, zero_c, (const double *)nullptr, (const double *)nullptr,
                        (uint32_t *)nullptr, StopCtl(), drift, zero_d);
-  else
-    hipLaunchKernelGGL((centroid_prep_frozen_kernel<1, false>), dim3(K_pad64 / 16), dim3(256), 0, st, cen, K, D, K_pad,
-                       DP, K_pad64, mu, finite, bias, bias2, cfil, reinterpret_cast<_Float16 *>(panelhi), stats,
-                       stats_next, zero_a, zero_b, zero_c, (const double *)nullptr, (const double *)nullptr,
-                       (uint32_t *)nullptr, StopCtl(), drift, zero_d);
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }
 
 // L2: the centroid update (delta / dcount_d: the fused reduce buffer, StopCtl as launch_apply_delta) and the next
@@ -252,51 +248,11 @@ hipError_t launch_centroid_panelhi(const float *centroids, uint32_t K, uint32_t 
 // one MFMA consumes 8 features per half-wave: the padded width must be at least 16
 bool lloyd_filter_f16_supported(uint32_t D, uint32_t DP) { return DP >= 16 && D <= DP; }
 
-template <int DP>
-static hipError_t launch_coarse2_dp(const LloydArgs &a, const void *rows, bool half_rows, const void *xcache,
-                                    const float *xmeta, const void *panelhi, uint32_t *undecided, float *und_thr,
-                                    uint32_t *duo, hipStream_t st) {
-  constexpr int NSET = DP <= 256 ? 2 : 1;
-  const size_t lds_bytes = 2 * 64 * (size_t)(DP * 2) + 512 + 64 + (size_t)DP * 4;
-  const uint32_t rows_per_block = 128u * NSET;
-  const uint32_t grid = (a.N + rows_per_block - 1) / rows_per_block;
-  const bool fast = a.D == (uint32_t)DP;
-  // 16x16x32 with two row sets (DP 32..256); DP 16 (one k-step of 32 features does not fit) and 512 keep 32x32x16
-  constexpr bool kS16 = NSET == 2 && DP >= 32;
-  const bool s16 = kS16 && a.coarse_mfma != 32;
-#define KMX_CRS2_LAUNCH_S(H, F, C, SRC, SHAPE)                                                                            \
-  hipLaunchKernelGGL((lloyd_coarse2_kernel<DP, H, F, C, NSET, 0, SHAPE>), dim3(grid), dim3(256), lds_bytes, st, SRC, xmeta, \
-                     a.N, a.D, reinterpret_cast<const float *>(panelhi), a.bias, a.mu, a.K_pad, a.K, a.stats,             \
-                     a.eps, a.tie_slack, a.assignments, a.assignments_prev, undecided, und_thr, a.counters, CarryArgs(), duo)
-#define KMX_CRS2_LAUNCH(H, F, C, SRC)                       \
-  do {                                                      \
-    if (s16) KMX_CRS2_LAUNCH_S(H, F, C, SRC, kS16 ? 16 : 32); \
-    else KMX_CRS2_LAUNCH_S(H, F, C, SRC, 32);               \
-  } while (0)
-  if (xcache) {
-    KMX_CRS2_LAUNCH(false, true, true, xcache);
-  } else if (half_rows) {
-    if (fast) KMX_CRS2_LAUNCH(true, true, false, rows); else KMX_CRS2_LAUNCH(true, false, false, rows);
-  } else {
-    if (fast) KMX_CRS2_LAUNCH(false, true, false, rows); else KMX_CRS2_LAUNCH(false, false, false, rows);
-  }
-#undef KMX_CRS2_LAUNCH
-#undef KMX_CRS2_LAUNCH_S
-  return hipGetLastError();
-}
-
 hipError_t launch_lloyd_coarse(const LloydArgs &a, const void *rows, bool half_rows, const void *xcache,
                                const float *xmeta, const void *panelhi, uint32_t *undecided, float *und_thr,
                                uint32_t *duo, hipStream_t st) {
-  switch (a.DP) {
-    case 16: return launch_coarse2_dp<16>(a, rows, half_rows, xcache, xmeta, panelhi, undecided, und_thr, duo, st);
-    case 32: return launch_coarse2_dp<32>(a, rows, half_rows, xcache, xmeta, panelhi, undecided, und_thr, duo, st);
-    case 64: return launch_coarse2_dp<64>(a, rows, half_rows, xcache, xmeta, panelhi, undecided, und_thr, duo, st);
-    case 128: return launch_coarse2_dp<128>(a, rows, half_rows, xcache, xmeta, panelhi, undecided, und_thr, duo, st);
-    case 256: return launch_coarse2_dp<256>(a, rows, half_rows, xcache, xmeta, panelhi, undecided, und_thr, duo, st);
-    case 512: return launch_coarse2_dp<512>(a, rows, half_rows, xcache, xmeta, panelhi, undecided, und_thr, duo, st);
-    default: return hipErrorInvalidValue;
-  }
+  return launch_lloyd_coarse_t<false>(a, rows, half_rows, xcache, xmeta, panelhi, undecided, und_thr, CarryArgs(),
+                                      0xFFFFFFFFu, duo, st);
 }
 
 hipError_t launch_lloyd_refine(const LloydArgs &a, const void *rows, bool half_rows, const void *panelhi,
@@ -380,34 +336,18 @@ __global__ __launch_bounds__(256) void row_cache_kernel(const void *__restrict__
   }
 }
 
-template <int DP>
-static hipError_t launch_row_cache_dp(const void *rows, bool half_rows, uint32_t N, uint32_t D, const float *mu,
-                                      void *xcache, float *xmeta, hipStream_t st) {
-  const uint32_t nblocks32 = (N + 255u) / 256u * 8u;
-  const bool fast = D == (uint32_t)DP;
-#define KMX_RC_LAUNCH(H, F)                                                                                       \
-  hipLaunchKernelGGL((row_cache_kernel<DP, H, F>), dim3(wave_row_grid(nblocks32)), dim3(256), 0, st, rows, N, D, mu, \
-                     reinterpret_cast<f16x8 *>(xcache), reinterpret_cast<float2 *>(xmeta), nblocks32)
-  if (half_rows) {
-    if (fast) KMX_RC_LAUNCH(true, true); else KMX_RC_LAUNCH(true, false);
-  } else {
-    if (fast) KMX_RC_LAUNCH(false, true); else KMX_RC_LAUNCH(false, false);
-  }
-#undef KMX_RC_LAUNCH
-  return hipGetLastError();
-}
-
 hipError_t launch_row_cache(const void *rows, bool half_rows, uint32_t N, uint32_t D, uint32_t DP, const float *mu,
                             void *xcache, float *xmeta, hipStream_t st) {
-  switch (DP) {
-    case 16: return launch_row_cache_dp<16>(rows, half_rows, N, D, mu, xcache, xmeta, st);
-    case 32: return launch_row_cache_dp<32>(rows, half_rows, N, D, mu, xcache, xmeta, st);
-    case 64: return launch_row_cache_dp<64>(rows, half_rows, N, D, mu, xcache, xmeta, st);
-    case 128: return launch_row_cache_dp<128>(rows, half_rows, N, D, mu, xcache, xmeta, st);
-    case 256: return launch_row_cache_dp<256>(rows, half_rows, N, D, mu, xcache, xmeta, st);
-    case 512: return launch_row_cache_dp<512>(rows, half_rows, N, D, mu, xcache, xmeta, st);
-    default: return hipErrorInvalidValue;
-  }
+  const uint32_t nblocks32 = (N + 255u) / 256u * 8u;
+  return with_width<LloydF16Widths>(DP, [&](auto W) {
+    return with_flag(half_rows, [&](auto H) {
+      return with_flag(D == (uint32_t)W(), [&](auto F) {
+        hipLaunchKernelGGL((row_cache_kernel<W(), H(), F()>), dim3(wave_row_grid(nblocks32)), dim3(256), 0, st, rows, N, D,
+                           mu, reinterpret_cast<f16x8 *>(xcache), reinterpret_cast<float2 *>(xmeta), nblocks32);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t preload_lloyd_f16_code() {   // (kernels.hpp: preload_code_objects)

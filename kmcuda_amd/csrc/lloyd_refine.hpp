@@ -460,19 +460,15 @@ static hipError_t launch_refine_dp_n(const LloydArgs &a, const void *rows, bool 
     if (want < 512u) want = 512u;
     if (want < grid) grid = want;
   }
-  const bool fast = a.D == (uint32_t)DP;
-#define KMX_RFN_LAUNCH(H, F)                                                                                       \
-  hipLaunchKernelGGL((lloyd_refine_kernel<DP, H, F, NSET, PAIRS>), dim3(grid), dim3(256), lds_bytes, st, rows, a.samples,  \
-                     a.N, a.D, reinterpret_cast<const float *>(panelhi), a.cfil, a.bias, a.mu, a.K_pad, a.K,        \
-                     a.stats, a.eps, a.tie_slack, a.assignments, a.assignments_prev, row_list, thr_list, n_list,    \
-                     a.flagged, a.pairs, a.counters, cy)
-  if (half_rows) {
-    if (fast) KMX_RFN_LAUNCH(true, true); else KMX_RFN_LAUNCH(true, false);
-  } else {
-    if (fast) KMX_RFN_LAUNCH(false, true); else KMX_RFN_LAUNCH(false, false);
-  }
-#undef KMX_RFN_LAUNCH
-  return hipGetLastError();
+  return with_flag(half_rows, [&](auto H) {
+    return with_flag(a.D == (uint32_t)DP, [&](auto F) {
+      hipLaunchKernelGGL((lloyd_refine_kernel<DP, H(), F(), NSET, PAIRS>), dim3(grid), dim3(256), lds_bytes, st, rows,
+                         a.samples, a.N, a.D, reinterpret_cast<const float *>(panelhi), a.cfil, a.bias, a.mu, a.K_pad, a.K,
+                         a.stats, a.eps, a.tie_slack, a.assignments, a.assignments_prev, row_list, thr_list, n_list,
+                         a.flagged, a.pairs, a.counters, cy);
+      return hipGetLastError();
+    });
+  });
 }
 
 template <int DP, bool PAIRS>
@@ -498,15 +494,9 @@ template <bool PAIRS>
 static hipError_t launch_lloyd_refine_t(const LloydArgs &a, const void *rows, bool half_rows, const void *panelhi,
                                const uint32_t *row_list, const float *thr_list, const uint32_t *n_list,
                                uint32_t rows_hint, const CarryArgs &cy, hipStream_t st) {
-  switch (a.DP) {
-    case 16: return launch_refine_dp<16, PAIRS>(a, rows, half_rows, panelhi, row_list, thr_list, n_list, rows_hint, cy, st);
-    case 32: return launch_refine_dp<32, PAIRS>(a, rows, half_rows, panelhi, row_list, thr_list, n_list, rows_hint, cy, st);
-    case 64: return launch_refine_dp<64, PAIRS>(a, rows, half_rows, panelhi, row_list, thr_list, n_list, rows_hint, cy, st);
-    case 128: return launch_refine_dp<128, PAIRS>(a, rows, half_rows, panelhi, row_list, thr_list, n_list, rows_hint, cy, st);
-    case 256: return launch_refine_dp<256, PAIRS>(a, rows, half_rows, panelhi, row_list, thr_list, n_list, rows_hint, cy, st);
-    case 512: return launch_refine_dp<512, PAIRS>(a, rows, half_rows, panelhi, row_list, thr_list, n_list, rows_hint, cy, st);
-    default: return hipErrorInvalidValue;
-  }
+  return with_width<LloydF16Widths>(a.DP, [&](auto DP) {
+    return launch_refine_dp<DP(), PAIRS>(a, rows, half_rows, panelhi, row_list, thr_list, n_list, rows_hint, cy, st);
+  });
 }
 
 

@@ -697,13 +697,11 @@ __global__ __launch_bounds__(256, 4) void wide_contenders_kernel(
 hipError_t launch_row_halves(const void *rows, bool half_rows, uint32_t N, uint32_t D, uint32_t DG, const float *mu,
                              void *xg, float *meta, hipStream_t st) {
   if (N == 0) return hipSuccess;
-  if (half_rows)
-    hipLaunchKernelGGL((row_halves_kernel<true>), dim3(wave_row_grid(N)), dim3(256), 0, st, rows, N, D, DG, mu,
+  return with_flag(half_rows, [&](auto H) {
+    hipLaunchKernelGGL((row_halves_kernel<H()>), dim3(wave_row_grid(N)), dim3(256), 0, st, rows, N, D, DG, mu,
                        reinterpret_cast<_Float16 *>(xg), reinterpret_cast<float4 *>(meta));
-  else
-    hipLaunchKernelGGL((row_halves_kernel<false>), dim3(wave_row_grid(N)), dim3(256), 0, st, rows, N, D, DG, mu,
-                       reinterpret_cast<_Float16 *>(xg), reinterpret_cast<float4 *>(meta));
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }
 
 size_t wide_cont_words(uint32_t N) { return (size_t)N * (kWideCap + 1); }
@@ -718,32 +716,25 @@ hipError_t launch_lloyd_wide(const LloydArgs &a, const void *xg, const float *me
   // Dynamic LDS beyond 64 KB is an opt-in that belongs to the CURRENT DEVICE's copy of the kernel (and shard workers
   // launch from their own threads): set for the instantiations this call launches, on every launch, like the other
   // launchers (lloyd.hip, update.hip, knn_f16.hip) -- and a refusal is the caller's error, not a launch failure later.
-  {
-    const int mode = !cy ? 0 : (!cy->row_list ? 2 : 3);
-    hipError_t e = hipSuccess;
-    if (mode == 0) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lloyd_wide_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWideLds0);
-    else if (mode == 2) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lloyd_wide_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWideLds0);
-    else e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lloyd_wide_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWideLds0);
+  auto pass = [&](auto MODE, size_t lds, const CarryArgs &c) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lloyd_wide_kernel<MODE()>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lloyd_wide_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWideLds1);
-    if (e != hipSuccess) return e;
-  }
-#define KMX_WIDE_LAUNCH(MODE, LDS, CY)                                                                                \
-  hipLaunchKernelGGL((lloyd_wide_kernel<MODE>), dim3(grid), dim3(512), LDS, st, reinterpret_cast<const _Float16 *>(xg), \
-                     reinterpret_cast<const float4 *>(meta), a.N, DG, reinterpret_cast<const _Float16 *>(panelhi),      \
-                     k_pad64, a.K, a.stats, a.eps, a.tie_slack, a.assignments, a.assignments_prev, undecided, und_thr,  \
-                     und_cont, a.counters, CY)
-  if (!cy) {
-    KMX_WIDE_LAUNCH(0, kWideLds0, CarryArgs());
-  } else if (!cy->row_list) {   // every row, leaving bounds
-    KMX_WIDE_LAUNCH(2, kWideLds0, *cy);
-  } else {   // the rows carry_skip_kernel listed: blocks past the (device-side) end of the list leave at once
-    KMX_WIDE_LAUNCH(3, kWideLds0, *cy);
-  }
+    hipLaunchKernelGGL((lloyd_wide_kernel<MODE()>), dim3(grid), dim3(512), lds, st, reinterpret_cast<const _Float16 *>(xg),
+                       reinterpret_cast<const float4 *>(meta), a.N, DG, reinterpret_cast<const _Float16 *>(panelhi),
+                       k_pad64, a.K, a.stats, a.eps, a.tie_slack, a.assignments, a.assignments_prev, undecided, und_thr,
+                       und_cont, a.counters, c);
+    return hipGetLastError();
+  };
+  using std::integral_constant;
+  // every row (cy: leaving bounds), or the rows carry_skip_kernel listed: blocks past the (device-side) end of the
+  // list leave at once
+  const hipError_t e = !cy             ? pass(integral_constant<int, 0>{}, kWideLds0, CarryArgs())
+                       : !cy->row_list ? pass(integral_constant<int, 2>{}, kWideLds0, *cy)
+                                       : pass(integral_constant<int, 3>{}, kWideLds0, *cy);
+  if (e != hipSuccess) return e;
   // the undecided rows: the grid covers the worst case, blocks past the (device-side) end of the list leave at once
-  KMX_WIDE_LAUNCH(1, kWideLds1, CarryArgs());
-#undef KMX_WIDE_LAUNCH
-  return hipGetLastError();
+  return pass(integral_constant<int, 1>{}, kWideLds1, CarryArgs());
 }
 
 hipError_t launch_wide_contenders(int metric, const LloydArgs &a, const float *centroids, uint32_t DG,
@@ -752,14 +743,14 @@ hipError_t launch_wide_contenders(int metric, const LloydArgs &a, const float *c
   const bool fast = a.D == DG && (((uintptr_t)a.samples) & 15u) == 0;
   const uint32_t want = (a.N + 3) / 4;
   const dim3 grid(want < 4096u ? want : 4096u);
-#define KMX_WC_LAUNCH(M, F)                                                                                           \
-  hipLaunchKernelGGL((wide_contenders_kernel<M, F>), grid, dim3(256), 0, st, a.samples, a.D, DG, a.K, centroids, a.csqr, \
-                     a.cfil, a.bias, a.mu, a.stats, a.eps, a.tie_slack, und_rows, und_cont, a.assignments,            \
-                     a.assignments_prev, a.flagged, a.pairs, a.counters)
-  if (metric == 0) { if (fast) KMX_WC_LAUNCH(0, true); else KMX_WC_LAUNCH(0, false); }
-  else { if (fast) KMX_WC_LAUNCH(1, true); else KMX_WC_LAUNCH(1, false); }
-#undef KMX_WC_LAUNCH
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    return with_flag(fast, [&](auto F) {
+      hipLaunchKernelGGL((wide_contenders_kernel<M(), F()>), grid, dim3(256), 0, st, a.samples, a.D, DG, a.K, centroids,
+                         a.csqr, a.cfil, a.bias, a.mu, a.stats, a.eps, a.tie_slack, und_rows, und_cont, a.assignments,
+                         a.assignments_prev, a.flagged, a.pairs, a.counters);
+      return hipGetLastError();
+    });
+  });
 }
 
 }  // namespace kmx

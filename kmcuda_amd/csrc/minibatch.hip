@@ -174,22 +174,17 @@ hipError_t launch_minibatch_update(int metric, const float *rows, const float *w
   // (the mapping depends on D and the rows' alignment only, as in launch_move_deltas)
   const bool vec4 = (D & 3u) == 0 && (((uintptr_t)rows) & 15u) == 0;
   const size_t lds = kMbThreads * 4 * sizeof(double) + ((metric == 1 && D <= kMbStash) ? (size_t)D * sizeof(double) : 0);
-#define KMX_MB(M, V, Wt)                                                                                          \
-  do {                                                                                                            \
-    hipError_t e__ = hipFuncSetAttribute(reinterpret_cast<const void *>(&minibatch_update_kernel<M, V, Wt>),      \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
-    if (e__ != hipSuccess) return e__;                                                                            \
-    hipLaunchKernelGGL((minibatch_update_kernel<M, V, Wt>), dim3(K), dim3(kMbThreads), lds, st, a);               \
-  } while (false)
-  if (metric == 0) {
-    if (weights) { if (vec4) KMX_MB(0, true, true); else KMX_MB(0, false, true); }
-    else { if (vec4) KMX_MB(0, true, false); else KMX_MB(0, false, false); }
-  } else {
-    if (weights) { if (vec4) KMX_MB(1, true, true); else KMX_MB(1, false, true); }
-    else { if (vec4) KMX_MB(1, true, false); else KMX_MB(1, false, false); }
-  }
-#undef KMX_MB
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    return with_flag(vec4, [&](auto V) {
+      return with_flag(weights != nullptr, [&](auto W) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&minibatch_update_kernel<M(), V(), W()>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((minibatch_update_kernel<M(), V(), W()>), dim3(K), dim3(kMbThreads), lds, st, a);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t launch_minibatch_draw_gather(const void *corpus, uint64_t N, uint32_t D, bool fp16, const float *weights,

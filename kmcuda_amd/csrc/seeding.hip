@@ -25,11 +25,10 @@ __global__ void kmpp_step_kernel(const float *__restrict__ samples, uint32_t N, 
 hipError_t launch_kmpp_step(int metric, const float *samples, uint32_t N, uint32_t D, const float *centroid,
                             uint32_t cc, float *dists, hipStream_t st) {
   const dim3 grid((N + 127) / 128), block(128);
-  if (metric == 0)
-    hipLaunchKernelGGL((kmpp_step_kernel<0>), grid, block, 0, st, samples, N, D, centroid, cc, dists);
-  else
-    hipLaunchKernelGGL((kmpp_step_kernel<1>), grid, block, 0, st, samples, N, D, centroid, cc, dists);
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((kmpp_step_kernel<M()>), grid, block, 0, st, samples, N, D, centroid, cc, dists);
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1049,17 +1048,24 @@ static hipError_t launch_kmpp_reduce(const void *block_stats, uint32_t nb, doubl
   return hipGetLastError();
 }
 
+// the exact chains of a step: every row (with the block statistics), or the rows of a list
+static hipError_t launch_kmpp_chains(int metric, uint32_t grid, const float *samples, uint32_t N, uint32_t D,
+                                     const float *centroid, uint32_t cc, float *dists, void *block_stats,
+                                     const uint32_t *list, const uint32_t *nlist, const uint32_t *fail, hipStream_t st) {
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((kmpp_step2_kernel<M()>), dim3(grid), dim3(kKmppBlock), 0, st, samples, N, D, centroid, cc, dists,
+                       reinterpret_cast<KmppBlockStat *>(block_stats), list, nlist, fail);
+    return hipGetLastError();
+  });
+}
+
 hipError_t launch_kmpp_step2(int metric, const float *samples, uint32_t N, uint32_t D, const float *centroid,
                              uint32_t cc, float *dists, void *block_stats, double *bpre, void *totals_host,
                              const uint32_t *fail, const KmppOutlierBuf &out, hipStream_t st, const float *weights,
                              float *terms) {
   const uint32_t nb = (N + kKmppBlock - 1) / kKmppBlock;
-  if (metric == 0)
-    hipLaunchKernelGGL((kmpp_step2_kernel<0>), dim3(nb), dim3(kKmppBlock), 0, st, samples, N, D, centroid, cc, dists,
-                       reinterpret_cast<KmppBlockStat *>(block_stats), (const uint32_t *)nullptr, (const uint32_t *)nullptr, fail);
-  else
-    hipLaunchKernelGGL((kmpp_step2_kernel<1>), dim3(nb), dim3(kKmppBlock), 0, st, samples, N, D, centroid, cc, dists,
-                       reinterpret_cast<KmppBlockStat *>(block_stats), (const uint32_t *)nullptr, (const uint32_t *)nullptr, fail);
+  const hipError_t e = launch_kmpp_chains(metric, nb, samples, N, D, centroid, cc, dists, block_stats, nullptr, nullptr, fail, st);
+  if (e != hipSuccess) return e;
   if (weights && launch_kmpp_weigh(dists, weights, N, terms, fail, st) != hipSuccess) return hipGetLastError();
   hipLaunchKernelGGL(kmpp_stats_kernel, dim3((nb + 3) / 4 < 2048u ? (nb + 3) / 4 : 2048u), dim3(256), 0, st,
                      weights ? terms : dists, N,
@@ -1094,30 +1100,26 @@ hipError_t launch_kmpp_step_filtered(int metric, const float *samples, uint32_t 
   const uint32_t nb = (N + kKmppBlock - 1) / kKmppBlock;
   const float eps = (float)(1.02 * ((double)D + 12.0) * 5.9604644775390625e-8);   // as the k-NN filter
   const uint32_t fgrid = (N + 127) / 128 < 1024u ? (N + 127) / 128 : 1024u;   // 16 waves per CU; one list atomic per wave
-#define KMX_KPP_FILTER1(P, M)                                                                                       \
-  hipLaunchKernelGGL((kmpp_filter_kernel<P, M>), dim3(fgrid), dim3(256), (size_t)DP * 4, st,                        \
-                     reinterpret_cast<const signed char *>(xs8), reinterpret_cast<const f32x4_kp *>(meta), mu, centroid, \
-                     N, D, DP, eps, dists, list, stats + 1, fail)
-#define KMX_KPP_FILTER(P)                                                                                           \
-  do {                                                                                                              \
-    if (metric == 0) KMX_KPP_FILTER1(P, 0); else KMX_KPP_FILTER1(P, 1);                                             \
-  } while (0)
+  auto filter = [&](auto P) {   // (PPL = DP / 128 where the kernel has it unrolled, 0 = any DP)
+    return with_metric(metric, [&](auto M) {
+      hipLaunchKernelGGL((kmpp_filter_kernel<P(), M()>), dim3(fgrid), dim3(256), (size_t)DP * 4, st,
+                         reinterpret_cast<const signed char *>(xs8), reinterpret_cast<const f32x4_kp *>(meta), mu, centroid,
+                         N, D, DP, eps, dists, list, stats + 1, fail);
+      return hipGetLastError();
+    });
+  };
+  using std::integral_constant;
+  hipError_t e;
   switch (DP / 128) {
-    case 1: KMX_KPP_FILTER(1); break;
-    case 2: KMX_KPP_FILTER(2); break;
-    case 3: KMX_KPP_FILTER(3); break;
-    case 4: KMX_KPP_FILTER(4); break;
-    default: KMX_KPP_FILTER(0); break;
+    case 1: e = filter(integral_constant<int, 1>{}); break;
+    case 2: e = filter(integral_constant<int, 2>{}); break;
+    case 3: e = filter(integral_constant<int, 3>{}); break;
+    case 4: e = filter(integral_constant<int, 4>{}); break;
+    default: e = filter(integral_constant<int, 0>{}); break;
   }
-#undef KMX_KPP_FILTER
-#undef KMX_KPP_FILTER1
-  const uint32_t lgrid = nb < 1024u ? nb : 1024u;
-  if (metric == 0)
-    hipLaunchKernelGGL((kmpp_step2_kernel<0>), dim3(lgrid), dim3(kKmppBlock), 0, st, samples, N, D, centroid, cc, dists,
-                       (KmppBlockStat *)nullptr, list, stats + 1, fail);
-  else
-    hipLaunchKernelGGL((kmpp_step2_kernel<1>), dim3(lgrid), dim3(kKmppBlock), 0, st, samples, N, D, centroid, cc, dists,
-                       (KmppBlockStat *)nullptr, list, stats + 1, fail);
+  if (e != hipSuccess) return e;
+  e = launch_kmpp_chains(metric, nb < 1024u ? nb : 1024u, samples, N, D, centroid, cc, dists, nullptr, list, stats + 1, fail, st);
+  if (e != hipSuccess) return e;
   if (weights && launch_kmpp_weigh(dists, weights, N, terms, fail, st) != hipSuccess) return hipGetLastError();
   hipLaunchKernelGGL(kmpp_stats_kernel, dim3((nb + 3) / 4 < 2048u ? (nb + 3) / 4 : 2048u), dim3(256), 0, st,
                      weights ? terms : dists, N,
@@ -1272,9 +1274,10 @@ __global__ void afk_min_dist_kernel(uint32_t m, uint32_t k, const float *__restr
 hipError_t launch_afk_qdist(int metric, const float *samples, uint32_t N, uint32_t D, const float *c1, float *dists,
                             hipStream_t st) {
   const dim3 grid((N + 127) / 128), block(128);
-  if (metric == 0) hipLaunchKernelGGL((afk_qdist_kernel<0>), grid, block, 0, st, samples, N, D, c1, dists);
-  else hipLaunchKernelGGL((afk_qdist_kernel<1>), grid, block, 0, st, samples, N, D, c1, dists);
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((afk_qdist_kernel<M()>), grid, block, 0, st, samples, N, D, c1, dists);
+    return hipGetLastError();
+  });
 }
 hipError_t launch_afk_q(float *q, uint32_t N, float dsum, hipStream_t st) {
   hipLaunchKernelGGL(afk_q_kernel, dim3((N + 255) / 256), dim3(256), 0, st, q, N, dsum);
@@ -1289,11 +1292,10 @@ hipError_t launch_afk_random_step(uint32_t m, uint64_t seed, uint64_t seq, const
 hipError_t launch_afk_min_dist(int metric, uint32_t m, uint32_t k, const float *samples, uint32_t D,
                                const uint32_t *choices, const float *centroids, float *min_dists, hipStream_t st) {
   const dim3 grid((m + 63) / 64), block(64);
-  if (metric == 0)
-    hipLaunchKernelGGL((afk_min_dist_kernel<0>), grid, block, 0, st, m, k, samples, D, choices, centroids, min_dists);
-  else
-    hipLaunchKernelGGL((afk_min_dist_kernel<1>), grid, block, 0, st, m, k, samples, D, choices, centroids, min_dists);
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((afk_min_dist_kernel<M()>), grid, block, 0, st, m, k, samples, D, choices, centroids, min_dists);
+    return hipGetLastError();
+  });
 }
 
 // LIBM_ACOS (kmamd_kmeans_assign's distance pass under KMCUDA_AMD_ASSIGN_DIST=member): the angle by acosf_fdlibm,

@@ -913,22 +913,15 @@ hipError_t launch_apply_delta(int metric, const double *delta, const int32_t *dc
                               uint32_t K, uint32_t D, float *centroids, uint32_t *ccounts, const StopCtl &stop,
                               hipStream_t st, const double *wtail, double *cweights) {
   const uint32_t bs = D >= 256 ? 256 : (D > 64 ? 128 : 64);
-  if (wtail) {
-    if (metric == 0)
-      hipLaunchKernelGGL((apply_delta_w_kernel<0>), dim3(K), dim3(bs), 0, st, delta, dcount, dcount_d, D, centroids,
+  return with_metric(metric, [&](auto M) {
+    if (wtail)
+      hipLaunchKernelGGL((apply_delta_w_kernel<M()>), dim3(K), dim3(bs), 0, st, delta, dcount, dcount_d, D, centroids,
                          ccounts, stop, wtail, cweights);
     else
-      hipLaunchKernelGGL((apply_delta_w_kernel<1>), dim3(K), dim3(bs), 0, st, delta, dcount, dcount_d, D, centroids,
-                         ccounts, stop, wtail, cweights);
+      hipLaunchKernelGGL((apply_delta_kernel<M()>), dim3(K), dim3(bs), 0, st, delta, dcount, dcount_d, D, centroids,
+                         ccounts, stop);
     return hipGetLastError();
-  }
-  if (metric == 0)
-    hipLaunchKernelGGL((apply_delta_kernel<0>), dim3(K), dim3(bs), 0, st, delta, dcount, dcount_d, D, centroids, ccounts,
-                       stop);
-  else
-    hipLaunchKernelGGL((apply_delta_kernel<1>), dim3(K), dim3(bs), 0, st, delta, dcount, dcount_d, D, centroids, ccounts,
-                       stop);
-  return hipGetLastError();
+  });
 }
 
 // several row shards on ONE device (KMCUDA_AMD_VIRTUAL_SHARDS): the all-reduce's stand-in.  Ascending buffer
@@ -1040,21 +1033,18 @@ hipError_t launch_adjust_exact(int metric, const float *samples, uint32_t N, uin
                      offsets2);
   const uint32_t grid = (K + 63) / 64;
   const size_t lds = (size_t)D * 64 * sizeof(float);
-  const bool use_lds = lds <= 128 * 1024;
-#define KMX_ADJ(M, L)                                                                                        \
-  hipLaunchKernelGGL((adjust_exact_kernel<M, L>), dim3(grid), dim3(64), (L) ? lds : 0, st, samples, D, K,    \
-                     rows_sorted, offsets2, centroids, ccounts, work)
-  if (use_lds) {
-    e = hipFuncSetAttribute(metric == 0 ? (const void *)adjust_exact_kernel<0, true>
-                                        : (const void *)adjust_exact_kernel<1, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (metric == 0) KMX_ADJ(0, true); else KMX_ADJ(1, true);
-  } else {
-    if (metric == 0) KMX_ADJ(0, false); else KMX_ADJ(1, false);
-  }
-#undef KMX_ADJ
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    return with_flag(lds <= 128 * 1024, [&](auto USE_LDS) {
+      if (USE_LDS()) {
+        const hipError_t e = hipFuncSetAttribute((const void *)adjust_exact_kernel<M(), true>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+      }
+      hipLaunchKernelGGL((adjust_exact_kernel<M(), USE_LDS()>), dim3(grid), dim3(64), USE_LDS() ? lds : 0, st, samples, D, K,
+                         rows_sorted, offsets2, centroids, ccounts, work);
+      return hipGetLastError();
+    });
+  });
 }
 
 // (kernels.hpp: preload_code_objects) touches one kernel of this translation unit: its code object -- with the radix

@@ -300,19 +300,15 @@ __global__ __launch_bounds__(128) void yy_local_filter_kernel(
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-#define KMX_DISPATCH(metric, kernel, grid, block, st, ...)                                    \
-  do {                                                                                        \
-    if ((metric) == 0) hipLaunchKernelGGL((kernel<0>), grid, block, 0, st, __VA_ARGS__);      \
-    else hipLaunchKernelGGL((kernel<1>), grid, block, 0, st, __VA_ARGS__);                    \
-  } while (0)
-
 hipError_t launch_yy_init(int metric, const float *xt, uint32_t len, uint32_t D, uint32_t G, const float *centroids,
                           const uint32_t *assignments, const uint32_t *cperm, const uint32_t *gstart, float *bounds,
                           hipStream_t st) {
   if (len == 0) return hipSuccess;
-  KMX_DISPATCH(metric, yy_init_kernel, dim3((len + 127) / 128), dim3(128), st, xt, len, D, G, centroids, assignments,
-               cperm, gstart, bounds);
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((yy_init_kernel<M()>), dim3((len + 127) / 128), dim3(128), 0, st, xt, len, D, G, centroids,
+                       assignments, cperm, gstart, bounds);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_yy_group_max(uint32_t K, uint32_t D, uint32_t G, const uint32_t *groups, const float *drifts,
@@ -324,7 +320,11 @@ hipError_t launch_yy_group_max(uint32_t K, uint32_t D, uint32_t G, const uint32_
 
 hipError_t launch_yy_drifts(int metric, const float *centroids, uint32_t K, uint32_t D, uint32_t G,
                             const uint32_t *groups, float *drifts, float *gdrifts, hipStream_t st) {
-  KMX_DISPATCH(metric, yy_calc_drifts_kernel, dim3((K + 63) / 64), dim3(64), st, centroids, K, D, drifts);
+  const hipError_t e = with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((yy_calc_drifts_kernel<M()>), dim3((K + 63) / 64), dim3(64), 0, st, centroids, K, D, drifts);
+    return hipGetLastError();
+  });
+  if (e != hipSuccess) return e;
   return launch_yy_group_max(K, D, G, groups, drifts, gdrifts, st);
 }
 
@@ -334,17 +334,15 @@ hipError_t launch_yy_global_filter(int metric, const float *samples, uint32_t le
                                    uint32_t *passed, uint32_t *counters, hipStream_t st) {
   if (len == 0) return hipSuccess;
   const size_t lds = (2 * 256 * 36 + 256) * sizeof(float);   // > 64 KB of dynamic LDS
-  const void *fn = metric == 0 ? (const void *)yy_global_filter_kernel<0> : (const void *)yy_global_filter_kernel<1>;
-  // (per device: the attribute belongs to the current device's copy of the kernel; setting it again is cheap)
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  if (metric == 0)
-    hipLaunchKernelGGL((yy_global_filter_kernel<0>), dim3((len + 255) / 256), dim3(256), lds, st, samples, len, D, K, G,
+  return with_metric(metric, [&](auto M) {
+    // (per device: the attribute belongs to the current device's copy of the kernel; setting it again is cheap)
+    const hipError_t e = hipFuncSetAttribute((const void *)yy_global_filter_kernel<M()>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((yy_global_filter_kernel<M()>), dim3((len + 255) / 256), dim3(256), lds, st, samples, len, D, K, G,
                        centroids, drifts, gdrifts, assignments, assignments_prev, bounds, passed, counters);
-  else
-    hipLaunchKernelGGL((yy_global_filter_kernel<1>), dim3((len + 255) / 256), dim3(256), lds, st, samples, len, D, K, G,
-                       centroids, drifts, gdrifts, assignments, assignments_prev, bounds, passed, counters);
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_yy_local_filter(int metric, const float *samples, uint32_t len, uint32_t D, uint32_t K, uint32_t G,
@@ -353,9 +351,11 @@ hipError_t launch_yy_local_filter(int metric, const float *samples, uint32_t len
                                   uint32_t *counters, hipStream_t st) {
   if (len == 0) return hipSuccess;
   // the passed count lives on the device: launch for the worst case, surplus threads exit at once
-  KMX_DISPATCH(metric, yy_local_filter_kernel, dim3((len + 127) / 128), dim3(128), st, samples, len, D, K, G, passed,
-               centroids, groups, drifts, gdrifts, assignments, bounds, counters);
-  return hipGetLastError();
+  return with_metric(metric, [&](auto M) {
+    hipLaunchKernelGGL((yy_local_filter_kernel<M()>), dim3((len + 127) / 128), dim3(128), 0, st, samples, len, D, K, G,
+                       passed, centroids, groups, drifts, gdrifts, assignments, bounds, counters);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace kmx

@@ -736,63 +736,43 @@ __global__ __launch_bounds__(256, 2) void yy_local_hint_kernel(YyArgs a) {
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-bool yy_hint_supported(uint32_t DP) { return DP >= 16 && DP <= 256; }
-
-template <int DP, int METRIC>
-static hipError_t launch_hint_t(const YyArgs &a, hipStream_t st) {
-  const size_t lds_bytes = 2 * 64 * DP * 2 + 512;
-  if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&yy_hint_kernel<DP, METRIC, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&yy_hint_kernel<DP, METRIC, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  const uint32_t grid = (a.len + 255) / 256;  // worst case; blocks beyond the passed count exit at once
-  if (a.D == (uint32_t)DP)
-    hipLaunchKernelGGL((yy_hint_kernel<DP, METRIC, true>), dim3(grid), dim3(256), lds_bytes, st, a);
-  else
-    hipLaunchKernelGGL((yy_hint_kernel<DP, METRIC, false>), dim3(grid), dim3(256), lds_bytes, st, a);
-  return hipGetLastError();
-}
-template <int DP, int METRIC>
-static hipError_t launch_local_hint_t(const YyArgs &a, hipStream_t st) {
-  const uint32_t grid = (a.len + 127) / 128;
-  const size_t lds_bytes = 2 * 64 * DP * 2 + 1024;
-  if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&yy_local_hint_kernel<DP, METRIC, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&yy_local_hint_kernel<DP, METRIC, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  if (a.D == (uint32_t)DP)
-    hipLaunchKernelGGL((yy_local_hint_kernel<DP, METRIC, true>), dim3(grid), dim3(256), lds_bytes, st, a);
-  else
-    hipLaunchKernelGGL((yy_local_hint_kernel<DP, METRIC, false>), dim3(grid), dim3(256), lds_bytes, st, a);
-  return hipGetLastError();
-}
-
-#define KMX_YYH_SWITCH(fn)                                                             \
-  switch (a.DP) {                                                                      \
-    case 16: return metric == 0 ? fn<16, 0>(a, st) : fn<16, 1>(a, st);                 \
-    case 32: return metric == 0 ? fn<32, 0>(a, st) : fn<32, 1>(a, st);                 \
-    case 64: return metric == 0 ? fn<64, 0>(a, st) : fn<64, 1>(a, st);                 \
-    case 128: return metric == 0 ? fn<128, 0>(a, st) : fn<128, 1>(a, st);              \
-    case 256: return metric == 0 ? fn<256, 0>(a, st) : fn<256, 1>(a, st);              \
-    default: return hipErrorInvalidValue;                                              \
-  }
+bool yy_hint_supported(uint32_t DP) { return DP != 0 && HintWidths::fit(DP) == DP; }
 
 hipError_t launch_yy_hint(int metric, const YyArgs &a, hipStream_t st) {
   if (a.len == 0) return hipSuccess;
-  KMX_YYH_SWITCH(launch_hint_t)
+  return with_width<HintWidths>(a.DP, [&](auto DP) {
+    return with_metric(metric, [&](auto M) {
+      return with_flag(a.D == (uint32_t)DP(), [&](auto FAST) {
+        const size_t lds_bytes = 2 * 64 * DP() * 2 + 512;
+        if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
+          const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&yy_hint_kernel<DP(), M(), FAST()>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+          if (e != hipSuccess) return e;
+        }
+        const uint32_t grid = (a.len + 255) / 256;  // worst case; blocks beyond the passed count exit at once
+        hipLaunchKernelGGL((yy_hint_kernel<DP(), M(), FAST()>), dim3(grid), dim3(256), lds_bytes, st, a);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t launch_yy_local_hint(int metric, const YyArgs &a, hipStream_t st) {
   if (a.len == 0) return hipSuccess;
-  KMX_YYH_SWITCH(launch_local_hint_t)
+  return with_width<HintWidths>(a.DP, [&](auto DP) {
+    return with_metric(metric, [&](auto M) {
+      return with_flag(a.D == (uint32_t)DP(), [&](auto FAST) {
+        const size_t lds_bytes = 2 * 64 * DP() * 2 + 1024;
+        if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
+          const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&yy_local_hint_kernel<DP(), M(), FAST()>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+          if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((yy_local_hint_kernel<DP(), M(), FAST()>), dim3((a.len + 127) / 128), dim3(256), lds_bytes, st, a);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 }  // namespace kmx

@@ -390,28 +390,17 @@ __global__ void yy_orig_panel_kernel(int metric, const float *__restrict__ centr
   if (threadIdx.x == 0) pbias[slot] = id != 0xFFFFFFFFu ? (metric == 0 ? (float)(-0.5 * n2) : 0.f) : -INFINITY;
 }
 
-template <int DP, int METRIC>
-static hipError_t launch_init_lds_t(const YyArgs &a, hipStream_t st) {
-  const size_t lds_bytes = (2 * 32 * (DP + 4) + 64 + 64 + 16) * sizeof(float);
-  const uint32_t grid = (a.len + 127) / 128;
-  if (a.D == (uint32_t)DP)
-    hipLaunchKernelGGL((yy_init_lds_kernel<DP, METRIC, true>), dim3(grid), dim3(256), lds_bytes, st, a);
-  else
-    hipLaunchKernelGGL((yy_init_lds_kernel<DP, METRIC, false>), dim3(grid), dim3(256), lds_bytes, st, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_yy_init_lds(int metric, const YyArgs &a, hipStream_t st) {
   if (a.len == 0) return hipSuccess;
-  switch (a.DP) {
-    case 8: return metric == 0 ? launch_init_lds_t<8, 0>(a, st) : launch_init_lds_t<8, 1>(a, st);
-    case 16: return metric == 0 ? launch_init_lds_t<16, 0>(a, st) : launch_init_lds_t<16, 1>(a, st);
-    case 32: return metric == 0 ? launch_init_lds_t<32, 0>(a, st) : launch_init_lds_t<32, 1>(a, st);
-    case 64: return metric == 0 ? launch_init_lds_t<64, 0>(a, st) : launch_init_lds_t<64, 1>(a, st);
-    case 128: return metric == 0 ? launch_init_lds_t<128, 0>(a, st) : launch_init_lds_t<128, 1>(a, st);
-    case 256: return metric == 0 ? launch_init_lds_t<256, 0>(a, st) : launch_init_lds_t<256, 1>(a, st);
-    default: return hipErrorInvalidValue;
-  }
+  return with_width<FilterWidths>(a.DP, [&](auto DP) {
+    return with_metric(metric, [&](auto M) {
+      return with_flag(a.D == (uint32_t)DP(), [&](auto FAST) {
+        const size_t lds_bytes = (2 * 32 * (DP() + 4) + 64 + 64 + 16) * sizeof(float);
+        hipLaunchKernelGGL((yy_init_lds_kernel<DP(), M(), FAST()>), dim3((a.len + 127) / 128), dim3(256), lds_bytes, st, a);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 hipError_t launch_yy_orig_panel(int metric, const float *centroids, uint32_t D, uint32_t DP, const uint32_t *pids,

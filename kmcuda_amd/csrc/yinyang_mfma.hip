@@ -233,30 +233,18 @@ __global__ __launch_bounds__(256, 2) void yy_local_mfma_kernel(YyArgs a) {
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-template <int DP, int METRIC>
-static hipError_t launch_local_t(const YyArgs &a, hipStream_t st) {
-  const size_t lds_bytes = (2 * 32 * (DP + 4) + 64 + 64) * sizeof(float);
-  const uint32_t grid = (a.len + 127) / 128;  // worst case; blocks beyond the passed count exit at once
-  if (a.D == (uint32_t)DP)
-    hipLaunchKernelGGL((yy_local_mfma_kernel<DP, METRIC, true>), dim3(grid), dim3(256), lds_bytes, st, a);
-  else
-    hipLaunchKernelGGL((yy_local_mfma_kernel<DP, METRIC, false>), dim3(grid), dim3(256), lds_bytes, st, a);
-  return hipGetLastError();
-}
-#define KMX_YY_SWITCH(fn)                                                              \
-  switch (a.DP) {                                                                      \
-    case 8: return metric == 0 ? fn<8, 0>(a, st) : fn<8, 1>(a, st);                    \
-    case 16: return metric == 0 ? fn<16, 0>(a, st) : fn<16, 1>(a, st);                 \
-    case 32: return metric == 0 ? fn<32, 0>(a, st) : fn<32, 1>(a, st);                 \
-    case 64: return metric == 0 ? fn<64, 0>(a, st) : fn<64, 1>(a, st);                 \
-    case 128: return metric == 0 ? fn<128, 0>(a, st) : fn<128, 1>(a, st);              \
-    case 256: return metric == 0 ? fn<256, 0>(a, st) : fn<256, 1>(a, st);              \
-    default: return hipErrorInvalidValue;                                              \
-  }
-
 hipError_t launch_yy_local_mfma(int metric, const YyArgs &a, hipStream_t st) {
   if (a.len == 0) return hipSuccess;
-  KMX_YY_SWITCH(launch_local_t)
+  return with_width<FilterWidths>(a.DP, [&](auto DP) {
+    return with_metric(metric, [&](auto M) {
+      return with_flag(a.D == (uint32_t)DP(), [&](auto FAST) {
+        const size_t lds_bytes = (2 * 32 * (DP() + 4) + 64 + 64) * sizeof(float);
+        const uint32_t grid = (a.len + 127) / 128;  // worst case; blocks beyond the passed count exit at once
+        hipLaunchKernelGGL((yy_local_mfma_kernel<DP(), M(), FAST()>), dim3(grid), dim3(256), lds_bytes, st, a);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 }  // namespace kmx
