@@ -415,6 +415,46 @@ int kmamd_knn_index_remove(kmamd_knn_index *ix, uint32_t n_ids, const uint32_t *
                            uint32_t *n_removed /* optional out, host */, int32_t device_ptrs);
 int kmamd_knn_index_radii(kmamd_knn_index *ix, float *radii /* host, clusters floats */);
 
+/* Filtered search: a query batch over a SUBSET of the corpus, for one call, without touching the index (DESIGN.md
+ * 4.17).  allow: one flag per corpus row id, n_rows bytes as the index counts them now (after any add / remove), on the
+ * side device_ptrs names; a row is allowed iff its flag is non-zero; one mask serves the whole batch.  A masked call
+ * returns, bit for bit in indices and distances, what the same call returns on the index kmamd_knn_index_create builds
+ * from the same rows and centroids with the assignments of every non-allowed row set to `clusters` -- remove()'s
+ * definition, for one call.  On every search path.  So:
+ *   - the flag of a row that has no cluster is ignored;
+ *   - with every flag set the call returns the bits of the unmasked call;
+ *   - with no row allowed every finite query gets index 0 at FLT_MAX in all k slots (a query with a NaN or inf feature
+ *     0xFFFFFFFF / NaN as ever);
+ *   - k up to n_rows stays valid; slots no allowed row fills hold what the fresh index puts there (index 0, FLT_MAX);
+ *   - computed query assignments and computed probe lists (query_assignments == NULL, probes == NULL) do not depend on
+ *     the mask: they rank centroids, not rows;
+ *   - the index is not modified.  If an allocation fails the call returns kmcudaMemoryAllocationFailure and the index
+ *     is still usable.  The per-call scratch is n_rows / 8 bytes of bits, 8 bytes per row for the member distances the
+ *     masked radii are reduced from and, for a host mask, its n_rows bytes staged on the device;
+ *   - NOT safe against a concurrent call on the same index, as the other calls are not.
+ * allow == NULL is exactly kmamd_knn_index_query / kmamd_knn_index_query_probe.  Every other argument, the refusals,
+ * the chunking (KMCUDA_AMD_KNN_QUERY_CHUNK; the mask is prepared once per call and shared by its chunks) and
+ * n_queries == 0 behave as in the call mirrored.  The cluster prunes -- the triangle test and the L2 per-query centroid
+ * bounds -- read the radii over the ALLOWED rows, the radii of that fresh index; a cluster without an allowed row is
+ * walked over like one without rows.  The f16-filtered search runs where the unmasked call's would; every other case
+ * (KMCUDA_AMD_KNN_EXACT, KMCUDA_AMD_FP16_STRICT, KMCUDA_AMD_FILTER=f32, an index or a query chunk that has left the
+ * f16 filter, more than 1024 features) takes the masked exact kernel: there is NO masked f32 filter.  The f16 filter
+ * still scores every row of a visited cluster (the mask drops candidates where survivors are queued).  Radius search
+ * takes no mask: kmamd_knn_index_radius_count / _fill have no such argument.
+ *   radii_allow   the radii a masked search with this mask prunes with (clusters floats, host; NaN: a cluster without
+ *                 an allowed row).  A window for tests, as kmamd_knn_index_radii.  allow == NULL: the index's own. */
+int kmamd_knn_index_query_allow(kmamd_knn_index *ix, uint32_t k, uint32_t n_queries, const void *queries,
+                                const uint32_t *query_assignments, uint32_t *neighbors, float *distances,
+                                uint32_t *query_assignments_out, int32_t device_ptrs,
+                                const uint8_t *allow /* optional, n_rows bytes */);
+int kmamd_knn_index_query_probe_allow(kmamd_knn_index *ix, uint32_t k, uint32_t nprobe, uint32_t n_queries,
+                                      const void *queries, const uint32_t *probes /* optional, n_queries x nprobe */,
+                                      uint32_t *neighbors, float *distances /* optional */,
+                                      uint32_t *probes_out /* optional, n_queries x nprobe */, int32_t device_ptrs,
+                                      const uint8_t *allow /* optional, n_rows bytes */);
+int kmamd_knn_index_radii_allow(kmamd_knn_index *ix, const uint8_t *allow /* optional, n_rows bytes */,
+                                int32_t device_ptrs /* where allow lies */, float *radii_host /* clusters floats */);
+
 /* Assigns rows to GIVEN centroids -- the "predict" of a trained K-means (no counterpart in the reference, whose
  * kmeans_cuda returns the assignments of the rows it was trained on only) -- with, as asked, the distance of every row
  * to its centroid and per-cluster statistics.  Stateless and synchronous; the caller owns all memory.

@@ -9,6 +9,8 @@ the same index: KnnIndex.query_radius, knn_query_radius; multi-probe (approximat
 clusters of every query or the clusters the caller lists: KnnIndex.query / knn_query with nprobe= or probes=.
 A live index: KnnIndex.add takes more rows in place, KnnIndex.remove takes rows out of every later search (ids stay
 stable, memory is not reclaimed); after either the index answers bit for bit as a freshly built one.
+Filtered search: KnnIndex.query / knn_query with allow= (one flag per row id) answer a batch over a subset of the
+corpus, exact or probed, bit for bit as an index without the other rows would, and leave the index as it is.
 New rows assigned to given centroids, with distances and cluster statistics (beyond the reference): kmeans_predict;
 the m nearest centroids of every row, in the order an assignment pass would find them: kmeans_predict_top.
 k-means|| seeding (beyond the reference), stand-alone -- kmeans_seed_parallel -- and as kmeans_cuda(init="k-means||").

@@ -26,6 +26,7 @@ EXPORTS = [
     "kmamd_knn_index_create", "kmamd_knn_index_query", "kmamd_knn_index_query_probe", "kmamd_knn_index_destroy",
     "kmamd_knn_index_radius_count", "kmamd_knn_index_radius_fill", "kmamd_knn_index_add", "kmamd_knn_index_info",
     "kmamd_knn_index_remove", "kmamd_knn_index_radii",
+    "kmamd_knn_index_query_allow", "kmamd_knn_index_query_probe_allow", "kmamd_knn_index_radii_allow",
     "kmamd_kmeans_assign", "kmamd_assigned_distances",
     "kmamd_kmeans_assign_top", "kmamd_assign_top_stats",
     "kmamd_kmeans_seed_parallel",
@@ -160,6 +161,12 @@ def lib():
     L.kmamd_knn_index_remove.argtypes = [vp, u32, vp, ctypes.POINTER(u32), i32]
     L.kmamd_knn_index_radii.restype = i32
     L.kmamd_knn_index_radii.argtypes = [vp, vp]
+    L.kmamd_knn_index_query_allow.restype = i32
+    L.kmamd_knn_index_query_allow.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, i32, vp]
+    L.kmamd_knn_index_query_probe_allow.restype = i32
+    L.kmamd_knn_index_query_probe_allow.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, vp, i32, vp]
+    L.kmamd_knn_index_radii_allow.restype = i32
+    L.kmamd_knn_index_radii_allow.argtypes = [vp, vp, i32, vp]
     L.kmamd_knn_index_destroy.restype = None
     L.kmamd_knn_index_destroy.argtypes = [vp]
     L.kmamd_kmeans_assign.restype = i32

@@ -512,7 +512,17 @@ struct KnnArgs {
   // ascending order without the own cluster, padded with 0xFFFFFFFF (launch_knn_probe_lists).  Unread otherwise.
   const uint32_t *plist = nullptr;
   uint32_t pw = 0;
+  // Masked search (kmamd_knn_index_query_allow / _probe_allow, the search kernels' MASK instantiations; DESIGN.md
+  // 4.17): bit p & 31 of allow_bits[p >> 5] says whether the corpus row at sorted position p may enter a heap
+  // (launch_knn_mask_pack: zeros behind the last clustered row, through the tile padding and one word further);
+  // allow_count[c] = the allowed rows of cluster c (0: the cluster is walked over like one without rows).  R then holds
+  // the radii over the allowed rows.  Unread otherwise.
+  const uint32_t *allow_bits = nullptr;
+  const uint32_t *allow_count = nullptr;
 };
+// the 64-bit words of KnnArgs::allow_bits for an index of N rows: every position a tile can name, plus the word the
+// f16 search's two-word read reaches behind it
+constexpr size_t knn_mask_words64(uint32_t N) { return ((size_t)N + KNN16_PAD_ROWS + 63) / 64 + 1; }
 constexpr int KNN_STATS = 5;
 constexpr uint32_t KNN_PROBE_MAX = 64;        // the widest probe list: one entry per lane
 constexpr uint32_t KNN_PROBE_BITMAP_K = 65536;  // the f16 probe search keeps a K-bit visit map in LDS: 8 KB at most
@@ -555,13 +565,15 @@ bool launch_knn_probe_order(const uint32_t *probes, uint32_t pw, const uint32_t 
                             uint32_t *keys_sorted, uint32_t *qperm, void *temp, size_t temp_bytes, hipStream_t st);
 // strict_h2 (both): the reference's half2 arithmetic on rows that hold half values (KMCUDA_AMD_FP16_STRICT)
 // probe (query mode only): own cluster, then KnnArgs::plist
+// mask (query mode only): the MASK instantiations, KnnArgs::allow_bits / allow_count set
 hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st, bool self = true,
-                            bool probe = false);
+                            bool probe = false, bool mask = false);
 hipError_t launch_knn_split(int metric, const float *xs, uint32_t N, uint32_t D, uint32_t DP, const float *mu,
                             void *xs16, float *n2c, float *mux, float *kbias, uint32_t *stats, hipStream_t st);
 // probe (query mode only, K <= KNN_PROBE_BITMAP_K): the PROBE instantiations
+// mask (query mode only, with or without probe): the MASK instantiations
 hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self = true,
-                                 bool probe = false);
+                                 bool probe = false, bool mask = false);
 hipError_t launch_knn_scatter(const uint32_t *sorted_out, const uint32_t *inv, uint32_t p_base, uint32_t p_end,
                               uint32_t k, uint32_t *neighbors, hipStream_t st);
 
@@ -608,6 +620,17 @@ struct KnnRemoveArgs {
 hipError_t launch_knn_remove_rows(const KnnRemoveArgs &a, hipStream_t st);
 // knn.hip: R[c] = the largest rdist of cluster c's sorted positions, NaN for an empty cluster (launch_knn_prep's last step)
 hipError_t launch_knn_radii(const float *rdist, const uint32_t *offsets, uint32_t K, float *R, hipStream_t st);
+
+// knn_mask.hip -- the allow-mask of a masked query (kmamd_knn_index_query_allow).
+// allow: one byte per row id (device), inv: sorted position -> row id (N), assigned: the device word that holds the
+// number of clustered rows (offsets + K).  bits (knn_mask_words64(N) words, all of them written): bit p & 63 of word
+// p >> 6 = allow[inv[p]] != 0 for p < *assigned, 0 from there on
+hipError_t launch_knn_mask_pack(const uint8_t *allow, const uint32_t *inv, uint32_t N, const uint32_t *assigned,
+                                unsigned long long *bits, hipStream_t st);
+// launch_knn_radii over the rows whose bit is set: R[c] = their largest rdist (NaN where cluster c has none),
+// count[c] = how many they are
+hipError_t launch_knn_masked_radii(const float *rdist, const uint32_t *offsets, uint32_t K, const uint32_t *bits,
+                                   float *R, uint32_t *count, hipStream_t st);
 
 // knn_radius.hip -- radius search of a query batch (kmamd_knn_index_radius_*).  `a` is the query mode's
 // KnnArgs (heaps / out / outd / k unread).  Query i of the chunk (caller's order; qinv: sorted query position -> i)

@@ -473,9 +473,12 @@ __global__ __launch_bounds__(256, 2) void knn_filter_kernel(KnnArgs a) {
 // SELF as in knn_filter_kernel: the self-join, or a query batch from the KnnArgs::q* buffers (nothing skipped)
 // PROBE (query mode): the own cluster, then the query's probe list (KnnArgs::plist: ascending ids, the own cluster left
 // out, 0xFFFFFFFF behind the last) instead of every cluster -- DESIGN.md 4.12
-template <int METRIC, bool H2, bool SELF, bool PROBE = false>
+// MASK (query mode): a candidate whose bit of KnnArgs::allow_bits is clear is passed over before its distance chain, a
+// cluster without an allowed row as one without rows (it holds nothing to push) -- DESIGN.md 4.17
+template <int METRIC, bool H2, bool SELF, bool PROBE = false, bool MASK = false>
 __global__ __launch_bounds__(64) void knn_exact_kernel(KnnArgs a) {
   static_assert(!(PROBE && SELF), "probe lists belong to a query batch");
+  static_assert(!(MASK && SELF), "an allow-mask belongs to a query batch");
   const uint32_t qp = a.p_base + blockIdx.x * blockDim.x + threadIdx.x;
   if (qp >= a.p_end) return;
   const uint32_t K = a.K, k = a.k, D = a.D, DP = a.DP;
@@ -514,10 +517,16 @@ __global__ __launch_bounds__(64) void knn_exact_kernel(KnnArgs a) {
       if (cd != cd) continue;
       if (cd - md - a.R[cls] > mndist) continue;
     }
+    if constexpr (MASK) {
+      if (a.allow_count[cls] == 0) continue;
+    }
     const uint32_t beg = a.offsets[cls], end = a.offsets[cls + 1];
     calced += end - beg;
     for (uint32_t cp = beg; cp < end; cp++) {
       if (SELF && cp == qp) continue;
+      if constexpr (MASK) {
+        if (!((a.allow_bits[cp >> 5] >> (cp & 31u)) & 1u)) continue;
+      }
       const float dist = H2 ? h2_distance<METRIC>(x, a.xs + (size_t)cp * DP, D)   // distance_tt, F = half2
                             : finalize<METRIC>(partial_vv<METRIC>(x, a.xs + (size_t)cp * DP, D));
       if (dist <= mndist) {
@@ -786,12 +795,19 @@ hipError_t launch_knn_filter(int metric, const KnnArgs &a, uint32_t nblocks, hip
   });
 }
 
-hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st, bool self, bool probe) {
+hipError_t launch_knn_exact(int metric, const KnnArgs &a, bool strict_h2, hipStream_t st, bool self, bool probe,
+                            bool mask) {
   if (a.p_end <= a.p_base) return hipSuccess;
   const dim3 grid((a.p_end - a.p_base + 63) / 64);
   if (probe && (self || !a.plist || a.pw == 0)) return hipErrorInvalidValue;
+  if (mask && (self || !a.allow_bits || !a.allow_count)) return hipErrorInvalidValue;
   return with_metric(metric, [&](auto M) {
     return with_flag(strict_h2, [&](auto H) {
+      if (mask)
+        return with_flag(probe, [&](auto P) {
+          hipLaunchKernelGGL((knn_exact_kernel<M(), H(), false, P(), true>), grid, dim3(64), 0, st, a);
+          return hipGetLastError();
+        });
       if (probe) {
         hipLaunchKernelGGL((knn_exact_kernel<M(), H(), false, true>), grid, dim3(64), 0, st, a);
         return hipGetLastError();

@@ -112,9 +112,14 @@ __global__ __launch_bounds__(256) void knn_split_kernel(const float *__restrict_
 // instead of 0..K-1, so the barrier per step is paid per cluster somebody probes; a query takes part in a step iff the
 // cluster is the next entry of its own list (a cursor per operand set: the lists and the walk both ascend).  Whatever
 // skips a barrier is decided from the map, offsets and C alone: block-uniform.
-template <int DP, int METRIC, bool FASTX, bool SELF, bool PROBE = false>
+// MASK (query mode): a candidate whose bit of KnnArgs::allow_bits is clear is dropped where tile padding
+// is dropped, when survivors are queued: the sub-tile's 32 bits (two words, the tile does not start on a word; the same
+// for every lane) are ANDed into the row mask.  The scores, the tile DMA, the LDS layout and the barriers are those of
+// the unmasked kernel; a cluster without an allowed row (KnnArgs::allow_count) is walked over like one without rows.
+template <int DP, int METRIC, bool FASTX, bool SELF, bool PROBE = false, bool MASK = false>
 __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void knn_filter_f16_kernel(KnnArgs a) {
   static_assert(!(PROBE && SELF), "probe lists belong to a query batch");
+  static_assert(!(MASK && SELF), "an allow-mask belongs to a query batch");
   constexpr int WV = knn16_waves(DP), NSET = knn16_nset(DP);
   constexpr int NKH = DP / 2;   // features per half-wave
   constexpr int KS = NKH / 8;   // k-steps = 16-byte chunks per half row
@@ -360,6 +365,9 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
       }
     }
     if (beg == end) continue;                     // nothing to visit (block-uniform)
+    if constexpr (MASK) {
+      if (a.allow_count[cls] == 0u) continue;     // no row of it may be returned (block-uniform)
+    }
     unsigned long long visiting = 0;
     uint32_t nvisit = 0;   // queries that visit the cluster BY THE REFERENCE'S RULE: what knn.cu:228 counts
 #pragma unroll
@@ -477,6 +485,12 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
 #pragma unroll
         for (int g = 0; g < 4; g++)
           rowmask |= (((m0 >> (4 * g)) & 0xFu) << (8 * g)) | (((m1 >> (4 * g)) & 0xFu) << (8 * g + 4));
+        if constexpr (MASK) {
+          // bit rho: may sorted position tile_base + rho be returned (wave-uniform; the word behind the last tile exists)
+          const uint32_t w = tile_base >> 5, sh = tile_base & 31u;
+          const unsigned long long two = ((unsigned long long)a.allow_bits[w + 1] << 32) | a.allow_bits[w];
+          rowmask &= (uint32_t)(two >> sh);
+        }
         while (__ballot(rowmask != 0u) != 0ull) {
           if (__ballot(qn_[e] == 4) != 0ull) flush(e);
           bool active = rowmask != 0u;
@@ -574,26 +588,30 @@ hipError_t launch_knn_split(int metric, const float *xs, uint32_t N, uint32_t D,
 }
 
 // PROBE (query mode): the tile ring's LDS plus the K-bit visit map
-template <int DP, int METRIC, bool SELF, bool PROBE>
+template <int DP, int METRIC, bool SELF, bool PROBE, bool MASK = false>
 static hipError_t launch_knn_f16_t(const KnnArgs &a, uint32_t nblocks, hipStream_t st) {
   const size_t lds_bytes = (size_t)knn16_nbuf(DP) * (32 * knn16_sub(DP) * DP * 2) + knn16_nbuf(DP) * 256 + 2 * knn16_waves(DP) * 4 +
                            (PROBE ? (size_t)((a.K + 31u) / 32u) * 4 : 0);
   return with_flag(a.D == (uint32_t)DP, [&](auto FAST) {
     if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, FAST(), SELF, PROBE>),
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_filter_f16_kernel<DP, METRIC, FAST(), SELF, PROBE, MASK>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
       if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, FAST(), SELF, PROBE>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
+    hipLaunchKernelGGL((knn_filter_f16_kernel<DP, METRIC, FAST(), SELF, PROBE, MASK>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, a);
     return hipGetLastError();
   });
 }
 
-hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self, bool probe) {
+hipError_t launch_knn_filter_f16(int metric, const KnnArgs &a, uint32_t nblocks, hipStream_t st, bool self, bool probe,
+                                 bool mask) {
   if (nblocks == 0) return hipSuccess;
   if (probe && (self || !a.plist || a.pw == 0 || a.K > KNN_PROBE_BITMAP_K)) return hipErrorInvalidValue;
+  if (mask && (self || !a.allow_bits || !a.allow_count)) return hipErrorInvalidValue;
   return with_width<KnnF16Widths>(a.DP, [&](auto DP) {
     return with_metric(metric, [&](auto M) {
+      if (mask)
+        return with_flag(probe, [&](auto P) { return launch_knn_f16_t<DP(), M(), false, P(), true>(a, nblocks, st); });
       if (probe) return launch_knn_f16_t<DP(), M(), false, true>(a, nblocks, st);
       return with_flag(self, [&](auto SELF) { return launch_knn_f16_t<DP(), M(), SELF(), false>(a, nblocks, st); });
     });

@@ -251,8 +251,11 @@ int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path,
                uint32_t nblocks, bool self, int verbosity, const uint32_t *probes, const uint32_t *qinv) {
   const bool f16 = path.use_f16;
   const bool probe = a.plist != nullptr;
+  const bool mask = a.allow_bits != nullptr;   // (the caller's a.R then: the radii over the allowed rows)
   const hipStream_t st = s.stream;
-  a.xs = s.xs; a.n2s = f16 ? s.n2c : s.n2s; a.inv = s.inv; a.offsets = s.offsets; a.mydist = s.mydist; a.R = s.R;
+  if (mask && (self || !a.allow_count || !a.R)) return kmcudaInvalidArguments;
+  const float *const R = mask ? a.R : s.R;
+  a.xs = s.xs; a.n2s = f16 ? s.n2c : s.n2s; a.inv = s.inv; a.offsets = s.offsets; a.mydist = s.mydist; a.R = R;
   a.C = s.C; a.stats = f16 ? s.stats_c : s.stats; a.N = s.N; a.D = s.D; a.DP = s.DP; a.K = s.K;
   a.eps = (float)(1.02 * ((double)s.D + 12.0) * ldexp(1.0, -24));  // the filters' slack, as the Lloyd filter
   a.calced = s.calced;
@@ -280,7 +283,7 @@ int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path,
       (void)hipGetLastError();
       if (verbosity > 1) printf("k-NN: no memory for the per-query centroid bounds, the reference's prune test alone\n");
     } else {
-      KMX_HIPRT(launch_knn_centroid_bounds(self ? s.xs : a.qxs, s.D, s.DP, a.p_base, a.p_end, s.centroids, s.K, s.R,
+      KMX_HIPRT(launch_knn_centroid_bounds(self ? s.xs : a.qxs, s.D, s.DP, a.p_base, a.p_end, s.centroids, s.K, R,
                                            x.lb, len, st));
       a.lb = x.lb;
       a.lb_stride = len;
@@ -293,15 +296,15 @@ int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path,
       if (sw.order != 0 && x.qperm &&
           launch_knn_query_order(x.lb, len, self ? s.offsets : a.qoffsets, s.K, a.p_base, a.p_end, x.keys_tmp,
                                  x.vals_tmp, x.keys_sorted, x.qperm, x.sort_temp, x.sort_bytes, st, sw.order,
-                                 self ? s.mydist : a.qmydist, s.R))
+                                 self ? s.mydist : a.qmydist, R))
         a.qperm = x.qperm;
       else
         (void)hipGetLastError();
     }
   }
-  if (probe)   // (no f32-filtered probe kernel: that path takes the exact one, as the radius search's does)
-    KMX_HIPRT(f16 ? launch_knn_filter_f16(s.metric, a, nblocks, st, false, true)
-                  : launch_knn_exact(s.metric, a, path.strict_h2, st, false, true));
+  if (probe || mask)   // (no f32-filtered probe or masked kernel: that path takes the exact one, as the radius search's does)
+    KMX_HIPRT(f16 ? launch_knn_filter_f16(s.metric, a, nblocks, st, false, probe, mask)
+                  : launch_knn_exact(s.metric, a, path.strict_h2, st, false, probe, mask));
   else
     KMX_HIPRT(!path.dp_filter ? launch_knn_exact(s.metric, a, path.strict_h2, st, self)
               : f16           ? launch_knn_filter_f16(s.metric, a, nblocks, st, self)

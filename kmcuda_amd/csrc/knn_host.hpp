@@ -103,7 +103,9 @@ std::vector<uint32_t> knn_xcd_plan(const std::vector<uint32_t> &plan);
 // the query order of the f16 search (buffers and sort scratch: `x`, with x.rows >= p_end - p_base) and picks the
 // kernel `path` names.  Probe mode (a.plist set, self = false): the PROBE kernels -- the f16 one where
 // `path` names the f16 filter, else the exact one -- without the centroid bounds; probes / qinv (the chunk's raw lists
-// and sorted position -> query, optional) give the f16 search its query order.
+// and sorted position -> query, optional) give the f16 search its query order.  Masked (a.allow_bits set, self =
+// false): the caller also sets a.allow_count and a.R, the radii over the allowed rows, which every
+// prune here reads instead of the shard's; the MASK kernels, the f16 one or the exact one as in probe mode.
 int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path, const KnnSwitches &sw,
                uint32_t nblocks, bool self, int verbosity, const uint32_t *probes = nullptr,
                const uint32_t *qinv = nullptr);

@@ -63,6 +63,15 @@ struct IndexState {
 };
 
 struct AddChunk;
+struct ArenaScratch;
+
+// What a masked call prepares once, for all its query chunks: the caller's flags as one bit per sorted
+// position, the allowed rows per cluster and the radii over them -- the radii of the index the call is defined by
+struct QueryMask {
+  uint32_t *bits = nullptr, *count = nullptr;
+  float *R = nullptr;
+  void fill_args(KnnArgs *a) const { a->allow_bits = bits; a->allow_count = count; a->R = R; }
+};
 
 class KnnIndex {
  public:
@@ -108,10 +117,13 @@ class KnnIndex {
   AssignTopRanker ranker;
   bool ranker_ready = false;
 
+  // allow (both; null: none): one flag per row id on the side device_ptrs names -- the masked search, DESIGN.md 4.17
   int query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
-            float *distances, uint32_t *qassign_out, int32_t device_ptrs);
+            float *distances, uint32_t *qassign_out, int32_t device_ptrs, const uint8_t *allow = nullptr);
   int query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queries, const uint32_t *probes_in,
-                  uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs);
+                  uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs,
+                  const uint8_t *allow = nullptr);
+  int prepare_mask(const uint8_t *allow, bool host, ArenaScratch &x, QueryMask *m);
   int radius(bool fill, float r, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *counts,
              uint32_t *qassign_out, const uint64_t *offsets, uint32_t *neighbors, float *distances, int32_t device_ptrs);
 
@@ -174,7 +186,7 @@ class KnnIndex {
 
   // ---- remove ----
   int remove(uint32_t n_ids, const uint32_t *ids, uint32_t *n_removed, int32_t device_ptrs);
-  int radii(float *out);
+  int radii(float *out, const uint8_t *allow = nullptr, int32_t device_ptrs = -1);
 };
 
 // n caller rows made cluster-sorted against this index: the buffers of one chunk of a query batch or of an add (sized
@@ -503,6 +515,25 @@ struct TopkResult {
   }
 };
 
+// The scratch of one call, taken from the index's arena and given back when the call ends, whichever way it ends
+// (behind a wait for the stream: kernels may still read it)
+struct ArenaScratch {
+  DeviceArena &a;
+  std::vector<void *> mine;
+  explicit ArenaScratch(DeviceArena &a_) : a(a_) {}
+  ~ArenaScratch() {
+    (void)hipStreamSynchronize(a.stream);
+    for (void *p : mine) a.release(p);
+  }
+  template <typename T>
+  int get(T **p, size_t count) {
+    const int rc = a.alloc(p, count);
+    if (rc == 0) mine.push_back(*p);
+    else (void)hipGetLastError();
+    return rc;
+  }
+};
+
 // the last wait of a query call (`what`: its name)
 int finish_query(const KnnIndex &ix, const char *what) {
   if (hipStreamSynchronize(ix.s.stream) == hipSuccess) return 0;
@@ -510,9 +541,37 @@ int finish_query(const KnnIndex &ix, const char *what) {
   return kmcudaRuntimeError;
 }
 
+// The mask of one call, enqueued on the index's stream; the scratch -- the staged bytes of a host
+// mask, N / 8 bytes of bits, the member distances -- is x's and goes with the call.  The radii are those of the index
+// the call is defined by, KnnIndex(rows, centroids, assignments with the denied rows' set to K): the chunked distances
+// by the member kernel a fresh index runs (the index keeps none: 4 bytes per row it would carry through every add and
+// remove, against one more pass over the rows per masked call), reduced over the allowed rows.
+int KnnIndex::prepare_mask(const uint8_t *allow, bool host, ArenaScratch &x, QueryMask *m) {
+  const uint32_t N = s.N, K = s.K;
+  const hipStream_t st = s.stream;
+  if (host) {
+    uint8_t *up = nullptr;
+    KNN_TRY(x.get(&up, N));
+    KMX_HIPCP(hipMemcpyAsync(up, allow, N, hipMemcpyHostToDevice, st));
+    allow = up;
+  }
+  unsigned long long *bits = nullptr;
+  float *mydist = nullptr, *rdist = nullptr;
+  KNN_TRY(x.get(&bits, knn_mask_words64(N)));
+  KNN_TRY(x.get(&mydist, N));
+  KNN_TRY(x.get(&rdist, N));
+  KNN_TRY(x.get(&m->R, K));
+  KNN_TRY(x.get(&m->count, K));
+  m->bits = reinterpret_cast<uint32_t *>(bits);
+  KMX_HIPRT(launch_knn_mask_pack(allow, s.inv, N, s.offsets + K, bits, st));
+  KMX_HIPRT(launch_knn_member(s.metric, s.xs, N, s.D, s.DP, s.offsets, K, s.centroids, mydist, rdist, path.strict_h2, st));
+  KMX_HIPRT(launch_knn_masked_radii(rdist, s.offsets, K, m->bits, m->R, m->count, st));
+  return 0;
+}
+
 // One query batch, in chunks of at most Qc queries; every buffer is sized for one chunk and reused.
 int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
-                    float *distances, uint32_t *qassign_out, int32_t device_ptrs) {
+                    float *distances, uint32_t *qassign_out, int32_t device_ptrs, const uint8_t *allow) {
   if (Q == 0) return 0;
   if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
   const hipStream_t st = s.stream;
@@ -520,11 +579,15 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
   const uint32_t Qc = knn_chunk_rows(kQueryChunkBytes, 4 * ((size_t)s.K + 2 * (size_t)k), sw.query_chunk, Q);
   const bool host = device_ptrs < 0;
 
+  ArenaScratch x(s);   // (before `c`: it waits for the stream, then releases)
+  QueryMask mask;
+  if (allow) KNN_TRY(prepare_mask(allow, host, x, &mask));
   // per-call buffers (freed with `c`), among them the sort scratch and the optional buffers of knn_search
   QueryChunk c;
   KNN_TRY(c.init(*this, Qc, !qassign_in));
   TopkResult res;
   KNN_TRY(res.init(c.w, Qc, k, host, distances != nullptr));
+  bool said = said_exact || verbosity <= 0;
   for (uint32_t q0 = 0; q0 < Q; q0 += Qc) {
     const uint32_t n = Q - q0 < Qc ? Q - q0 : Qc;
     KNN_TRY(c.prepare(*this, q0, n, queries, qassign_in, qassign_out, host));
@@ -532,6 +595,16 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
     KnnArgs a;
     c.fill_args(&a);
     res.fill_args(&a);
+    if (allow) {
+      // There is no f32-filtered masked search (as there is no such probe search): whatever is not the f16 filter
+      // takes the exact kernel.
+      if (!c.cp.use_f16) c.cp.dp_filter = 0;
+      if (!c.cp.use_f16 && !said) {
+        printf("k-NN masked query: every candidate is evaluated with the exact arithmetic (no f32-filtered masked search)\n");
+        said = true;
+      }
+      mask.fill_args(&a);
+    }
     a.p_end = c.cp.dp_filter ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
     KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity));
     KNN_TRY(res.deliver(q0, n, c.b.inv, neighbors, distances, st));
@@ -541,7 +614,8 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
 
 // One probed query batch: query() with the cluster loop driven by every query's probe list.
 int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queries, const uint32_t *probes_in,
-                          uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs) {
+                          uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs,
+                          const uint8_t *allow) {
   if (Q == 0) return 0;
   if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
   const uint32_t K = s.K;
@@ -551,6 +625,9 @@ int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queri
   const uint32_t Qc = knn_chunk_rows(kQueryChunkBytes, 4 * ((size_t)pw + 2 * (size_t)k), sw.query_chunk, Q);
   const bool host = device_ptrs < 0;
 
+  ArenaScratch x(s);   // (before `c`: it waits for the stream, then releases)
+  QueryMask mask;
+  if (allow) KNN_TRY(prepare_mask(allow, host, x, &mask));
   QueryChunk c;
   KNN_TRY(c.init(*this, Qc, false));
   DeviceArena &w = c.w;
@@ -588,6 +665,7 @@ int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queri
     res.fill_args(&a);
     a.p_end = c.cp.use_f16 ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
     a.plist = pr.lists; a.pw = pw;
+    if (allow) mask.fill_args(&a);
     KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity, pr.raw, c.b.inv));
     KNN_TRY(res.deliver(q0, n, c.b.inv, neighbors, distances, st));
   }
@@ -764,25 +842,6 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
   if (sw.stats) KNN_TRY(report_stats(*this, fill ? "radius fill" : "radius count"));
   return raised ? kmcudaInvalidArguments : 0;   // a query's hit count differs from its range
 }
-
-// The scratch of one call, taken from the index's arena and given back when the call ends, whichever way it ends
-// (behind a wait for the stream: kernels may still read it)
-struct ArenaScratch {
-  DeviceArena &a;
-  std::vector<void *> mine;
-  explicit ArenaScratch(DeviceArena &a_) : a(a_) {}
-  ~ArenaScratch() {
-    (void)hipStreamSynchronize(a.stream);
-    for (void *p : mine) a.release(p);
-  }
-  template <typename T>
-  int get(T **p, size_t count) {
-    const int rc = a.alloc(p, count);
-    if (rc == 0) mine.push_back(*p);
-    else (void)hipGetLastError();
-    return rc;
-  }
-};
 
 // A state under construction (none yet: nothing to do): released with the call, behind a wait for the stream, unless
 // the index has adopted it
@@ -988,11 +1047,14 @@ int KnnIndex::remove(uint32_t n_ids, const uint32_t *ids, uint32_t *n_removed, i
   return 0;
 }
 
-// R on the host (a window for tests: the radii are otherwise invisible)
-int KnnIndex::radii(float *out) {
+// R on the host (a window for tests: the radii are otherwise invisible); allow: the radii a masked search prunes with
+int KnnIndex::radii(float *out, const uint8_t *allow, int32_t device_ptrs) {
   if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
+  ArenaScratch x(s);
+  QueryMask mask;
+  if (allow) KNN_TRY(prepare_mask(allow, device_ptrs < 0, x, &mask));
   KMX_HIPRT(hipStreamSynchronize(s.stream));
-  KMX_HIPCP(hipMemcpy(out, s.R, (size_t)s.K * sizeof(float), hipMemcpyDeviceToHost));
+  KMX_HIPCP(hipMemcpy(out, allow ? mask.R : s.R, (size_t)s.K * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1053,9 +1115,20 @@ int kmamd_knn_index_query(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, co
   return h->ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs);
 }
 
-int kmamd_knn_index_query_probe(kmamd_knn_index *h, uint32_t k, uint32_t nprobe, uint32_t n_queries,
-                                const void *queries, const uint32_t *probes, uint32_t *neighbors, float *distances,
-                                uint32_t *probes_out, int32_t device_ptrs) {
+int kmamd_knn_index_query_allow(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, const void *queries,
+                                const uint32_t *query_assignments, uint32_t *neighbors, float *distances,
+                                uint32_t *query_assignments_out, int32_t device_ptrs, const uint8_t *allow) {
+  if (!query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
+  if (n_queries == 0) return kmcudaSuccess;
+  if (!queries || !neighbors) return kmcudaInvalidArguments;
+  sync_callers_writes(device_ptrs);
+  return h->ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs,
+                     allow);
+}
+
+int kmamd_knn_index_query_probe_allow(kmamd_knn_index *h, uint32_t k, uint32_t nprobe, uint32_t n_queries,
+                                      const void *queries, const uint32_t *probes, uint32_t *neighbors, float *distances,
+                                      uint32_t *probes_out, int32_t device_ptrs, const uint8_t *allow) {
   if (!query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
   KnnIndex &ix = h->ix;
   if (nprobe < 1 || nprobe > KNN_PROBE_MAX || nprobe > ix.s.K) return kmcudaInvalidArguments;
@@ -1064,7 +1137,14 @@ int kmamd_knn_index_query_probe(kmamd_knn_index *h, uint32_t k, uint32_t nprobe,
   if (n_queries == 0) return kmcudaSuccess;
   if (!queries || !neighbors) return kmcudaInvalidArguments;
   sync_callers_writes(device_ptrs);
-  return ix.query_probe(k, nprobe, n_queries, queries, probes, neighbors, distances, probes_out, device_ptrs);
+  return ix.query_probe(k, nprobe, n_queries, queries, probes, neighbors, distances, probes_out, device_ptrs, allow);
+}
+
+int kmamd_knn_index_query_probe(kmamd_knn_index *h, uint32_t k, uint32_t nprobe, uint32_t n_queries,
+                                const void *queries, const uint32_t *probes, uint32_t *neighbors, float *distances,
+                                uint32_t *probes_out, int32_t device_ptrs) {
+  return kmamd_knn_index_query_probe_allow(h, k, nprobe, n_queries, queries, probes, neighbors, distances, probes_out,
+                                           device_ptrs, nullptr);
 }
 
 static bool radius_call_ok(kmamd_knn_index *h, float radius, int32_t device_ptrs) {
@@ -1126,6 +1206,13 @@ int kmamd_knn_index_remove(kmamd_knn_index *h, uint32_t n_ids, const uint32_t *i
 int kmamd_knn_index_radii(kmamd_knn_index *h, float *radii) {
   if (!h || !radii) return kmcudaInvalidArguments;
   return h->ix.radii(radii);
+}
+
+int kmamd_knn_index_radii_allow(kmamd_knn_index *h, const uint8_t *allow, int32_t device_ptrs, float *radii_host) {
+  if (!h || !radii_host) return kmcudaInvalidArguments;
+  if (device_ptrs >= 0 && device_ptrs != h->ix.s.dev) return kmcudaInvalidArguments;
+  if (allow) sync_callers_writes(device_ptrs);
+  return h->ix.radii(radii_host, allow, device_ptrs);
 }
 
 int kmamd_knn_index_info(kmamd_knn_index *h, uint32_t *n_rows, uint32_t *n_clustered, int *filter) {

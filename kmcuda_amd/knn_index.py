@@ -31,6 +31,12 @@ centroids, assignments with assignments[ids] = K) would.  Ids are stable: n_rows
 (the rows move to the no-cluster tail; no compaction, no reuse of ids), and an index that has left the f16 filter stays
 where it is.  index.radii() reads the clusters' radii (a window for tests).
 
+Filtered search, DESIGN.md 4.17: index.query(queries, k, allow=mask) answers the batch over a subset of the corpus --
+mask is one flag per row id (n_rows of them, bool or uint8, on the queries' side); the lists are exactly -- indices and
+distance bits -- those of KnnIndex(rows, centroids, assignments with assignments[~mask] = K), for this call only: the
+index is not modified, and the next call may bring another mask.  It composes with nprobe / probes.  query_radius takes
+no mask.
+
 numpy in, numpy out (neighbors uint32, distances float32, assignments uint32).  torch tensors on the index's device
 in, torch tensors on that device out (neighbors / assignments int32: 0xFFFFFFFF reads -1), with no host round trip;
 the call orders with torch's work on the device (it waits for the device first and its outputs are complete when
@@ -214,6 +220,35 @@ def _check_probes(nprobe, probes, nq, clusters, q_dev, query_assignments, device
     return nprobe, p
 
 
+def _check_allow(allow, n_rows, q_dev, device):
+    """The allow-mask of a masked query as contiguous uint8 (numpy array / tensor on the index's device), or None."""
+    if allow is None:
+        return None
+    if _is_torch(allow):
+        import torch
+        if not q_dev:
+            raise TypeError("\"allow\" must be of the same kind as \"queries\" (numpy array or torch tensor)")
+        if allow.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("\"allow\" must be a 1D bool or uint8 tensor")
+        if allow.dim() != 1:
+            raise ValueError("\"allow\" must be a 1D tensor")
+        if not allow.is_cuda or allow.device.index != device:
+            raise ValueError("\"allow\" must be on the index's device")
+        if allow.shape[0] != n_rows:
+            raise ValueError("\"allow\" must have one flag per row of the index (%d)" % n_rows)
+        allow = allow.contiguous()
+        return allow.view(torch.uint8) if allow.dtype == torch.bool else allow
+    if not isinstance(allow, numpy.ndarray) or allow.dtype not in (numpy.bool_, numpy.uint8):
+        raise TypeError("\"allow\" must be a 1D bool or uint8 numpy array")
+    if q_dev:
+        raise TypeError("\"allow\" must be of the same kind as \"queries\" (numpy array or torch tensor)")
+    if allow.ndim != 1:
+        raise ValueError("\"allow\" must be a 1D numpy array")
+    if allow.shape[0] != n_rows:
+        raise ValueError("\"allow\" must have one flag per row of the index (%d)" % n_rows)
+    return numpy.ascontiguousarray(allow).view(numpy.uint8)
+
+
 def _check_radius(radius):
     if isinstance(radius, bool) or not isinstance(radius, (int, float, numpy.integer, numpy.floating)):
         raise TypeError("\"radius\" must be a real number")
@@ -268,20 +303,26 @@ class KnnIndex:
         self.h = h
 
     def query(self, queries, k, query_assignments=None, return_distances=True, return_assignments=False,
-              nprobe=None, probes=None, return_probes=False):
+              nprobe=None, probes=None, return_probes=False, allow=None):
         """The k nearest corpus rows of every query row: neighbors (Q x k corpus row indices), then, as asked,
         distances (Q x k float32, the exact distances the search compared) and the queries' clusters (Q).
         nprobe / probes: the multi-probe search (module docstring) -- only the clusters of every
         query's probe list are visited; return_assignments is then column 0 of the lists and return_probes appends the
-        Q x nprobe lists used (uint32 numpy / int32 tensor, K where fewer qualify)."""
+        Q x nprobe lists used (uint32 numpy / int32 tensor, K where fewer qualify).
+        allow: the filtered search (module docstring) -- one flag per row of the index (n_rows; 1-D
+        bool / uint8, numpy or a tensor on the index's device, as the queries are); only rows whose flag is set are
+        returned, exactly as by a fresh index on which every other row has lost its cluster.  Composes with nprobe /
+        probes and every return_* flag; the queries' clusters and computed probe lists do not depend on it."""
         if not getattr(self, "h", None):
             raise ValueError("the index is closed")
         k = _check_k(k, self.n_rows)
         q, nq, q_dev, qa = _check_queries(queries, self.fp16, self.features, self.clusters, query_assignments,
                                           self.device)
         nprobe, pr = _check_probes(nprobe, probes, nq, self.clusters, q_dev, query_assignments, self.device, self.fp16)
+        al = _check_allow(allow, self.n_rows, q_dev, self.device)
         if nprobe is not None:
-            return self._query_probe(q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes)
+            return self._query_probe(q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes,
+                                     al)
         if return_probes:
             raise ValueError("\"return_probes\" needs \"nprobe\" or \"probes\"")
         if q_dev:
@@ -295,14 +336,15 @@ class KnnIndex:
             dist = numpy.empty((nq, k), numpy.float32) if return_distances else None
             asg = numpy.empty((nq,), numpy.uint32) if return_assignments else None
         if nq:
-            rc = self.lib.kmamd_knn_index_query(self.h, k, nq, _ptr(q), _ptr(qa) if qa is not None else None, _ptr(nb),
-                                                _ptr(dist) if dist is not None else None,
-                                                _ptr(asg) if asg is not None else None, self.device if q_dev else -1)
+            rc = self.lib.kmamd_knn_index_query_allow(self.h, k, nq, _ptr(q), _ptr(qa) if qa is not None else None,
+                                                      _ptr(nb), _ptr(dist) if dist is not None else None,
+                                                      _ptr(asg) if asg is not None else None,
+                                                      self.device if q_dev else -1, _ptr(al) if al is not None else None)
             _raise_for(rc, "kmamd_knn_index_query")
         out = (nb,) + ((dist,) if return_distances else ()) + ((asg,) if return_assignments else ())
         return out[0] if len(out) == 1 else out
 
-    def _query_probe(self, q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes):
+    def _query_probe(self, q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes, al=None):
         want_lists = return_assignments or return_probes
         if q_dev:
             import torch
@@ -315,10 +357,12 @@ class KnnIndex:
             dist = numpy.empty((nq, k), numpy.float32) if return_distances else None
             used = numpy.empty((nq, nprobe), numpy.uint32) if want_lists else None
         if nq:
-            rc = self.lib.kmamd_knn_index_query_probe(self.h, k, nprobe, nq, _ptr(q), _ptr(pr) if pr is not None else None,
-                                                      _ptr(nb), _ptr(dist) if dist is not None else None,
-                                                      _ptr(used) if used is not None else None,
-                                                      self.device if q_dev else -1)
+            rc = self.lib.kmamd_knn_index_query_probe_allow(self.h, k, nprobe, nq, _ptr(q),
+                                                            _ptr(pr) if pr is not None else None, _ptr(nb),
+                                                            _ptr(dist) if dist is not None else None,
+                                                            _ptr(used) if used is not None else None,
+                                                            self.device if q_dev else -1,
+                                                            _ptr(al) if al is not None else None)
             _raise_for(rc, "kmamd_knn_index_query_probe")
         out = (nb,) + ((dist,) if return_distances else ())
         if return_assignments:
@@ -467,6 +511,21 @@ class KnnIndex:
         _raise_for(rc, "kmamd_knn_index_radii")
         return out
 
+    def radii_allow(self, allow):
+        """The radii a query with the mask `allow` (a numpy mask, or a tensor on the index's device) prunes with: over
+        the allowed rows, NaN for a cluster without one -- radii() of the fresh index the masked call is defined by.
+        numpy float32 (clusters,).  A window for tests, as radii()."""
+        if not getattr(self, "h", None):
+            raise ValueError("the index is closed")
+        on_dev = _is_torch(allow)
+        al = _check_allow(allow, self.n_rows, on_dev, self.device)
+        if al is None:
+            raise TypeError("\"allow\" must be a 1D bool or uint8 numpy array or tensor")
+        out = numpy.empty((self.clusters,), numpy.float32)
+        rc = self.lib.kmamd_knn_index_radii_allow(self.h, _ptr(al), self.device if on_dev else -1, _ptr(out))
+        _raise_for(rc, "kmamd_knn_index_radii_allow")
+        return out
+
     def info(self):
         """(n_rows, n_clustered, filter): the rows of the index, those of them that have a cluster, and the search it
         runs -- 2: the f16 matrix-core filter, 1: the f32 one, 0: every candidate evaluated exactly."""
@@ -497,7 +556,7 @@ class KnnIndex:
 
 def knn_query(k, samples, centroids, assignments, queries, metric="L2", device=0, query_assignments=None,
               return_distances=True, return_assignments=False, verbosity=0, nprobe=None, probes=None,
-              return_probes=False):
+              return_probes=False, allow=None):
     """One-shot KnnIndex(samples, centroids, assignments, metric, device).query(queries, k, ...): every argument is
     checked before the device is touched."""
     _get_metric(metric)
@@ -507,10 +566,11 @@ def knn_query(k, samples, centroids, assignments, queries, metric="L2", device=0
     np_, _ = _check_probes(nprobe, probes, nq, clusters, q_dev, query_assignments, device, fp16)
     if np_ is None and return_probes:
         raise ValueError("\"return_probes\" needs \"nprobe\" or \"probes\"")
+    _check_allow(allow, n, q_dev, device)
     with KnnIndex(samples, centroids, assignments, metric=metric, device=device, verbosity=verbosity) as ix:
         return ix.query(queries, k, query_assignments=query_assignments, return_distances=return_distances,
                         return_assignments=return_assignments, nprobe=nprobe, probes=probes,
-                        return_probes=return_probes)
+                        return_probes=return_probes, allow=allow)
 
 
 def knn_query_radius(radius, samples, centroids, assignments, queries, metric="L2", device=0, query_assignments=None,
