@@ -440,7 +440,8 @@ int kmamd_knn_index_radii(kmamd_knn_index *ix, float *radii /* host, clusters fl
  * (KMCUDA_AMD_KNN_EXACT, KMCUDA_AMD_FP16_STRICT, KMCUDA_AMD_FILTER=f32, an index or a query chunk that has left the
  * f16 filter, more than 1024 features) takes the masked exact kernel: there is NO masked f32 filter.  The f16 filter
  * still scores every row of a visited cluster (the mask drops candidates where survivors are queued).  Radius search
- * takes no mask: kmamd_knn_index_radius_count / _fill have no such argument.
+ * through kmamd_knn_index_radius_count / _fill: that pair takes no mask; the masked radius search is
+ * kmamd_knn_index_radius_count_allow / _fill_allow below.
  *   radii_allow   the radii a masked search with this mask prunes with (clusters floats, host; NaN: a cluster without
  *                 an allowed row).  A window for tests, as kmamd_knn_index_radii.  allow == NULL: the index's own. */
 int kmamd_knn_index_query_allow(kmamd_knn_index *ix, uint32_t k, uint32_t n_queries, const void *queries,
@@ -454,6 +455,43 @@ int kmamd_knn_index_query_probe_allow(kmamd_knn_index *ix, uint32_t k, uint32_t 
                                       const uint8_t *allow /* optional, n_rows bytes */);
 int kmamd_knn_index_radii_allow(kmamd_knn_index *ix, const uint8_t *allow /* optional, n_rows bytes */,
                                 int32_t device_ptrs /* where allow lies */, float *radii_host /* clusters floats */);
+
+/* Masked radius search: kmamd_knn_index_radius_count / _fill over a SUBSET of the corpus, for one
+ * call.  allow as in kmamd_knn_index_query_allow: one flag per corpus row id, n_rows bytes as the index counts them now,
+ * on the side device_ptrs names.  A hit of query q under mask allow and radius r is a corpus row i with
+ *     assignments[i] < clusters   and   allow[i] != 0   and   d(q, i) <= r,
+ * d the exact distance kmamd_knn_index_query returns and compares; hits come in ascending (cluster id, row id) order.
+ * That is what the unmasked radius call returns on the index kmamd_knn_index_create builds from the same rows and
+ * centroids with every denied row's assignment set to `clusters`, and equally the unmasked result of THIS index with
+ * the denied rows struck out -- a radius result is a brute-force set, so both are the same bits, on every search path
+ * and under every chunking.  So:
+ *   - the flag of a row that has no cluster is ignored;
+ *   - with every flag set the calls return the bits of the unmasked calls;
+ *   - with no row allowed every count is 0, and a fill whose offsets are all equal succeeds and writes nothing;
+ *   - a query with a NaN or inf feature has no hits;
+ *   - query_assignments still only group the queries and feed the cluster prune;
+ *   - the index is not modified.  If an allocation fails the call returns kmcudaMemoryAllocationFailure and the index
+ *     is still usable (the per-call scratch is that of kmamd_knn_index_query_allow);
+ *   - NOT safe against a concurrent call on the same index;
+ *   - the fill contract is unchanged: the offsets are checked before any write, and a query whose hit count differs
+ *     from its range gives InvalidArguments after the search with nothing written outside the ranges -- which is what
+ *     a count under one mask followed by a fill under another gets.  The count and the fill each prepare the mask: the
+ *     two calls are stateless;
+ *   - n_queries == 0 is success before the mask is looked at, and the unmasked call's refusals come first, in its order.
+ * allow == NULL is exactly kmamd_knn_index_radius_count / _fill (which are these calls with NULL).  The cluster prunes
+ * read the radii over the ALLOWED rows; a cluster without an allowed row is walked over like one without rows.  The
+ * masked f16 kernel runs where the unmasked one would and does not score a 32-row sub-tile none of whose rows is
+ * allowed; everything else (KMCUDA_AMD_KNN_EXACT, KMCUDA_AMD_FP16_STRICT -- which still prunes nothing --,
+ * KMCUDA_AMD_FILTER=f32, more than 1024 features, an index or a chunk that has left the half range) takes the masked
+ * exact kernel.  KMCUDA_AMD_KNN_STATS prints the same lines ("radius count" / "radius fill"). */
+int kmamd_knn_index_radius_count_allow(kmamd_knn_index *ix, float radius, uint32_t n_queries, const void *queries,
+                                       const uint32_t *query_assignments, uint32_t *counts,
+                                       uint32_t *query_assignments_out, int32_t device_ptrs,
+                                       const uint8_t *allow /* optional, n_rows bytes */);
+int kmamd_knn_index_radius_fill_allow(kmamd_knn_index *ix, float radius, uint32_t n_queries, const void *queries,
+                                      const uint32_t *query_assignments, const uint64_t *offsets,
+                                      uint32_t *neighbors, float *distances /* optional */, int32_t device_ptrs,
+                                      const uint8_t *allow /* optional, n_rows bytes */);
 
 /* Assigns rows to GIVEN centroids -- the "predict" of a trained K-means (no counterpart in the reference, whose
  * kmeans_cuda returns the assignments of the rows it was trained on only) -- with, as asked, the distance of every row

@@ -11,6 +11,8 @@ A live index: KnnIndex.add takes more rows in place, KnnIndex.remove takes rows 
 stable, memory is not reclaimed); after either the index answers bit for bit as a freshly built one.
 Filtered search: KnnIndex.query / knn_query with allow= (one flag per row id) answer a batch over a subset of the
 corpus, exact or probed, bit for bit as an index without the other rows would, and leave the index as it is.
+Masked radius search: KnnIndex.query_radius_allow / knn_query_radius with allow= -- query_radius's result with the
+denied rows struck out, bit for bit.
 New rows assigned to given centroids, with distances and cluster statistics (beyond the reference): kmeans_predict;
 the m nearest centroids of every row, in the order an assignment pass would find them: kmeans_predict_top.
 k-means|| seeding (beyond the reference), stand-alone -- kmeans_seed_parallel -- and as kmeans_cuda(init="k-means||").

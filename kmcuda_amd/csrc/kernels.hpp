@@ -649,9 +649,13 @@ struct KnnRadiusArgs {
   float *distances;           // optional
   uint32_t *flag;             // fill form: |= 1 if a query's hit count differs from its range
 };
-hipError_t launch_knn_radius_f16(int metric, const KnnRadiusArgs &ra, uint32_t nblocks, bool fill, hipStream_t st);
+// mask (both): the MASK instantiations (kmamd_knn_index_radius_*_allow) -- ra.a.allow_bits / allow_count
+// set (hipErrorInvalidValue otherwise) and ra.a.R the radii over the allowed rows
+hipError_t launch_knn_radius_f16(int metric, const KnnRadiusArgs &ra, uint32_t nblocks, bool fill, hipStream_t st,
+                                 bool mask = false);
 // every sorted query position of [a.p_base, a.p_end), the queries without a cluster included (no hits)
-hipError_t launch_knn_radius_exact(int metric, const KnnRadiusArgs &ra, bool strict_h2, bool fill, hipStream_t st);
+hipError_t launch_knn_radius_exact(int metric, const KnnRadiusArgs &ra, bool strict_h2, bool fill, hipStream_t st,
+                                   bool mask = false);
 // the queries of [a.p_base, a.p_end) the f16 kernel's block plan leaves out (no cluster): count 0 / an empty range
 hipError_t launch_knn_radius_rest(const KnnRadiusArgs &ra, bool fill, hipStream_t st);
 // *flag |= 1 if offsets[0 .. n] (device) decreases somewhere

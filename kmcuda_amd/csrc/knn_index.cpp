@@ -124,8 +124,10 @@ class KnnIndex {
                   uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs,
                   const uint8_t *allow = nullptr);
   int prepare_mask(const uint8_t *allow, bool host, ArenaScratch &x, QueryMask *m);
+  // allow (null: none): as query()'s -- the masked radius search, DESIGN.md 4.18
   int radius(bool fill, float r, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *counts,
-             uint32_t *qassign_out, const uint64_t *offsets, uint32_t *neighbors, float *distances, int32_t device_ptrs);
+             uint32_t *qassign_out, const uint64_t *offsets, uint32_t *neighbors, float *distances, int32_t device_ptrs,
+             const uint8_t *allow = nullptr);
 
   // ---- add ----
   int add(uint32_t n_rows, const void *rows, const uint32_t *assign_in, uint32_t *assign_out, int32_t device_ptrs);
@@ -676,9 +678,11 @@ int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queri
 
 // Radius search of one query batch: counts (fill = false) or the hits at the caller's CSR offsets.
 // Chunked as query(); a chunk's lb table (L2, up to 1024 features: the prune test) stays within kQueryChunkBytes.
+// allow: the masked search -- the mask is prepared once, behind the unmasked call's refusals, and every
+// chunk prunes with the radii over the allowed rows and runs the MASK kernels.
 int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *counts,
                      uint32_t *qassign_out, const uint64_t *offsets, uint32_t *neighbors, float *distances,
-                     int32_t device_ptrs) {
+                     int32_t device_ptrs, const uint8_t *allow) {
   if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
   const uint32_t D = s.D, DP = s.DP, K = s.K;
   const int metric = s.metric;
@@ -724,6 +728,10 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
     ~Staging() { (void)hipFree(nb); (void)hipFree(dist); }
   } stage;
 
+  ArenaScratch mx(s);   // (before `c`: it waits for the stream, then releases)
+  QueryMask mask;
+  if (allow) KNN_TRY(prepare_mask(allow, host, mx, &mask));
+  const float *R = allow ? mask.R : s.R;   // what the prune tests read: the radii over the rows that may be returned
   QueryChunk c;
   KNN_TRY(c.init(*this, Qc, !qassign_in));
   // (a fill's first chunk may be shorter than Qc, and the assignment pass reads Qc rows: defined values for them)
@@ -786,15 +794,16 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
     a.eps = (float)(1.02 * ((double)D + 12.0) * ldexp(1.0, -24));  // the filter's slack, as knn_search
     a.calced = s.calced;
     a.xs16 = s.xs16; a.mux = s.mux; a.kbias = s.kbias; a.mu2 = s.mu2;
+    if (allow) mask.fill_args(&a);   // (there is no masked f32 filter either: whatever is not the f16 kernel is the exact one)
     if (use_lb && c.assigned) {
-      KMX_HIPRT(launch_knn_centroid_bounds(c.b.xs, D, DP, 0, c.assigned, s.centroids, K, s.R, c.scratch.lb, c.assigned, st));
+      KMX_HIPRT(launch_knn_centroid_bounds(c.b.xs, D, DP, 0, c.assigned, s.centroids, K, R, c.scratch.lb, c.assigned, st));
       a.lb = c.scratch.lb;
       a.lb_stride = c.assigned;
       // queries that want the same clusters into the same waves, as knn_search orders them
       if (f16 && c.scratch.qperm) {
         KnnScratch &x = c.scratch;
         if (launch_knn_query_order(x.lb, c.assigned, c.offsets, K, 0, c.assigned, x.keys_tmp, x.vals_tmp, x.keys_sorted,
-                                   x.qperm, x.sort_temp, x.sort_bytes, st, sw.order, c.b.mydist, s.R))
+                                   x.qperm, x.sort_temp, x.sort_bytes, st, sw.order, c.b.mydist, R))
           a.qperm = x.qperm;
         else
           (void)hipGetLastError();
@@ -818,12 +827,12 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
       }
     }
     if (f16) {
-      KMX_HIPRT(launch_knn_radius_f16(metric, ra, (uint32_t)(c.plan.size() / 2), fill, st));
+      KMX_HIPRT(launch_knn_radius_f16(metric, ra, (uint32_t)(c.plan.size() / 2), fill, st, allow != nullptr));
       KnnRadiusArgs rest = ra;
       rest.a.p_base = c.assigned; rest.a.p_end = n;
       KMX_HIPRT(launch_knn_radius_rest(rest, fill, st));
     } else {
-      KMX_HIPRT(launch_knn_radius_exact(metric, ra, c.cp.strict_h2, fill, st));
+      KMX_HIPRT(launch_knn_radius_exact(metric, ra, c.cp.strict_h2, fill, st, allow != nullptr));
     }
     if (host && !fill)
       KMX_HIPCP(hipMemcpyAsync(counts + q0, counts_dev, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -1153,26 +1162,40 @@ static bool radius_call_ok(kmamd_knn_index *h, float radius, int32_t device_ptrs
   return device_ptrs < 0 || device_ptrs == h->ix.s.dev;
 }
 
-int kmamd_knn_index_radius_count(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
-                                 const uint32_t *query_assignments, uint32_t *counts, uint32_t *query_assignments_out,
-                                 int32_t device_ptrs) {
+int kmamd_knn_index_radius_count_allow(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
+                                       const uint32_t *query_assignments, uint32_t *counts,
+                                       uint32_t *query_assignments_out, int32_t device_ptrs, const uint8_t *allow) {
   if (!radius_call_ok(h, radius, device_ptrs)) return kmcudaInvalidArguments;
   if (n_queries == 0) return kmcudaSuccess;
   if (!queries || !counts) return kmcudaInvalidArguments;
   sync_callers_writes(device_ptrs);
   return h->ix.radius(false, radius, n_queries, queries, query_assignments, counts, query_assignments_out, nullptr,
-                      nullptr, nullptr, device_ptrs);
+                      nullptr, nullptr, device_ptrs, allow);
 }
 
-int kmamd_knn_index_radius_fill(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
-                                const uint32_t *query_assignments, const uint64_t *offsets, uint32_t *neighbors,
-                                float *distances, int32_t device_ptrs) {
+int kmamd_knn_index_radius_count(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
+                                 const uint32_t *query_assignments, uint32_t *counts, uint32_t *query_assignments_out,
+                                 int32_t device_ptrs) {
+  return kmamd_knn_index_radius_count_allow(h, radius, n_queries, queries, query_assignments, counts,
+                                            query_assignments_out, device_ptrs, nullptr);
+}
+
+int kmamd_knn_index_radius_fill_allow(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
+                                      const uint32_t *query_assignments, const uint64_t *offsets, uint32_t *neighbors,
+                                      float *distances, int32_t device_ptrs, const uint8_t *allow) {
   if (!radius_call_ok(h, radius, device_ptrs)) return kmcudaInvalidArguments;
   if (n_queries == 0) return kmcudaSuccess;
   if (!queries || !offsets || !neighbors) return kmcudaInvalidArguments;
   sync_callers_writes(device_ptrs);
   return h->ix.radius(true, radius, n_queries, queries, query_assignments, nullptr, nullptr, offsets, neighbors,
-                      distances, device_ptrs);
+                      distances, device_ptrs, allow);
+}
+
+int kmamd_knn_index_radius_fill(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
+                                const uint32_t *query_assignments, const uint64_t *offsets, uint32_t *neighbors,
+                                float *distances, int32_t device_ptrs) {
+  return kmamd_knn_index_radius_fill_allow(h, radius, n_queries, queries, query_assignments, offsets, neighbors,
+                                           distances, device_ptrs, nullptr);
 }
 
 int kmamd_knn_index_add(kmamd_knn_index *h, uint32_t n_rows, const void *rows, const uint32_t *assignments,

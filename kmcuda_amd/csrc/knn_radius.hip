@@ -19,6 +19,14 @@
 //   lb[c][q] > r                                       with the table of knn_centroid_bounds_kernel (KnnArgs::lb), else
 //   C[c][c_q] - d(q, c_q) - R[c] - margin > r          margin = prune_abs + prune_rel * (C + d + R), from the host;
 //   prune_abs = inf: no cluster is pruned (the half2 arithmetic).  A NaN term compares false: the cluster is visited.
+//
+// MASK (kmamd_knn_index_radius_count_allow / _fill_allow): a candidate whose bit of KnnArgs::allow_bits
+// is clear is no hit; KnnArgs::R holds the radii over the allowed rows, and a cluster without one (allow_count, R = NaN:
+// no prune test speaks) is walked over like one without rows.  The f16 kernel takes a sub-tile's 32 bits from two words
+// (the same for every lane) and ANDs them into the row mask; a sub-tile whose bits are all clear is not scored at all.
+// The bits from the cluster's end on (the next cluster's rows, the padding) do not count.  wait_tiles counts a wave's
+// DMAs per tile, so every wave issues for every tile exactly the pieces the unmasked kernel issues, in their order,
+// whatever it skips: the MASK kernels issue a sub-tile's pieces in front of its k-steps, not between them.
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
@@ -96,7 +104,7 @@ __device__ __forceinline__ bool rad_triangle_prunes(const KnnRadiusArgs &ra, uin
 
 }  // namespace
 
-template <int DP, int METRIC, bool FASTX, bool FILL>
+template <int DP, int METRIC, bool FASTX, bool FILL, bool MASK = false>
 __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void knn_radius_f16_kernel(KnnRadiusArgs ra) {
   const KnnArgs &a = ra.a;
   constexpr int WV = knn16_waves(DP), NSET = knn16_nset(DP);
@@ -260,6 +268,9 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
   for (uint32_t cls = 0; cls < K; cls++) {   // ascending cluster id: the order of the output
     const uint32_t beg = a.offsets[cls], end = a.offsets[cls + 1];
     if (beg == end) continue;                     // nothing to visit (block-uniform)
+    if constexpr (MASK) {
+      if (a.allow_count[cls] == 0u) continue;     // no row of it may be returned (block-uniform)
+    }
     bool pruned[NSET];
 #pragma unroll
     for (int e = 0; e < NSET; e++) {
@@ -404,20 +415,45 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
         for (int sub = 0; sub < SUB; sub++) {
           // (a last tile of one sub-tile only has no tile NBUF - 1 ahead: no piece is lost by the break)
           if (sub > 0 && tile_base + 32u * sub >= end) break;   // block-uniform
-          mfma_tile(buf, sub, dma, dma_base, dma_buf);
+          [[maybe_unused]] uint32_t allowed = 0;   // MASK: bit rho: may sorted position tile_base + 32 sub + rho be returned
+          if constexpr (MASK) {
+            // (the same for every lane, kept in a scalar register; the sub-tile starts below end <= N: the word behind
+            //  it exists.  The bits from `end` on are the next cluster's, or the padding's: not this sub-tile's rows)
+            const uint32_t sb = tile_base + 32u * sub, w = sb >> 5, sh = sb & 31u, left = end - sb;
+            const unsigned long long two = ((unsigned long long)a.allow_bits[w + 1] << 32) | a.allow_bits[w];
+            allowed = (uint32_t)(two >> sh) & (left < 32u ? (1u << left) - 1u : 0xFFFFFFFFu);
+            allowed = (uint32_t)__builtin_amdgcn_readfirstlane((int)allowed);
+            // The DMA pieces mfma_tile's k-steps of this sub-tile carry in the unmasked kernel -- piece slot / DSTR at slot
+            // sub * KS + j where slot % DSTR == 0 and slot / DSTR <= PPW -- and, behind the last sub-tile, the remainder
+            // up to PPW: consecutive pieces, issued HERE, in front of the decision, by every wave whatever it skips (the
+            // buffer is tile t - 1's: free since the barrier above).  One copy of the address arithmetic for both ways
+            // on: a second copy in a skip branch beside mfma_tile's cost 8 to 12 VGPRs and a wave per SIMD at DP 16 / 64.
+            if (dma) {
+              const int first = (sub * KS + DSTR - 1) / DSTR, last_slot = (sub * KS + KS - 1) / DSTR;
+              const int last = sub == SUB - 1 || last_slot > PPW ? PPW : last_slot;
+#pragma unroll
+              for (int i = first; i <= last; i++) issue_piece(dma_base, dma_buf, i);
+            }
+            if (allowed == 0u) continue;   // block-uniform: no row of it can be a hit -- not scored, not counted as scored
+          }
+          mfma_tile(buf, sub, dma && !MASK, dma_base, dma_buf);
           {   // statistics (wave-uniform)
             scored += NSET == 1 ? 1u : nsets_live;
             scored_sets += nsets_live;
             const uint32_t left = end - (tile_base + 32u * sub);
             useful += (unsigned long long)nvisit * (left < 32u ? left : 32u);
           }
-          if (sub == SUB - 1 && dma) {   // pieces the slots did not cover (very short rows)
+          if (sub == SUB - 1 && dma && !MASK) {   // pieces the slots did not cover (very short rows)
 #pragma unroll
             for (int i = (SUB * KS - 1) / DSTR + 1; i <= PPW; i++) issue_piece(dma_base, dma_buf, i);
           }
           uint32_t rowmask[NSET];
 #pragma unroll
           for (int e = 0; e < NSET; e++) rowmask[e] = score_mask(e);
+          if constexpr (MASK) {
+#pragma unroll
+            for (int e = 0; e < NSET; e++) rowmask[e] &= allowed;
+          }
 #pragma unroll
           for (int e = 0; e < NSET; e++) drain(e, rowmask[e], tile_base + 32u * sub);
         }
@@ -449,7 +485,7 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
 }
 
 // one thread per sorted query position of [p_base, p_end); a query without a cluster (a NaN or inf feature) has no hits
-template <int METRIC, bool H2, bool FILL>
+template <int METRIC, bool H2, bool FILL, bool MASK = false>
 __global__ __launch_bounds__(64) void knn_radius_exact_kernel(KnnRadiusArgs ra) {
   const KnnArgs &a = ra.a;
   const uint32_t qp = a.p_base + blockIdx.x * blockDim.x + threadIdx.x;
@@ -470,9 +506,15 @@ __global__ __launch_bounds__(64) void knn_radius_exact_kernel(KnnRadiusArgs ra) 
     for (uint32_t cls = 0; cls < K; cls++) {
       const uint32_t beg = a.offsets[cls], end = a.offsets[cls + 1];
       if (beg == end) continue;
+      if constexpr (MASK) {
+        if (a.allow_count[cls] == 0u) continue;   // no row of it may be returned
+      }
       if (a.lb ? a.lb[(size_t)cls * a.lb_stride + (qp - a.p_base)] > r : rad_triangle_prunes(ra, cls, mycls, md)) continue;
       calced += end - beg;
       for (uint32_t cp = beg; cp < end; cp++) {
+        if constexpr (MASK) {
+          if (((a.allow_bits[cp >> 5] >> (cp & 31u)) & 1u) == 0u) continue;
+        }
         const float dist = H2 ? h2_distance<METRIC>(x, a.xs + (size_t)cp * DP, D)   // distance_tt, F = half2
                               : rad_distance<METRIC>(x, a.xs + (size_t)cp * DP, D);
         if (dist <= r) {   // (a NaN distance is no hit)
@@ -513,37 +555,45 @@ __global__ void knn_radius_offsets_kernel(const unsigned long long *__restrict__
   if (i < n && offsets[i] > offsets[i + 1]) atomicOr(flag, 1u);
 }
 
-template <int DP, int METRIC, bool FILL>
+template <int DP, int METRIC, bool FILL, bool MASK>
 static hipError_t launch_knn_radius_f16_t(const KnnRadiusArgs &ra, uint32_t nblocks, hipStream_t st) {
   const size_t lds_bytes = (size_t)knn16_nbuf(DP) * (32 * knn16_sub(DP) * DP * 2) + knn16_nbuf(DP) * 256 + 2 * knn16_waves(DP) * 4;
   return with_flag(ra.a.D == (uint32_t)DP, [&](auto FAST) {
     if (lds_bytes > 65536) {   // (per launch: the attribute belongs to the current device's copy of the kernel)
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_radius_f16_kernel<DP, METRIC, FAST(), FILL>),
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_radius_f16_kernel<DP, METRIC, FAST(), FILL, MASK>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
       if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((knn_radius_f16_kernel<DP, METRIC, FAST(), FILL>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, ra);
+    hipLaunchKernelGGL((knn_radius_f16_kernel<DP, METRIC, FAST(), FILL, MASK>), dim3(nblocks), dim3(knn16_waves(DP) * 64), lds_bytes, st, ra);
     return hipGetLastError();
   });
 }
 
-hipError_t launch_knn_radius_f16(int metric, const KnnRadiusArgs &ra, uint32_t nblocks, bool fill, hipStream_t st) {
+hipError_t launch_knn_radius_f16(int metric, const KnnRadiusArgs &ra, uint32_t nblocks, bool fill, hipStream_t st,
+                                 bool mask) {
+  if (mask && (!ra.a.allow_bits || !ra.a.allow_count)) return hipErrorInvalidValue;
   if (nblocks == 0) return hipSuccess;
   return with_width<KnnF16Widths>(ra.a.DP, [&](auto DP) {
     return with_metric(metric, [&](auto M) {
-      return with_flag(fill, [&](auto FILL) { return launch_knn_radius_f16_t<DP(), M(), FILL()>(ra, nblocks, st); });
+      return with_flag(fill, [&](auto FILL) {
+        return with_flag(mask, [&](auto MASK) { return launch_knn_radius_f16_t<DP(), M(), FILL(), MASK()>(ra, nblocks, st); });
+      });
     });
   });
 }
 
-hipError_t launch_knn_radius_exact(int metric, const KnnRadiusArgs &ra, bool strict_h2, bool fill, hipStream_t st) {
+hipError_t launch_knn_radius_exact(int metric, const KnnRadiusArgs &ra, bool strict_h2, bool fill, hipStream_t st,
+                                   bool mask) {
+  if (mask && (!ra.a.allow_bits || !ra.a.allow_count)) return hipErrorInvalidValue;
   if (ra.a.p_end <= ra.a.p_base) return hipSuccess;
   const dim3 grid((ra.a.p_end - ra.a.p_base + 63) / 64);
   return with_metric(metric, [&](auto M) {
     return with_flag(strict_h2, [&](auto H) {
       return with_flag(fill, [&](auto FILL) {
-        hipLaunchKernelGGL((knn_radius_exact_kernel<M(), H(), FILL()>), grid, dim3(64), 0, st, ra);
-        return hipGetLastError();
+        return with_flag(mask, [&](auto MASK) {
+          hipLaunchKernelGGL((knn_radius_exact_kernel<M(), H(), FILL(), MASK()>), grid, dim3(64), 0, st, ra);
+          return hipGetLastError();
+        });
       });
     });
   });

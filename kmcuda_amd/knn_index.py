@@ -35,7 +35,8 @@ Filtered search, DESIGN.md 4.17: index.query(queries, k, allow=mask) answers the
 mask is one flag per row id (n_rows of them, bool or uint8, on the queries' side); the lists are exactly -- indices and
 distance bits -- those of KnnIndex(rows, centroids, assignments with assignments[~mask] = K), for this call only: the
 index is not modified, and the next call may bring another mask.  It composes with nprobe / probes.  query_radius takes
-no mask.
+no mask; query_radius_allow(queries, radius, mask) is the masked radius search: query_radius's result
+with the denied rows struck out, bit for bit, and knn_query_radius(..., allow=mask) its one-shot form.
 
 numpy in, numpy out (neighbors uint32, distances float32, assignments uint32).  torch tensors on the index's device
 in, torch tensors on that device out (neighbors / assignments int32: 0xFFFFFFFF reads -1), with no host round trip;
@@ -378,12 +379,28 @@ class KnnIndex:
         distances]): offsets int64 of Q + 1 entries, neighbors / distances flat of length offsets[-1], query i owning
         [offsets[i]:offsets[i + 1]] in ascending (cluster id, row index) order, or by (distance, row index) with sort.
         The search runs twice, once to count and once to fill; the queries' clusters are computed once."""
+        return self._query_radius(queries, radius, None, False, query_assignments, return_distances, sort, count_only)
+
+    def query_radius_allow(self, queries, radius, allow, query_assignments=None, return_distances=True, sort=False,
+                           count_only=False):
+        """query_radius over the rows the mask allows (DESIGN.md 4.18): allow is one flag per row of the index (n_rows;
+        1-D bool / uint8, numpy or a tensor on the index's device, as the queries are), and the result is exactly
+        query_radius's -- the same return value, bit for bit -- with the denied rows struck out; equally, what a fresh
+        index on which every denied row has lost its cluster returns.  The index is not modified.  The count and the
+        fill each prepare the mask (two stateless calls)."""
+        return self._query_radius(queries, radius, allow, True, query_assignments, return_distances, sort, count_only)
+
+    def _query_radius(self, queries, radius, allow, masked, query_assignments, return_distances, sort, count_only):
         if not getattr(self, "h", None):
             raise ValueError("the index is closed")
         r = _check_radius(radius)
         _check_radius_flags(return_distances, sort, count_only)
         q, nq, q_dev, qa = _check_queries(queries, self.fp16, self.features, self.clusters, query_assignments,
                                           self.device)
+        al = _check_allow(allow, self.n_rows, q_dev, self.device)
+        if masked and al is None:
+            raise TypeError("\"allow\" must be a 1D bool or uint8 numpy array or tensor")
+        alp = _ptr(al) if al is not None else None
         dptr = self.device if q_dev else -1
         if q_dev:
             import torch
@@ -394,9 +411,10 @@ class KnnIndex:
             counts = numpy.zeros((nq,), numpy.uint32)
             asg = numpy.empty((nq,), numpy.uint32) if qa is None else None
         if nq:
-            rc = self.lib.kmamd_knn_index_radius_count(self.h, r, nq, _ptr(q), _ptr(qa) if qa is not None else None,
-                                                       _ptr(counts), _ptr(asg) if asg is not None else None, dptr)
-            _raise_for(rc, "kmamd_knn_index_radius_count")
+            rc = self.lib.kmamd_knn_index_radius_count_allow(self.h, r, nq, _ptr(q),
+                                                             _ptr(qa) if qa is not None else None, _ptr(counts),
+                                                             _ptr(asg) if asg is not None else None, dptr, alp)
+            _raise_for(rc, "kmamd_knn_index_radius_count_allow" if masked else "kmamd_knn_index_radius_count")
         if count_only:
             return counts
         if qa is None:
@@ -415,9 +433,9 @@ class KnnIndex:
             nb = numpy.empty((total,), numpy.uint32)
             dist = numpy.empty((total,), numpy.float32) if return_distances else None
         if nq and total:
-            rc = self.lib.kmamd_knn_index_radius_fill(self.h, r, nq, _ptr(q), _ptr(qa), _ptr(offsets), _ptr(nb),
-                                                      _ptr(dist) if dist is not None else None, dptr)
-            _raise_for(rc, "kmamd_knn_index_radius_fill")
+            rc = self.lib.kmamd_knn_index_radius_fill_allow(self.h, r, nq, _ptr(q), _ptr(qa), _ptr(offsets), _ptr(nb),
+                                                            _ptr(dist) if dist is not None else None, dptr, alp)
+            _raise_for(rc, "kmamd_knn_index_radius_fill_allow" if masked else "kmamd_knn_index_radius_fill")
         if sort:
             nb, dist = _sort_slices(offsets, nb, dist)
         return (offsets, nb, dist) if return_distances else (offsets, nb)
@@ -574,14 +592,19 @@ def knn_query(k, samples, centroids, assignments, queries, metric="L2", device=0
 
 
 def knn_query_radius(radius, samples, centroids, assignments, queries, metric="L2", device=0, query_assignments=None,
-                     return_distances=True, sort=False, count_only=False, verbosity=0):
-    """One-shot KnnIndex(samples, centroids, assignments, metric, device).query_radius(queries, radius, ...): every
-    argument is checked before the device is touched."""
+                     return_distances=True, sort=False, count_only=False, verbosity=0, allow=None):
+    """One-shot KnnIndex(samples, centroids, assignments, metric, device).query_radius(queries, radius, ...), or with
+    allow= (one flag per sample) .query_radius_allow(queries, radius, allow, ...): every argument is checked before the
+    device is touched."""
     _get_metric(metric)
     _, _, _, fp16, n, d, clusters, _ = _check_corpus(samples, centroids, assignments, device)
     _check_radius(radius)
     _check_radius_flags(return_distances, sort, count_only)
-    _check_queries(queries, fp16, d, clusters, query_assignments, device)
+    _, _, q_dev, _ = _check_queries(queries, fp16, d, clusters, query_assignments, device)
+    _check_allow(allow, n, q_dev, device)
     with KnnIndex(samples, centroids, assignments, metric=metric, device=device, verbosity=verbosity) as ix:
+        if allow is not None:
+            return ix.query_radius_allow(queries, radius, allow, query_assignments=query_assignments,
+                                         return_distances=return_distances, sort=sort, count_only=count_only)
         return ix.query_radius(queries, radius, query_assignments=query_assignments,
                                return_distances=return_distances, sort=sort, count_only=count_only)

@@ -7,7 +7,15 @@ kmeans_cuda), `--queries` FRESH draws from the same mixture, at the radius whose
 Prints the times of the count pass, the fill pass with and without distances, and of index.query(k = --hits) on the
 same index and build; the ratio (count + fill with distances) / query; and, from one more count and fill under
 KMCUDA_AMD_KNN_STATS, the radius searches' counters.  Every time is a host clock around a synchronous call on device tensors
-(the calls wait for the device before they return); the first call of each kind is warm-up and is reported apart."""
+(the calls wait for the device before they return); the first call of each kind is warm-up and is reported apart.
+
+`--allow-fraction f` (several allowed) adds the MASKED radius search (kmamd_knn_index_radius_count_allow / _fill_allow,
+DESIGN.md 4.18) beside the unmasked one: for every fraction a device-resident mask that allows about f of the rows --
+`--mask-layout random`: every row with probability f; `runs`: the row ids in contiguous runs of 4096, a run allowed with
+probability f (a mask that is not random: ids drawn together come from the same stretch of the corpus) --, its masked
+count and fill (with distances, at the offsets of its own count), the mask preparation alone (radii_allow: the same
+pack, member pass and reduction, plus a K-float copy), and the counters of one masked count.  `--unmasked-only` stops
+after the count and fill timings (for a comparison of two builds)."""
 import argparse
 import ctypes
 import os
@@ -25,6 +33,11 @@ def main():
     ap.add_argument("--queries", type=int, default=100000)
     ap.add_argument("--hits", type=int, default=20)
     ap.add_argument("--repeat", type=int, default=3, help="timed calls of each kind after one warm-up call")
+    ap.add_argument("--allow-fraction", type=float, action="append", default=[],
+                    help="also time the masked search with about this fraction of the rows allowed (repeatable)")
+    ap.add_argument("--mask-layout", choices=("random", "runs"), default="random",
+                    help="runs: the allowed ids come in contiguous runs of 4096 ids")
+    ap.add_argument("--unmasked-only", action="store_true", help="count and fill only")
     args = ap.parse_args()
     import torch
     from kmcuda_amd import KnnIndex, kmeans_cuda
@@ -91,13 +104,18 @@ def main():
     print("radius %.6g: hits per query min %d / median %d / mean %.1f / max %d, %d in all, %d queries without a hit" %
           (r, int(c.min()), int(c.median()), float(c.double().mean()), int(c.max()), total, int((c == 0).sum())), flush=True)
     results = {}
-    for name, fn in (("count", count), ("fill with distances", lambda: fill(True)),
-                     ("fill without distances", lambda: fill(False)), ("query(k=%d)" % k, lambda: ix.query(q, k)),
-                     ("query_radius (count + fill, Python)", lambda: ix.query_radius(q, r))):
+    arms = (("count", count), ("fill with distances", lambda: fill(True)),
+            ("fill without distances", lambda: fill(False)), ("query(k=%d)" % k, lambda: ix.query(q, k)),
+            ("query_radius (count + fill, Python)", lambda: ix.query_radius(q, r)))
+    for name, fn in arms[:2] if args.unmasked_only else arms:
         warm, runs = timed(fn)
         results[name] = min(runs)
         print("%-40s warm-up %.4f s; %s s" % (name, warm, " / ".join("%.4f" % t for t in runs)), flush=True)
     both = results["count"] + results["fill with distances"]
+    if args.unmasked_only:
+        print("count + fill with distances = %.4f s (best of %d each)" % (both, args.repeat), flush=True)
+        ix.close()
+        return
     print("count + fill with distances = %.4f s; query(k=%d) = %.4f s; ratio %.2f (best of %d each)" %
           (both, k, results["query(k=%d)" % k], both / results["query(k=%d)" % k], args.repeat), flush=True)
     # the counters of one pass of each (printed by the library)
@@ -106,6 +124,46 @@ def main():
     fill(True)
     del os.environ["KMCUDA_AMD_KNN_STATS"]
     print("all pairs: %d" % (n * Q), flush=True)
+    # ---- the masked search ----
+    for f in args.allow_fraction:
+        if args.mask_layout == "random":
+            mask = torch.rand((n,), device=dev, generator=gen) < f
+        else:
+            runs_ok = torch.rand(((n + 4095) // 4096,), device=dev, generator=gen) < f
+            mask = runs_ok.repeat_interleave(4096)[:n].contiguous()
+        m8 = mask.view(torch.uint8)
+        mcounts = torch.zeros((Q,), dtype=torch.int32, device=dev)
+
+        def mcount():
+            _raise_for(ix.lib.kmamd_knn_index_radius_count_allow(ix.h, r, Q, vp(q.data_ptr()), vp(qa.data_ptr()),
+                                                                 vp(mcounts.data_ptr()), None, 0, vp(m8.data_ptr())), "count")
+        mcount()
+        moffsets = torch.zeros((Q + 1,), dtype=torch.int64, device=dev)
+        torch.cumsum(mcounts.to(torch.int64), 0, out=moffsets[1:])
+        mtotal = int(moffsets[-1])
+        mnb = torch.empty((max(mtotal, 1),), dtype=torch.int32, device=dev)
+        md = torch.empty((max(mtotal, 1),), dtype=torch.float32, device=dev)
+
+        def mfill():
+            _raise_for(ix.lib.kmamd_knn_index_radius_fill_allow(ix.h, r, Q, vp(q.data_ptr()), vp(qa.data_ptr()),
+                                                                vp(moffsets.data_ptr()), vp(mnb.data_ptr()),
+                                                                vp(md.data_ptr()), 0, vp(m8.data_ptr())), "fill")
+        print("mask %s, fraction %g: %d of %d rows allowed, %d hits in all (unmasked %d)" %
+              (args.mask_layout, f, int(mask.sum()), n, mtotal, total), flush=True)
+        mres = {}
+        for name, fn in (("masked count", mcount), ("masked fill with distances", mfill),
+                         ("mask preparation alone (radii_allow)", lambda: ix.radii_allow(mask))):
+            warm, runs = timed(fn)
+            mres[name] = min(runs)
+            print("%-40s warm-up %.4f s; %s s" % (name, warm, " / ".join("%.4f" % t for t in runs)), flush=True)
+        print("fraction %g: masked count %.4f s (unmasked %.4f, x%.2f), masked fill %.4f s (unmasked %.4f, x%.2f), two "
+              "mask preparations %.4f s" % (f, mres["masked count"], results["count"], mres["masked count"] / results["count"],
+                                            mres["masked fill with distances"], results["fill with distances"],
+                                            mres["masked fill with distances"] / results["fill with distances"],
+                                            2 * mres["mask preparation alone (radii_allow)"]), flush=True)
+        os.environ["KMCUDA_AMD_KNN_STATS"] = "1"
+        mcount()
+        del os.environ["KMCUDA_AMD_KNN_STATS"]
     ix.close()
 
 
