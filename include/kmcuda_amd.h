@@ -493,6 +493,34 @@ int kmamd_knn_index_radius_fill_allow(kmamd_knn_index *ix, float radius, uint32_
                                       uint32_t *neighbors, float *distances /* optional */, int32_t device_ptrs,
                                       const uint8_t *allow /* optional, n_rows bytes */);
 
+/* Capped search: the k nearest rows of every query, but only those within max_distance -- the hybrid
+ * search (radius plus a limit on the count) in one pass.  max_distance = r is a float32 that is not NaN and >= 0 (else
+ * InvalidArguments, before any device call); +inf is accepted and means FLT_MAX.  The list of a query is the list of
+ * kmamd_knn_index_query (of _query_probe when probed, of the _allow forms when masked) with ONE change: wherever that
+ * procedure reads kth, it reads min(kth, r).  So
+ *   - a candidate is pushed iff distance <= min(kth, r) -- inclusive: a row at exactly r is returned;
+ *   - a cluster is skipped iff C[c][c_q] - d(q, c_q) - R[c] > min(kth, r), and the f16 search's second test reads
+ *     lb[c][q] > min(kth, r);
+ *   - the heap is the same heap: k slots of (FLT_MAX, index 0) at the start, popped into the same sorted order.  The
+ *     real entries of a row are those with distance <= r and they come first; a slot no row within r filled holds
+ *     index 0 at FLT_MAX, as the filler tail of query does;
+ *   - a query with a NaN or inf feature still gets 0xFFFFFFFF / NaN;
+ *   - with r = FLT_MAX (or inf) the call returns the bits of the uncapped call, fillers included.
+ * On data without distance ties this is query's list with every entry beyond r replaced by the filler; the procedure
+ * above is the definition.  The cap is live from the first candidate: the filters' threshold and both cluster prunes
+ * start at r instead of FLT_MAX, so a query with fewer than k rows within r no longer scans the corpus.  One cap per
+ * call (no per-query array).  Every other argument, the refusals (a null handle among them), the chunking, allow (NULL:
+ * no mask) and n_queries == 0 behave as in kmamd_knn_index_query_allow / kmamd_knn_index_query_probe_allow, which are
+ * these calls at FLT_MAX; the same kernels run on the same paths.  KMCUDA_AMD_KNN_STATS: query_capped prints the
+ * search's counters as "capped query" at the end of the call, query_probe_capped the "probe query" line. */
+int kmamd_knn_index_query_capped(kmamd_knn_index *ix, uint32_t k, float max_distance, uint32_t n_queries,
+    const void *queries, const uint32_t *query_assignments, uint32_t *neighbors, float *distances,
+    uint32_t *query_assignments_out, int32_t device_ptrs, const uint8_t *allow /* optional */);
+
+int kmamd_knn_index_query_probe_capped(kmamd_knn_index *ix, uint32_t k, float max_distance, uint32_t nprobe,
+    uint32_t n_queries, const void *queries, const uint32_t *probes, uint32_t *neighbors, float *distances,
+    uint32_t *probes_out, int32_t device_ptrs, const uint8_t *allow /* optional */);
+
 /* Assigns rows to GIVEN centroids -- the "predict" of a trained K-means (no counterpart in the reference, whose
  * kmeans_cuda returns the assignments of the rows it was trained on only) -- with, as asked, the distance of every row
  * to its centroid and per-cluster statistics.  Stateless and synchronous; the caller owns all memory.

@@ -13,6 +13,8 @@ Filtered search: KnnIndex.query / knn_query with allow= (one flag per row id) an
 corpus, exact or probed, bit for bit as an index without the other rows would, and leave the index as it is.
 Masked radius search: KnnIndex.query_radius_allow / knn_query_radius with allow= -- query_radius's result with the
 denied rows struck out, bit for bit.
+Capped search: KnnIndex.query / knn_query with max_distance= return the k nearest rows within that distance, the cap
+pruning from the first candidate on (exact, probed or masked); return_counts= appends the real entries per query.
 New rows assigned to given centroids, with distances and cluster statistics (beyond the reference): kmeans_predict;
 the m nearest centroids of every row, in the order an assignment pass would find them: kmeans_predict_top.
 k-means|| seeding (beyond the reference), stand-alone -- kmeans_seed_parallel -- and as kmeans_cuda(init="k-means||").

@@ -28,6 +28,7 @@ EXPORTS = [
     "kmamd_knn_index_remove", "kmamd_knn_index_radii",
     "kmamd_knn_index_query_allow", "kmamd_knn_index_query_probe_allow", "kmamd_knn_index_radii_allow",
     "kmamd_knn_index_radius_count_allow", "kmamd_knn_index_radius_fill_allow",
+    "kmamd_knn_index_query_capped", "kmamd_knn_index_query_probe_capped",
     "kmamd_kmeans_assign", "kmamd_assigned_distances",
     "kmamd_kmeans_assign_top", "kmamd_assign_top_stats",
     "kmamd_kmeans_seed_parallel",
@@ -172,6 +173,10 @@ def lib():
     L.kmamd_knn_index_radius_count_allow.argtypes = [vp, f32, u32, vp, vp, vp, vp, i32, vp]
     L.kmamd_knn_index_radius_fill_allow.restype = i32
     L.kmamd_knn_index_radius_fill_allow.argtypes = [vp, f32, u32, vp, vp, vp, vp, vp, i32, vp]
+    L.kmamd_knn_index_query_capped.restype = i32
+    L.kmamd_knn_index_query_capped.argtypes = [vp, u32, f32, u32, vp, vp, vp, vp, vp, i32, vp]
+    L.kmamd_knn_index_query_probe_capped.restype = i32
+    L.kmamd_knn_index_query_probe_capped.argtypes = [vp, u32, f32, u32, u32, vp, vp, vp, vp, vp, i32, vp]
     L.kmamd_knn_index_destroy.restype = None
     L.kmamd_knn_index_destroy.argtypes = [vp]
     L.kmamd_kmeans_assign.restype = i32

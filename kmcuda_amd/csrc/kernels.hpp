@@ -519,6 +519,10 @@ struct KnnArgs {
   // the radii over the allowed rows.  Unread otherwise.
   const uint32_t *allow_bits = nullptr;
   const uint32_t *allow_count = nullptr;
+  // Capped search (kmamd_knn_index_query_capped / _probe_capped): wherever the procedure reads the kth
+  // distance it reads min(kth, cap) -- the push test, both cluster tests and the filters' threshold.  Read in query
+  // mode only (knn_cuda's SELF instantiations never load it); FLT_MAX: the uncapped search, bit for bit.
+  float cap = 3.402823466e+38f;
 };
 // the 64-bit words of KnnArgs::allow_bits for an index of N rows: every position a tile can name, plus the word the
 // f16 search's two-word read reaches behind it

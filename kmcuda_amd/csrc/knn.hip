@@ -293,6 +293,7 @@ __global__ __launch_bounds__(256, 2) void knn_filter_kernel(KnnArgs a) {
     }
   }
   float mndist = 3.402823466e+38f;
+  if constexpr (!SELF) mndist = a.cap;   // the capped search reads min(kth, cap) for kth
 
   // Filter threshold in accumulator space ("k-NN filter bound"): a candidate can only
   // be accepted by the reference if  acc >= amin.
@@ -444,6 +445,7 @@ __global__ __launch_bounds__(256, 2) void knn_filter_kernel(KnnArgs a) {
             if (h == 0 && active && dist <= mndist) {  // knn.cu:209-212
               knn_push_sample(k, dist, a.inv[cp], heap);
               mndist = heap[0];
+              if constexpr (!SELF) mndist = fminf(mndist, a.cap);
             }
             mndist = __shfl(mndist, col);
             amin = amin_of(mndist);
@@ -500,6 +502,7 @@ __global__ __launch_bounds__(64) void knn_exact_kernel(KnnArgs a) {
     reinterpret_cast<uint32_t *>(heap)[2 * i + 1] = 0;
   }
   float mndist = 3.402823466e+38f;
+  if constexpr (!SELF) mndist = a.cap;   // the capped search reads min(kth, cap) for kth
   unsigned long long calced = 0;
   const uint32_t *plist = PROBE ? a.plist + (size_t)(qp - a.p_base) * a.pw : nullptr;
   const uint32_t nsteps = PROBE ? a.pw : K;
@@ -532,6 +535,7 @@ __global__ __launch_bounds__(64) void knn_exact_kernel(KnnArgs a) {
       if (dist <= mndist) {
         knn_push_sample(k, dist, a.inv[cp], heap);
         mndist = heap[0];
+        if constexpr (!SELF) mndist = fminf(mndist, a.cap);
       }
     }
   }

@@ -191,6 +191,7 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
       }
     }
     mndist[e] = kFltMaxK;
+    if constexpr (!SELF) mndist[e] = a.cap;   // the capped search reads min(kth, cap) for kth
     const float qn = sqrtf(qn2[e]) * 1.0001f;
     // operand rounding of the hi.hi-only score, in the units of the respective test
     const float e_round = 9.78e-4f * qn * nmx;
@@ -285,6 +286,7 @@ __global__ __launch_bounds__(knn16_waves(DP) * 64, knn16_blocks_per_cu(DP)) void
       if (h == 0 && i < qn_[e] && dist[i] <= mnd) {  // knn.cu:209-212
         knn_push_sample(k, dist[i], a.inv[qc[e][i]], heap);
         mnd = heap[0];
+        if constexpr (!SELF) mnd = fminf(mnd, a.cap);
       }
     }
     mndist[e] = __shfl(mnd, col);

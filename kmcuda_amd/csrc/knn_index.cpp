@@ -37,6 +37,8 @@ namespace {
 
 // lb (K floats per query) and the heaps (2k floats per query) of one chunk of queries stay within this budget
 constexpr size_t kQueryChunkBytes = (size_t)4 << 30;
+// KnnArgs::cap of a search without a cap (FLT_MAX: the heap's own filler, so min(kth, cap) = kth)
+constexpr float kNoCap = 3.402823466e+38f;
 
 // The centred half copy of a state or chunk of N rows ends in KNN16_PAD_ROWS rows / biases of zeros (the filter's tile
 // DMA reads whole tiles), as launch_knn_split leaves them
@@ -118,11 +120,13 @@ class KnnIndex {
   bool ranker_ready = false;
 
   // allow (both; null: none): one flag per row id on the side device_ptrs names -- the masked search, DESIGN.md 4.17
+  // cap (both; FLT_MAX: none): the capped search, DESIGN.md 4.19 -- min(kth, cap) wherever the procedure reads kth
   int query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
-            float *distances, uint32_t *qassign_out, int32_t device_ptrs, const uint8_t *allow = nullptr);
+            float *distances, uint32_t *qassign_out, int32_t device_ptrs, const uint8_t *allow = nullptr,
+            float cap = kNoCap, bool capped_call = false);
   int query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queries, const uint32_t *probes_in,
                   uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs,
-                  const uint8_t *allow = nullptr);
+                  const uint8_t *allow = nullptr, float cap = kNoCap);
   int prepare_mask(const uint8_t *allow, bool host, ArenaScratch &x, QueryMask *m);
   // allow (null: none): as query()'s -- the masked radius search, DESIGN.md 4.18
   int radius(bool fill, float r, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *counts,
@@ -573,7 +577,8 @@ int KnnIndex::prepare_mask(const uint8_t *allow, bool host, ArenaScratch &x, Que
 
 // One query batch, in chunks of at most Qc queries; every buffer is sized for one chunk and reused.
 int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
-                    float *distances, uint32_t *qassign_out, int32_t device_ptrs, const uint8_t *allow) {
+                    float *distances, uint32_t *qassign_out, int32_t device_ptrs, const uint8_t *allow, float cap,
+                    bool capped_call) {
   if (Q == 0) return 0;
   if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
   const hipStream_t st = s.stream;
@@ -589,6 +594,9 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
   KNN_TRY(c.init(*this, Qc, !qassign_in));
   TopkResult res;
   KNN_TRY(res.init(c.w, Qc, k, host, distances != nullptr));
+  // (the counters line is the capped call's alone: the uncapped query prints what it always printed)
+  const bool stats = capped_call && sw.stats;
+  if (stats) KMX_HIPRT(hipMemsetAsync(s.calced, 0, KNN_STATS * sizeof(unsigned long long), st));
   bool said = said_exact || verbosity <= 0;
   for (uint32_t q0 = 0; q0 < Q; q0 += Qc) {
     const uint32_t n = Q - q0 < Qc ? Q - q0 : Qc;
@@ -597,6 +605,7 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
     KnnArgs a;
     c.fill_args(&a);
     res.fill_args(&a);
+    a.cap = cap;
     if (allow) {
       // There is no f32-filtered masked search (as there is no such probe search): whatever is not the f16 filter
       // takes the exact kernel.
@@ -611,13 +620,15 @@ int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t 
     KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity));
     KNN_TRY(res.deliver(q0, n, c.b.inv, neighbors, distances, st));
   }
-  return finish_query(*this, "query");
+  KNN_TRY(finish_query(*this, "query"));
+  if (stats) KNN_TRY(report_stats(*this, "capped query"));
+  return 0;
 }
 
 // One probed query batch: query() with the cluster loop driven by every query's probe list.
 int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queries, const uint32_t *probes_in,
                           uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs,
-                          const uint8_t *allow) {
+                          const uint8_t *allow, float cap) {
   if (Q == 0) return 0;
   if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
   const uint32_t K = s.K;
@@ -667,6 +678,7 @@ int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queri
     res.fill_args(&a);
     a.p_end = c.cp.use_f16 ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
     a.plist = pr.lists; a.pw = pw;
+    a.cap = cap;
     if (allow) mask.fill_args(&a);
     KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity, pr.raw, c.b.inv));
     KNN_TRY(res.deliver(q0, n, c.b.inv, neighbors, distances, st));
@@ -1085,6 +1097,13 @@ static bool query_call_ok(kmamd_knn_index *h, uint32_t k, int32_t device_ptrs) {
   return device_ptrs < 0 || device_ptrs == h->ix.s.dev;
 }
 
+// max_distance of the capped calls: not NaN, >= 0; +inf (and whatever exceeds FLT_MAX) means FLT_MAX, no cap
+static bool cap_ok(float *cap) {
+  if (!(*cap >= 0.f)) return false;
+  if (*cap > kNoCap) *cap = kNoCap;
+  return true;
+}
+
 extern "C" {
 
 int kmamd_knn_index_create(kmamd_knn_index **out, int device, int metric, int fp16x2, uint32_t n_rows,
@@ -1114,14 +1133,23 @@ int kmamd_knn_index_create(kmamd_knn_index **out, int device, int metric, int fp
   return kmcudaSuccess;
 }
 
-int kmamd_knn_index_query(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, const void *queries,
-                          const uint32_t *query_assignments, uint32_t *neighbors, float *distances,
-                          uint32_t *query_assignments_out, int32_t device_ptrs) {
-  if (!query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
+int kmamd_knn_index_query_capped(kmamd_knn_index *h, uint32_t k, float max_distance, uint32_t n_queries,
+                                 const void *queries, const uint32_t *query_assignments, uint32_t *neighbors,
+                                 float *distances, uint32_t *query_assignments_out, int32_t device_ptrs,
+                                 const uint8_t *allow) {
+  if (!cap_ok(&max_distance) || !query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
   if (n_queries == 0) return kmcudaSuccess;
   if (!queries || !neighbors) return kmcudaInvalidArguments;
   sync_callers_writes(device_ptrs);
-  return h->ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs);
+  return h->ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs,
+                     allow, max_distance, true);
+}
+
+int kmamd_knn_index_query(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, const void *queries,
+                          const uint32_t *query_assignments, uint32_t *neighbors, float *distances,
+                          uint32_t *query_assignments_out, int32_t device_ptrs) {
+  return kmamd_knn_index_query_allow(h, k, n_queries, queries, query_assignments, neighbors, distances,
+                                     query_assignments_out, device_ptrs, nullptr);
 }
 
 int kmamd_knn_index_query_allow(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, const void *queries,
@@ -1132,13 +1160,14 @@ int kmamd_knn_index_query_allow(kmamd_knn_index *h, uint32_t k, uint32_t n_queri
   if (!queries || !neighbors) return kmcudaInvalidArguments;
   sync_callers_writes(device_ptrs);
   return h->ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs,
-                     allow);
+                     allow, kNoCap, false);
 }
 
-int kmamd_knn_index_query_probe_allow(kmamd_knn_index *h, uint32_t k, uint32_t nprobe, uint32_t n_queries,
-                                      const void *queries, const uint32_t *probes, uint32_t *neighbors, float *distances,
-                                      uint32_t *probes_out, int32_t device_ptrs, const uint8_t *allow) {
-  if (!query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
+int kmamd_knn_index_query_probe_capped(kmamd_knn_index *h, uint32_t k, float max_distance, uint32_t nprobe,
+                                       uint32_t n_queries, const void *queries, const uint32_t *probes,
+                                       uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs,
+                                       const uint8_t *allow) {
+  if (!cap_ok(&max_distance) || !query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
   KnnIndex &ix = h->ix;
   if (nprobe < 1 || nprobe > KNN_PROBE_MAX || nprobe > ix.s.K) return kmcudaInvalidArguments;
   // the reference's half2 arithmetic has no ranking (kmamd_kmeans_assign_top refuses it likewise): the caller's lists only
@@ -1146,7 +1175,15 @@ int kmamd_knn_index_query_probe_allow(kmamd_knn_index *h, uint32_t k, uint32_t n
   if (n_queries == 0) return kmcudaSuccess;
   if (!queries || !neighbors) return kmcudaInvalidArguments;
   sync_callers_writes(device_ptrs);
-  return ix.query_probe(k, nprobe, n_queries, queries, probes, neighbors, distances, probes_out, device_ptrs, allow);
+  return ix.query_probe(k, nprobe, n_queries, queries, probes, neighbors, distances, probes_out, device_ptrs, allow,
+                        max_distance);
+}
+
+int kmamd_knn_index_query_probe_allow(kmamd_knn_index *h, uint32_t k, uint32_t nprobe, uint32_t n_queries,
+                                      const void *queries, const uint32_t *probes, uint32_t *neighbors, float *distances,
+                                      uint32_t *probes_out, int32_t device_ptrs, const uint8_t *allow) {
+  return kmamd_knn_index_query_probe_capped(h, k, kNoCap, nprobe, n_queries, queries, probes, neighbors, distances,
+                                            probes_out, device_ptrs, allow);
 }
 
 int kmamd_knn_index_query_probe(kmamd_knn_index *h, uint32_t k, uint32_t nprobe, uint32_t n_queries,

@@ -38,6 +38,12 @@ index is not modified, and the next call may bring another mask.  It composes wi
 no mask; query_radius_allow(queries, radius, mask) is the masked radius search: query_radius's result
 with the denied rows struck out, bit for bit, and knn_query_radius(..., allow=mask) its one-shot form.
 
+Capped search, DESIGN.md 4.19: index.query(queries, k, max_distance=r) returns the k nearest rows WITHIN distance r --
+the same procedure reading min(kth, r) wherever it reads kth, so the cap prunes from the first candidate on instead of
+being applied to a finished list.  The real entries (distance <= r, inclusive) come first, the remaining slots hold
+index 0 at FLT_MAX; return_counts=True appends the number of real entries per query.  r = inf (or FLT_MAX) returns the
+bits of the call without a cap.  It composes with query_assignments, nprobe / probes, allow and every return_* flag.
+
 numpy in, numpy out (neighbors uint32, distances float32, assignments uint32).  torch tensors on the index's device
 in, torch tensors on that device out (neighbors / assignments int32: 0xFFFFFFFF reads -1), with no host round trip;
 the call orders with torch's work on the device (it waits for the device first and its outputs are complete when
@@ -263,6 +269,35 @@ def _check_radius(radius):
     return float(r)
 
 
+FLT_MAX = float(numpy.finfo(numpy.float32).max)
+
+
+def _check_max_distance(max_distance):
+    """The cap of a capped query as a Python float that is exact in float32 (inf: FLT_MAX), or None: no cap."""
+    if max_distance is None:
+        return None
+    if hasattr(max_distance, "ndim") and not isinstance(max_distance, numpy.generic):   # a 0-d array or tensor
+        if max_distance.ndim != 0:
+            raise TypeError("\"max_distance\" must be a real number")
+        max_distance = max_distance.item()
+    if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float, numpy.integer, numpy.floating)):
+        raise TypeError("\"max_distance\" must be a real number")
+    with numpy.errstate(over="ignore"):
+        r = numpy.float32(max_distance)
+    if numpy.isnan(r) or r < 0:
+        raise ValueError("\"max_distance\" must not be NaN and must be >= 0")
+    return min(float(r), FLT_MAX)
+
+
+def _real_counts(dist, cap):
+    """Per query, the entries of its list that are rows: distance <= cap (no cap: < FLT_MAX); NaN rows count 0."""
+    real = dist <= cap if cap is not None else dist < FLT_MAX
+    if _is_torch(dist):
+        import torch
+        return real.sum(dim=1, dtype=torch.int32)
+    return real.sum(axis=1).astype(numpy.uint32)
+
+
 def _check_radius_flags(return_distances, sort, count_only):
     if sort and not count_only and not return_distances:
         raise ValueError("\"sort\" orders by distance: it needs return_distances=True")
@@ -304,7 +339,7 @@ class KnnIndex:
         self.h = h
 
     def query(self, queries, k, query_assignments=None, return_distances=True, return_assignments=False,
-              nprobe=None, probes=None, return_probes=False, allow=None):
+              nprobe=None, probes=None, return_probes=False, allow=None, max_distance=None, return_counts=False):
         """The k nearest corpus rows of every query row: neighbors (Q x k corpus row indices), then, as asked,
         distances (Q x k float32, the exact distances the search compared) and the queries' clusters (Q).
         nprobe / probes: the multi-probe search (module docstring) -- only the clusters of every
@@ -313,17 +348,26 @@ class KnnIndex:
         allow: the filtered search (module docstring) -- one flag per row of the index (n_rows; 1-D
         bool / uint8, numpy or a tensor on the index's device, as the queries are); only rows whose flag is set are
         returned, exactly as by a fresh index on which every other row has lost its cluster.  Composes with nprobe /
-        probes and every return_* flag; the queries' clusters and computed probe lists do not depend on it."""
+        probes and every return_* flag; the queries' clusters and computed probe lists do not depend on it.
+        max_distance: the capped search (module docstring) -- a real number r >= 0 (inf: no cap); the
+        k nearest rows within r, by the same procedure reading min(kth, r) for kth.  The real entries (distance <= r)
+        come first; the slots behind them hold index 0 at FLT_MAX.  Composes with everything above.
+        return_counts: appends, last, the number of real entries per query (uint32 numpy / int32 tensor) -- entries
+        with distance <= r, or < FLT_MAX without a cap; 0 for a query with a NaN or inf feature."""
         if not getattr(self, "h", None):
             raise ValueError("the index is closed")
         k = _check_k(k, self.n_rows)
+        cap = _check_max_distance(max_distance)
+        want_distances = return_distances
+        return_distances = return_distances or return_counts   # (the counts are made from the distances)
         q, nq, q_dev, qa = _check_queries(queries, self.fp16, self.features, self.clusters, query_assignments,
                                           self.device)
         nprobe, pr = _check_probes(nprobe, probes, nq, self.clusters, q_dev, query_assignments, self.device, self.fp16)
         al = _check_allow(allow, self.n_rows, q_dev, self.device)
         if nprobe is not None:
-            return self._query_probe(q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes,
-                                     al)
+            out = self._query_probe(q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes,
+                                    al, cap)
+            return self._with_counts(out, want_distances, return_counts, cap)
         if return_probes:
             raise ValueError("\"return_probes\" needs \"nprobe\" or \"probes\"")
         if q_dev:
@@ -336,16 +380,34 @@ class KnnIndex:
             nb = numpy.empty((nq, k), numpy.uint32)
             dist = numpy.empty((nq, k), numpy.float32) if return_distances else None
             asg = numpy.empty((nq,), numpy.uint32) if return_assignments else None
-        if nq:
+        if nq and cap is not None:
+            rc = self.lib.kmamd_knn_index_query_capped(self.h, k, cap, nq, _ptr(q), _ptr(qa) if qa is not None else None,
+                                                       _ptr(nb), _ptr(dist) if dist is not None else None,
+                                                       _ptr(asg) if asg is not None else None,
+                                                       self.device if q_dev else -1, _ptr(al) if al is not None else None)
+            _raise_for(rc, "kmamd_knn_index_query_capped")
+        elif nq:
             rc = self.lib.kmamd_knn_index_query_allow(self.h, k, nq, _ptr(q), _ptr(qa) if qa is not None else None,
                                                       _ptr(nb), _ptr(dist) if dist is not None else None,
                                                       _ptr(asg) if asg is not None else None,
                                                       self.device if q_dev else -1, _ptr(al) if al is not None else None)
             _raise_for(rc, "kmamd_knn_index_query")
         out = (nb,) + ((dist,) if return_distances else ()) + ((asg,) if return_assignments else ())
-        return out[0] if len(out) == 1 else out
+        return self._with_counts(out[0] if len(out) == 1 else out, want_distances, return_counts, cap)
 
-    def _query_probe(self, q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes, al=None):
+    @staticmethod
+    def _with_counts(out, want_distances, return_counts, cap):
+        """`out` of a query that fetched the distances (at [1]) for the counts: the counts appended, the distances
+        dropped again if the caller did not ask for them."""
+        if not return_counts:
+            return out
+        out = out + (_real_counts(out[1], cap),)
+        if not want_distances:
+            out = out[:1] + out[2:]
+        return out
+
+    def _query_probe(self, q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes, al=None,
+                     cap=None):
         want_lists = return_assignments or return_probes
         if q_dev:
             import torch
@@ -357,7 +419,15 @@ class KnnIndex:
             nb = numpy.empty((nq, k), numpy.uint32)
             dist = numpy.empty((nq, k), numpy.float32) if return_distances else None
             used = numpy.empty((nq, nprobe), numpy.uint32) if want_lists else None
-        if nq:
+        if nq and cap is not None:
+            rc = self.lib.kmamd_knn_index_query_probe_capped(self.h, k, cap, nprobe, nq, _ptr(q),
+                                                             _ptr(pr) if pr is not None else None, _ptr(nb),
+                                                             _ptr(dist) if dist is not None else None,
+                                                             _ptr(used) if used is not None else None,
+                                                             self.device if q_dev else -1,
+                                                             _ptr(al) if al is not None else None)
+            _raise_for(rc, "kmamd_knn_index_query_probe_capped")
+        elif nq:
             rc = self.lib.kmamd_knn_index_query_probe_allow(self.h, k, nprobe, nq, _ptr(q),
                                                             _ptr(pr) if pr is not None else None, _ptr(nb),
                                                             _ptr(dist) if dist is not None else None,
@@ -574,10 +644,11 @@ class KnnIndex:
 
 def knn_query(k, samples, centroids, assignments, queries, metric="L2", device=0, query_assignments=None,
               return_distances=True, return_assignments=False, verbosity=0, nprobe=None, probes=None,
-              return_probes=False, allow=None):
+              return_probes=False, allow=None, max_distance=None, return_counts=False):
     """One-shot KnnIndex(samples, centroids, assignments, metric, device).query(queries, k, ...): every argument is
     checked before the device is touched."""
     _get_metric(metric)
+    _check_max_distance(max_distance)
     _, _, _, fp16, n, d, clusters, _ = _check_corpus(samples, centroids, assignments, device)
     _check_k(k, n)
     _, nq, q_dev, _ = _check_queries(queries, fp16, d, clusters, query_assignments, device)
@@ -588,7 +659,8 @@ def knn_query(k, samples, centroids, assignments, queries, metric="L2", device=0
     with KnnIndex(samples, centroids, assignments, metric=metric, device=device, verbosity=verbosity) as ix:
         return ix.query(queries, k, query_assignments=query_assignments, return_distances=return_distances,
                         return_assignments=return_assignments, nprobe=nprobe, probes=probes,
-                        return_probes=return_probes, allow=allow)
+                        return_probes=return_probes, allow=allow, max_distance=max_distance,
+                        return_counts=return_counts)
 
 
 def knn_query_radius(radius, samples, centroids, assignments, queries, metric="L2", device=0, query_assignments=None,

@@ -5,6 +5,13 @@ by kmeans_cuda with the same settings), the queries are `--queries` FRESH draws 
 Reports the index build and the query time separately, then checks `--check` queries against a float64 torch brute
 force (a list may differ from it only where two candidates tie within fp32 rounding).
 
+--max-distance R | pNN: the capped search beside the uncapped one -- R a distance, pNN the NN-th
+percentile of the uncapped call's k-th distances on the same batch (--cap-k: of the distances to the cap-k-th
+neighbour instead, for "k = 100 capped at the median 10th-neighbour distance").  After the warm-up the two calls
+alternate `--repeat` times in this one run; then the KMCUDA_AMD_KNN_STATS counters of both (the uncapped one's through
+the capped entry point at FLT_MAX, which is the same search) and the mean number of real entries.  --radius also times
+query_radius(R, sort=True), the alternative a caller has without the cap.
+
 The matching knn_cuda() figure -- the same number of queries through the self-join -- is
     python scripts/config_d.py --samples 8000000 --shard 0/8   (1M of the 8M rows)"""
 import argparse
@@ -24,6 +31,10 @@ def main():
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--check", type=int, default=1000)
     ap.add_argument("--repeat", type=int, default=2, help="query calls (the first one includes warm-up)")
+    ap.add_argument("--max-distance", default=None, help="a distance, or pNN: a percentile of the k-th distances")
+    ap.add_argument("--cap-k", type=int, default=None, help="pNN is taken over the distances to this neighbour")
+    ap.add_argument("--nprobe", type=int, default=None, help="with --max-distance: the probed search")
+    ap.add_argument("--radius", action="store_true", help="with --max-distance: time query_radius(sort=True) too")
     args = ap.parse_args()
     import torch
     from kmcuda_amd import KnnIndex, kmeans_cuda
@@ -68,6 +79,8 @@ def main():
         times.append(time.perf_counter() - ta)
     print("kmeans_cuda %.3f s; KnnIndex build %.3f s; query %s s for %d queries (k=%d) => %.3e lists/s" %
           (t1 - t0, t3 - t2, " / ".join("%.3f" % t for t in times), Q, k, Q / min(times)), flush=True)
+    if args.max_distance is not None:
+        capped_runs(args, torch, ix, q, k, dist)
     if args.check:
         rows = torch.randperm(Q, device=dev, generator=gen)[:args.check]
         qq = q[rows].double()
@@ -90,6 +103,47 @@ def main():
         print("brute-force check (float64): %d of %d queries differ; max relative error of the returned squared "
               "distances %.2e" % (int(bad.sum()), len(rows), float(dd_err.max())), flush=True)
     ix.close()
+
+
+def capped_runs(args, torch, ix, q, k, dist):
+    """The capped call against the uncapped one, alternating; the counters of both; the real entries."""
+    kw = {} if args.nprobe is None else {"nprobe": args.nprobe}
+    if args.max_distance.startswith("p"):
+        col = (args.cap_k or k) - 1
+        base = dist if args.nprobe is None else ix.query(q, k, **kw)[1]
+        kth = base[:, col]
+        cap = float(torch.quantile(kth[kth < 3.0e38][:4000000].double(), float(args.max_distance[1:]) / 100.0))
+    else:
+        cap = float(args.max_distance)
+    ix.query(q, k, max_distance=cap, **kw)   # warm-up
+    t_cap, t_plain = [], []
+    for _ in range(max(1, args.repeat)):
+        for times, extra in ((t_cap, {"max_distance": cap}), (t_plain, {})):
+            torch.cuda.synchronize()
+            ta = time.perf_counter()
+            res = ix.query(q, k, **kw, **extra)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - ta)
+    counts = ix.query(q, k, max_distance=cap, return_counts=True, **kw)[-1]
+    fmt = lambda ts: " / ".join("%.3f" % t for t in ts)   # noqa: E731
+    print("max_distance %.6g (%s%s): capped %s s; uncapped %s s; mean real entries %.2f of k=%d" % (
+        cap, args.max_distance, "" if args.nprobe is None else ", nprobe=%d" % args.nprobe, fmt(t_cap), fmt(t_plain),
+        float(counts.double().mean()), k), flush=True)
+    os.environ["KMCUDA_AMD_KNN_STATS"] = "1"   # the library prints the counters at the end of a capped call
+    print("counters, capped then uncapped (FLT_MAX through the capped entry point):", flush=True)
+    ix.query(q, k, max_distance=cap, **kw)
+    ix.query(q, k, max_distance=float("inf"), **kw)
+    del os.environ["KMCUDA_AMD_KNN_STATS"]
+    if args.radius:
+        times = []
+        for _ in range(max(1, args.repeat)):
+            torch.cuda.synchronize()
+            ta = time.perf_counter()
+            offsets, _, _ = ix.query_radius(q, cap, sort=True)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - ta)
+        print("query_radius(%.6g, sort=True): %s s; %.2f hits per query before the cut to k" % (
+            cap, fmt(times), float(offsets[-1]) / len(q)), flush=True)
 
 
 if __name__ == "__main__":
