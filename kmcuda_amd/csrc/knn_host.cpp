@@ -247,68 +247,80 @@ std::vector<uint32_t> knn_xcd_plan(const std::vector<uint32_t> &plan) {
   return ordered;
 }
 
+void knn_corpus_args(const KnnShard &s, bool f16, const float *R, KnnArgs *a) {
+  a->xs = s.xs; a->n2s = f16 ? s.n2c : s.n2s; a->inv = s.inv; a->offsets = s.offsets; a->mydist = s.mydist; a->R = R;
+  a->C = s.C; a->stats = f16 ? s.stats_c : s.stats; a->N = s.N; a->D = s.D; a->DP = s.DP; a->K = s.K;
+  a->eps = (float)(1.02 * ((double)s.D + 12.0) * ldexp(1.0, -24));  // the filters' slack, as the Lloyd filter
+  a->calced = s.calced;
+  a->xs16 = s.xs16; a->mux = s.mux; a->kbias = s.kbias; a->mu2 = s.mu2;
+}
+
+int knn_bound_queries(const KnnShard &s, const KnnScratch &x, const float *qxs, const uint32_t *qoffsets,
+                      const float *qmydist, uint32_t p_base, uint32_t p_end, const float *R, int order, KnnArgs *a) {
+  const uint32_t len = p_end - p_base;
+  KMX_HIPRT(launch_knn_centroid_bounds(qxs, s.D, s.DP, p_base, p_end, s.centroids, s.K, R, x.lb, len, s.stream));
+  a->lb = x.lb;
+  a->lb_stride = len;
+  // queries that want the same clusters into the same waves (update.hip: launch_knn_query_order): by the other
+  // cluster that can come closest, then by their distance to their own centroid (mode 3); KMCUDA_AMD_KNN_ORDER=0:
+  // sorted-position order, 1: the closest other cluster alone, 2: the distance alone
+  // (A/B: 1.911 / 1.882 / 1.860 / 1.839e12 pairs scored for config D's share, profiles/r6aj_*)
+  if (order != 0 && x.qperm) {
+    if (launch_knn_query_order(x.lb, len, qoffsets, s.K, p_base, p_end, x.keys_tmp, x.vals_tmp, x.keys_sorted, x.qperm,
+                               x.sort_temp, x.sort_bytes, s.stream, order, qmydist, R))
+      a->qperm = x.qperm;
+    else
+      (void)hipGetLastError();
+  }
+  return 0;
+}
+
 int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path, const KnnSwitches &sw,
-               uint32_t nblocks, bool self, int verbosity, const uint32_t *probes, const uint32_t *qinv) {
+               uint32_t nblocks, bool self, int verbosity, const KnnProbeOrder *probe_order) {
   const bool f16 = path.use_f16;
   const bool probe = a.plist != nullptr;
   const bool mask = a.allow_bits != nullptr;   // (the caller's a.R then: the radii over the allowed rows)
   const hipStream_t st = s.stream;
-  if (mask && (self || !a.allow_count || !a.R)) return kmcudaInvalidArguments;
+  if ((probe || mask) && (self || (path.dp_filter && !f16))) return kmcudaInvalidArguments;
+  if (mask && (!a.allow_count || !a.R)) return kmcudaInvalidArguments;
   const float *const R = mask ? a.R : s.R;
-  a.xs = s.xs; a.n2s = f16 ? s.n2c : s.n2s; a.inv = s.inv; a.offsets = s.offsets; a.mydist = s.mydist; a.R = R;
-  a.C = s.C; a.stats = f16 ? s.stats_c : s.stats; a.N = s.N; a.D = s.D; a.DP = s.DP; a.K = s.K;
-  a.eps = (float)(1.02 * ((double)s.D + 12.0) * ldexp(1.0, -24));  // the filters' slack, as the Lloyd filter
-  a.calced = s.calced;
-  a.xs16 = s.xs16; a.mux = s.mux; a.kbias = s.kbias; a.mu2 = s.mu2;
-  // The tighter cluster test of the f16 search (knn_f16.hip: the query's own distance to every centroid instead of
-  // the triangle bound for it).  4 K bytes per query; without that memory, or with KMCUDA_AMD_KNN_TIGHT=0, the
-  // reference's prune test decides alone.  Same neighbour lists either way.
+  knn_corpus_args(s, f16, R, &a);
   const uint32_t len = a.p_end - a.p_base;
+  // (the query order is an optimisation: sorted-position order without its buffer)
+  auto want_qperm = [&]() {
+    if (sw.order != 0 && !x.qperm && hipMalloc((void **)&x.qperm, x.rows * sizeof(uint32_t)) != hipSuccess) {
+      x.qperm = nullptr;
+      (void)hipGetLastError();
+    }
+    return sw.order != 0 && x.qperm;
+  };
   if (probe) {
     // Probe mode: no second cluster test -- the probed clusters are the nearest ones, where it rarely
     // fires, and its table is K floats per query.  The queries of a cluster go into waves by the second entry of their
-    // raw lists instead (the query order is an optimisation: sorted-position order without it).
-    if (self) return kmcudaInvalidArguments;
-    if (f16 && len != 0 && sw.order != 0 && probes && qinv && a.pw >= 2) {
-      if (!x.qperm && hipMalloc((void **)&x.qperm, x.rows * sizeof(uint32_t)) != hipSuccess) x.qperm = nullptr;
-      if (x.qperm && launch_knn_probe_order(probes, a.pw, qinv, a.qoffsets, s.K, a.p_base, a.p_end, x.keys_tmp, x.vals_tmp,
-                                            x.keys_sorted, x.qperm, x.sort_temp, x.sort_bytes, st))
+    // raw lists instead.
+    if (f16 && len != 0 && probe_order && a.pw >= 2 && want_qperm()) {
+      if (launch_knn_probe_order(probe_order->raw, a.pw, probe_order->qinv, a.qoffsets, s.K, a.p_base, a.p_end, x.keys_tmp,
+                                 x.vals_tmp, x.keys_sorted, x.qperm, x.sort_temp, x.sort_bytes, st))
         a.qperm = x.qperm;
       else
         (void)hipGetLastError();
     }
   } else if (f16 && s.metric == 0 && s.D <= 1024 && len != 0 && sw.tight) {
+    // The tighter cluster test of the f16 search (knn_f16.hip: the query's own distance to every centroid instead of
+    // the triangle bound for it).  4 K bytes per query; without that memory, or with KMCUDA_AMD_KNN_TIGHT=0, the
+    // reference's prune test decides alone.  Same neighbour lists either way.
     if (!x.lb && hipMalloc((void **)&x.lb, (size_t)s.K * x.rows * sizeof(float)) != hipSuccess) {
       x.lb = nullptr;
       (void)hipGetLastError();
       if (verbosity > 1) printf("k-NN: no memory for the per-query centroid bounds, the reference's prune test alone\n");
     } else {
-      KMX_HIPRT(launch_knn_centroid_bounds(self ? s.xs : a.qxs, s.D, s.DP, a.p_base, a.p_end, s.centroids, s.K, R,
-                                           x.lb, len, st));
-      a.lb = x.lb;
-      a.lb_stride = len;
-      // queries that want the same clusters into the same waves (update.hip: launch_knn_query_order): by the
-      // other cluster that can come closest, then by their distance to their own centroid (mode 3);
-      // KMCUDA_AMD_KNN_ORDER=0: sorted-position order, 1: the closest other cluster alone, 2: the distance alone
-      // (A/B: 1.911 / 1.882 / 1.860 / 1.839e12 pairs scored for config D's share, profiles/r6aj_*)
-      if (sw.order != 0 && !x.qperm && hipMalloc((void **)&x.qperm, x.rows * sizeof(uint32_t)) != hipSuccess)
-        x.qperm = nullptr;
-      if (sw.order != 0 && x.qperm &&
-          launch_knn_query_order(x.lb, len, self ? s.offsets : a.qoffsets, s.K, a.p_base, a.p_end, x.keys_tmp,
-                                 x.vals_tmp, x.keys_sorted, x.qperm, x.sort_temp, x.sort_bytes, st, sw.order,
-                                 self ? s.mydist : a.qmydist, R))
-        a.qperm = x.qperm;
-      else
-        (void)hipGetLastError();
+      KNN_TRY(knn_bound_queries(s, x, self ? s.xs : a.qxs, self ? s.offsets : a.qoffsets, self ? s.mydist : a.qmydist,
+                                a.p_base, a.p_end, R, want_qperm() ? sw.order : 0, &a));
     }
   }
-  if (probe || mask)   // (no f32-filtered probe or masked kernel: that path takes the exact one, as the radius search's does)
-    KMX_HIPRT(f16 ? launch_knn_filter_f16(s.metric, a, nblocks, st, false, probe, mask)
-                  : launch_knn_exact(s.metric, a, path.strict_h2, st, false, probe, mask));
-  else
-    KMX_HIPRT(!path.dp_filter ? launch_knn_exact(s.metric, a, path.strict_h2, st, self)
-              : f16           ? launch_knn_filter_f16(s.metric, a, nblocks, st, self)
-                              : launch_knn_filter(s.metric, a, nblocks, st, self));
+  KMX_HIPRT(!path.dp_filter ? launch_knn_exact(s.metric, a, path.strict_h2, st, self, probe, mask)
+            : f16           ? launch_knn_filter_f16(s.metric, a, nblocks, st, self, probe, mask)
+                            : launch_knn_filter(s.metric, a, nblocks, st, self));
   return 0;
 }
 

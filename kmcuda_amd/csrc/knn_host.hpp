@@ -98,17 +98,34 @@ inline uint32_t knn_qpb(bool use_f16, uint32_t DP) { return use_f16 ? knn_qpb_f1
 // KMCUDA_AMD_KNN_XCD: the plan with the blocks of one query cluster on one XCD (empty slots: 0xFFFFFFFF)
 std::vector<uint32_t> knn_xcd_plan(const std::vector<uint32_t> &plan);
 
+// The corpus side of a search's arguments from the prepared shard: f16 = the f16 filter's norms and statistics (else
+// the plain ones), R = the radii every prune reads (the shard's, or a mask's over the allowed rows), eps = the filters'
+// slack.  knn_search fills it; the radius search, which launches kernels of its own, calls it too.
+void knn_corpus_args(const KnnShard &s, bool f16, const float *R, KnnArgs *a);
+
+// The second cluster test's table and the query order made from it (L2, D <= 1024), for the sorted query positions
+// [p_base, p_end) of the rows qxs (CSR qoffsets, distances to the own centroid qmydist): x.lb, which the caller has
+// allocated for p_end - p_base queries (the table's stride), gets every query's bound for every centroid under the
+// radii R, and a->lb / a->lb_stride name it; order != 0 and x.qperm there: the queries of a cluster grouped into waves
+// by mode `order` (a->qperm; left null where the sort cannot run: sorted-position order, the same lists).
+int knn_bound_queries(const KnnShard &s, const KnnScratch &x, const float *qxs, const uint32_t *qoffsets,
+                      const float *qmydist, uint32_t p_base, uint32_t p_end, const float *R, int order, KnnArgs *a);
+
+// What gives a probed f16 search its query order: the chunk's raw lists (query order) and sorted position -> query
+struct KnnProbeOrder {
+  const uint32_t *raw = nullptr, *qinv = nullptr;
+};
+
 // One search launch on s.stream.  The caller fills the query side of `a` (p_base / p_end, blocks, heaps, out and, with
 // self = false, the q* fields); this adds the corpus side from the prepared shard, the per-query centroid bounds and
 // the query order of the f16 search (buffers and sort scratch: `x`, with x.rows >= p_end - p_base) and picks the
-// kernel `path` names.  Probe mode (a.plist set, self = false): the PROBE kernels -- the f16 one where
-// `path` names the f16 filter, else the exact one -- without the centroid bounds; probes / qinv (the chunk's raw lists
-// and sorted position -> query, optional) give the f16 search its query order.  Masked (a.allow_bits set, self =
-// false): the caller also sets a.allow_count and a.R, the radii over the allowed rows, which every
-// prune here reads instead of the shard's; the MASK kernels, the f16 one or the exact one as in probe mode.
+// kernel `path` names: the exact one (dp_filter = 0), else the f16 or the f32 filter.  Probe mode (a.plist set, self =
+// false): the PROBE kernels, without the centroid bounds; probe_order (null: none) gives the f16 search
+// its query order.  Masked (a.allow_bits set, self = false): the caller also sets a.allow_count and
+// a.R, the radii over the allowed rows, which every prune here reads instead of the shard's; the MASK kernels.  There
+// is no f32-filtered probe or masked kernel: such a call names the f16 filter or none (refused otherwise).
 int knn_search(const KnnShard &s, KnnScratch &x, KnnArgs a, const KnnPath &path, const KnnSwitches &sw,
-               uint32_t nblocks, bool self, int verbosity, const uint32_t *probes = nullptr,
-               const uint32_t *qinv = nullptr);
+               uint32_t nblocks, bool self, int verbosity, const KnnProbeOrder *probe_order);
 
 // Rows [p_base, p_end) of a search's output (`out` on src_dev in sorted-position order; null: 0xFFFFFFFF, no
 // neighbours) into the caller's `neighbors` on device `dev`, by `inv` of src_dev; waits for it.

@@ -11,9 +11,10 @@
 // is its nearest centroid (kmamd_lloyd_assign's arithmetic and tie rule) unless the caller passes one; any cluster id
 // gives the same lists (the prune is rigorous), only the work differs.
 //
-// query_probe() is the approximate mode: the same procedure with one more skip rule -- a cluster that
-// is not in the query's probe list is never visited.  The lists are the caller's, or the ranking of
-// kmamd_kmeans_assign_top run here on the index's own centroids (AssignTopRanker, assign_top_job.cpp).
+// Every top-k entry point is one call, topk(), of one request (TopkRequest).  With probe lists it is the approximate
+// mode: the same procedure with one more skip rule -- a cluster that is not in the query's probe list
+// is never visited.  The lists are the caller's, or the ranking of kmamd_kmeans_assign_top run here on the index's own
+// centroids (AssignTopRanker, assign_top_job.cpp).
 //
 // add() takes more rows into the index: the new rows are prepared chunk by chunk with the launches a
 // fresh index's rows go through and merged into new cluster-sorted copies (knn_merge.hip); the index's own buffers stay
@@ -67,6 +68,40 @@ struct IndexState {
 struct AddChunk;
 struct ArenaScratch;
 
+// One top-k call on the index: what the kmamd_knn_index_query* entry points ask of KnnIndex::topk
+struct TopkRequest {
+  uint32_t k = 0, Q = 0;
+  float cap = kNoCap;   // the capped search, DESIGN.md 4.19 -- min(kth, cap) wherever the procedure reads kth
+  const void *queries = nullptr;
+  const uint32_t *qassign_in = nullptr;   // (neither of the two with probe lists: column 0 stands in)
+  uint32_t *qassign_out = nullptr;
+  uint32_t *neighbors = nullptr;
+  float *distances = nullptr;
+  const uint8_t *allow = nullptr;   // the masked search, DESIGN.md 4.17: one flag per row id on the side device_ptrs names
+  int32_t device_ptrs = -1;
+  const char *report = nullptr;   // what the KMCUDA_AMD_KNN_STATS line calls this call (null: it prints none)
+  // the probed search, DESIGN.md 4.12 (pw = 0: none)
+  uint32_t pw = 0;
+  const uint32_t *probes_in = nullptr;   // the caller's lists, or null: ranked here
+  uint32_t *probes_out = nullptr;        // optional
+};
+
+// One radius call: counts (fill = false), or the hits at the caller's CSR offsets
+struct RadiusRequest {
+  bool fill = false;
+  float r = 0.f;
+  uint32_t Q = 0;
+  const void *queries = nullptr;
+  const uint32_t *qassign_in = nullptr;
+  uint32_t *qassign_out = nullptr;
+  uint32_t *counts = nullptr;          // (count)
+  const uint64_t *offsets = nullptr;   // (fill, as neighbors and the optional distances)
+  uint32_t *neighbors = nullptr;
+  float *distances = nullptr;
+  const uint8_t *allow = nullptr;   // the masked radius search, DESIGN.md 4.18
+  int32_t device_ptrs = -1;
+};
+
 // What a masked call prepares once, for all its query chunks: the caller's flags as one bit per sorted
 // position, the allowed rows per cluster and the radii over them -- the radii of the index the call is defined by
 struct QueryMask {
@@ -119,19 +154,9 @@ class KnnIndex {
   AssignTopRanker ranker;
   bool ranker_ready = false;
 
-  // allow (both; null: none): one flag per row id on the side device_ptrs names -- the masked search, DESIGN.md 4.17
-  // cap (both; FLT_MAX: none): the capped search, DESIGN.md 4.19 -- min(kth, cap) wherever the procedure reads kth
-  int query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
-            float *distances, uint32_t *qassign_out, int32_t device_ptrs, const uint8_t *allow = nullptr,
-            float cap = kNoCap, bool capped_call = false);
-  int query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queries, const uint32_t *probes_in,
-                  uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs,
-                  const uint8_t *allow = nullptr, float cap = kNoCap);
+  int topk(const TopkRequest &rq);
   int prepare_mask(const uint8_t *allow, bool host, ArenaScratch &x, QueryMask *m);
-  // allow (null: none): as query()'s -- the masked radius search, DESIGN.md 4.18
-  int radius(bool fill, float r, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *counts,
-             uint32_t *qassign_out, const uint64_t *offsets, uint32_t *neighbors, float *distances, int32_t device_ptrs,
-             const uint8_t *allow = nullptr);
+  int radius(const RadiusRequest &rq);
 
   // ---- add ----
   int add(uint32_t n_rows, const void *rows, const uint32_t *assign_in, uint32_t *assign_out, int32_t device_ptrs);
@@ -298,10 +323,30 @@ struct ProbeSide {
   AssignTopRanker ranker;                // (computed lists, K >= 2)
   bool rank_exact = false;
   uint32_t *raw = nullptr, *lists = nullptr;
+
+  // for chunks of at most Qc queries (buffers: w's); the ranking's centroid preparation is made on the index's first
+  // probed call that brings no lists of its own
+  int init(KnnIndex &ix, DeviceArena &w, uint32_t Qc, const TopkRequest &rq) {
+    pw = rq.pw; probes_in = rq.probes_in; probes_out = rq.probes_out;
+    KNN_TRY(w.alloc(&raw, (size_t)Qc * pw));
+    KNN_TRY(w.alloc(&lists, (size_t)Qc * pw));
+    if (probes_in || ix.s.K < 2) return 0;
+    if (!ix.ranker_ready) {
+      KNN_TRY(ix.ranker.prepare(ix.s, ix.s.metric, ix.s.centroids, ix.s.K, ix.s.D, false));
+      ix.ranker_ready = true;
+    }
+    ranker = ix.ranker;
+    rank_exact = assign_top_exact_only();
+    return ranker.reserve(w, Qc);
+  }
 };
 
-// A chunk of queries, shared by query(), query_probe() and the radius calls: the queries' clusters, the sorted chunk
-// and the block plan of its search.
+// What a chunk of queries is prepared for.  There is a matrix-core filter on f32 for the plain top-k search alone: a
+// search with probe lists or a mask, and the radius search, take the f16 filter or the exact kernel.
+enum class ChunkUse { topk, topk_subset, radius };   // (subset: probe lists and / or a mask)
+
+// A chunk of queries, shared by the top-k and the radius calls: the queries' clusters, the sorted chunk and the block
+// plan of its search.
 struct QueryChunk : SortedChunk {
   uint32_t *qeff = nullptr, *blocks = nullptr;
   std::unique_ptr<Engine> eng;   // (a member of the derived type: it goes before the arena whose stream it uses)
@@ -327,7 +372,8 @@ struct QueryChunk : SortedChunk {
 
   // queries [q0, q0 + n) of the batch; waits for the stream once (the CSR offsets and the flags reach the host)
   // pr: probe mode -- the chunk's lists are fetched or ranked, their column 0 stands in for qassign_in
-  int prepare(const KnnIndex &ix, uint32_t q0, uint32_t n, const void *queries, const uint32_t *qassign_in,
+  // Leaves in `cp` the search the chunk takes for `use` (the one place that decides it), split and planned for it.
+  int prepare(const KnnIndex &ix, ChunkUse use, uint32_t q0, uint32_t n, const void *queries, const uint32_t *qassign_in,
               uint32_t *qassign_out, bool host, ProbeSide *pr = nullptr) {
     const KnnShard &s = ix.s;
     const uint32_t D = s.D, K = s.K;
@@ -375,6 +421,10 @@ struct QueryChunk : SortedChunk {
     if (knn_leaves_half_range(&cp.use_f16, &cp.dp_filter, D, flags[1]) && ix.verbosity > 0)
       printf("k-NN query: a centred query leaves the half range, %s\n",
              cp.dp_filter && !pr ? "the f32 matrix-core filter" : "the exact search");
+    // no f32 filter but the plain top-k search's: whatever is not the f16 filter there takes the exact kernel
+    if (use != ChunkUse::topk && !cp.use_f16) cp.dp_filter = 0;
+    // nor an f16 probe search at a K its visit map has no room for
+    if (pr && K > KNN_PROBE_BITMAP_K) { cp.use_f16 = false; cp.dp_filter = 0; }
     if (cp.use_f16) KNN_TRY(split(ix, n));
     assigned = offs[K];
     knn_block_plan(offs.data(), K, knn_qpb(cp.use_f16, s.DP), &plan);
@@ -383,10 +433,11 @@ struct QueryChunk : SortedChunk {
     return 0;
   }
 
-  // the query side of a search launch over this chunk
-  void fill_args(KnnArgs *a) const {
+  // the query side of a search launch over this chunk of n queries
+  void fill_args(KnnArgs *a, uint32_t n) const {
     a->blocks = blocks;
     a->p_base = 0;
+    a->p_end = cp.dp_filter ? assigned : n;   // (the exact kernel also fills the unassigned queries)
     a->qxs = b.xs; a->qn2s = cp.use_f16 ? b.n2c : b.n2s; a->qmux = b.mux; a->qmydist = b.mydist; a->qxs16 = b.xs16; a->qoffsets = offsets;
   }
 };
@@ -575,194 +626,201 @@ int KnnIndex::prepare_mask(const uint8_t *allow, bool host, ArenaScratch &x, Que
   return 0;
 }
 
-// One query batch, in chunks of at most Qc queries; every buffer is sized for one chunk and reused.
-int KnnIndex::query(uint32_t k, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *neighbors,
-                    float *distances, uint32_t *qassign_out, int32_t device_ptrs, const uint8_t *allow, float cap,
-                    bool capped_call) {
-  if (Q == 0) return 0;
+// One query batch, in chunks of at most Qc queries; every buffer is sized for one chunk and reused.  With probe lists
+//  the cluster loop of the search is driven by every query's list.
+int KnnIndex::topk(const TopkRequest &rq) {
+  if (rq.Q == 0) return 0;
   if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
   const hipStream_t st = s.stream;
   const KnnSwitches sw = knn_switches();
-  const uint32_t Qc = knn_chunk_rows(kQueryChunkBytes, 4 * ((size_t)s.K + 2 * (size_t)k), sw.query_chunk, Q);
-  const bool host = device_ptrs < 0;
+  const bool host = rq.device_ptrs < 0, probed = rq.pw != 0;
+  const ChunkUse use = probed || rq.allow ? ChunkUse::topk_subset : ChunkUse::topk;
+  const char *const what = probed ? "probe query" : "query";
+  // what a chunk keeps per query besides its heaps (2k floats): the probe lists, else the lb table (K floats)
+  const size_t query_bytes = 4 * ((probed ? (size_t)rq.pw : (size_t)s.K) + 2 * (size_t)rq.k);
+  const uint32_t Qc = knn_chunk_rows(kQueryChunkBytes, query_bytes, sw.query_chunk, rq.Q);
 
   ArenaScratch x(s);   // (before `c`: it waits for the stream, then releases)
   QueryMask mask;
-  if (allow) KNN_TRY(prepare_mask(allow, host, x, &mask));
+  if (rq.allow) KNN_TRY(prepare_mask(rq.allow, host, x, &mask));
   // per-call buffers (freed with `c`), among them the sort scratch and the optional buffers of knn_search
   QueryChunk c;
-  KNN_TRY(c.init(*this, Qc, !qassign_in));
+  KNN_TRY(c.init(*this, Qc, !probed && !rq.qassign_in));
+  ProbeSide pr;
+  if (probed) KNN_TRY(pr.init(*this, c.w, Qc, rq));
+  const KnnProbeOrder probe_order{pr.raw, c.b.inv};
   TopkResult res;
-  KNN_TRY(res.init(c.w, Qc, k, host, distances != nullptr));
-  // (the counters line is the capped call's alone: the uncapped query prints what it always printed)
-  const bool stats = capped_call && sw.stats;
+  KNN_TRY(res.init(c.w, Qc, rq.k, host, rq.distances != nullptr));
+  // the counters line, where the call has a name for it (the plain query prints what it always printed)
+  const bool stats = rq.report && sw.stats;
   if (stats) KMX_HIPRT(hipMemsetAsync(s.calced, 0, KNN_STATS * sizeof(unsigned long long), st));
   bool said = said_exact || verbosity <= 0;
-  for (uint32_t q0 = 0; q0 < Q; q0 += Qc) {
-    const uint32_t n = Q - q0 < Qc ? Q - q0 : Qc;
-    KNN_TRY(c.prepare(*this, q0, n, queries, qassign_in, qassign_out, host));
-    KNN_TRY(res.clear(n, st));
-    KnnArgs a;
-    c.fill_args(&a);
-    res.fill_args(&a);
-    a.cap = cap;
-    if (allow) {
-      // There is no f32-filtered masked search (as there is no such probe search): whatever is not the f16 filter
-      // takes the exact kernel.
-      if (!c.cp.use_f16) c.cp.dp_filter = 0;
-      if (!c.cp.use_f16 && !said) {
-        printf("k-NN masked query: every candidate is evaluated with the exact arithmetic (no f32-filtered masked search)\n");
-        said = true;
-      }
-      mask.fill_args(&a);
-    }
-    a.p_end = c.cp.dp_filter ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
-    KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity));
-    KNN_TRY(res.deliver(q0, n, c.b.inv, neighbors, distances, st));
-  }
-  KNN_TRY(finish_query(*this, "query"));
-  if (stats) KNN_TRY(report_stats(*this, "capped query"));
-  return 0;
-}
-
-// One probed query batch: query() with the cluster loop driven by every query's probe list.
-int KnnIndex::query_probe(uint32_t k, uint32_t pw, uint32_t Q, const void *queries, const uint32_t *probes_in,
-                          uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs,
-                          const uint8_t *allow, float cap) {
-  if (Q == 0) return 0;
-  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
-  const uint32_t K = s.K;
-  const hipStream_t st = s.stream;
-  const KnnSwitches sw = knn_switches();
-  // (no lb table here: the heaps and the lists of a chunk within the budget)
-  const uint32_t Qc = knn_chunk_rows(kQueryChunkBytes, 4 * ((size_t)pw + 2 * (size_t)k), sw.query_chunk, Q);
-  const bool host = device_ptrs < 0;
-
-  ArenaScratch x(s);   // (before `c`: it waits for the stream, then releases)
-  QueryMask mask;
-  if (allow) KNN_TRY(prepare_mask(allow, host, x, &mask));
-  QueryChunk c;
-  KNN_TRY(c.init(*this, Qc, false));
-  DeviceArena &w = c.w;
-  ProbeSide pr;
-  pr.pw = pw; pr.probes_in = probes_in; pr.probes_out = probes_out;
-  KNN_TRY(w.alloc(&pr.raw, (size_t)Qc * pw));
-  KNN_TRY(w.alloc(&pr.lists, (size_t)Qc * pw));
-  if (!probes_in && K >= 2) {
-    if (!ranker_ready) {
-      KNN_TRY(ranker.prepare(s, s.metric, s.centroids, K, s.D, false));
-      ranker_ready = true;
-    }
-    pr.ranker = ranker;
-    pr.rank_exact = assign_top_exact_only();
-    KNN_TRY(pr.ranker.reserve(w, Qc));
-  }
-  TopkResult res;
-  KNN_TRY(res.init(w, Qc, k, host, distances != nullptr));
-  if (sw.stats) KMX_HIPRT(hipMemsetAsync(s.calced, 0, KNN_STATS * sizeof(unsigned long long), st));
-  bool said = said_exact || verbosity <= 0;
-  for (uint32_t q0 = 0; q0 < Q; q0 += Qc) {
-    const uint32_t n = Q - q0 < Qc ? Q - q0 : Qc;
-    KNN_TRY(c.prepare(*this, q0, n, queries, nullptr, nullptr, host, &pr));
-    // There is no f32-filtered probe search (as there is no such radius search): whatever is not the f16 filter takes
-    // the exact kernel, and so does a K the f16 search's visit map has no room for.  (The chunk was split and planned
-    // for the f16 search only if it stays one.)
-    if (c.cp.use_f16 && K > KNN_PROBE_BITMAP_K) c.cp.use_f16 = false;
-    if (!c.cp.use_f16 && !said) {
-      printf("k-NN probe query: every candidate is evaluated with the exact arithmetic (no f32-filtered probe search)\n");
+  for (uint32_t q0 = 0; q0 < rq.Q; q0 += Qc) {
+    const uint32_t n = rq.Q - q0 < Qc ? rq.Q - q0 : Qc;
+    KNN_TRY(c.prepare(*this, use, q0, n, rq.queries, rq.qassign_in, rq.qassign_out, host, probed ? &pr : nullptr));
+    if (use == ChunkUse::topk_subset && !c.cp.use_f16 && !said) {
+      printf(probed ? "k-NN probe query: every candidate is evaluated with the exact arithmetic (no f32-filtered probe search)\n"
+                    : "k-NN masked query: every candidate is evaluated with the exact arithmetic (no f32-filtered masked search)\n");
       said = true;
     }
     KNN_TRY(res.clear(n, st));
     KnnArgs a;
-    c.fill_args(&a);
+    c.fill_args(&a, n);
     res.fill_args(&a);
-    a.p_end = c.cp.use_f16 ? c.assigned : n;   // (the exact kernel also fills the unassigned queries)
-    a.plist = pr.lists; a.pw = pw;
-    a.cap = cap;
-    if (allow) mask.fill_args(&a);
-    KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity, pr.raw, c.b.inv));
-    KNN_TRY(res.deliver(q0, n, c.b.inv, neighbors, distances, st));
+    a.cap = rq.cap;
+    if (probed) { a.plist = pr.lists; a.pw = rq.pw; }
+    if (rq.allow) mask.fill_args(&a);
+    KNN_TRY(knn_search(s, c.scratch, a, c.cp, sw, (uint32_t)(c.plan.size() / 2), false, verbosity,
+                       probed ? &probe_order : nullptr));
+    KNN_TRY(res.deliver(q0, n, c.b.inv, rq.neighbors, rq.distances, st));
   }
-  KNN_TRY(finish_query(*this, "probe query"));
-  if (sw.stats) KNN_TRY(report_stats(*this, "probe query"));
+  KNN_TRY(finish_query(*this, what));
+  if (stats) KNN_TRY(report_stats(*this, rq.report));
   return 0;
 }
 
-// Radius search of one query batch: counts (fill = false) or the hits at the caller's CSR offsets.
-// Chunked as query(); a chunk's lb table (L2, up to 1024 features: the prune test) stays within kQueryChunkBytes.
-// allow: the masked search -- the mask is prepared once, behind the unmasked call's refusals, and every
-// chunk prunes with the radii over the allowed rows and runs the MASK kernels.
-int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const uint32_t *qassign_in, uint32_t *counts,
-                     uint32_t *qassign_out, const uint64_t *offsets, uint32_t *neighbors, float *distances,
-                     int32_t device_ptrs, const uint8_t *allow) {
-  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
-  const uint32_t D = s.D, DP = s.DP, K = s.K;
-  const int metric = s.metric;
-  const hipStream_t st = s.stream;
-  const KnnSwitches sw = knn_switches();
-  const bool host = device_ptrs < 0;
-  const uint32_t Qc = knn_chunk_rows(kQueryChunkBytes, 4 * (size_t)K, sw.query_chunk, Q);
-
+// The answer of a radius call on its way to the caller: counts, or the hits at the caller's CSR offsets.  A caller on
+// the device is written in place; for one on the host a chunk's counts, or its CSR range, are staged on the device (a
+// chunk is split until its range fits kQueryChunkBytes).
+struct RadiusResult {
+  const RadiusRequest &rq;
+  bool host = false;
+  hipStream_t st = nullptr;
   DeviceArena own;   // this call's own device buffers (nothing to release: the index's stream)
-  own.dev = s.dev;
-  own.stream = nullptr;
-  uint32_t *flag = nullptr, *counts_dev = nullptr;
+  uint32_t *flag = nullptr;   // raised by a fill in which a query's hit count differs from its range
+  uint32_t *counts_dev = nullptr;
   uint64_t *offsets_dev = nullptr;
-  KNN_TRY(own.alloc(&flag, 1));
-  KMX_HIPRT(hipMemsetAsync(flag, 0, sizeof(uint32_t), st));
-  auto flag_raised = [&](bool *raised) -> int {
-    uint32_t f = 0;
-    KMX_HIPCP(hipMemcpyAsync(&f, flag, sizeof(f), hipMemcpyDeviceToHost, st));
-    KMX_HIPRT(hipStreamSynchronize(st));
-    *raised = f != 0;
-    return 0;
-  };
-  // ---- fill: the offsets must not decrease, checked before anything is written ----
-  if (fill) {
-    if (host) {
-      for (uint32_t i = 0; i < Q; i++)
-        if (offsets[i] > offsets[i + 1]) return kmcudaInvalidArguments;
-      KNN_TRY(own.alloc(&offsets_dev, (size_t)Qc + 1));
-    } else {
-      KMX_HIPRT(launch_knn_radius_offsets_check(offsets, Q, flag, st));
-      bool raised = false;
-      KNN_TRY(flag_raised(&raised));
-      if (raised) return kmcudaInvalidArguments;
-    }
-  } else if (host) {
-    KNN_TRY(own.alloc(&counts_dev, Qc));
-  }
-  // host buffers: one chunk's CSR range is staged on the device, within this budget (a chunk is split until it fits)
-  const size_t hit_bytes = sizeof(uint32_t) + (distances ? sizeof(float) : 0);
   struct Staging {
     void *nb = nullptr, *dist = nullptr;
     uint64_t cap = 0;
     ~Staging() { (void)hipFree(nb); (void)hipFree(dist); }
   } stage;
+  uint64_t range = 0;   // the hits of the chunk begun last (a fill to the host)
 
-  ArenaScratch mx(s);   // (before `c`: it waits for the stream, then releases)
-  QueryMask mask;
-  if (allow) KNN_TRY(prepare_mask(allow, host, mx, &mask));
-  const float *R = allow ? mask.R : s.R;   // what the prune tests read: the radii over the rows that may be returned
-  QueryChunk c;
-  KNN_TRY(c.init(*this, Qc, !qassign_in));
-  // (a fill's first chunk may be shorter than Qc, and the assignment pass reads Qc rows: defined values for them)
-  if (fill && host && !qassign_in) KMX_HIPRT(hipMemsetAsync(c.rows, 0, (size_t)Qc * D * sizeof(float), st));
-  // the cluster prune: the lb table (L2, D <= 1024, rows the bounds kernel can read four features at a time), else
-  // the triangle test with a margin for the rounding of its computed terms; the half2 arithmetic's
-  // distances carry half-precision errors no such margin covers: nothing is pruned there
-  const bool use_lb = metric == 0 && D <= 1024 && (DP & 3u) == 0 && !path.strict_h2;
-  // (tests/test_radius_bound_model.py restates these constants and reads them back from this file: change both)
-  float prune_abs = 0.f, prune_rel = 0.f;
-  if (path.strict_h2) {
-    prune_abs = INFINITY;
-  } else if (metric == 0) {
-    prune_rel = (float)(1e-5 + 4e-9 * (double)D);
+  explicit RadiusResult(const RadiusRequest &rq_) : rq(rq_) {}
+
+  int flag_raised(bool *raised) const {   // (waits for the stream)
+    uint32_t f = 0;
+    KMX_HIPCP(hipMemcpyAsync(&f, flag, sizeof(f), hipMemcpyDeviceToHost, st));
+    KMX_HIPRT(hipStreamSynchronize(st));
+    *raised = f != 0;
+    return 0;
+  }
+  // for chunks of at most Qc queries.  A fill's offsets must not decrease: checked here, before anything is written
+  int init(const KnnShard &s, uint32_t Qc) {
+    host = rq.device_ptrs < 0;
+    st = s.stream;
+    own.dev = s.dev;
+    own.stream = nullptr;
+    KNN_TRY(own.alloc(&flag, 1));
+    KMX_HIPRT(hipMemsetAsync(flag, 0, sizeof(uint32_t), st));
+    if (!rq.fill) return host ? own.alloc(&counts_dev, Qc) : 0;
+    if (host) {
+      for (uint32_t i = 0; i < rq.Q; i++)
+        if (rq.offsets[i] > rq.offsets[i + 1]) return kmcudaInvalidArguments;
+      return own.alloc(&offsets_dev, (size_t)Qc + 1);
+    }
+    KMX_HIPRT(launch_knn_radius_offsets_check(rq.offsets, rq.Q, flag, st));
+    bool raised = false;
+    KNN_TRY(flag_raised(&raised));
+    return raised ? kmcudaInvalidArguments : 0;
+  }
+  // the chunk from q0 on: of its *n queries as many as the staging budget holds, and a staging that holds their range
+  int begin_chunk(uint32_t q0, uint32_t *n) {
+    if (!rq.fill || !host) return 0;
+    const size_t hit_bytes = sizeof(uint32_t) + (rq.distances ? sizeof(float) : 0);
+    *n = knn_fill_chunk_rows(rq.offsets, q0, *n, kQueryChunkBytes / hit_bytes);
+    range = rq.offsets[q0 + *n] - rq.offsets[q0];
+    if (range <= stage.cap) return 0;
+    (void)hipStreamSynchronize(st);   // (the copies out of the old buffers)
+    (void)hipFree(stage.nb); (void)hipFree(stage.dist);
+    stage.nb = stage.dist = nullptr;
+    stage.cap = 0;
+    if (hipMalloc(&stage.nb, range * sizeof(uint32_t)) != hipSuccess ||
+        (rq.distances && hipMalloc(&stage.dist, range * sizeof(float)) != hipSuccess)) {
+      (void)hipGetLastError();
+      return kmcudaMemoryAllocationFailure;
+    }
+    stage.cap = range;
+    return 0;
+  }
+  // where the search of the chunk begun last (n queries from q0 on) writes
+  int fill_args(uint32_t q0, uint32_t n, KnnRadiusArgs *ra) const {
+    ra->counts = host ? counts_dev : (rq.counts ? rq.counts + q0 : nullptr);
+    ra->offsets = nullptr; ra->out_base = 0; ra->neighbors = nullptr; ra->distances = nullptr; ra->flag = flag;
+    if (rq.fill && host) {
+      KMX_HIPCP(hipMemcpyAsync(offsets_dev, rq.offsets + q0, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      // (slots of a range the search does not fill -- the call then fails -- read 0xFF)
+      if (range) KMX_HIPRT(hipMemsetAsync(stage.nb, 0xFF, range * sizeof(uint32_t), st));
+      if (range && rq.distances) KMX_HIPRT(hipMemsetAsync(stage.dist, 0xFF, range * sizeof(float), st));
+      ra->offsets = offsets_dev; ra->out_base = rq.offsets[q0];
+      ra->neighbors = static_cast<uint32_t *>(stage.nb); ra->distances = static_cast<float *>(stage.dist);
+    } else if (rq.fill) {
+      ra->offsets = rq.offsets + q0;
+      ra->neighbors = rq.neighbors; ra->distances = rq.distances;
+    }
+    return 0;
+  }
+  // that chunk to a caller on the host.  (The next chunk overwrites these buffers: the stream orders it behind this
+  // one's kernels and copies.)
+  int deliver(uint32_t q0, uint32_t n) const {
+    if (!host) return 0;
+    if (!rq.fill)
+      KMX_HIPCP(hipMemcpyAsync(rq.counts + q0, counts_dev, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    else if (range) {
+      const uint64_t at = rq.offsets[q0];
+      KMX_HIPCP(hipMemcpyAsync(rq.neighbors + at, stage.nb, range * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      if (rq.distances)
+        KMX_HIPCP(hipMemcpyAsync(rq.distances + at, stage.dist, range * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    return 0;
+  }
+};
+
+// The margins of the radius search's cluster prune where no lb table decides: the triangle test with a
+// margin for the rounding of its computed terms; the half2 arithmetic's distances carry half-precision errors no such
+// margin covers: nothing is pruned there.
+// (tests/test_radius_bound_model.py restates these constants and reads them back from this file: change both)
+void radius_prune_margins(const KnnIndex &ix, KnnRadiusArgs *ra) {
+  const uint32_t D = ix.s.D;
+  const bool fp16 = ix.fp16;
+  ra->prune_abs = ra->prune_rel = 0.f;
+  if (ix.path.strict_h2) {
+    ra->prune_abs = INFINITY;
+  } else if (ix.s.metric == 0) {
+    ra->prune_rel = (float)(1e-5 + 4e-9 * (double)D);
   } else {
     // four computed angles, each acos of a product that is off by at most dp: |acos(a) - acos(b)| <= sqrt(2 |a - b|) * 1.01
     const double dp = (fp16 ? 1.0e-3 : 1.0e-6) + 1.0e-8 * (double)D;
-    prune_abs = (float)(4.0 * 1.01 * sqrt(2.0 * dp));
+    ra->prune_abs = (float)(4.0 * 1.01 * sqrt(2.0 * dp));
   }
+}
+
+// Radius search of one query batch, chunked as topk(); a chunk's lb table (L2, up to 1024 features:
+// the prune test) stays within kQueryChunkBytes.  allow: the masked search -- the mask is prepared
+// once, behind the unmasked call's refusals, and every chunk prunes with the radii over the allowed rows and runs the
+// MASK kernels.
+int KnnIndex::radius(const RadiusRequest &rq) {
+  if (hipSetDevice(s.dev) != hipSuccess) return kmcudaNoSuchDevice;
+  const uint32_t D = s.D, K = s.K;
+  const hipStream_t st = s.stream;
+  const KnnSwitches sw = knn_switches();
+  const bool host = rq.device_ptrs < 0, fill = rq.fill, masked = rq.allow != nullptr;
+  const uint32_t Qc = knn_chunk_rows(kQueryChunkBytes, 4 * (size_t)K, sw.query_chunk, rq.Q);
+
+  RadiusResult res(rq);
+  KNN_TRY(res.init(s, Qc));
+  ArenaScratch mx(s);   // (before `c`: it waits for the stream, then releases)
+  QueryMask mask;
+  if (masked) KNN_TRY(prepare_mask(rq.allow, host, mx, &mask));
+  const float *R = masked ? mask.R : s.R;   // what the prune tests read: the radii over the rows that may be returned
+  QueryChunk c;
+  KNN_TRY(c.init(*this, Qc, !rq.qassign_in));
+  // (a fill's first chunk may be shorter than Qc, and the assignment pass reads Qc rows: defined values for them)
+  if (fill && host && !rq.qassign_in) KMX_HIPRT(hipMemsetAsync(c.rows, 0, (size_t)Qc * D * sizeof(float), st));
+  // the cluster prune: the lb table (L2, D <= 1024, rows the bounds kernel can read four features at a time; the call
+  // fails without its memory), else the triangle test with its margins
+  const bool use_lb = s.metric == 0 && D <= 1024 && (s.DP & 3u) == 0 && !path.strict_h2;
   if (use_lb && hipMalloc((void **)&c.scratch.lb, (size_t)K * Qc * sizeof(float)) != hipSuccess) {
     c.scratch.lb = nullptr;
     (void)hipGetLastError();
@@ -775,88 +833,37 @@ int KnnIndex::radius(bool fill, float r, uint32_t Q, const void *queries, const 
   if (sw.stats) KMX_HIPRT(hipMemsetAsync(s.calced, 0, KNN_STATS * sizeof(unsigned long long), st));
 
   uint32_t n = 0;
-  for (uint32_t q0 = 0; q0 < Q; q0 += n) {
-    n = Q - q0 < Qc ? Q - q0 : Qc;
-    uint64_t range = 0;
-    if (fill && host) {
-      while (n > 1 && (offsets[q0 + n] - offsets[q0]) > kQueryChunkBytes / hit_bytes) n = (n + 1) / 2;
-      range = offsets[q0 + n] - offsets[q0];
-      if (range > stage.cap) {
-        (void)hipStreamSynchronize(st);   // (the copies out of the old buffers)
-        (void)hipFree(stage.nb); (void)hipFree(stage.dist);
-        stage.nb = stage.dist = nullptr;
-        stage.cap = 0;
-        if (hipMalloc(&stage.nb, range * sizeof(uint32_t)) != hipSuccess ||
-            (distances && hipMalloc(&stage.dist, range * sizeof(float)) != hipSuccess)) {
-          (void)hipGetLastError();
-          return kmcudaMemoryAllocationFailure;
-        }
-        stage.cap = range;
-      }
-    }
-    KNN_TRY(c.prepare(*this, q0, n, queries, qassign_in, qassign_out, host));
-    const bool f16 = c.cp.use_f16;   // (no f32-filtered radius kernel: that path takes the exact one)
+  for (uint32_t q0 = 0; q0 < rq.Q; q0 += n) {
+    n = rq.Q - q0 < Qc ? rq.Q - q0 : Qc;
+    KNN_TRY(res.begin_chunk(q0, &n));
+    KNN_TRY(c.prepare(*this, ChunkUse::radius, q0, n, rq.queries, rq.qassign_in, rq.qassign_out, host));
+    const bool f16 = c.cp.use_f16;
     KnnRadiusArgs ra;
     KnnArgs &a = ra.a;
-    c.fill_args(&a);
+    c.fill_args(&a, n);
     a.k = 0; a.heaps = nullptr; a.out = nullptr; a.outd = nullptr;
-    a.p_end = f16 ? c.assigned : n;
-    a.xs = s.xs; a.n2s = f16 ? s.n2c : s.n2s; a.inv = s.inv; a.offsets = s.offsets; a.mydist = s.mydist; a.R = s.R;
-    a.C = s.C; a.stats = f16 ? s.stats_c : s.stats; a.N = s.N; a.D = D; a.DP = DP; a.K = K;
-    a.eps = (float)(1.02 * ((double)D + 12.0) * ldexp(1.0, -24));  // the filter's slack, as knn_search
-    a.calced = s.calced;
-    a.xs16 = s.xs16; a.mux = s.mux; a.kbias = s.kbias; a.mu2 = s.mu2;
-    if (allow) mask.fill_args(&a);   // (there is no masked f32 filter either: whatever is not the f16 kernel is the exact one)
-    if (use_lb && c.assigned) {
-      KMX_HIPRT(launch_knn_centroid_bounds(c.b.xs, D, DP, 0, c.assigned, s.centroids, K, R, c.scratch.lb, c.assigned, st));
-      a.lb = c.scratch.lb;
-      a.lb_stride = c.assigned;
-      // queries that want the same clusters into the same waves, as knn_search orders them
-      if (f16 && c.scratch.qperm) {
-        KnnScratch &x = c.scratch;
-        if (launch_knn_query_order(x.lb, c.assigned, c.offsets, K, 0, c.assigned, x.keys_tmp, x.vals_tmp, x.keys_sorted,
-                                   x.qperm, x.sort_temp, x.sort_bytes, st, sw.order, c.b.mydist, R))
-          a.qperm = x.qperm;
-        else
-          (void)hipGetLastError();
-      }
-    }
-    ra.radius = r; ra.prune_abs = prune_abs; ra.prune_rel = prune_rel;
+    knn_corpus_args(s, f16, R, &a);
+    if (masked) mask.fill_args(&a);
+    // the bounds of every assigned query, and (f16) the order that brings queries that want the same clusters into
+    // the same waves
+    if (use_lb && c.assigned)
+      KNN_TRY(knn_bound_queries(s, c.scratch, c.b.xs, c.offsets, c.b.mydist, 0, c.assigned, R, f16 ? sw.order : 0, &a));
+    ra.radius = rq.r;
+    radius_prune_margins(*this, &ra);
     ra.qinv = c.b.inv;
-    ra.counts = host ? counts_dev : (counts ? counts + q0 : nullptr);
-    ra.offsets = nullptr; ra.out_base = 0; ra.neighbors = nullptr; ra.distances = nullptr; ra.flag = flag;
-    if (fill) {
-      if (host) {
-        KMX_HIPCP(hipMemcpyAsync(offsets_dev, offsets + q0, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        // (slots of a range the search does not fill -- the call then fails -- read 0xFF)
-        if (range) KMX_HIPRT(hipMemsetAsync(stage.nb, 0xFF, range * sizeof(uint32_t), st));
-        if (range && distances) KMX_HIPRT(hipMemsetAsync(stage.dist, 0xFF, range * sizeof(float), st));
-        ra.offsets = offsets_dev; ra.out_base = offsets[q0];
-        ra.neighbors = static_cast<uint32_t *>(stage.nb); ra.distances = static_cast<float *>(stage.dist);
-      } else {
-        ra.offsets = offsets + q0;
-        ra.neighbors = neighbors; ra.distances = distances;
-      }
-    }
+    KNN_TRY(res.fill_args(q0, n, &ra));
     if (f16) {
-      KMX_HIPRT(launch_knn_radius_f16(metric, ra, (uint32_t)(c.plan.size() / 2), fill, st, allow != nullptr));
+      KMX_HIPRT(launch_knn_radius_f16(s.metric, ra, (uint32_t)(c.plan.size() / 2), fill, st, masked));
       KnnRadiusArgs rest = ra;
       rest.a.p_base = c.assigned; rest.a.p_end = n;
       KMX_HIPRT(launch_knn_radius_rest(rest, fill, st));
     } else {
-      KMX_HIPRT(launch_knn_radius_exact(metric, ra, c.cp.strict_h2, fill, st, allow != nullptr));
+      KMX_HIPRT(launch_knn_radius_exact(s.metric, ra, c.cp.strict_h2, fill, st, masked));
     }
-    if (host && !fill)
-      KMX_HIPCP(hipMemcpyAsync(counts + q0, counts_dev, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (host && fill && range) {
-      KMX_HIPCP(hipMemcpyAsync(neighbors + offsets[q0], stage.nb, range * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      if (distances)
-        KMX_HIPCP(hipMemcpyAsync(distances + offsets[q0], stage.dist, range * sizeof(float), hipMemcpyDeviceToHost, st));
-    }
-    // (the next chunk overwrites these buffers: the stream orders it behind this one's kernels and copies)
+    KNN_TRY(res.deliver(q0, n));
   }
   bool raised = false;
-  if (flag_raised(&raised) != 0) {
+  if (res.flag_raised(&raised) != 0) {
     if (verbosity > 0) printf("k-NN radius search failed: %s\n", hipGetErrorString(hipGetLastError()));
     return kmcudaRuntimeError;
   }
@@ -1090,18 +1097,40 @@ static void sync_callers_writes(int32_t device_ptrs) {
   if (device_ptrs >= 0 && hipSetDevice(device_ptrs) == hipSuccess) (void)hipDeviceSynchronize();
 }
 
-// the arguments query and query_probe share
-static bool query_call_ok(kmamd_knn_index *h, uint32_t k, int32_t device_ptrs) {
-  if (!h) return false;
-  if (k == 0 || k > 65535u || k > h->ix.s.N) return false;
-  return device_ptrs < 0 || device_ptrs == h->ix.s.dev;
-}
-
 // max_distance of the capped calls: not NaN, >= 0; +inf (and whatever exceeds FLT_MAX) means FLT_MAX, no cap
 static bool cap_ok(float *cap) {
   if (!(*cap >= 0.f)) return false;
   if (*cap > kNoCap) *cap = kNoCap;
   return true;
+}
+
+// Every top-k entry point behind its request: the refusals in their order, the empty batch, the call.  probed: rq.pw
+// is the caller's nprobe, any value
+static int topk_call(kmamd_knn_index *h, TopkRequest rq, bool probed) {
+  if (!cap_ok(&rq.cap) || !h) return kmcudaInvalidArguments;
+  KnnIndex &ix = h->ix;
+  if (rq.k == 0 || rq.k > 65535u || rq.k > ix.s.N) return kmcudaInvalidArguments;
+  if (rq.device_ptrs >= 0 && rq.device_ptrs != ix.s.dev) return kmcudaInvalidArguments;
+  if (probed) {
+    if (rq.pw < 1 || rq.pw > KNN_PROBE_MAX || rq.pw > ix.s.K) return kmcudaInvalidArguments;
+    // the reference's half2 arithmetic has no ranking (kmamd_kmeans_assign_top refuses it likewise): the caller's lists only
+    if (!rq.probes_in && ix.fp16 && (ix.path.strict_h2 || knn_switches().fp16_strict)) return kmcudaInvalidArguments;
+  }
+  if (rq.Q == 0) return kmcudaSuccess;
+  if (!rq.queries || !rq.neighbors) return kmcudaInvalidArguments;
+  sync_callers_writes(rq.device_ptrs);
+  return ix.topk(rq);
+}
+
+// ... and every radius entry point
+static int radius_call(kmamd_knn_index *h, const RadiusRequest &rq) {
+  if (!h) return kmcudaInvalidArguments;
+  if (!(rq.r >= 0.f) || rq.r > 3.402823466e+38f) return kmcudaInvalidArguments;   // NaN, negative or infinite
+  if (rq.device_ptrs >= 0 && rq.device_ptrs != h->ix.s.dev) return kmcudaInvalidArguments;
+  if (rq.Q == 0) return kmcudaSuccess;
+  if (!rq.queries || (rq.fill ? !rq.offsets || !rq.neighbors : !rq.counts)) return kmcudaInvalidArguments;
+  sync_callers_writes(rq.device_ptrs);
+  return h->ix.radius(rq);
 }
 
 extern "C" {
@@ -1137,12 +1166,12 @@ int kmamd_knn_index_query_capped(kmamd_knn_index *h, uint32_t k, float max_dista
                                  const void *queries, const uint32_t *query_assignments, uint32_t *neighbors,
                                  float *distances, uint32_t *query_assignments_out, int32_t device_ptrs,
                                  const uint8_t *allow) {
-  if (!cap_ok(&max_distance) || !query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
-  if (n_queries == 0) return kmcudaSuccess;
-  if (!queries || !neighbors) return kmcudaInvalidArguments;
-  sync_callers_writes(device_ptrs);
-  return h->ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs,
-                     allow, max_distance, true);
+  TopkRequest rq;
+  rq.k = k; rq.cap = max_distance; rq.Q = n_queries; rq.queries = queries;
+  rq.qassign_in = query_assignments; rq.qassign_out = query_assignments_out;
+  rq.neighbors = neighbors; rq.distances = distances; rq.allow = allow; rq.device_ptrs = device_ptrs;
+  rq.report = "capped query";
+  return topk_call(h, rq, false);
 }
 
 int kmamd_knn_index_query(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, const void *queries,
@@ -1155,28 +1184,23 @@ int kmamd_knn_index_query(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, co
 int kmamd_knn_index_query_allow(kmamd_knn_index *h, uint32_t k, uint32_t n_queries, const void *queries,
                                 const uint32_t *query_assignments, uint32_t *neighbors, float *distances,
                                 uint32_t *query_assignments_out, int32_t device_ptrs, const uint8_t *allow) {
-  if (!query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
-  if (n_queries == 0) return kmcudaSuccess;
-  if (!queries || !neighbors) return kmcudaInvalidArguments;
-  sync_callers_writes(device_ptrs);
-  return h->ix.query(k, n_queries, queries, query_assignments, neighbors, distances, query_assignments_out, device_ptrs,
-                     allow, kNoCap, false);
+  TopkRequest rq;   // (no cap, and no counters line: the uncapped query prints what it always printed)
+  rq.k = k; rq.Q = n_queries; rq.queries = queries;
+  rq.qassign_in = query_assignments; rq.qassign_out = query_assignments_out;
+  rq.neighbors = neighbors; rq.distances = distances; rq.allow = allow; rq.device_ptrs = device_ptrs;
+  return topk_call(h, rq, false);
 }
 
 int kmamd_knn_index_query_probe_capped(kmamd_knn_index *h, uint32_t k, float max_distance, uint32_t nprobe,
                                        uint32_t n_queries, const void *queries, const uint32_t *probes,
                                        uint32_t *neighbors, float *distances, uint32_t *probes_out, int32_t device_ptrs,
                                        const uint8_t *allow) {
-  if (!cap_ok(&max_distance) || !query_call_ok(h, k, device_ptrs)) return kmcudaInvalidArguments;
-  KnnIndex &ix = h->ix;
-  if (nprobe < 1 || nprobe > KNN_PROBE_MAX || nprobe > ix.s.K) return kmcudaInvalidArguments;
-  // the reference's half2 arithmetic has no ranking (kmamd_kmeans_assign_top refuses it likewise): the caller's lists only
-  if (!probes && ix.fp16 && (ix.path.strict_h2 || knn_switches().fp16_strict)) return kmcudaInvalidArguments;
-  if (n_queries == 0) return kmcudaSuccess;
-  if (!queries || !neighbors) return kmcudaInvalidArguments;
-  sync_callers_writes(device_ptrs);
-  return ix.query_probe(k, nprobe, n_queries, queries, probes, neighbors, distances, probes_out, device_ptrs, allow,
-                        max_distance);
+  TopkRequest rq;
+  rq.k = k; rq.cap = max_distance; rq.Q = n_queries; rq.queries = queries;
+  rq.pw = nprobe; rq.probes_in = probes; rq.probes_out = probes_out;
+  rq.neighbors = neighbors; rq.distances = distances; rq.allow = allow; rq.device_ptrs = device_ptrs;
+  rq.report = "probe query";
+  return topk_call(h, rq, true);
 }
 
 int kmamd_knn_index_query_probe_allow(kmamd_knn_index *h, uint32_t k, uint32_t nprobe, uint32_t n_queries,
@@ -1193,21 +1217,14 @@ int kmamd_knn_index_query_probe(kmamd_knn_index *h, uint32_t k, uint32_t nprobe,
                                            device_ptrs, nullptr);
 }
 
-static bool radius_call_ok(kmamd_knn_index *h, float radius, int32_t device_ptrs) {
-  if (!h) return false;
-  if (!(radius >= 0.f) || radius > 3.402823466e+38f) return false;   // NaN, negative or infinite
-  return device_ptrs < 0 || device_ptrs == h->ix.s.dev;
-}
-
 int kmamd_knn_index_radius_count_allow(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
                                        const uint32_t *query_assignments, uint32_t *counts,
                                        uint32_t *query_assignments_out, int32_t device_ptrs, const uint8_t *allow) {
-  if (!radius_call_ok(h, radius, device_ptrs)) return kmcudaInvalidArguments;
-  if (n_queries == 0) return kmcudaSuccess;
-  if (!queries || !counts) return kmcudaInvalidArguments;
-  sync_callers_writes(device_ptrs);
-  return h->ix.radius(false, radius, n_queries, queries, query_assignments, counts, query_assignments_out, nullptr,
-                      nullptr, nullptr, device_ptrs, allow);
+  RadiusRequest rq;
+  rq.r = radius; rq.Q = n_queries; rq.queries = queries;
+  rq.qassign_in = query_assignments; rq.qassign_out = query_assignments_out;
+  rq.counts = counts; rq.allow = allow; rq.device_ptrs = device_ptrs;
+  return radius_call(h, rq);
 }
 
 int kmamd_knn_index_radius_count(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
@@ -1220,12 +1237,11 @@ int kmamd_knn_index_radius_count(kmamd_knn_index *h, float radius, uint32_t n_qu
 int kmamd_knn_index_radius_fill_allow(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
                                       const uint32_t *query_assignments, const uint64_t *offsets, uint32_t *neighbors,
                                       float *distances, int32_t device_ptrs, const uint8_t *allow) {
-  if (!radius_call_ok(h, radius, device_ptrs)) return kmcudaInvalidArguments;
-  if (n_queries == 0) return kmcudaSuccess;
-  if (!queries || !offsets || !neighbors) return kmcudaInvalidArguments;
-  sync_callers_writes(device_ptrs);
-  return h->ix.radius(true, radius, n_queries, queries, query_assignments, nullptr, nullptr, offsets, neighbors,
-                      distances, device_ptrs, allow);
+  RadiusRequest rq;
+  rq.fill = true; rq.r = radius; rq.Q = n_queries; rq.queries = queries;
+  rq.qassign_in = query_assignments;
+  rq.offsets = offsets; rq.neighbors = neighbors; rq.distances = distances; rq.allow = allow; rq.device_ptrs = device_ptrs;
+  return radius_call(h, rq);
 }
 
 int kmamd_knn_index_radius_fill(kmamd_knn_index *h, float radius, uint32_t n_queries, const void *queries,
@@ -1242,7 +1258,7 @@ int kmamd_knn_index_add(kmamd_knn_index *h, uint32_t n_rows, const void *rows, c
   if (n_rows > 0 && !rows) return kmcudaInvalidArguments;
   if (device_ptrs >= 0 && device_ptrs != ix.s.dev) return kmcudaInvalidArguments;
   if (!knn_add_fits(ix.s.N, n_rows)) return kmcudaInvalidArguments;
-  // the reference's half2 arithmetic has no assignment pass (query_probe refuses its ranking likewise): the caller's only
+  // the reference's half2 arithmetic has no assignment pass (a probed query refuses its ranking likewise): the caller's only
   if (!assignments && ix.fp16 && (ix.path.strict_h2 || knn_switches().fp16_strict)) return kmcudaInvalidArguments;
   const uint32_t first = ix.s.N;
   if (n_rows != 0) {

@@ -113,7 +113,7 @@ class KnnJob {
       KnnArgs a;
       a.blocks = s.blocks; a.k = k; a.p_base = s.p_base; a.p_end = s.p_end; a.heaps = s.heaps; a.out = s.out;
       s.scratch.rows = len;
-      KNN_TRY(knn_search(s, s.scratch, a, path, sw, (uint32_t)(plan.size() / 2), true, verbosity));
+      KNN_TRY(knn_search(s, s.scratch, a, path, sw, (uint32_t)(plan.size() / 2), true, verbosity, nullptr));
     }
     return 0;
   }

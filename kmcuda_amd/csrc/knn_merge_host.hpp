@@ -43,6 +43,14 @@ inline uint32_t knn_chunk_rows(size_t budget, size_t row_bytes, size_t forced, u
   return rows < n ? (uint32_t)rows : n;
 }
 
+// The queries of one chunk of a radius fill to a caller on the host, whose hits are staged on the device: of the n (>=
+// 1) queries from q0 on, as many as have their CSR range offsets[q0 + n] - offsets[q0] (non-decreasing offsets) within
+// max_hits -- n halved, rounding up, until it fits; a single query larger than that stays a chunk of its own
+inline uint32_t knn_fill_chunk_rows(const uint64_t *offsets, uint32_t q0, uint32_t n, uint64_t max_hits) {
+  while (n > 1 && offsets[(size_t)q0 + n] - offsets[q0] > max_hits) n = (n + 1) / 2;
+  return n;
+}
+
 // ... of an add: a chunk's staged fp32 rows (D floats), its sorted fp32 copy (DP floats), the centred halves (DP) and
 // the per-row scalars and sort scratch (some 48 bytes)
 inline uint32_t knn_add_chunk_rows(uint32_t n, uint32_t D, uint32_t DP, size_t budget, size_t forced) {

@@ -323,6 +323,10 @@ def _ptr(x):
     return ctypes.c_void_p(x.data_ptr() if _is_torch(x) else x.ctypes.data)
 
 
+def _opt_ptr(x):
+    return _ptr(x) if x is not None else None
+
+
 class KnnIndex:
     """A corpus prepared for k-NN queries on one GPU (kmamd_knn_index_create)."""
 
@@ -364,36 +368,46 @@ class KnnIndex:
                                           self.device)
         nprobe, pr = _check_probes(nprobe, probes, nq, self.clusters, q_dev, query_assignments, self.device, self.fp16)
         al = _check_allow(allow, self.n_rows, q_dev, self.device)
-        if nprobe is not None:
-            out = self._query_probe(q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes,
-                                    al, cap)
-            return self._with_counts(out, want_distances, return_counts, cap)
-        if return_probes:
+        probed = nprobe is not None
+        if return_probes and not probed:
             raise ValueError("\"return_probes\" needs \"nprobe\" or \"probes\"")
-        if q_dev:
-            import torch
-            dev = torch.device("cuda", self.device)
-            nb = torch.empty((nq, k), dtype=torch.int32, device=dev)
-            dist = torch.empty((nq, k), dtype=torch.float32, device=dev) if return_distances else None
-            asg = torch.empty((nq,), dtype=torch.int32, device=dev) if return_assignments else None
+        nb = self._out((nq, k), "u", q_dev)
+        dist = self._out((nq, k), "f", q_dev) if return_distances else None
+        # the lists of the call: the probe lists (in: the caller's, out: those used), or the queries' clusters
+        if probed:
+            lists_in = pr
+            lists_out = self._out((nq, nprobe), "u", q_dev) if return_assignments or return_probes else None
         else:
-            nb = numpy.empty((nq, k), numpy.uint32)
-            dist = numpy.empty((nq, k), numpy.float32) if return_distances else None
-            asg = numpy.empty((nq,), numpy.uint32) if return_assignments else None
-        if nq and cap is not None:
-            rc = self.lib.kmamd_knn_index_query_capped(self.h, k, cap, nq, _ptr(q), _ptr(qa) if qa is not None else None,
-                                                       _ptr(nb), _ptr(dist) if dist is not None else None,
-                                                       _ptr(asg) if asg is not None else None,
-                                                       self.device if q_dev else -1, _ptr(al) if al is not None else None)
-            _raise_for(rc, "kmamd_knn_index_query_capped")
-        elif nq:
-            rc = self.lib.kmamd_knn_index_query_allow(self.h, k, nq, _ptr(q), _ptr(qa) if qa is not None else None,
-                                                      _ptr(nb), _ptr(dist) if dist is not None else None,
-                                                      _ptr(asg) if asg is not None else None,
-                                                      self.device if q_dev else -1, _ptr(al) if al is not None else None)
-            _raise_for(rc, "kmamd_knn_index_query")
-        out = (nb,) + ((dist,) if return_distances else ()) + ((asg,) if return_assignments else ())
+            lists_in = qa
+            lists_out = self._out((nq,), "u", q_dev) if return_assignments else None
+        if nq:
+            # (the capped entry points print the KMCUDA_AMD_KNN_STATS line the uncapped query does not: never for cap=None)
+            name = "kmamd_knn_index_query_probe" if probed else "kmamd_knn_index_query"
+            entry = name + ("_allow" if cap is None else "_capped")
+            args = [self.h, k] + ([] if cap is None else [cap]) + ([nprobe] if probed else [])
+            args += [nq, _ptr(q), _opt_ptr(lists_in), _ptr(nb), _opt_ptr(dist), _opt_ptr(lists_out),
+                     self.device if q_dev else -1, _opt_ptr(al)]
+            _raise_for(getattr(self.lib, entry)(*args), name if cap is None else entry)
+        out = (nb,) + ((dist,) if return_distances else ())
+        if probed:
+            if return_assignments:
+                col0 = lists_out[:, 0]
+                out += ((col0.contiguous() if q_dev else numpy.ascontiguousarray(col0)),)
+            if return_probes:
+                out += (lists_out,)
+        elif return_assignments:
+            out += (lists_out,)
         return self._with_counts(out[0] if len(out) == 1 else out, want_distances, return_counts, cap)
+
+    def _out(self, shape, kind, on_dev, zeros=False):
+        """An output array of a call on the side its inputs are on: a tensor on the index's device (kind "u", row ids,
+        cluster ids and counts: int32; "f": float32) or a numpy array (uint32 / float32)."""
+        if on_dev:
+            import torch
+            make = torch.zeros if zeros else torch.empty
+            return make(shape, dtype=torch.int32 if kind == "u" else torch.float32,
+                        device=torch.device("cuda", self.device))
+        return (numpy.zeros if zeros else numpy.empty)(shape, numpy.uint32 if kind == "u" else numpy.float32)
 
     @staticmethod
     def _with_counts(out, want_distances, return_counts, cap):
@@ -405,42 +419,6 @@ class KnnIndex:
         if not want_distances:
             out = out[:1] + out[2:]
         return out
-
-    def _query_probe(self, q, nq, q_dev, k, nprobe, pr, return_distances, return_assignments, return_probes, al=None,
-                     cap=None):
-        want_lists = return_assignments or return_probes
-        if q_dev:
-            import torch
-            dev = torch.device("cuda", self.device)
-            nb = torch.empty((nq, k), dtype=torch.int32, device=dev)
-            dist = torch.empty((nq, k), dtype=torch.float32, device=dev) if return_distances else None
-            used = torch.empty((nq, nprobe), dtype=torch.int32, device=dev) if want_lists else None
-        else:
-            nb = numpy.empty((nq, k), numpy.uint32)
-            dist = numpy.empty((nq, k), numpy.float32) if return_distances else None
-            used = numpy.empty((nq, nprobe), numpy.uint32) if want_lists else None
-        if nq and cap is not None:
-            rc = self.lib.kmamd_knn_index_query_probe_capped(self.h, k, cap, nprobe, nq, _ptr(q),
-                                                             _ptr(pr) if pr is not None else None, _ptr(nb),
-                                                             _ptr(dist) if dist is not None else None,
-                                                             _ptr(used) if used is not None else None,
-                                                             self.device if q_dev else -1,
-                                                             _ptr(al) if al is not None else None)
-            _raise_for(rc, "kmamd_knn_index_query_probe_capped")
-        elif nq:
-            rc = self.lib.kmamd_knn_index_query_probe_allow(self.h, k, nprobe, nq, _ptr(q),
-                                                            _ptr(pr) if pr is not None else None, _ptr(nb),
-                                                            _ptr(dist) if dist is not None else None,
-                                                            _ptr(used) if used is not None else None,
-                                                            self.device if q_dev else -1,
-                                                            _ptr(al) if al is not None else None)
-            _raise_for(rc, "kmamd_knn_index_query_probe")
-        out = (nb,) + ((dist,) if return_distances else ())
-        if return_assignments:
-            out += ((used[:, 0].contiguous() if q_dev else numpy.ascontiguousarray(used[:, 0])),)
-        if return_probes:
-            out += (used,)
-        return out[0] if len(out) == 1 else out
 
     def query_radius(self, queries, radius, query_assignments=None, return_distances=True, sort=False,
                      count_only=False):
@@ -470,41 +448,32 @@ class KnnIndex:
         al = _check_allow(allow, self.n_rows, q_dev, self.device)
         if masked and al is None:
             raise TypeError("\"allow\" must be a 1D bool or uint8 numpy array or tensor")
-        alp = _ptr(al) if al is not None else None
+        alp = _opt_ptr(al)
         dptr = self.device if q_dev else -1
-        if q_dev:
-            import torch
-            dev = torch.device("cuda", self.device)
-            counts = torch.zeros((nq,), dtype=torch.int32, device=dev)
-            asg = torch.empty((nq,), dtype=torch.int32, device=dev) if qa is None else None
-        else:
-            counts = numpy.zeros((nq,), numpy.uint32)
-            asg = numpy.empty((nq,), numpy.uint32) if qa is None else None
+        counts = self._out((nq,), "u", q_dev, zeros=True)
+        asg = self._out((nq,), "u", q_dev) if qa is None else None
         if nq:
-            rc = self.lib.kmamd_knn_index_radius_count_allow(self.h, r, nq, _ptr(q),
-                                                             _ptr(qa) if qa is not None else None, _ptr(counts),
-                                                             _ptr(asg) if asg is not None else None, dptr, alp)
+            rc = self.lib.kmamd_knn_index_radius_count_allow(self.h, r, nq, _ptr(q), _opt_ptr(qa), _ptr(counts),
+                                                             _opt_ptr(asg), dptr, alp)
             _raise_for(rc, "kmamd_knn_index_radius_count_allow" if masked else "kmamd_knn_index_radius_count")
         if count_only:
             return counts
         if qa is None:
             qa = asg   # the fill groups the queries as the count did
         if q_dev:
-            offsets = torch.zeros((nq + 1,), dtype=torch.int64, device=dev)
+            import torch
+            offsets = torch.zeros((nq + 1,), dtype=torch.int64, device=counts.device)
             # (a count reads as a negative int32 from 2^31 on)
             torch.cumsum(counts.to(torch.int64) & 0xFFFFFFFF, 0, out=offsets[1:])
-            total = int(offsets[-1])   # the one value that reaches the host
-            nb = torch.empty((total,), dtype=torch.int32, device=dev)
-            dist = torch.empty((total,), dtype=torch.float32, device=dev) if return_distances else None
         else:
             offsets = numpy.zeros((nq + 1,), numpy.int64)
             numpy.cumsum(counts, out=offsets[1:])
-            total = int(offsets[-1])
-            nb = numpy.empty((total,), numpy.uint32)
-            dist = numpy.empty((total,), numpy.float32) if return_distances else None
+        total = int(offsets[-1])   # (from the device: the one value that reaches the host)
+        nb = self._out((total,), "u", q_dev)
+        dist = self._out((total,), "f", q_dev) if return_distances else None
         if nq and total:
             rc = self.lib.kmamd_knn_index_radius_fill_allow(self.h, r, nq, _ptr(q), _ptr(qa), _ptr(offsets), _ptr(nb),
-                                                            _ptr(dist) if dist is not None else None, dptr, alp)
+                                                            _opt_ptr(dist), dptr, alp)
             _raise_for(rc, "kmamd_knn_index_radius_fill_allow" if masked else "kmamd_knn_index_radius_fill")
         if sort:
             nb, dist = _sort_slices(offsets, nb, dist)
@@ -534,16 +503,9 @@ class KnnIndex:
                              "(kmeans_predict refuses it too): pass \"assignments\"")
         if self.n_rows + n > 0xFFFFFFFE:
             raise ValueError("an index holds at most 0xFFFFFFFE rows")
-        out = None
-        if return_assignments:
-            if on_dev:
-                import torch
-                out = torch.empty((n,), dtype=torch.int32, device=torch.device("cuda", self.device))
-            else:
-                out = numpy.empty((n,), numpy.uint32)
+        out = self._out((n,), "u", on_dev) if return_assignments else None
         first = u32(self.n_rows)
-        rc = self.lib.kmamd_knn_index_add(self.h, n, _ptr(r), _ptr(a) if a is not None else None,
-                                          _ptr(out) if out is not None else None, ctypes.byref(first),
+        rc = self.lib.kmamd_knn_index_add(self.h, n, _ptr(r), _opt_ptr(a), _opt_ptr(out), ctypes.byref(first),
                                           self.device if on_dev else -1)
         _raise_for(rc, "kmamd_knn_index_add")
         self.n_rows += n

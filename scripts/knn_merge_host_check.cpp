@@ -149,6 +149,39 @@ int main() {
           }
     }
   }
+  // the chunk of a radius fill whose hits are staged: halved until its CSR range fits
+  {
+    const uint64_t offs[8] = {0, 10, 20, 30, 40, 50, 60, 70};
+    CHECK(knn_fill_chunk_rows(offs, 0, 7, 70) == 7);   // fits as it is
+    CHECK(knn_fill_chunk_rows(offs, 2, 5, 50) == 5);   // (from q0 on: offs[7] - offs[2])
+    CHECK(knn_fill_chunk_rows(offs, 0, 7, 69) == 4);   // one halving of an odd n rounds up
+    CHECK(knn_fill_chunk_rows(offs, 0, 7, 15) == 1);   // 7 -> 4 -> 2 -> 1
+    CHECK(knn_fill_chunk_rows(offs, 0, 7, 20) == 2);
+    CHECK(knn_fill_chunk_rows(offs, 3, 4, 25) == 2);
+    CHECK(knn_fill_chunk_rows(offs, 0, 1, 0) == 1);    // a single query larger than the budget stays
+    CHECK(knn_fill_chunk_rows(offs, 6, 1, 9) == 1);
+    CHECK(knn_fill_chunk_rows(offs, 0, 5, 0) == 1);
+    const uint64_t empty[4] = {5, 5, 5, 5};
+    CHECK(knn_fill_chunk_rows(empty, 0, 3, 0) == 3);   // empty ranges fit any budget
+    // offsets near 2^63 and above: the difference is what counts
+    const uint64_t top = (uint64_t)1 << 63;
+    const uint64_t big[6] = {top - 3, top - 1, top, top + 4, top + 4, top + 9};
+    CHECK(knn_fill_chunk_rows(big, 0, 5, 12) == 5);
+    CHECK(knn_fill_chunk_rows(big, 0, 5, 11) == 3);    // big[3] - big[0] = 7
+    CHECK(knn_fill_chunk_rows(big, 0, 5, 6) == 2);     // 5 -> 3 -> 2: big[2] - big[0] = 3
+    CHECK(knn_fill_chunk_rows(big, 1, 4, 5) == 2);     // 4 -> 2: big[3] - big[1] = 5
+    // against the loop the radius call used to spell out, at every start, length and budget of a random CSR
+    std::mt19937 rng(5);
+    std::vector<uint64_t> o(41, top - 100);
+    for (size_t i = 1; i < o.size(); i++) o[i] = o[i - 1] + rng() % 9;
+    for (uint32_t q0 = 0; q0 < 40; q0++)
+      for (uint32_t n0 = 1; q0 + n0 <= 40; n0++)
+        for (uint64_t budget : {(uint64_t)0, (uint64_t)1, (uint64_t)7, (uint64_t)40, (uint64_t)1000}) {
+          uint32_t n = n0;
+          while (n > 1 && (o[q0 + n] - o[q0]) > budget) n = (n + 1) / 2;
+          CHECK(knn_fill_chunk_rows(o.data(), q0, n0, budget) == n);
+        }
+  }
   printf(failures ? "%d checks FAILED\n" : "knn_merge_host_check: all checks passed\n", failures);
   return failures ? 1 : 0;
 }

@@ -368,6 +368,25 @@ def test_device_tensors(path, monkeypatch):
         check_expect(ix.text, path)
 
 
+@pytest.mark.parametrize("device", [False, True])
+@pytest.mark.parametrize("path", ["f16", "exact"])
+def test_mask_probes_and_cap_in_one_chunk_loop(path, device, monkeypatch):
+    """allow, nprobe and max_distance together over four chunks (the last one partial): the restatement's lists, and
+    bit for bit those of the same call in one chunk."""
+    x, c, a, _, corpus, ref = fixture(16)
+    q = batch(x, c, 0.05, seed=5, fresh=200)
+    assert len(q) == 250
+    mask = masks(a, len(c))["half"].view(numpy.uint8)
+    cap = float(numpy.percentile(ref[1][:, 9], 60))
+    with Index(x, c, a, env=PATHS[path], monkeypatch=monkeypatch, device=device) as ix:
+        whole = check_capped(ix, corpus, q, 10, cap, allow=mask, nprobe=3, what=(path, device, "whole"))
+        monkeypatch.setenv("KMCUDA_AMD_KNN_QUERY_CHUNK", "64")
+        chunked = check_capped(ix, corpus, q, 10, cap, allow=mask, nprobe=3, what=(path, device, "chunked"))
+        check_expect(ix.text, path)
+    same(whole, chunked, (path, device))
+    assert (whole[2] == chunked[2]).all() and 0 < whole[2].sum() < whole[0].size
+
+
 @pytest.mark.parametrize("tight", [0, 1])
 @pytest.mark.parametrize("order", [0, 1, 2, 3])
 def test_query_order_and_centroid_bounds(order, tight, monkeypatch):
