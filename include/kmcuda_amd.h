@@ -574,9 +574,9 @@ int kmamd_kmeans_assign(int metric, uint32_t samples_size, uint16_t features_siz
  * 1 <= m <= min(clusters_size, 64).  samples_size == 0 is success.  InvalidArguments before any device work, with the
  * outputs untouched: m out of range, and everything kmamd_kmeans_assign refuses (bad sizes, null pointers, device_ptrs
  * naming another device, KMCUDA_AMD_FP16_STRICT=1 with fp16x2 rows).
- * Rows of up to 256 features (and up to 2^19 centroids) are filtered on the matrix cores: exact keys are evaluated only
- * for the centroids whose score lies within the filter's error bound of the m-th best; wider rows take the exhaustive
- * exact kernel.  KMCUDA_AMD_ASSIGN_TOP=exact: that kernel alone for every shape (the cross-check; the same bits).
+ * Rows of every width (against up to 2^19 centroids) are filtered on the matrix cores: exact keys are evaluated only
+ * for the centroids whose score lies within the filter's error bound of the m-th best; more centroids take the
+ * exhaustive exact kernel.  KMCUDA_AMD_ASSIGN_TOP=exact: that kernel alone for every shape (the cross-check; the same bits).
  * KMCUDA_AMD_ASSIGN_TOP_ROWS=<rows> (tests): rows per score matrix of the filtered path.  No floating-point atomics: two
  * identical calls give identical bits. */
 int kmamd_kmeans_assign_top(int metric, uint32_t samples_size, uint16_t features_size, uint32_t clusters_size,

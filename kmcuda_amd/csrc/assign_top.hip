@@ -7,7 +7,8 @@
 //                       (lloyd_exact_kernel's layout), the best m kept in a list that lives one entry per lane
 //   assign_top_scores   rows x centroids^T on the f32 matrix cores with the centred panel of centroid_prep
 //                       (lloyd_filter_kernel's tile loop); writes a sub-chunk's score matrix once and, per row, the
-//                       bound 2E, the clamp limits and the NaN-first-feature flag
+//                       bound 2E, the clamp limits and the NaN-first-feature flag (up to 256 features; wider rows:
+//                       assign_top_scores_wide of assign_top_wide.hip, which leaves the same two arrays)
 //   assign_top_select   one wave per row over that matrix: the m-th best score v_m, then the exact key of every
 //                       contender (score >= cut) and the best m of them; rows the superset argument does not cover go
 //                       to a list for assign_top_exact
@@ -454,7 +455,8 @@ hipError_t launch_assign_top_exact(int metric, const float *samples, uint32_t N,
 hipError_t launch_assign_top_filter(const AssignTopFilter &a, const float *samples, uint32_t n, uint32_t row0,
                                     uint32_t *top, hipStream_t st) {
   if (n == 0) return hipSuccess;
-  const hipError_t e = with_width<FilterWidths>(a.DP, [&](auto DP) {
+  // rows beyond the register filter's widths: the streamed score kernel (assign_top_wide.hip), the same select
+  const auto scores_resident = [&](auto DP) {
     return with_flag(a.D == (uint32_t)DP() && (((uintptr_t)samples) & 15u) == 0, [&](auto FAST) {
       const size_t lds_bytes = (2 * 32 * (DP() + 4) + 64) * sizeof(float);
       // (per launch: the attribute belongs to the current device's copy of the kernel)
@@ -465,7 +467,9 @@ hipError_t launch_assign_top_filter(const AssignTopFilter &a, const float *sampl
                          samples, n, a.D, a.cfil, a.bias, a.mu, a.K_pad, a.stats, a.eps, a.metric, a.scores, a.meta);
       return hipGetLastError();
     });
-  });
+  };
+  const hipError_t e = a.DP > 256u ? launch_assign_top_scores_wide(a, samples, n, st)
+                                   : with_width<FilterWidths>(a.DP, scores_resident);
   if (e != hipSuccess) return e;
   return with_metric(a.metric, [&](auto M) {
     hipLaunchKernelGGL((assign_top_select_kernel<M()>), dim3(wave_row_grid(n)), dim3(256), 0, st, samples, n, a.D,

@@ -3,9 +3,10 @@
 //
 // The rows go through in chunks (host_job.hpp: assign_chunk_rows, RowStage): the kernels of assign_top.hip, copy out.
 // The centroids are prepared once per call (launch_centroid_prep: exact squared norms, the transposed panel, the centred
-// panel and its bound).  Rows of up to 256 features take the filtered path, a sub-chunk's score matrix at a time
-// (budgeted like the k-NN search's bound matrix); wider rows, KMCUDA_AMD_ASSIGN_TOP=exact and the rows the filter hands
-// over take the exhaustive kernel.
+// panel and its bound).  The rows take the filtered path, a sub-chunk's score matrix at a time (budgeted like the k-NN
+// search's bound matrix): up to 256 features the register-resident score kernel, beyond them the streamed one
+// (assign_top_wide.hip); KMCUDA_AMD_ASSIGN_TOP=exact, a panel too wide for the budget and the rows the filter hands over
+// take the exhaustive kernel.
 // The centroid preparation and the per-chunk ranking are AssignTopRanker's two halves (knn_host.hpp): the k-NN index
 // prepares once and ranks the chunks of its probed queries with them (knn_index.cpp).
 #include <math.h>
@@ -36,6 +37,8 @@ int AssignTopRanker::prepare(DeviceArena &w, int metric_, const float *cen_, uin
   const hipStream_t st = w.stream;
   K_pad = (K + 31) / 32 * 32; Kt = (K + 63) / 64 * 64;
   DP = exact_only ? 0 : filter_dp_for(D);
+  // wider than the register filter: the panel at D rounded up to the streamed score kernel's 32-feature chunk
+  if (!exact_only && DP == 0) DP = (D + 31) / 32 * 32;
   // (128 rows of scores are the least a launch writes: a panel too wide for the budget takes the exact kernel)
   if ((size_t)K_pad * sizeof(float) * 128 > kTopScoreBytes) DP = 0;
   KNN_TRY(w.alloc(&csqr, K));

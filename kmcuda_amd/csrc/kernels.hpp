@@ -358,8 +358,8 @@ hipError_t launch_minibatch_draw_gather(const void *corpus, uint64_t N, uint32_t
 hipError_t launch_assign_top_exact(int metric, const float *samples, uint32_t N, uint32_t D, const float *ct,
                                    const float *csqr, uint32_t K, uint32_t Kt, uint32_t m, const uint32_t *rows,
                                    const uint32_t *nrows, uint32_t *top, unsigned long long *evaluated, hipStream_t st);
-// the filtered path: what centroid_prep left (cfil, bias, mu, stats: launch_centroid_prep; DP = filter_dp_for(D) != 0)
-// and the buffers of one sub-chunk: scores (rows x K_pad floats), meta (rows x 4 floats); fb_rows / fb_count: the rows
+// the filtered path: what centroid_prep left (cfil, bias, mu, stats: launch_centroid_prep; DP = filter_dp_for(D), or
+// D rounded up to 32 where that is 0: the streamed score kernel of assign_top_wide.hip) and the buffers of one sub-chunk: scores (rows x K_pad floats), meta (rows x 4 floats); fb_rows / fb_count: the rows
 // handed to launch_assign_top_exact (chunk-relative indices; fb_count zeroed by the owner)
 struct AssignTopFilter {
   int metric;
@@ -372,6 +372,8 @@ struct AssignTopFilter {
   uint32_t *fb_rows, *fb_count;
   unsigned long long *evaluated;
 };
+// assign_top_wide.hip: a.scores and a.meta of n rows at a.DP > 256, a multiple of 32 (launch_assign_top_filter calls it)
+hipError_t launch_assign_top_scores_wide(const AssignTopFilter &a, const float *samples, uint32_t n, hipStream_t st);
 // rows [row0, row0 + n) of a chunk: `samples` and `top` point at row row0
 hipError_t launch_assign_top_filter(const AssignTopFilter &a, const float *samples, uint32_t n, uint32_t row0,
                                     uint32_t *top, hipStream_t st);
