@@ -692,6 +692,52 @@ int kmamd_minibatch_read(kmamd_minibatch *h, float *centroids, double *cluster_w
                          int32_t device_ptrs);
 void kmamd_minibatch_destroy(kmamd_minibatch *h);
 
+/* Batched K-means: `problems` (B) independent small problems of samples_size (N) rows x features_size (D) features and
+ * clusters_size (K) centroids each, in one launch train (beyond the reference).  Stateless and
+ * synchronous; the caller owns all memory.  L2, fp32 only.
+ *   layout 0 "problems"  samples is B x N x D, dense; assignments (and distances) are B x N
+ *   layout 1 "columns"   samples is N x (B * D), dense; problem b is the column block [b * D, (b + 1) * D) of every row,
+ *                        read in place through the row stride (the product-quantiser layout); assignments are N x B
+ *   centroids            B x K x D
+ *   device, device_ptrs  as kmamd_kmeans_assign: one device id; -1: every buffer on the host, else every buffer on
+ *                        that device, which must be `device`
+ * Limits: 1 <= B <= 65535, 1 <= D <= 64, K >= 1 and K8 * DP <= 16384, where DP = the narrowest of 4, 8, 16, 32, 64 that
+ * holds D and K8 = K rounded up to a multiple of 8 -- K <= 4096, 2048, 1024, 512, 256 by rung: kmamd_batched_max_clusters.
+ * (The fp32 panel, K8 * DP * 4 bytes, and the update's fp64 cells, K8 * DP * 8 bytes, each stay resident in a block's
+ * LDS.)  Everything else -- metric != 0, fp16x2 != 0, sample weights, a null pointer, device_ptrs naming another
+ * device -- is InvalidArguments before any device work, with the outputs untouched; nothing is routed elsewhere.
+ *
+ * kmamd_kmeans_assign_batched: ONE assignment pass, new rows against B given centroid sets ("encode").
+ *   assignments  for problem b, bit for bit what kmamd_kmeans_assign gives for that problem's N x D slice and
+ *                centroids: the reference's round-down-FMA Kahan chains, strict `<` in ascending centroid order, K for a
+ *                row whose first feature is NaN or whose distances are all NaN.  codes_u8 != 0 (K <= 256 only): uint8
+ *                codes instead of uint32 (a row without a cluster gets the low byte of K).
+ *   distances    optional, laid out as the assignments: the reference's distance to that centroid, NaN without one.
+ *   samples_size == 0 is success.
+ *
+ * kmamd_kmeans_batched: the whole run.  A pass of a problem = one assignment pass, then every centroid that has members
+ * <- the fp64 sum of its member rows (ascending row order within a block of rows, the blocks in ascending order: no
+ * floating-point atomics, two identical calls give identical bits) divided by their number in fp64, rounded once to
+ * fp32; a centroid without members keeps its bits.  A problem stops after the pass in which at most tolerance * N rows
+ * changed their assignment (every row does in the first pass), or after max_iter passes -- decided on the device,
+ * per problem; the others go on.  K <= N.
+ *   init         0: centroids holds the initial centroids; 1 "random": centroid c of problem b starts as row
+ *                floor(h(seed, b, t) N / 2^64) for the first draws t = 0, 1, ... that give K DISTINCT rows (h: the
+ *                stateless hash of kmamd_kmeans_seed_parallel)
+ *   weights      must be null (per-row sample weights are refused)
+ *   tolerance in [0, 1], max_iter >= 1
+ *   assignments  uint32, final; iterations[b]: the passes problem b ran. */
+uint32_t kmamd_batched_max_clusters(uint32_t features_size);   /* 0: no such width */
+int kmamd_kmeans_assign_batched(uint32_t problems, uint32_t samples_size, uint16_t features_size,
+                                uint32_t clusters_size, int32_t layout, int metric, int32_t fp16x2, int device,
+                                int32_t device_ptrs, int32_t verbosity, int32_t codes_u8, const float *samples,
+                                const float *centroids, void *assignments, float *distances /* optional */);
+int kmamd_kmeans_batched(uint32_t problems, uint32_t samples_size, uint16_t features_size, uint32_t clusters_size,
+                         int32_t layout, int metric, int32_t fp16x2, int32_t init, float tolerance, uint32_t max_iter,
+                         uint32_t seed, int device, int32_t device_ptrs, int32_t verbosity, const float *samples,
+                         const float *weights /* must be null */, float *centroids /* in (init 0) / out */,
+                         uint32_t *assignments, uint32_t *iterations /* problems */);
+
 /* host -> raw device pointer copy on `device` (what python.cc:330-345 does with cudaMemcpy for imported
  * centroids in device-pointer mode; lets a binding without a HIP runtime of its own fill caller-owned memory). */
 int kmamd_copy_to_device(int device, void *dst, const void *host_src, size_t bytes);

@@ -20,9 +20,12 @@ the m nearest centroids of every row, in the order an assignment pass would find
 k-means|| seeding (beyond the reference), stand-alone -- kmeans_seed_parallel -- and as kmeans_cuda(init="k-means||").
 Mini-batch K-means on a model that stays on the GPU (beyond the reference): MiniBatchKMeans (partial_fit, fit) and the
 one-shot kmeans_minibatch.
+Batched K-means over many small independent problems in one call (beyond the reference; product-quantiser codebooks
+in place through a row stride): kmeans_batched, kmeans_predict_batched.
 """
 from .api import kmeans_cuda, knn_cuda, supports_fp16  # noqa: F401
 from .knn_index import KnnIndex, knn_query, knn_query_radius  # noqa: F401
 from .predict import kmeans_predict, kmeans_predict_top  # noqa: F401
 from .seed import kmeans_seed_parallel  # noqa: F401
 from .minibatch import MiniBatchKMeans, kmeans_minibatch  # noqa: F401
+from .batched import kmeans_batched, kmeans_predict_batched  # noqa: F401

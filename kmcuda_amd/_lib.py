@@ -34,6 +34,7 @@ EXPORTS = [
     "kmamd_kmeans_seed_parallel",
     "kmamd_minibatch_create", "kmamd_minibatch_step", "kmamd_minibatch_fit", "kmamd_minibatch_read",
     "kmamd_minibatch_destroy",
+    "kmamd_kmeans_batched", "kmamd_kmeans_assign_batched", "kmamd_batched_max_clusters",
     "kmamd_copy_to_device", "kmamd_profile_reset", "kmamd_profile_read", "kmamd_profile_enable", "kmamd_filter_kind", "kmamd_build_arch",
 ]
 
@@ -200,6 +201,14 @@ def lib():
     L.kmamd_minibatch_read.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_uint64), i32]
     L.kmamd_minibatch_destroy.restype = None
     L.kmamd_minibatch_destroy.argtypes = [vp]
+    L.kmamd_batched_max_clusters.restype = u32
+    L.kmamd_batched_max_clusters.argtypes = [u32]
+    L.kmamd_kmeans_assign_batched.restype = i32
+    L.kmamd_kmeans_assign_batched.argtypes = [u32, u32, ctypes.c_uint16, u32, i32, i32, i32, i32, i32, i32, i32, vp, vp,
+                                              vp, vp]
+    L.kmamd_kmeans_batched.restype = i32
+    L.kmamd_kmeans_batched.argtypes = [u32, u32, ctypes.c_uint16, u32, i32, i32, i32, i32, f32, u32, u32, i32, i32, i32,
+                                       vp, vp, vp, vp, vp]
     L.kmamd_copy_to_device.restype = i32
     L.kmamd_copy_to_device.argtypes = [i32, vp, vp, ctypes.c_size_t]
     L.kmamd_build_arch.restype = ctypes.c_char_p

@@ -382,6 +382,32 @@ hipError_t launch_assign_top_distances(int metric, const float *samples, uint32_
                                        const float *centroids, uint32_t K, uint32_t m, const uint32_t *top,
                                        float *dists, hipStream_t st);
 
+// lloyd_batched.hip -- K-means over many small independent problems (kmamd_kmeans_batched / _assign_batched,
+// batched_job.cpp).  Row `s` of problem `b` starts at rows + s * row_stride + b * prob_stride (floats),
+// its assignment (and distance) lies at s * out_row_stride + b * out_prob_stride.  A problem's rows are cut into G
+// chunks of R rows (R a multiple of 256); block (chunk, b) handles rows [chunk * R, min(N, (chunk + 1) * R)).
+struct BatchedGeom {
+  const float *rows;
+  uint32_t B, N, D, K, G, R;
+  uint64_t row_stride, prob_stride, out_row_stride, out_prob_stride;
+};
+// One assignment pass of every problem that has not stopped (stop == nullptr: of every problem).  assignments: uint32,
+// or uint8 codes (codes_u8; K <= 256, the low byte of K for a row without a cluster).  changed != nullptr: an
+// assignment is written only where it differs and changed[b] += the number of such rows (the training loop; uint32
+// assignments).  dists (optional): distance_vv<0>(row, centroid[assignment]), NaN without a cluster.
+hipError_t launch_batched_assign(const BatchedGeom &g, const float *centroids, void *assignments, bool codes_u8,
+                                 float *dists, uint32_t *changed, const uint32_t *stop, uint32_t pass, hipStream_t st);
+// The update of pass `pass`: fp64 partial sums per (block, centroid) (psum: B * G * K8 * DP doubles, pcnt: B * G * K8,
+// K8 = K rounded up to 8), then centroid <- (float)(sum / count) where count != 0, changed[b] read and zeroed, and
+// stop[b] <- pass where changed[b] <= tolerance * N or pass >= max_iter.
+hipError_t launch_batched_update(const BatchedGeom &g, const uint32_t *assignments, double *psum, uint32_t *pcnt,
+                                 float *centroids, uint32_t *changed, uint32_t *stop, uint32_t pass, uint32_t max_iter,
+                                 float tolerance, hipStream_t st);
+size_t batched_partial_lds_bytes(uint32_t K, uint32_t DP);
+// centroids[b][c] <- row picks[b * K + c] of problem b
+hipError_t launch_batched_gather(const BatchedGeom &g, const uint32_t *picks, float *centroids, hipStream_t st);
+hipError_t launch_batched_fill(uint32_t *p, uint64_t n, uint32_t v, hipStream_t st);
+
 // yinyang.hip (reference: kmeans.cu:431-672)
 hipError_t launch_yy_init(int metric, const float *xt, uint32_t len, uint32_t D, uint32_t G, const float *centroids,
                           const uint32_t *assignments, const uint32_t *cperm, const uint32_t *gstart, float *bounds,

@@ -27,6 +27,7 @@ using FilterWidths = Widths<8, 16, 32, 64, 128, 256>;                  // the f3
 using LloydF16Widths = Widths<16, 32, 64, 128, 256, 512>;              // the two-stage f16 Lloyd filter
 using KnnF16Widths = Widths<16, 32, 64, 128, 256, 512, 768, 1024>;     // the f16 k-NN / radius filters
 using HintWidths = Widths<16, 32, 64, 128, 256>;                       // the hinted Yinyang local filter
+using BatchedWidths = Widths<4, 8, 16, 32, 64>;                        // batched K-means: the row in registers
 
 // f(std::integral_constant<int, V>{}) for the rung V == dp of ladder L; hipErrorInvalidValue without one
 template <class L, class F>
@@ -44,5 +45,7 @@ hipError_t with_metric(int metric, F &&f) {
 inline uint32_t filter_dp_for(uint32_t D) { return FilterWidths::fit(D); }
 // + 512 for 256 < D <= 512: the two-stage f16 Lloyd filter only
 inline uint32_t lloyd_dp_for(uint32_t D) { return filter_dp_for(D) ? filter_dp_for(D) : LloydF16Widths::fit(D); }
+// 0: wider than the batched kernels take (D > 64)
+inline uint32_t batched_dp_for(uint32_t D) { return BatchedWidths::fit(D); }
 
 }  // namespace kmx
