@@ -738,6 +738,32 @@ int kmamd_kmeans_batched(uint32_t problems, uint32_t samples_size, uint16_t feat
                          const float *weights /* must be null */, float *centroids /* in (init 0) / out */,
                          uint32_t *assignments, uint32_t *iterations /* problems */);
 
+/* Top-k search over product-quantiser codes by asymmetric distance computation (beyond the reference; DESIGN.md
+ * 4.21): the search that the codes of kmamd_kmeans_assign_batched (layout 1, codes_u8) are made for.  Stateless and
+ * synchronous; the caller owns all memory.  L2, fp32 only.
+ *   queries    queries_size (Q) x features_size, features_size == subspaces * sub_features
+ *   codebooks  subspaces (M) x sub_clusters (ksub) x sub_features (dsub): kmamd_kmeans_batched's centroids, B = M
+ *   codes      samples_size (N) x M uint8, row-major
+ *   indices    Q x k uint32, distances Q x k float: the squared distances, no root taken
+ *   device, device_ptrs  as kmamd_kmeans_assign_batched
+ * The result, to the bit (separate round-to-nearest fp32 operations, no FMA):
+ *   T[q][m][c] = sum_j fl(fl(x_j - y_j)^2), j ascending from the j = 0 term, x the query's m-th sub-vector and y
+ *                codebooks[m][c]; +inf for c >= ksub (a code byte that names no codeword is infinitely far, no error)
+ *   d(q, i)    = sum_m T[q][m][codes[i][m]], m ascending from the m = 0 term
+ *   the k first rows by (d ascending, row ascending), a NaN d behind +inf: numpy.argsort(d, kind="stable")[:k].
+ * Nothing else -- launch shape, query or row chunking, arrival order -- reaches a bit of the output.
+ * Limits: 1 <= M <= 64, 1 <= dsub <= 64, 1 <= ksub <= 256, 1 <= N < 2^32, 1 <= k <= min(N, 256); Q == 0 is success.
+ * Everything else -- metric != 0, fp16x2 != 0, features_size != M * dsub, a null pointer, device_ptrs naming another
+ * device -- is InvalidArguments before any device work, with the outputs untouched; nothing is routed elsewhere.
+ * The queries are chunked inside the call (their tables stay within a fixed device budget); the codes are not.
+ *
+ * kmamd_pq_query_tile: the queries a scan block serves (their tables share its LDS), 0 where M or k is out of range. */
+uint32_t kmamd_pq_query_tile(uint32_t subspaces, uint32_t k);
+int kmamd_pq_search(uint32_t queries_size, uint64_t samples_size, uint32_t features_size, uint32_t subspaces,
+                    uint32_t sub_features, uint32_t sub_clusters, uint32_t k, int metric, int32_t fp16x2, int device,
+                    int32_t device_ptrs, int32_t verbosity, const float *queries, const float *codebooks,
+                    const uint8_t *codes, uint32_t *indices, float *distances);
+
 /* host -> raw device pointer copy on `device` (what python.cc:330-345 does with cudaMemcpy for imported
  * centroids in device-pointer mode; lets a binding without a HIP runtime of its own fill caller-owned memory). */
 int kmamd_copy_to_device(int device, void *dst, const void *host_src, size_t bytes);

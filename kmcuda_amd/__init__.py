@@ -22,6 +22,8 @@ Mini-batch K-means on a model that stays on the GPU (beyond the reference): Mini
 one-shot kmeans_minibatch.
 Batched K-means over many small independent problems in one call (beyond the reference; product-quantiser codebooks
 in place through a row stride): kmeans_batched, kmeans_predict_batched.
+Top-k search over the uint8 product-quantiser codes those calls produce, by asymmetric distance computation (beyond
+the reference): pq_search.
 """
 from .api import kmeans_cuda, knn_cuda, supports_fp16  # noqa: F401
 from .knn_index import KnnIndex, knn_query, knn_query_radius  # noqa: F401
@@ -29,3 +31,4 @@ from .predict import kmeans_predict, kmeans_predict_top  # noqa: F401
 from .seed import kmeans_seed_parallel  # noqa: F401
 from .minibatch import MiniBatchKMeans, kmeans_minibatch  # noqa: F401
 from .batched import kmeans_batched, kmeans_predict_batched  # noqa: F401
+from .pq import pq_search  # noqa: F401

@@ -408,6 +408,26 @@ size_t batched_partial_lds_bytes(uint32_t K, uint32_t DP);
 hipError_t launch_batched_gather(const BatchedGeom &g, const uint32_t *picks, float *centroids, hipStream_t st);
 hipError_t launch_batched_fill(uint32_t *p, uint64_t n, uint32_t v, hipStream_t st);
 
+// pq_scan.hip -- top-k search over product-quantiser codes (kmamd_pq_search, pq_job.cpp).  codes is
+// N x M uint8; the rows are cut into G chunks of R rows (R a multiple of 256); block (chunk, query tile) keeps the k
+// smallest keys (bits(d) << 32 | row) of its chunk for each of the QT queries of its tile.
+struct PqGeom {
+  const uint8_t *codes;
+  uint64_t N, R;
+  uint32_t M, k, QT, cap, G;   // QT = pq_query_tile(M, k), cap = pq_candidate_cap(k)
+};
+// queries per scan block: 16, 8 or 4 with two blocks in a CU's LDS, else 4 or 2 with one; 0: M or k out of range
+uint32_t pq_query_tile(uint32_t M, uint32_t k);
+uint32_t pq_candidate_cap(uint32_t k);   // keys in a query's candidate buffer: a power of two >= max(64, 2k)
+size_t pq_scan_lds_bytes(uint32_t M, uint32_t k, uint32_t QT);
+// tables[query tile][m][code < 256][q in tile] of Qc queries, the last tile padded: ceil(Qc / QT) * QT * M * 256 floats
+hipError_t launch_pq_tables(const float *queries, uint32_t Qc, const float *codebooks, uint32_t M, uint32_t dsub,
+                            uint32_t ksub, uint32_t QT, float *tables, hipStream_t st);
+// part[(query * G + chunk) * k ..): the chunk's k smallest keys in ascending order, ~0 where it has fewer
+hipError_t launch_pq_scan(const PqGeom &g, const float *tables, uint32_t queries, uint64_t *part, hipStream_t st);
+hipError_t launch_pq_merge(const uint64_t *part, uint32_t queries, uint32_t G, uint32_t k, uint32_t *indices,
+                           float *distances, hipStream_t st);
+
 // yinyang.hip (reference: kmeans.cu:431-672)
 hipError_t launch_yy_init(int metric, const float *xt, uint32_t len, uint32_t D, uint32_t G, const float *centroids,
                           const uint32_t *assignments, const uint32_t *cperm, const uint32_t *gstart, float *bounds,

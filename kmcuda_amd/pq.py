@@ -1,0 +1,110 @@
+"""Top-k search over product-quantiser codes by asymmetric distance computation (C ABI: kmamd_pq_search,
+include/kmcuda_amd.h) -- the search the codes of the batched calls are made for.
+
+    codebooks, _, _ = kmeans_batched(x, 256, init="random", layout="columns", problems=M)
+    codes = kmeans_predict_batched(x, codebooks, layout="columns", dtype=numpy.uint8)
+    indices, distances = pq_search(queries, codebooks, codes, 10)
+
+queries is (Q, M * dsub) float32, codebooks (M, ksub, dsub) float32, codes (N, M) uint8.  For every query a table of
+its squared sub-space distances to every codeword, T[m][c] = sum_j fl(fl(x_j - y_j)^2) in ascending j, +inf for
+c >= ksub; a row's distance is sum_m T[m][codes[i][m]] in ascending m (fp32, no FMA, no root); the k first rows by
+(distance, row index) come back, bit for bit numpy.argsort(d, kind="stable")[:k] of that arithmetic, a NaN distance
+behind +inf.  1 <= M <= 64, 1 <= dsub <= 64, 1 <= ksub <= 256, 1 <= N < 2^32, 1 <= k <= min(N, 256); L2 and float32
+only.  numpy in, numpy out (indices uint32); torch tensors on `device` in, torch tensors out (indices int32); the three
+operands must be of the same kind.  Every argument is checked before the device is touched; what is out of range is
+refused, never routed elsewhere.
+"""
+import numpy
+
+from . import _lib
+from .api import _get_metric, _raise_for
+from .batched import _f32, _out
+from .knn_index import _is_torch, _ptr
+
+_LDS_PER_CU = 160 << 10          # pq_scan.hip: kPqLdsPerCu
+
+
+def _candidate_cap(k):
+    cap = 64
+    while cap < 2 * k:
+        cap <<= 1
+    return cap
+
+
+def _scan_lds_bytes(m, k, qt):
+    return qt * (m * 1024 + _candidate_cap(k) * 8 + 16) + 16
+
+
+def query_tile(subspaces, k):
+    """The queries one scan block serves (kmamd_pq_query_tile): their tables share the block's LDS.  16, 8 or 4 where
+    two blocks fit a CU's LDS, else 4 or 2 with one; 0: `subspaces` or `k` out of range."""
+    if not 1 <= subspaces <= 64 or not 1 <= k <= 256:
+        return 0
+    for qt in (16, 8, 4):
+        if _scan_lds_bytes(subspaces, k, qt) <= _LDS_PER_CU // 2:
+            return qt
+    for qt in (4, 2):
+        if _scan_lds_bytes(subspaces, k, qt) <= _LDS_PER_CU:
+            return qt
+    return 0
+
+
+def _codes(x, device):
+    """(contiguous (N, M) uint8 array-or-tensor, on_device)"""
+    if _is_torch(x):
+        import torch
+        if x.dtype != torch.uint8:
+            raise TypeError("\"codes\" must be a uint8 tensor")
+        if x.dim() != 2:
+            raise ValueError("\"codes\" must be a 2D tensor")
+        if not x.is_cuda or x.device.index != device:
+            raise ValueError("\"codes\" must be on device %d (or be a numpy array)" % device)
+        return x.contiguous(), True
+    if not isinstance(x, numpy.ndarray) or x.dtype != numpy.uint8:
+        raise TypeError("\"codes\" must be a uint8 numpy array")
+    if x.ndim != 2:
+        raise ValueError("\"codes\" must be a 2D numpy array")
+    return numpy.ascontiguousarray(x), False
+
+
+def pq_search(queries, codebooks, codes, k, *, metric="L2", device=0, verbosity=0):
+    """(indices, distances), each (Q, k): the k rows of `codes` nearest to every query by ADC (module docstring)."""
+    if _get_metric(metric) != 0:
+        raise ValueError("pq_search supports the L2 metric only")
+    if isinstance(device, bool) or not isinstance(device, (int, numpy.integer)) or device < 0:
+        raise ValueError("\"device\" must be a device id >= 0")
+    if isinstance(k, bool) or not isinstance(k, (int, numpy.integer)):
+        raise TypeError("\"k\" must be an integer")
+    q, q_dev = _f32(queries, "queries", 2, int(device))
+    b, b_dev = _f32(codebooks, "codebooks", 3, int(device))
+    c, c_dev = _codes(codes, int(device))
+    if not q_dev == b_dev == c_dev:
+        raise TypeError("\"queries\", \"codebooks\" and \"codes\" must be of the same kind")
+    m, ksub, dsub = (int(v) for v in b.shape)
+    n = int(c.shape[0])
+    if not 1 <= m <= 64:
+        raise ValueError("the number of sub-spaces must be in [1, 64]")
+    if not 1 <= dsub <= 64:
+        raise ValueError("the number of features per sub-space must be in [1, 64]")
+    if not 1 <= ksub <= 256:
+        raise ValueError("the number of codewords per sub-space must be in [1, 256]")
+    if int(c.shape[1]) != m:
+        raise ValueError("\"codes\" must have one column per sub-space: (N, %d)" % m)
+    if int(q.shape[1]) != m * dsub:
+        raise ValueError("\"queries\" must have %d columns" % (m * dsub))
+    if not 1 <= n <= 0xFFFFFFFF:
+        raise ValueError("the number of code rows must be in [1, 2^32)")
+    if not 1 <= k <= min(n, 256):
+        raise ValueError("\"k\" must be in [1, min(N, 256)]")
+    nq = int(q.shape[0])
+    if nq > 0xFFFFFFFF:
+        raise ValueError("too many queries")
+    idx = _out((nq, int(k)), numpy.uint32, q_dev, device)
+    dist = _out((nq, int(k)), numpy.float32, q_dev, device)
+    if nq == 0:
+        return idx, dist
+    rc = _lib.lib().kmamd_pq_search(nq, n, m * dsub, m, dsub, ksub, int(k), 0, 0, int(device),
+                                    int(device) if q_dev else -1, int(verbosity), _ptr(q), _ptr(b), _ptr(c),
+                                    _ptr(idx), _ptr(dist))
+    _raise_for(rc, "kmamd_pq_search")
+    return idx, dist
