@@ -764,6 +764,48 @@ int kmamd_pq_search(uint32_t queries_size, uint64_t samples_size, uint32_t featu
                     int32_t device_ptrs, int32_t verbosity, const float *queries, const float *codebooks,
                     const uint8_t *codes, uint32_t *indices, float *distances);
 
+/* IVF-PQ search (beyond the reference): product-quantiser codes of RESIDUALS (row minus its coarse
+ * centroid) kept in cluster lists; a query scans the lists of the clusters it probes only.  Stateless and synchronous;
+ * the caller owns all memory.  L2, fp32 only.
+ *   queries    queries_size (Q) x features_size (D), D == subspaces * sub_features
+ *   centroids  clusters_size (K) x D, the coarse centroids
+ *   codebooks  subspaces (M) x sub_clusters (ksub) x sub_features (dsub), trained on residuals
+ *   codes      list_rows (L) x M uint8, in list order; ids  L uint32, the caller's row id of every list position
+ *   offsets    K + 1 uint32: list c is the positions [offsets[c], offsets[c + 1])
+ *   probes     Q x nprobe uint32, required (kmamd_kmeans_assign_top's output serves).  A query's probe set is the
+ *              distinct entries < K of its row; entries >= K and repeated entries are ignored.
+ *   indices    Q x k uint32 (ids), distances Q x k float: the squared distances, no root taken
+ * The result, to the bit (separate round-to-nearest fp32 operations, no FMA), for query x and probed cluster p:
+ *   r_j      = fl(x_j - centroids[p][j])
+ *   T[m][c]  = sum_j fl(fl(r_{m dsub + j} - codebooks[m][c][j])^2), j ascending from the j = 0 term; +inf for c >= ksub
+ *   d(x,pos) = sum_m T[m][codes[pos][m]], m ascending from the m = 0 term, for every pos of list p
+ *   the k smallest of all probed positions by the unsigned key (bits(d) << 32) | ids[pos], NaN canonical (0x7FC00000:
+ *   behind +inf).  Slots no probed row fills -- all k of a query without a valid probe -- hold index 0xFFFFFFFF and a
+ *   NaN distance.  Launch shape, pair order, query and row chunking and arrival order reach no bit.
+ * Limits: pq_search's M, dsub, ksub and 1 <= k <= 256 (k may exceed the rows a query reaches); 1 <= L <= 2^32 - 2;
+ * 1 <= nprobe <= min(K, 64); Q == 0 is success.  Everything else -- metric != 0, fp16x2 != 0, D != M * dsub, a null
+ * pointer, device_ptrs naming another device -- is InvalidArguments before any device work, with the outputs
+ * untouched.  The contents of offsets, ids, codes and probes are not validated and need not be: list bounds are
+ * clamped into [0, L] (an end before its start is an empty list), a probe >= K is skipped, a code byte >= ksub is
+ * infinitely far; no contents make the kernels read or write out of range.
+ * The queries are chunked inside the call (KMCUDA_AMD_IVFPQ_QUERY_CHUNK: queries per chunk); the index is not.
+ *
+ * kmamd_ivfpq_query_tile: the (query, probe) pairs a scan block serves, 0 where M or k is out of range.
+ * kmamd_ivfpq_row_split: the splits every probed list is cut into for a launch of `pairs` pairs; 0: an argument is 0.
+ * kmamd_ivfpq_residuals: residuals[i][j] = fl(samples[i][j] - centroids[assignments[i]][j]), NaN for a row whose
+ * assignment is >= K: what the codebooks are trained on and the corpus is encoded from.  N < 2^32. */
+uint32_t kmamd_ivfpq_query_tile(uint32_t subspaces, uint32_t k);
+uint32_t kmamd_ivfpq_row_split(uint64_t pairs, uint32_t query_tile, uint64_t list_rows);
+int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t features_size, uint32_t clusters_size,
+                       uint32_t subspaces, uint32_t sub_features, uint32_t sub_clusters, uint32_t k, uint32_t nprobe,
+                       int metric, int32_t fp16x2, int device, int32_t device_ptrs, int32_t verbosity,
+                       const float *queries, const float *centroids, const float *codebooks, const uint8_t *codes,
+                       const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes, uint32_t *indices,
+                       float *distances);
+int kmamd_ivfpq_residuals(uint64_t samples_size, uint32_t features_size, uint32_t clusters_size, int device,
+                          int32_t device_ptrs, int32_t verbosity, const float *samples, const float *centroids,
+                          const uint32_t *assignments, float *residuals);
+
 /* host -> raw device pointer copy on `device` (what python.cc:330-345 does with cudaMemcpy for imported
  * centroids in device-pointer mode; lets a binding without a HIP runtime of its own fill caller-owned memory). */
 int kmamd_copy_to_device(int device, void *dst, const void *host_src, size_t bytes);

@@ -24,6 +24,8 @@ Batched K-means over many small independent problems in one call (beyond the ref
 in place through a row stride): kmeans_batched, kmeans_predict_batched.
 Top-k search over the uint8 product-quantiser codes those calls produce, by asymmetric distance computation (beyond
 the reference): pq_search.
+IVF-PQ (beyond the reference): codes of residuals in cluster lists, probed by the same ADC scan -- ivfpq_train,
+IvfPqIndex (search), ivfpq_search on a caller's own lists.
 """
 from .api import kmeans_cuda, knn_cuda, supports_fp16  # noqa: F401
 from .knn_index import KnnIndex, knn_query, knn_query_radius  # noqa: F401
@@ -32,3 +34,4 @@ from .seed import kmeans_seed_parallel  # noqa: F401
 from .minibatch import MiniBatchKMeans, kmeans_minibatch  # noqa: F401
 from .batched import kmeans_batched, kmeans_predict_batched  # noqa: F401
 from .pq import pq_search  # noqa: F401
+from .ivfpq import IvfPqIndex, ivfpq_search, ivfpq_train  # noqa: F401

@@ -36,6 +36,7 @@ EXPORTS = [
     "kmamd_minibatch_destroy",
     "kmamd_kmeans_batched", "kmamd_kmeans_assign_batched", "kmamd_batched_max_clusters",
     "kmamd_pq_search", "kmamd_pq_query_tile",
+    "kmamd_ivfpq_search", "kmamd_ivfpq_residuals", "kmamd_ivfpq_query_tile", "kmamd_ivfpq_row_split",
     "kmamd_copy_to_device", "kmamd_profile_reset", "kmamd_profile_read", "kmamd_profile_enable", "kmamd_filter_kind", "kmamd_build_arch",
 ]
 
@@ -215,6 +216,15 @@ def lib():
     L.kmamd_pq_search.restype = i32
     L.kmamd_pq_search.argtypes = [u32, ctypes.c_uint64, u32, u32, u32, u32, u32, i32, i32, i32, i32, i32, vp, vp, vp,
                                   vp, vp]
+    L.kmamd_ivfpq_query_tile.restype = u32
+    L.kmamd_ivfpq_query_tile.argtypes = [u32, u32]
+    L.kmamd_ivfpq_row_split.restype = u32
+    L.kmamd_ivfpq_row_split.argtypes = [ctypes.c_uint64, u32, ctypes.c_uint64]
+    L.kmamd_ivfpq_search.restype = i32
+    L.kmamd_ivfpq_search.argtypes = [u32, ctypes.c_uint64, u32, u32, u32, u32, u32, u32, u32, i32, i32, i32, i32, i32,
+                                     vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.kmamd_ivfpq_residuals.restype = i32
+    L.kmamd_ivfpq_residuals.argtypes = [ctypes.c_uint64, u32, u32, i32, i32, i32, vp, vp, vp, vp]
     L.kmamd_copy_to_device.restype = i32
     L.kmamd_copy_to_device.argtypes = [i32, vp, vp, ctypes.c_size_t]
     L.kmamd_build_arch.restype = ctypes.c_char_p

@@ -1,0 +1,165 @@
+// ivfpq_job.cpp -- kmamd_ivfpq_search, kmamd_ivfpq_residuals, kmamd_ivfpq_query_tile and kmamd_ivfpq_row_split of
+// include/kmcuda_amd.h: IVF-PQ search.  The kernels are ivfpq_scan.hip's and pq_scan.hip's merge;
+// nothing here goes through an Engine.
+//
+// The index goes to the device whole.  The queries are cut into chunks whose partial keys stay within kIvfPqPartBytes;
+// per chunk seven launches on one stream -- the pair sort (clear, count, prefix, scatter), the fill of the partial
+// keys, scan, merge -- and no host round trip before the end.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <algorithm>
+
+#include "../../include/kmcuda_amd.h"
+#include "host_job.hpp"
+
+using namespace kmx;
+
+namespace {
+
+constexpr size_t kIvfPqPartBytes = (size_t)512 << 20;   // the partial keys of one query chunk at one row split
+
+// Queries per chunk; KMCUDA_AMD_IVFPQ_QUERY_CHUNK: queries per chunk (the tests force small chunks)
+uint32_t ivfpq_query_chunk(uint32_t nprobe, uint32_t k) {
+  size_t chunk = kIvfPqPartBytes / ((size_t)nprobe * k * sizeof(uint64_t));
+  if (const char *v = getenv("KMCUDA_AMD_IVFPQ_QUERY_CHUNK")) {
+    const long long n = atoll(v);
+    if (n > 0) chunk = (size_t)std::min<long long>(n, 1 << 20);
+  }
+  return (uint32_t)(chunk < 1 ? 1 : chunk);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t kmamd_ivfpq_query_tile(uint32_t subspaces, uint32_t k) { return ivfpq_query_tile(subspaces, k); }
+
+uint32_t kmamd_ivfpq_row_split(uint64_t pairs, uint32_t query_tile, uint64_t list_rows) {
+  return ivfpq_row_split(pairs, query_tile, list_rows);
+}
+
+int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t features_size, uint32_t clusters_size,
+                       uint32_t subspaces, uint32_t sub_features, uint32_t sub_clusters, uint32_t k, uint32_t nprobe,
+                       int metric, int32_t fp16x2, int device, int32_t device_ptrs, int32_t verbosity,
+                       const float *queries, const float *centroids, const float *codebooks, const uint8_t *codes,
+                       const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes, uint32_t *indices,
+                       float *distances) {
+  const uint32_t Q = queries_size, K = clusters_size, M = subspaces, dsub = sub_features, ksub = sub_clusters;
+  const uint64_t L = list_rows;
+  // everything that is refused, before any device work
+  if (M == 0 || M > 64 || dsub == 0 || dsub > 64 || ksub == 0 || ksub > 256) return kmcudaInvalidArguments;
+  if (features_size != M * dsub || metric != 0 || fp16x2 != 0) return kmcudaInvalidArguments;
+  if (L == 0 || L > 0xFFFFFFFEull || k == 0 || k > 256) return kmcudaInvalidArguments;
+  if (K == 0 || nprobe == 0 || nprobe > std::min(K, 64u)) return kmcudaInvalidArguments;
+  if (device < 0 || (device_ptrs >= 0 && device_ptrs != device)) return kmcudaInvalidArguments;
+  if (!centroids || !codebooks || !codes || !ids || !offsets) return kmcudaInvalidArguments;
+  if (Q != 0 && (!queries || !probes || !indices || !distances)) return kmcudaInvalidArguments;
+  if (Q == 0) return kmcudaSuccess;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return kmcudaNoSuchDevice;
+  if (hipSetDevice(device) != hipSuccess) return kmcudaNoSuchDevice;
+  g_verbosity = verbosity;
+  const bool host = device_ptrs < 0;
+  if (!host) (void)hipDeviceSynchronize();   // the caller's writes, as kmamd_kmeans_assign
+
+  DeviceArena w;
+  w.dev = device;
+  w.stream = pooled_stream_acquire(device);
+  if (!w.stream) return kmcudaRuntimeError;
+  const hipStream_t st = w.stream;
+  const float *qry = nullptr;
+  const uint32_t *prb = nullptr;
+  IvfPqGeom g{};
+  KNN_TRY(w.stage_in(queries, (size_t)Q * features_size, device_ptrs, &qry));
+  KNN_TRY(w.stage_in(probes, (size_t)Q * nprobe, device_ptrs, &prb));
+  KNN_TRY(w.stage_in(centroids, (size_t)K * features_size, device_ptrs, &g.centroids));
+  KNN_TRY(w.stage_in(codebooks, (size_t)M * ksub * dsub, device_ptrs, &g.codebooks));
+  KNN_TRY(w.stage_in(codes, (size_t)L * M, device_ptrs, &g.codes));
+  KNN_TRY(w.stage_in(ids, (size_t)L, device_ptrs, &g.ids));
+  KNN_TRY(w.stage_in(offsets, (size_t)K + 1, device_ptrs, &g.offsets));
+  uint32_t *idx = indices;
+  float *dist = distances;
+  if (host) {
+    KNN_TRY(w.alloc(&idx, (size_t)Q * k));
+    KNN_TRY(w.alloc(&dist, (size_t)Q * k));
+  }
+  g.L = L; g.K = K; g.M = M; g.dsub = dsub; g.ksub = ksub; g.k = k; g.nprobe = nprobe;
+  g.QT = ivfpq_query_tile(M, k);
+  g.cap = pq_candidate_cap(k);
+  const uint32_t chunk = std::min(ivfpq_query_chunk(nprobe, k), Q);
+  // the full chunks and the last one differ in their row split: the keys are sized for the larger of the two
+  size_t part_keys = 0;
+  for (uint32_t qc : {chunk, Q % chunk})
+    if (qc != 0)
+      part_keys = std::max(part_keys, (size_t)qc * nprobe * ivfpq_row_split((uint64_t)qc * nprobe, g.QT, L) * k);
+  uint32_t *hist = nullptr, *pair_start = nullptr, *tile_start = nullptr, *cursor = nullptr, *pairs = nullptr;
+  uint64_t *part = nullptr;
+  KNN_TRY(w.alloc(&hist, (size_t)K));
+  KNN_TRY(w.alloc(&pair_start, (size_t)K + 1));
+  KNN_TRY(w.alloc(&tile_start, (size_t)K + 1));
+  KNN_TRY(w.alloc(&cursor, (size_t)K + 1));
+  KNN_TRY(w.alloc(&pairs, (size_t)chunk * nprobe));
+  KNN_TRY(w.alloc(&part, part_keys));
+  for (uint32_t q0 = 0; q0 < Q; q0 += chunk) {
+    const uint32_t qc = std::min(chunk, Q - q0), P = qc * nprobe;
+    g.S = ivfpq_row_split(P, g.QT, L);
+    const uint32_t tiles = (uint32_t)std::min<uint64_t>(P, (uint64_t)(P + g.QT - 1) / g.QT + K);
+    if (verbosity > 1)
+      printf("ivfpq_search: queries [%u, %u), %u pairs, tile %u, at most %u tiles x %u row splits\n", q0, q0 + qc, P,
+             g.QT, tiles, g.S);
+    KMX_HIPRT(launch_ivfpq_group(prb + (size_t)q0 * nprobe, P, nprobe, K, g.QT, hist, pair_start, tile_start, cursor,
+                                 pairs, st));
+    KMX_HIPRT(launch_batched_fill(reinterpret_cast<uint32_t *>(part), (uint64_t)P * g.S * k * 2, ~0u, st));
+    KMX_HIPRT(launch_ivfpq_scan(g, qry + (size_t)q0 * features_size, tiles, pair_start, tile_start, pairs, part, st));
+    KMX_HIPRT(launch_pq_merge(part, qc, nprobe * g.S, k, idx + (size_t)q0 * k, dist + (size_t)q0 * k, st));
+  }
+  if (host) {
+    KMX_HIPCP(hipMemcpyAsync(indices, idx, (size_t)Q * k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KMX_HIPCP(hipMemcpyAsync(distances, dist, (size_t)Q * k * sizeof(float), hipMemcpyDeviceToHost, st));
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    if (verbosity > 0) printf("kmamd_ivfpq_search failed: %s\n", hipGetErrorString(hipGetLastError()));
+    return kmcudaRuntimeError;
+  }
+  return kmcudaSuccess;
+}
+
+int kmamd_ivfpq_residuals(uint64_t samples_size, uint32_t features_size, uint32_t clusters_size, int device,
+                          int32_t device_ptrs, int32_t verbosity, const float *samples, const float *centroids,
+                          const uint32_t *assignments, float *residuals) {
+  const uint64_t N = samples_size;
+  const uint32_t D = features_size, K = clusters_size;
+  if (D == 0 || K == 0 || N > 0xFFFFFFFFull) return kmcudaInvalidArguments;
+  if (device < 0 || (device_ptrs >= 0 && device_ptrs != device)) return kmcudaInvalidArguments;
+  if (!centroids || (N != 0 && (!samples || !assignments || !residuals))) return kmcudaInvalidArguments;
+  if (N == 0) return kmcudaSuccess;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return kmcudaNoSuchDevice;
+  if (hipSetDevice(device) != hipSuccess) return kmcudaNoSuchDevice;
+  g_verbosity = verbosity;
+  const bool host = device_ptrs < 0;
+  if (!host) (void)hipDeviceSynchronize();
+
+  DeviceArena w;
+  w.dev = device;
+  w.stream = pooled_stream_acquire(device);
+  if (!w.stream) return kmcudaRuntimeError;
+  const hipStream_t st = w.stream;
+  const float *x = nullptr, *cen = nullptr;
+  const uint32_t *a = nullptr;
+  KNN_TRY(w.stage_in(samples, (size_t)N * D, device_ptrs, &x));
+  KNN_TRY(w.stage_in(centroids, (size_t)K * D, device_ptrs, &cen));
+  KNN_TRY(w.stage_in(assignments, (size_t)N, device_ptrs, &a));
+  float *out = residuals;
+  if (host) KNN_TRY(w.alloc(&out, (size_t)N * D));
+  KMX_HIPRT(launch_ivfpq_residuals(x, cen, a, N, D, K, out, st));
+  if (host) KMX_HIPCP(hipMemcpyAsync(residuals, out, (size_t)N * D * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    if (verbosity > 0) printf("kmamd_ivfpq_residuals failed: %s\n", hipGetErrorString(hipGetLastError()));
+    return kmcudaRuntimeError;
+  }
+  return kmcudaSuccess;
+}
+
+}  // extern "C"

@@ -428,6 +428,36 @@ hipError_t launch_pq_scan(const PqGeom &g, const float *tables, uint32_t queries
 hipError_t launch_pq_merge(const uint64_t *part, uint32_t queries, uint32_t G, uint32_t k, uint32_t *indices,
                            float *distances, hipStream_t st);
 
+// ivfpq_scan.hip -- IVF-PQ search (kmamd_ivfpq_search, ivfpq_job.cpp).  codes is L x M uint8 in list
+// order, ids[pos] the caller's row id of list position pos, list c the positions [offsets[c], offsets[c + 1]) clamped
+// into [0, L].  A scan block owns up to QT (query, rank) pairs of one cluster and one of S splits of that cluster's list.
+struct IvfPqGeom {
+  const float *centroids, *codebooks;   // K x (M * dsub); M x ksub x dsub
+  const uint8_t *codes;
+  const uint32_t *ids, *offsets;
+  uint64_t L;
+  uint32_t K, M, dsub, ksub, k, nprobe, QT, cap, S;   // QT = ivfpq_query_tile(M, k), cap = pq_candidate_cap(k)
+};
+constexpr uint32_t kIvfPqBlocks = 512;   // the scan grid aims at two blocks per CU
+// pairs per scan block: pq_query_tile's rule with the staged residual sub-vectors (QT x 64 floats) added to the block
+uint32_t ivfpq_query_tile(uint32_t M, uint32_t k);
+size_t ivfpq_scan_lds_bytes(uint32_t M, uint32_t k, uint32_t QT);
+// row splits of every probed list for a launch of `pairs` (query, rank) pairs over L list positions: 1 once
+// ceil(pairs / QT) reaches kIvfPqBlocks, else ceil(kIvfPqBlocks / ceil(pairs / QT)), at most ceil(L / 256) -- no list
+// has more 256-row steps; 0: an argument is 0
+uint32_t ivfpq_row_split(uint64_t pairs, uint32_t QT, uint64_t L);
+// the counting sort of the P = Qc * nprobe pairs by cluster: hist K, pair_start / tile_start / cursor K + 1, pairs P
+hipError_t launch_ivfpq_group(const uint32_t *probes, uint32_t P, uint32_t nprobe, uint32_t K, uint32_t QT,
+                              uint32_t *hist, uint32_t *pair_start, uint32_t *tile_start, uint32_t *cursor,
+                              uint32_t *pairs, hipStream_t st);
+// part[((query * nprobe + rank) * S + split) * k ..): the k smallest keys (bits(d) << 32 | id) of that pair in that
+// split, ascending, ~0 where it has fewer; untouched for dead pairs and empty splits (pre-fill with ~0).  `tiles` is
+// an upper bound of the tile count: min(P, ceil(P / QT) + K)
+hipError_t launch_ivfpq_scan(const IvfPqGeom &g, const float *queries, uint32_t tiles, const uint32_t *pair_start,
+                             const uint32_t *tile_start, const uint32_t *pairs, uint64_t *part, hipStream_t st);
+hipError_t launch_ivfpq_residuals(const float *x, const float *centroids, const uint32_t *a, uint64_t N, uint32_t D,
+                                  uint32_t K, float *out, hipStream_t st);
+
 // yinyang.hip (reference: kmeans.cu:431-672)
 hipError_t launch_yy_init(int metric, const float *xt, uint32_t len, uint32_t D, uint32_t G, const float *centroids,
                           const uint32_t *assignments, const uint32_t *cperm, const uint32_t *gstart, float *bounds,

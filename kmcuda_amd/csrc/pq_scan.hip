@@ -12,7 +12,8 @@
 //              VGPRs (the next step's already in flight).  For every byte ONE LDS
 //              read fetches the QT adjacent entries T[m][code][0..QT) -- ds_read_b128 per four queries -- and feeds QT
 //              independent add chains, m ascending from the m = 0 term.
-//              Selection: per query an LDS buffer of `cap` >= 2k keys (bits(d) << 32 | row, NaN canonical), a count and
+//              Selection (pq_select.hpp, shared with ivfpq_scan.hip):
+//              per query an LDS buffer of `cap` >= 2k keys (bits(d) << 32 | row, NaN canonical), a count and
 //              a threshold key that every lane holds in registers.  A lane appends a key only below the threshold (one
 //              LDS integer atomic per wave and query, by ballot); a buffer that fills is sorted by the block (bitonic),
 //              cut to its k smallest keys and lowers the threshold; lanes that found no room try again against the new
@@ -24,16 +25,13 @@
 #include <math.h>
 
 #include "kernels.hpp"
+#include "pq_select.hpp"
 
 namespace kmx {
 
 namespace {
 
-constexpr int kPqThreads = 256;                  // pq_scan: one row per thread and step, a 256-row tile
-constexpr uint64_t kPqNoKey = ~0ull;             // above every key: bits(d) is at most the canonical NaN's
-constexpr uint32_t kPqNanBits = 0x7FC00000u;
 constexpr uint32_t kPqTableQueries = 64;         // pq_tables: queries per block, a multiple of every query tile
-constexpr uint32_t kPqLdsPerCu = 160u << 10;     // gfx950
 
 __global__ __launch_bounds__(kPqThreads) void pq_tables_kernel(const float *__restrict__ queries, uint32_t Qc,
                                                                const float *__restrict__ codebooks, uint32_t M,
@@ -61,85 +59,11 @@ __global__ __launch_bounds__(kPqThreads) void pq_tables_kernel(const float *__re
   }
 }
 
-// the M code bytes of row `row` (zeros for a lane without a row) into w[0 .. 16): byte m is bits 8 (m % 4) of w[m / 4]
-template <bool VEC>
-__device__ __forceinline__ void pq_load_codes(const uint8_t *__restrict__ codes, uint64_t row, bool have, uint32_t M,
-                                              bool dwords, uint32_t (&w)[16]) {
-#pragma unroll
-  for (int i = 0; i < 16; i++) w[i] = 0;
-  if (!have) return;
-  const uint8_t *p = codes + row * M;
-  if (VEC) {   // M is a multiple of 16 and the matrix 16-byte aligned
-#pragma unroll
-    for (int g = 0; g < 4; g++)
-      if ((uint32_t)g * 16 < M) {
-        const uint4 v = reinterpret_cast<const uint4 *>(p)[g];
-        w[g * 4] = v.x; w[g * 4 + 1] = v.y; w[g * 4 + 2] = v.z; w[g * 4 + 3] = v.w;
-      }
-  } else if (dwords) {   // M a multiple of 4 and the matrix 4-byte aligned
-#pragma unroll
-    for (int i = 0; i < 16; i++)
-      if ((uint32_t)i * 4 < M) w[i] = reinterpret_cast<const uint32_t *>(p)[i];
-  } else {
-#pragma unroll
-    for (int m = 0; m < 64; m++)
-      if ((uint32_t)m < M) w[m / 4] |= (uint32_t)p[m] << (8 * (m % 4));
-  }
-}
-
-template <int QT>
-__device__ __forceinline__ void pq_lookup(const float *__restrict__ e, float (&v)[QT]) {
-  if (QT == 2) {
-    const float2 a = *reinterpret_cast<const float2 *>(e);
-    v[0] = a.x; v[1] = a.y;
-  } else {
-#pragma unroll
-    for (int j = 0; j < QT / 4; j++) {
-      const float4 a = reinterpret_cast<const float4 *>(e)[j];
-      v[j * 4] = a.x; v[j * 4 + 1] = a.y; v[j * 4 + 2] = a.z; v[j * 4 + 3] = a.w;
-    }
-  }
-}
-
-// The block sorts the buffers named in `need` (cnt[q] keys each, the rest padded) and keeps their k smallest keys.
-template <int QT>
-__device__ __forceinline__ void pq_reduce(uint64_t *buf, uint64_t *thr, uint32_t *cnt, uint32_t cap, uint32_t k,
-                                          uint32_t need, uint32_t t) {
-#pragma unroll
-  for (int q = 0; q < QT; q++)
-    if (need >> q & 1u) {
-      const uint32_t n = cnt[q] < cap ? cnt[q] : cap;
-      for (uint32_t j = n + t; j < cap; j += kPqThreads) buf[q * cap + j] = kPqNoKey;
-    }
-  __syncthreads();
-  for (uint32_t size = 2; size <= cap; size <<= 1)
-    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-#pragma unroll
-      for (int q = 0; q < QT; q++)
-        if (need >> q & 1u)
-          for (uint32_t i = t; i < cap / 2; i += kPqThreads) {
-            const uint32_t lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-            const uint64_t a = buf[q * cap + lo], b = buf[q * cap + hi];
-            if ((a > b) == ((lo & size) == 0)) {
-              buf[q * cap + lo] = b;
-              buf[q * cap + hi] = a;
-            }
-          }
-      __syncthreads();
-    }
-  if (t < (uint32_t)QT && (need >> t & 1u)) {
-    const uint32_t n = cnt[t] < cap ? cnt[t] : cap, kept = n < k ? n : k;
-    cnt[t] = kept;
-    thr[t] = kept >= k ? buf[t * cap + k - 1] : kPqNoKey;
-  }
-  __syncthreads();
-}
-
 template <int QT, bool VEC>
 __global__ __launch_bounds__(kPqThreads) void pq_scan_kernel(PqGeom g, const float *__restrict__ tables,
                                                              uint32_t queries, uint64_t *__restrict__ part) {
   extern __shared__ float4 pq_lds4[];
-  const uint32_t M = g.M, k = g.k, cap = g.cap, t = threadIdx.x, lane = t & 63u;
+  const uint32_t M = g.M, k = g.k, cap = g.cap, t = threadIdx.x;
   const uint32_t chunk = blockIdx.x % g.G, tile = blockIdx.x / g.G;
   float *T = reinterpret_cast<float *>(pq_lds4);                          // M x 256 x QT
   uint64_t *buf = reinterpret_cast<uint64_t *>(T + (size_t)QT * M * 256);   // QT x cap
@@ -168,21 +92,7 @@ __global__ __launch_bounds__(kPqThreads) void pq_scan_kernel(PqGeom g, const flo
     pq_load_codes<VEC>(g.codes, next, next < r1, M, dwords, wn);
 
     float acc[QT];
-#pragma unroll
-    for (int grp = 0; grp < 4; grp++)
-      if ((uint32_t)grp * 16 < M) {
-#pragma unroll
-        for (int b = 0; b < 16; b++) {
-          const int m = grp * 16 + b;
-          if (VEC || (uint32_t)m < M) {
-            const uint32_t code = (w[m / 4] >> (8 * (m % 4))) & 0xFFu;
-            float v[QT];
-            pq_lookup<QT>(T + ((size_t)m * 256 + code) * QT, v);
-#pragma unroll
-            for (int q = 0; q < QT; q++) acc[q] = m == 0 ? v[q] : acc[q] + v[q];
-          }
-        }
-      }
+    pq_score<QT, VEC>(T, w, M, acc);
 
     uint64_t key[QT];
     uint32_t todo = 0;
@@ -192,39 +102,7 @@ __global__ __launch_bounds__(kPqThreads) void pq_scan_kernel(PqGeom g, const flo
       key[q] = (uint64_t)bits << 32 | (uint32_t)row;
       if (row < r1 && key[q] < limit[q]) todo |= 1u << q;
     }
-    for (;;) {
-      round++;
-#pragma unroll
-      for (int q = 0; q < QT; q++) {
-        const bool mine = todo >> q & 1u;
-        const uint64_t mask = __ballot(mine);
-        if (mask) {
-          const uint32_t leader = (uint32_t)__ffsll((long long)mask) - 1u, n = (uint32_t)__popcll(mask);
-          uint32_t at = 0;
-          if (lane == leader) at = atomicAdd(cnt + q, n);
-          at = (uint32_t)__shfl((int)at, (int)leader, 64);
-          const uint32_t pos = at + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-          if (mine && pos < cap) {
-            buf[q * cap + pos] = key[q];
-            todo &= ~(1u << q);
-          }
-          if (lane == leader && at + n >= cap) *full = round;
-        }
-      }
-      __syncthreads();
-      // a later round can only write a larger number, and only after every thread has left this one
-      if (*reinterpret_cast<volatile uint32_t *>(full) != round) break;
-      uint32_t need = 0;
-#pragma unroll
-      for (int q = 0; q < QT; q++)
-        if (cnt[q] >= cap) need |= 1u << q;
-      pq_reduce<QT>(buf, thr, cnt, cap, k, need, t);
-#pragma unroll
-      for (int q = 0; q < QT; q++) {
-        limit[q] = thr[q];
-        if (!(key[q] < limit[q])) todo &= ~(1u << q);
-      }
-    }
+    pq_append<QT>(buf, thr, cnt, full, cap, k, t, key, todo, limit, round);
   }
   pq_reduce<QT>(buf, thr, cnt, cap, k, (1u << QT) - 1u, t);
 #pragma unroll

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""IVF-PQ search on device-resident operands against pq_search on the same shape in the same session,
+with recall against an exact torch brute force over the full rows, and the two floors of the probed scan.
+
+    python scripts/ivfpq_bench.py                      # N=1M x 256, K=1024, M=32 x 8, Q=10000 and 100, k=10
+    python scripts/ivfpq_bench.py --rows 100000 --clusters 128 --queries 1000 --repeat 3
+
+Data: a Gaussian mixture of `clusters` components (centres 2 * randn, unit noise); the mixture's centres serve as the
+coarse centroids (no K-means is run: the subject is the search); queries are fresh draws of the mixture.  Codebooks are
+trained on --train-rows rows: on residuals for the index, on the raw rows for pq_search.  Every time is the median
+[min, max] of --repeat runs behind a warm-up, by a host clock around calls that end in a device synchronise.
+`search_ms` is IvfPqIndex.search (kmeans_predict_top + the probed scan), `scan_ms` ivfpq_search with the probes given.
+Floors: Q nprobe (N / K) M table lookups of 4 bytes against the LDS rate (256 CUs x 128 B/clk x 2.4 GHz), and the table
+build's Q nprobe 256 D 3 lane operations against 256 CUs x 64 lanes x 2.4 GHz.  There is no CPU path."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+LDS_BYTES_PER_S = 256 * 128 * 2.4e9
+LANE_OPS_PER_S = 256 * 64 * 2.4e9
+
+
+def _median_ms(fn, repeat, sync):
+    fn()
+    sync()
+    laps = []
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        laps.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(laps), min(laps), max(laps)
+
+
+def exact_topk(queries, rows, k, chunk=256):
+    import torch
+    norms = (rows * rows).sum(1)
+    out = []
+    for q0 in range(0, queries.shape[0], chunk):
+        q = queries[q0:q0 + chunk]
+        out.append(torch.topk(norms[None] - 2 * (q @ rows.T), k, dim=1, largest=False).indices)
+    return torch.cat(out)
+
+
+def recall(found, truth):
+    hit = (found.long()[:, :, None] == truth[:, None, :]).any(2)
+    return float(hit.float().mean())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1000000)
+    ap.add_argument("--features", type=int, default=256)
+    ap.add_argument("--clusters", type=int, default=1024)
+    ap.add_argument("--subspaces", type=int, default=32)
+    ap.add_argument("--queries", default="10000,100")
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--nprobe", default="1,4,16,64")
+    ap.add_argument("--train-rows", type=int, default=100000)
+    ap.add_argument("--repeat", type=int, default=5)
+    args = ap.parse_args()
+    import torch
+    from kmcuda_amd import (IvfPqIndex, ivfpq_search, ivfpq_train, kmeans_batched, kmeans_predict_batched,
+                            kmeans_predict_top, pq_search)
+    from kmcuda_amd.ivfpq import query_tile, row_split
+    if not torch.cuda.is_available():
+        sys.exit("ivfpq_bench needs a GPU")
+    dev = torch.device("cuda", 0)
+    sync = torch.cuda.synchronize
+    n, d, kc, m, k = args.rows, args.features, args.clusters, args.subspaces, args.k
+    gen = torch.Generator(device=dev).manual_seed(1)
+    centres = 2 * torch.randn((kc, d), generator=gen, device=dev)
+
+    def draw(count):
+        labels = torch.randint(0, kc, (count,), generator=gen, device=dev)
+        return centres[labels] + torch.randn((count, d), generator=gen, device=dev)
+    rows = draw(n)
+    train = rows[:args.train_rows].contiguous()
+    t0 = time.perf_counter()
+    books = ivfpq_train(train, centres, m, max_iter=10, seed=1)
+    index = IvfPqIndex(rows, centres, books)
+    sync()
+    build_s = time.perf_counter() - t0
+    raw_books, _, _ = kmeans_batched(train, 256, init="random", layout="columns", problems=m, max_iter=10, seed=1)
+    raw_codes = kmeans_predict_batched(rows, raw_books, layout="columns", dtype="uint8")
+    lens = (index.offsets[1:] - index.offsets[:-1]).long()
+    print(json.dumps({"index": {"N": n, "D": d, "K": kc, "M": m, "dsub": d // m, "train_and_build_s": build_s,
+                                "list_rows": [int(lens.min()), float(lens.float().mean()), int(lens.max())]}}),
+          flush=True)
+    for nq in (int(v) for v in args.queries.split(",")):
+        queries = draw(nq)
+        truth = exact_topk(queries, rows, k)
+        flat = _median_ms(lambda: pq_search(queries, raw_books, raw_codes, k), args.repeat, sync)
+        print(json.dumps({"pq_search": {"Q": nq, "k": k, "ms": flat, "us_per_query": flat[0] * 1e3 / nq,
+                                        "recall": recall(pq_search(queries, raw_books, raw_codes, k)[0], truth)},
+                          "note": "[median, min, max] of %d runs" % args.repeat}), flush=True)
+        for nprobe in (int(v) for v in args.nprobe.split(",")):
+            probes = kmeans_predict_top(queries, centres, nprobe, return_distances=False)
+            whole = _median_ms(lambda: index.search(queries, k, nprobe=nprobe), args.repeat, sync)
+            scan = _median_ms(lambda: ivfpq_search(queries, centres, books, index.codes, index.ids, index.offsets,
+                                                   probes, k), args.repeat, sync)
+            found = index.search(queries, k, nprobe=nprobe)[0]
+            qt = query_tile(m, k)
+            print(json.dumps({
+                "ivfpq": {"Q": nq, "k": k, "nprobe": nprobe, "pair_tile": qt,
+                          "row_split": row_split(nq * nprobe, qt, int(index.codes.shape[0]))},
+                "search_ms": whole, "scan_ms": scan, "scan_us_per_query": scan[0] * 1e3 / nq,
+                "recall": recall(found, truth), "pq_search_over_scan": flat[0] / scan[0],
+                "lds_floor_ms": nq * nprobe * (n / kc) * m * 4 / LDS_BYTES_PER_S * 1e3,
+                "table_build_floor_ms": nq * nprobe * 256 * d * 3 / LANE_OPS_PER_S * 1e3}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
