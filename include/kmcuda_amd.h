@@ -806,6 +806,24 @@ int kmamd_ivfpq_residuals(uint64_t samples_size, uint32_t features_size, uint32_
                           int32_t device_ptrs, int32_t verbosity, const float *samples, const float *centroids,
                           const uint32_t *assignments, float *residuals);
 
+/* Exact re-ranking of per-query candidate lists, the step behind an approximate shortlist (kmamd_ivfpq_search's
+ * indices, for one): queries Q x D and samples N x D float32, candidates Q x R uint32; indices and distances Q x k.
+ * For query q every position j with id = candidates[q][j] < N contributes the key (bits(d) << 32) | id, where
+ *   d = distance(queries[q], samples[id]): the reference's L2 distance (round-down FMA on the difference, the
+ *   inverted-c Kahan fold in ascending feature order, sqrtf) -- the bits kmamd_kmeans_assign's distances and the k-NN
+ *   index's have --, NaN canonical (0x7FC00000: behind +inf), -0 as +0.
+ * Entries >= N -- kmamd_ivfpq_search's 0xFFFFFFFF padding among them -- are ignored; an id listed twice appears twice.
+ * The k smallest keys come back ascending, with the canonical distance; slots no candidate fills hold index
+ * 0xFFFFFFFF and a NaN distance.  Launch shape reaches no bit.
+ * Limits: 1 <= k <= 256, k <= R <= 1024, D >= 1, 1 <= N <= 2^32 - 2; Q == 0 is success.  Everything else --
+ * metric != 0, fp16x2 != 0, a null pointer, device_ptrs naming another device -- is InvalidArguments before any device
+ * work, with the outputs untouched.  Host operands (device_ptrs < 0) are staged whole, `samples` included: the call
+ * is meant for operands that live on the device. */
+int kmamd_knn_rerank(uint32_t queries_size, uint64_t samples_size, uint32_t features_size, uint32_t candidates_size,
+                     uint32_t k, int metric, int32_t fp16x2, int device, int32_t device_ptrs, int32_t verbosity,
+                     const float *queries, const float *samples, const uint32_t *candidates, uint32_t *indices,
+                     float *distances);
+
 /* host -> raw device pointer copy on `device` (what python.cc:330-345 does with cudaMemcpy for imported
  * centroids in device-pointer mode; lets a binding without a HIP runtime of its own fill caller-owned memory). */
 int kmamd_copy_to_device(int device, void *dst, const void *host_src, size_t bytes);

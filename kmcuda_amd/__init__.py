@@ -26,6 +26,8 @@ Top-k search over the uint8 product-quantiser codes those calls produce, by asym
 the reference): pq_search.
 IVF-PQ (beyond the reference): codes of residuals in cluster lists, probed by the same ADC scan -- ivfpq_train,
 IvfPqIndex (search), ivfpq_search on a caller's own lists.
+Exact re-ranking of per-query candidate lists against the raw rows, the step behind such a shortlist (beyond the
+reference): knn_rerank, and IvfPqIndex(keep_rows=True).search(refine=).
 """
 from .api import kmeans_cuda, knn_cuda, supports_fp16  # noqa: F401
 from .knn_index import KnnIndex, knn_query, knn_query_radius  # noqa: F401
@@ -34,4 +36,4 @@ from .seed import kmeans_seed_parallel  # noqa: F401
 from .minibatch import MiniBatchKMeans, kmeans_minibatch  # noqa: F401
 from .batched import kmeans_batched, kmeans_predict_batched  # noqa: F401
 from .pq import pq_search  # noqa: F401
-from .ivfpq import IvfPqIndex, ivfpq_search, ivfpq_train  # noqa: F401
+from .ivfpq import IvfPqIndex, ivfpq_search, ivfpq_train, knn_rerank  # noqa: F401

@@ -458,6 +458,16 @@ hipError_t launch_ivfpq_scan(const IvfPqGeom &g, const float *queries, uint32_t 
 hipError_t launch_ivfpq_residuals(const float *x, const float *centroids, const uint32_t *a, uint64_t N, uint32_t D,
                                   uint32_t K, float *out, hipStream_t st);
 
+// knn_rerank.hip -- exact re-ranking (kmamd_knn_rerank, knn_rerank_job.cpp).  For every query the k
+// smallest keys bits(d) << 32 | id over the entries id < N of its R candidates (1 <= k <= R <= 1024, k <= 256), d the
+// L2 distance as launch_assigned_distances gives it, NaN canonical and -0 as +0; ascending, index 0xFFFFFFFF and a NaN
+// distance in the slots no candidate fills.  One launch.
+uint32_t knn_rerank_query_block(uint32_t R);   // queries per block step: 256 / R, 1 for R > 256
+size_t knn_rerank_lds_bytes(uint32_t R);
+hipError_t launch_knn_rerank(const float *queries, uint32_t Q, const float *rows, uint32_t N, uint32_t D,
+                             const uint32_t *candidates, uint32_t R, uint32_t k, uint32_t *indices, float *distances,
+                             hipStream_t st);
+
 // yinyang.hip (reference: kmeans.cu:431-672)
 hipError_t launch_yy_init(int metric, const float *xt, uint32_t len, uint32_t D, uint32_t G, const float *centroids,
                           const uint32_t *assignments, const uint32_t *cperm, const uint32_t *gstart, float *bounds,

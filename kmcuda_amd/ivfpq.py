@@ -14,6 +14,9 @@ distance sum_m T[m][codes[pos][m]] in ascending m (fp32, no FMA, no root); the k
 uint32) and distance NaN.  Limits as pq_search, 1 <= nprobe <= min(K, 64), at most 2^32 - 2 list positions; L2 and
 float32 only.  numpy in, numpy out (integers uint32); torch tensors on `device` in, torch tensors out (int32); all
 operands must be of the same kind.  Every argument is checked before the device is touched.
+
+knn_rerank (kmamd_knn_rerank; DESIGN.md 4.23) re-ranks such a shortlist against the raw rows by the exact L2 distance;
+IvfPqIndex(..., keep_rows=True).search(..., refine=f) does both: a shortlist of k * f, then the exact k.
 """
 import numpy
 
@@ -192,16 +195,60 @@ def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, 
     return idx, dist
 
 
+def knn_rerank(queries, rows, candidates, k, *, metric="L2", device=0, verbosity=0):
+    """(indices, distances), each (Q, k): the k nearest of every query's own candidates by the exact L2 distance
+    (kmamd_knn_rerank) -- the step behind an approximate shortlist.  `candidates` is (Q, R) row ids of
+    `rows` (N, D), k <= R <= 1024; entries >= N, ivfpq_search's padding among them, are ignored and an id listed twice
+    appears twice.  The distances are kmeans_predict's and KnnIndex.query's bits (NaN behind +inf, -0 as +0); ties go
+    to the smaller id; slots no candidate fills hold index -1 (0xFFFFFFFF in numpy's uint32) and distance NaN.
+    Operand kinds as ivfpq_search.  Host operands are staged whole, `rows` included: keep them on the device."""
+    if _get_metric(metric) != 0:
+        raise ValueError("knn_rerank supports the L2 metric only")
+    device = _device(device)
+    if isinstance(k, bool) or not isinstance(k, (int, numpy.integer)):
+        raise TypeError("\"k\" must be an integer")
+    q, on_dev = _f32(queries, "queries", 2, device)
+    x, x_dev = _f32(rows, "rows", 2, device)
+    nq, d = (int(v) for v in q.shape)
+    n = int(x.shape[0])
+    if d < 1 or int(x.shape[1]) != d:
+        raise ValueError("\"queries\" and \"rows\" must have the same number of features, at least 1")
+    if not 1 <= n <= 0xFFFFFFFE:
+        raise ValueError("the number of rows must be in [1, 2^32 - 2]")
+    if getattr(candidates, "ndim", 0) != 2:
+        raise ValueError("\"candidates\" must be a 2D array, (Q, R)")
+    r = int(candidates.shape[1])
+    if not 1 <= r <= 1024:
+        raise ValueError("the number of candidates per query must be in [1, 1024]")
+    c, c_dev = _u32(candidates, "candidates", (nq, r), device)
+    if not on_dev == x_dev == c_dev:
+        raise TypeError("all operands must be of the same kind")
+    if not 1 <= k <= min(r, 256):
+        raise ValueError("\"k\" must be in [1, min(R, 256)]")
+    if nq > 0xFFFFFFFF:
+        raise ValueError("too many queries")
+    idx = _out((nq, int(k)), numpy.uint32, on_dev, device)
+    dist = _out((nq, int(k)), numpy.float32, on_dev, device)
+    if nq == 0:
+        return idx, dist
+    rc = _lib.lib().kmamd_knn_rerank(nq, n, d, r, int(k), 0, 0, device, device if on_dev else -1, int(verbosity),
+                                     _ptr(q), _ptr(x), _ptr(c), _ptr(idx), _ptr(dist))
+    _raise_for(rc, "kmamd_knn_rerank")
+    return idx, dist
+
+
 class IvfPqIndex:
     """`rows` encoded against `codebooks` (ivfpq_train's) and kept as cluster lists: .codes (L, M) uint8 in list order,
     .ids (L,) the row of every list position, .offsets (K + 1,), beside .centroids and .codebooks.  Lists come from a
     stable sort by assignment (a list's ids ascend); rows with assignment K are left out."""
 
-    def __init__(self, rows, centroids, codebooks, assignments=None, *, metric="L2", device=0, verbosity=0):
+    def __init__(self, rows, centroids, codebooks, assignments=None, *, metric="L2", device=0, verbosity=0,
+                 keep_rows=False):
         if _get_metric(metric) != 0:
             raise ValueError("IVF-PQ supports the L2 metric only")
         self.device, self.verbosity = _device(device), int(verbosity)
         x, c, a, on_dev = _corpus(rows, centroids, assignments, self.device)
+        self.rows = x if keep_rows else None       # the checked array itself, no copy: search(refine=) reads it
         b = _check_books(codebooks, int(x.shape[1]), on_dev, self.device)
         if a is None:
             a = kmeans_predict(x, c, device=self.device, verbosity=verbosity)
@@ -231,9 +278,21 @@ class IvfPqIndex:
             raise ValueError("no row has a cluster")
         self.centroids, self.codebooks, self.codes = c, b, codes[order]
 
-    def search(self, queries, k, nprobe=1, probes=None):
+    def search(self, queries, k, nprobe=1, probes=None, refine=None):
         """(indices, distances) of the k nearest stored rows among the `nprobe` nearest clusters of every query
-        (kmeans_predict_top's ranking), or among the clusters `probes` (Q, nprobe) lists."""
+        (kmeans_predict_top's ranking), or among the clusters `probes` (Q, nprobe) lists.
+        refine: an integer factor >= 1 with k * refine <= 256, on an index built with keep_rows=True: the search runs
+        at k * refine and knn_rerank picks the k nearest of that shortlist against the kept rows.  The distances are
+        then exact L2 distances (kmeans_predict's bits), not ADC sums of squares."""
+        if refine is not None:
+            if isinstance(refine, bool) or not isinstance(refine, (int, numpy.integer)) or refine < 1:
+                raise ValueError("\"refine\" must be an integer >= 1")
+            if not isinstance(k, (int, numpy.integer)) or isinstance(k, bool) or not 1 <= k * refine <= 256:
+                raise ValueError("\"k\" must be an integer >= 1 with k * refine <= 256")
+            if getattr(self, "rows", None) is None:
+                raise ValueError("\"refine\" needs an index built with keep_rows=True")
+            shortlist, _ = self.search(queries, int(k * refine), nprobe, probes)
+            return knn_rerank(queries, self.rows, shortlist, int(k), device=self.device, verbosity=self.verbosity)
         if probes is None:
             q, _ = _f32(queries, "queries", 2, self.device)
             clusters = int(self.centroids.shape[0])
