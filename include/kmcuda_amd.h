@@ -806,6 +806,33 @@ int kmamd_ivfpq_residuals(uint64_t samples_size, uint32_t features_size, uint32_
                           int32_t device_ptrs, int32_t verbosity, const float *samples, const float *centroids,
                           const uint32_t *assignments, float *residuals);
 
+/* IVF-PQ search from precomputed terms (beyond the reference): a method variant of the search above
+ * with its own arithmetic, and so its own bits.  Over a sub-space, with g the probed centroid and y a codeword,
+ * |x - g - y|^2 = |x - g|^2 + (|y|^2 + 2 g.y) - 2 x.y: the second term is a table of the index, the third is built
+ * once per query, and a pair's table entry costs one subtraction.  Separate round-to-nearest fp32 operations, no FMA,
+ * every chain in ascending index from its first term:
+ *   terms[p][m][c] = fl(n + 2 s), n = sum_j fl(y_j y_j), s = sum_j fl(g_{m,j} y_j)   (clusters_size x M x ksub floats)
+ *   B[m][c]  = sum_j fl(x_{m,j} y_j)
+ *   T[m][c]  = fl(terms[p][m][c] - 2 B[m][c]), +inf for c >= ksub
+ *   t1       = sum_{j < D} fl(fl(x_j - g_j)^2), one chain over all D features
+ *   d(x,pos) = fl(t1 + sum_m T[m][codes[pos][m]]), m ascending from the m = 0 term; a result that is negative or -0
+ *              becomes +0 (cancellation can leave one, and the keys compare distance bits as unsigned integers)
+ * Probe set, key, NaN, padding, list bounds, limits, refusals and chunking are kmamd_ivfpq_search's; a null `terms` is
+ * refused like any other null pointer.  `terms` is read as given: other numbers give the sums those numbers define.
+ * A query chunk also keeps its B (M KB per query) within 512 MB, whatever KMCUDA_AMD_IVFPQ_QUERY_CHUNK asks for.
+ * The pair tile of this scan is kmamd_pq_query_tile(M, k): its block stages no residuals.
+ * kmamd_ivfpq_terms fills `terms` for an index; limits and refusals as above (K >= 1, D == M * dsub, no null). */
+int kmamd_ivfpq_terms(uint32_t clusters_size, uint32_t features_size, uint32_t subspaces, uint32_t sub_features,
+                      uint32_t sub_clusters, int device, int32_t device_ptrs, int32_t verbosity,
+                      const float *centroids, const float *codebooks, float *terms);
+int kmamd_ivfpq_search_precomputed(uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
+                                   uint32_t clusters_size, uint32_t subspaces, uint32_t sub_features,
+                                   uint32_t sub_clusters, uint32_t k, uint32_t nprobe, int metric, int32_t fp16x2,
+                                   int device, int32_t device_ptrs, int32_t verbosity, const float *queries,
+                                   const float *centroids, const float *codebooks, const uint8_t *codes,
+                                   const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
+                                   const float *terms, uint32_t *indices, float *distances);
+
 /* Exact re-ranking of per-query candidate lists, the step behind an approximate shortlist (kmamd_ivfpq_search's
  * indices, for one): queries Q x D and samples N x D float32, candidates Q x R uint32; indices and distances Q x k.
  * For query q every position j with id = candidates[q][j] < N contributes the key (bits(d) << 32) | id, where

@@ -25,7 +25,8 @@ in place through a row stride): kmeans_batched, kmeans_predict_batched.
 Top-k search over the uint8 product-quantiser codes those calls produce, by asymmetric distance computation (beyond
 the reference): pq_search.
 IVF-PQ (beyond the reference): codes of residuals in cluster lists, probed by the same ADC scan -- ivfpq_train,
-IvfPqIndex (search), ivfpq_search on a caller's own lists.
+IvfPqIndex (search), ivfpq_search on a caller's own lists.  The precomputed-term variant of that search (its own
+bits, opt-in): ivfpq_terms, ivfpq_search(terms=), IvfPqIndex(precomputed=True).
 Exact re-ranking of per-query candidate lists against the raw rows, the step behind such a shortlist (beyond the
 reference): knn_rerank, and IvfPqIndex(keep_rows=True).search(refine=).
 """
@@ -36,4 +37,4 @@ from .seed import kmeans_seed_parallel  # noqa: F401
 from .minibatch import MiniBatchKMeans, kmeans_minibatch  # noqa: F401
 from .batched import kmeans_batched, kmeans_predict_batched  # noqa: F401
 from .pq import pq_search  # noqa: F401
-from .ivfpq import IvfPqIndex, ivfpq_search, ivfpq_train, knn_rerank  # noqa: F401
+from .ivfpq import IvfPqIndex, ivfpq_search, ivfpq_terms, ivfpq_train, knn_rerank  # noqa: F401

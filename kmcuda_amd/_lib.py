@@ -37,6 +37,7 @@ EXPORTS = [
     "kmamd_kmeans_batched", "kmamd_kmeans_assign_batched", "kmamd_batched_max_clusters",
     "kmamd_pq_search", "kmamd_pq_query_tile",
     "kmamd_ivfpq_search", "kmamd_ivfpq_residuals", "kmamd_ivfpq_query_tile", "kmamd_ivfpq_row_split",
+    "kmamd_ivfpq_terms", "kmamd_ivfpq_search_precomputed",
     "kmamd_knn_rerank",
     "kmamd_copy_to_device", "kmamd_profile_reset", "kmamd_profile_read", "kmamd_profile_enable", "kmamd_filter_kind", "kmamd_build_arch",
 ]
@@ -224,6 +225,10 @@ def lib():
     L.kmamd_ivfpq_search.restype = i32
     L.kmamd_ivfpq_search.argtypes = [u32, ctypes.c_uint64, u32, u32, u32, u32, u32, u32, u32, i32, i32, i32, i32, i32,
                                      vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.kmamd_ivfpq_search_precomputed.restype = i32     # kmamd_ivfpq_search's arguments with `terms` before the outputs
+    L.kmamd_ivfpq_search_precomputed.argtypes = L.kmamd_ivfpq_search.argtypes + [vp]
+    L.kmamd_ivfpq_terms.restype = i32
+    L.kmamd_ivfpq_terms.argtypes = [u32, u32, u32, u32, u32, i32, i32, i32, vp, vp, vp]
     L.kmamd_ivfpq_residuals.restype = i32
     L.kmamd_ivfpq_residuals.argtypes = [ctypes.c_uint64, u32, u32, i32, i32, i32, vp, vp, vp, vp]
     L.kmamd_knn_rerank.restype = i32

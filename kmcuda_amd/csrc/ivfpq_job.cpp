@@ -1,10 +1,11 @@
-// ivfpq_job.cpp -- kmamd_ivfpq_search, kmamd_ivfpq_residuals, kmamd_ivfpq_query_tile and kmamd_ivfpq_row_split of
-// include/kmcuda_amd.h: IVF-PQ search.  The kernels are ivfpq_scan.hip's and pq_scan.hip's merge;
-// nothing here goes through an Engine.
+// ivfpq_job.cpp -- kmamd_ivfpq_search, kmamd_ivfpq_search_precomputed, kmamd_ivfpq_terms, kmamd_ivfpq_residuals,
+// kmamd_ivfpq_query_tile and kmamd_ivfpq_row_split of include/kmcuda_amd.h: IVF-PQ search.  The
+// kernels are ivfpq_scan.hip's and pq_scan.hip's merge; nothing here goes through an Engine.
 //
 // The index goes to the device whole.  The queries are cut into chunks whose partial keys stay within kIvfPqPartBytes;
 // per chunk seven launches on one stream -- the pair sort (clear, count, prefix, scatter), the fill of the partial
-// keys, scan, merge -- and no host round trip before the end.
+// keys, scan, merge -- and no host round trip before the end.  The precomputed search adds two launches per chunk, the
+// chunk's query terms and pair norms, and keeps the query terms within kIvfPqPartBytes as well.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -19,32 +20,26 @@ namespace {
 
 constexpr size_t kIvfPqPartBytes = (size_t)512 << 20;   // the partial keys of one query chunk at one row split
 
-// Queries per chunk; KMCUDA_AMD_IVFPQ_QUERY_CHUNK: queries per chunk (the tests force small chunks)
-uint32_t ivfpq_query_chunk(uint32_t nprobe, uint32_t k) {
+// Queries per chunk; KMCUDA_AMD_IVFPQ_QUERY_CHUNK: queries per chunk (the tests force small chunks).  qterm_subspaces:
+// M where the chunk's query terms (M KB per query) are held as well -- a bound the override does not lift, because the
+// scan indexes them in 32 bits --, else 0
+uint32_t ivfpq_query_chunk(uint32_t nprobe, uint32_t k, uint32_t qterm_subspaces) {
   size_t chunk = kIvfPqPartBytes / ((size_t)nprobe * k * sizeof(uint64_t));
   if (const char *v = getenv("KMCUDA_AMD_IVFPQ_QUERY_CHUNK")) {
     const long long n = atoll(v);
     if (n > 0) chunk = (size_t)std::min<long long>(n, 1 << 20);
   }
+  if (qterm_subspaces) chunk = std::min(chunk, kIvfPqPartBytes / ((size_t)qterm_subspaces * 256 * sizeof(float)));
   return (uint32_t)(chunk < 1 ? 1 : chunk);
 }
 
-}  // namespace
-
-extern "C" {
-
-uint32_t kmamd_ivfpq_query_tile(uint32_t subspaces, uint32_t k) { return ivfpq_query_tile(subspaces, k); }
-
-uint32_t kmamd_ivfpq_row_split(uint64_t pairs, uint32_t query_tile, uint64_t list_rows) {
-  return ivfpq_row_split(pairs, query_tile, list_rows);
-}
-
-int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t features_size, uint32_t clusters_size,
-                       uint32_t subspaces, uint32_t sub_features, uint32_t sub_clusters, uint32_t k, uint32_t nprobe,
-                       int metric, int32_t fp16x2, int device, int32_t device_ptrs, int32_t verbosity,
-                       const float *queries, const float *centroids, const float *codebooks, const uint8_t *codes,
-                       const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes, uint32_t *indices,
-                       float *distances) {
+// Both searches: with `precomputed` the tables come from `terms`, else from the residuals (4.22).
+int ivfpq_search_job(bool precomputed, uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
+                     uint32_t clusters_size, uint32_t subspaces, uint32_t sub_features, uint32_t sub_clusters,
+                     uint32_t k, uint32_t nprobe, int metric, int32_t fp16x2, int device, int32_t device_ptrs,
+                     int32_t verbosity, const float *queries, const float *centroids, const float *codebooks,
+                     const uint8_t *codes, const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
+                     const float *terms, uint32_t *indices, float *distances) {
   const uint32_t Q = queries_size, K = clusters_size, M = subspaces, dsub = sub_features, ksub = sub_clusters;
   const uint64_t L = list_rows;
   // everything that is refused, before any device work
@@ -53,7 +48,7 @@ int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t featu
   if (L == 0 || L > 0xFFFFFFFEull || k == 0 || k > 256) return kmcudaInvalidArguments;
   if (K == 0 || nprobe == 0 || nprobe > std::min(K, 64u)) return kmcudaInvalidArguments;
   if (device < 0 || (device_ptrs >= 0 && device_ptrs != device)) return kmcudaInvalidArguments;
-  if (!centroids || !codebooks || !codes || !ids || !offsets) return kmcudaInvalidArguments;
+  if (!centroids || !codebooks || !codes || !ids || !offsets || (precomputed && !terms)) return kmcudaInvalidArguments;
   if (Q != 0 && (!queries || !probes || !indices || !distances)) return kmcudaInvalidArguments;
   if (Q == 0) return kmcudaSuccess;
   int ndev = 0;
@@ -78,6 +73,8 @@ int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t featu
   KNN_TRY(w.stage_in(codes, (size_t)L * M, device_ptrs, &g.codes));
   KNN_TRY(w.stage_in(ids, (size_t)L, device_ptrs, &g.ids));
   KNN_TRY(w.stage_in(offsets, (size_t)K + 1, device_ptrs, &g.offsets));
+  const float *trm = nullptr;
+  if (precomputed) KNN_TRY(w.stage_in(terms, (size_t)K * M * ksub, device_ptrs, &trm));
   uint32_t *idx = indices;
   float *dist = distances;
   if (host) {
@@ -85,9 +82,9 @@ int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t featu
     KNN_TRY(w.alloc(&dist, (size_t)Q * k));
   }
   g.L = L; g.K = K; g.M = M; g.dsub = dsub; g.ksub = ksub; g.k = k; g.nprobe = nprobe;
-  g.QT = ivfpq_query_tile(M, k);
+  g.QT = precomputed ? pq_query_tile(M, k) : ivfpq_query_tile(M, k);   // no staging tile in the precomputed block
   g.cap = pq_candidate_cap(k);
-  const uint32_t chunk = std::min(ivfpq_query_chunk(nprobe, k), Q);
+  const uint32_t chunk = std::min(ivfpq_query_chunk(nprobe, k, precomputed ? M : 0), Q);
   // the full chunks and the last one differ in their row split: the keys are sized for the larger of the two
   size_t part_keys = 0;
   for (uint32_t qc : {chunk, Q % chunk})
@@ -101,17 +98,30 @@ int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t featu
   KNN_TRY(w.alloc(&cursor, (size_t)K + 1));
   KNN_TRY(w.alloc(&pairs, (size_t)chunk * nprobe));
   KNN_TRY(w.alloc(&part, part_keys));
+  float *qterms = nullptr, *norms = nullptr;
+  if (precomputed) {
+    KNN_TRY(w.alloc(&qterms, (size_t)chunk * M * 256));
+    KNN_TRY(w.alloc(&norms, (size_t)chunk * nprobe));
+  }
   for (uint32_t q0 = 0; q0 < Q; q0 += chunk) {
     const uint32_t qc = std::min(chunk, Q - q0), P = qc * nprobe;
     g.S = ivfpq_row_split(P, g.QT, L);
     const uint32_t tiles = (uint32_t)std::min<uint64_t>(P, (uint64_t)(P + g.QT - 1) / g.QT + K);
     if (verbosity > 1)
-      printf("ivfpq_search: queries [%u, %u), %u pairs, tile %u, at most %u tiles x %u row splits\n", q0, q0 + qc, P,
-             g.QT, tiles, g.S);
+      printf("ivfpq_search%s: queries [%u, %u), %u pairs, tile %u, at most %u tiles x %u row splits\n",
+             precomputed ? " (precomputed)" : "", q0, q0 + qc, P, g.QT, tiles, g.S);
     KMX_HIPRT(launch_ivfpq_group(prb + (size_t)q0 * nprobe, P, nprobe, K, g.QT, hist, pair_start, tile_start, cursor,
                                  pairs, st));
     KMX_HIPRT(launch_batched_fill(reinterpret_cast<uint32_t *>(part), (uint64_t)P * g.S * k * 2, ~0u, st));
-    KMX_HIPRT(launch_ivfpq_scan(g, qry + (size_t)q0 * features_size, tiles, pair_start, tile_start, pairs, part, st));
+    const float *qc_rows = qry + (size_t)q0 * features_size;
+    const uint32_t *qc_probes = prb + (size_t)q0 * nprobe;
+    if (precomputed) {
+      KMX_HIPRT(launch_ivfpq_query_terms(qc_rows, qc, g.codebooks, M, dsub, ksub, qterms, st));
+      KMX_HIPRT(launch_ivfpq_pair_norms(qc_rows, g.centroids, qc_probes, P, nprobe, K, features_size, norms, st));
+      KMX_HIPRT(launch_ivfpq_scan_pre(g, trm, qterms, norms, tiles, pair_start, tile_start, pairs, part, st));
+    } else {
+      KMX_HIPRT(launch_ivfpq_scan(g, qc_rows, tiles, pair_start, tile_start, pairs, part, st));
+    }
     KMX_HIPRT(launch_pq_merge(part, qc, nprobe * g.S, k, idx + (size_t)q0 * k, dist + (size_t)q0 * k, st));
   }
   if (host) {
@@ -120,6 +130,74 @@ int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t featu
   }
   if (hipStreamSynchronize(st) != hipSuccess) {
     if (verbosity > 0) printf("kmamd_ivfpq_search failed: %s\n", hipGetErrorString(hipGetLastError()));
+    return kmcudaRuntimeError;
+  }
+  return kmcudaSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t kmamd_ivfpq_query_tile(uint32_t subspaces, uint32_t k) { return ivfpq_query_tile(subspaces, k); }
+
+uint32_t kmamd_ivfpq_row_split(uint64_t pairs, uint32_t query_tile, uint64_t list_rows) {
+  return ivfpq_row_split(pairs, query_tile, list_rows);
+}
+
+int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t features_size, uint32_t clusters_size,
+                       uint32_t subspaces, uint32_t sub_features, uint32_t sub_clusters, uint32_t k, uint32_t nprobe,
+                       int metric, int32_t fp16x2, int device, int32_t device_ptrs, int32_t verbosity,
+                       const float *queries, const float *centroids, const float *codebooks, const uint8_t *codes,
+                       const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes, uint32_t *indices,
+                       float *distances) {
+  return ivfpq_search_job(false, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
+                          sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity, queries, centroids,
+                          codebooks, codes, ids, offsets, probes, nullptr, indices, distances);
+}
+
+int kmamd_ivfpq_search_precomputed(uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
+                                   uint32_t clusters_size, uint32_t subspaces, uint32_t sub_features,
+                                   uint32_t sub_clusters, uint32_t k, uint32_t nprobe, int metric, int32_t fp16x2,
+                                   int device, int32_t device_ptrs, int32_t verbosity, const float *queries,
+                                   const float *centroids, const float *codebooks, const uint8_t *codes,
+                                   const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
+                                   const float *terms, uint32_t *indices, float *distances) {
+  return ivfpq_search_job(true, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
+                          sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity, queries, centroids,
+                          codebooks, codes, ids, offsets, probes, terms, indices, distances);
+}
+
+int kmamd_ivfpq_terms(uint32_t clusters_size, uint32_t features_size, uint32_t subspaces, uint32_t sub_features,
+                      uint32_t sub_clusters, int device, int32_t device_ptrs, int32_t verbosity,
+                      const float *centroids, const float *codebooks, float *terms) {
+  const uint32_t K = clusters_size, M = subspaces, dsub = sub_features, ksub = sub_clusters;
+  if (M == 0 || M > 64 || dsub == 0 || dsub > 64 || ksub == 0 || ksub > 256) return kmcudaInvalidArguments;
+  if (features_size != M * dsub || K == 0) return kmcudaInvalidArguments;
+  if (device < 0 || (device_ptrs >= 0 && device_ptrs != device)) return kmcudaInvalidArguments;
+  if (!centroids || !codebooks || !terms) return kmcudaInvalidArguments;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return kmcudaNoSuchDevice;
+  if (hipSetDevice(device) != hipSuccess) return kmcudaNoSuchDevice;
+  g_verbosity = verbosity;
+  const bool host = device_ptrs < 0;
+  if (!host) (void)hipDeviceSynchronize();
+
+  DeviceArena w;
+  w.dev = device;
+  w.stream = pooled_stream_acquire(device);
+  if (!w.stream) return kmcudaRuntimeError;
+  const hipStream_t st = w.stream;
+  const float *cen = nullptr, *books = nullptr;
+  const size_t count = (size_t)K * M * ksub;
+  KNN_TRY(w.stage_in(centroids, (size_t)K * features_size, device_ptrs, &cen));
+  KNN_TRY(w.stage_in(codebooks, (size_t)M * ksub * dsub, device_ptrs, &books));
+  float *out = terms;
+  if (host) KNN_TRY(w.alloc(&out, count));
+  KMX_HIPRT(launch_ivfpq_terms(cen, books, K, M, dsub, ksub, out, st));
+  if (host) KMX_HIPCP(hipMemcpyAsync(terms, out, count * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    if (verbosity > 0) printf("kmamd_ivfpq_terms failed: %s\n", hipGetErrorString(hipGetLastError()));
     return kmcudaRuntimeError;
   }
   return kmcudaSuccess;

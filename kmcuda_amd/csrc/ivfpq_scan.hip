@@ -25,6 +25,21 @@
 //              is what dead pairs and splits past a list's end leave behind.  launch_pq_merge reduces them per query.
 //   ivfpq_residuals   out[i][j] = fl(x[i][j] - centroids[a[i]][j]), NaN where a[i] >= K: what the codebooks are trained
 //              on and the corpus is encoded from.
+//
+// The precomputed-term variant (kmamd_ivfpq_search_precomputed) splits a pair's table entry
+// |x - g - y|^2 over a sub-space into |x - g|^2 + (|y|^2 + 2 g.y) - 2 x.y, with arithmetic -- and bits -- of its own:
+//   ivfpq_terms        once per index: A[cluster][m][c] = fl(n + 2 s), n = sum_j fl(y_j y_j), s = sum_j fl(g_j y_j).
+//              grid = (sub-space, group of 64 clusters); the codeword panel in LDS at stride dsub | 1, the group's
+//              centroid sub-vectors beside it (broadcast reads); thread c owns codeword c, one entry per cluster.
+//   ivfpq_query_terms  once per query chunk: B[query][m][256], B = sum_j fl(x_j y_j): pq_tables' grid and panel with
+//              a product in place of a squared difference; a pair's sub-space is one 1 KB line.  Columns >= ksub are
+//              not written and never read.
+//   ivfpq_pair_norms   one thread per pair: t1 = sum_{j < D} fl(fl(x_j - g_j)^2) of the live pairs.
+//   ivfpq_scan_pre     ivfpq_scan with another prologue: no staging tile and no barrier per sub-space.  Thread c
+//              loads A[cluster][m][c] and the QT values B[query of slot q][m][c] of 16 / QT sub-spaces at a time, the
+//              next group's loads issued before this group's entries T = fl(A - 2 B) go to LDS with the same wide
+//              store; one barrier, then the same stream.  Behind pq_score a lane adds its slot's t1 (in registers) and
+//              turns a result that is negative or -0 into +0 before the key is formed.
 #include <float.h>
 #include <math.h>
 
@@ -163,12 +178,82 @@ __device__ __forceinline__ void ivfpq_build_tables(const IvfPqGeom &g, const flo
   }
 }
 
-template <int QT, bool VEC>
-__global__ __launch_bounds__(kPqThreads) void ivfpq_scan_kernel(IvfPqGeom g, const float *__restrict__ queries,
-                                                                const uint32_t *__restrict__ pair_start,
-                                                                const uint32_t *__restrict__ tile_start,
-                                                                const uint32_t *__restrict__ pairs,
-                                                                uint64_t *__restrict__ part) {
+constexpr int kIvfPqPreLoads = 16;   // B values a thread keeps in flight per group of the precomputed prologue
+
+// The tables of the block's pairs from precomputed terms: T[m][code][q] = fl(A[m][code] - 2 B[query of q][m][code]),
+// +inf for code >= ksub and for a slot without a pair.  a_row: the cluster's M x ksub terms; t1[q]: the slot's norm.
+// B is indexed in 32 bits: the host keeps a chunk's B within 2^27 floats.  One barrier, at the end.
+template <int QT>
+__device__ __forceinline__ void ivfpq_fill_tables(const IvfPqGeom &g, const float *__restrict__ a_row,
+                                                  const float *__restrict__ qterms, const float *__restrict__ norms,
+                                                  const uint32_t *pid, uint32_t live, float *T, uint32_t t,
+                                                  float (&t1)[QT]) {
+  constexpr int G = kIvfPqPreLoads / QT;
+  const uint32_t M = g.M, ksub = g.ksub;
+  const bool col = t < ksub;
+  uint32_t at[QT];   // B's index of (query of slot q, m = 0, column t)
+#pragma unroll
+  for (int q = 0; q < QT; q++) {
+    const bool have = (uint32_t)q < live;
+    const uint32_t pair = have ? pid[q] : 0u;
+    at[q] = have ? (pair / g.nprobe * M) * 256u + t : 0u;
+    t1[q] = have ? norms[pair] : 0.0f;
+  }
+  float a[G], b[G][QT], an[G], bn[G][QT];
+  auto load = [&](uint32_t m0, float (&av)[G], float (&bv)[G][QT]) {
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+      const uint32_t m = m0 + i;
+      av[i] = 0.0f;
+#pragma unroll
+      for (int q = 0; q < QT; q++) bv[i][q] = 0.0f;
+      if (col && m < M) {
+        av[i] = a_row[m * ksub + t];
+#pragma unroll
+        for (int q = 0; q < QT; q++)
+          if ((uint32_t)q < live) bv[i][q] = qterms[at[q] + m * 256u];
+      }
+    }
+  };
+  load(0, an, bn);
+  for (uint32_t m0 = 0; m0 < M; m0 += G) {
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+      a[i] = an[i];
+#pragma unroll
+      for (int q = 0; q < QT; q++) b[i][q] = bn[i][q];
+    }
+    load(m0 + G, an, bn);   // in flight over this group's stores
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+      const uint32_t m = m0 + i;
+      if (m < M) {
+        float e[QT];
+#pragma unroll
+        for (int q = 0; q < QT; q++) e[q] = col && (uint32_t)q < live ? a[i] - 2.0f * b[i][q] : INFINITY;
+        float *dst = T + ((size_t)m * 256 + t) * QT;
+        if (QT == 2) {
+          *reinterpret_cast<float2 *>(dst) = make_float2(e[0], e[1]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < QT / 4; j++)
+            reinterpret_cast<float4 *>(dst)[j] = make_float4(e[j * 4], e[j * 4 + 1], e[j * 4 + 2], e[j * 4 + 3]);
+        }
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// One scan block.  PRE: the tables come from precomputed terms (terms, qterms, norms; `queries` unused), the block has
+// no staging tile and a lane adds its slot's norm to the score; else they are built from `queries` and the centroid.
+template <int QT, bool VEC, bool PRE>
+__device__ __forceinline__ void ivfpq_scan_block(const IvfPqGeom &g, const float *__restrict__ queries,
+                                                 const float *__restrict__ terms, const float *__restrict__ qterms,
+                                                 const float *__restrict__ norms,
+                                                 const uint32_t *__restrict__ pair_start,
+                                                 const uint32_t *__restrict__ tile_start,
+                                                 const uint32_t *__restrict__ pairs, uint64_t *__restrict__ part) {
   extern __shared__ float4 ivfpq_lds4[];
   const uint32_t M = g.M, k = g.k, cap = g.cap, K = g.K, t = threadIdx.x;
   const uint32_t split = blockIdx.x % g.S, tile = blockIdx.x / g.S;
@@ -190,8 +275,8 @@ __global__ __launch_bounds__(kPqThreads) void ivfpq_scan_kernel(IvfPqGeom g, con
   const uint32_t live = left < (uint32_t)QT ? left : (uint32_t)QT;
 
   float *T = reinterpret_cast<float *>(ivfpq_lds4);                          // M x 256 x QT
-  float *stage = T + (size_t)QT * M * 256;                                   // QT x 64
-  uint64_t *buf = reinterpret_cast<uint64_t *>(stage + QT * kIvfPqStage);    // QT x cap
+  float *stage = T + (size_t)QT * M * 256;                                   // QT x 64; none with PRE
+  uint64_t *buf = reinterpret_cast<uint64_t *>(stage + (PRE ? 0 : QT * kIvfPqStage));   // QT x cap
   uint64_t *thr = buf + (size_t)QT * cap;                                    // QT
   uint32_t *cnt = reinterpret_cast<uint32_t *>(thr + QT);                    // QT
   uint32_t *pid = cnt + QT;                                                  // QT
@@ -203,7 +288,11 @@ __global__ __launch_bounds__(kPqThreads) void ivfpq_scan_kernel(IvfPqGeom g, con
   }
   if (t == 0) *full = 0;
   __syncthreads();
-  ivfpq_build_tables<QT>(g, queries, g.centroids + (size_t)c * M * g.dsub, pid, stage, T, t);
+  float t1[PRE ? QT : 1];   // the norms of the block's pairs
+  if constexpr (PRE)
+    ivfpq_fill_tables<QT>(g, terms + (size_t)c * M * g.ksub, qterms, norms, pid, live, T, t, t1);
+  else
+    ivfpq_build_tables<QT>(g, queries, g.centroids + (size_t)c * M * g.dsub, pid, stage, T, t);
 
   const bool dwords = (M & 3u) == 0 && (reinterpret_cast<uintptr_t>(g.codes) & 3u) == 0;
   uint64_t limit[QT];   // every lane's copy of thr[]
@@ -227,6 +316,10 @@ __global__ __launch_bounds__(kPqThreads) void ivfpq_scan_kernel(IvfPqGeom g, con
     uint32_t todo = 0;
 #pragma unroll
     for (int q = 0; q < QT; q++) {
+      if constexpr (PRE) {
+        const float d = t1[q] + acc[q];
+        acc[q] = d <= 0.0f ? 0.0f : d;   // cancellation can leave a negative sum: the keys compare bits unsigned
+      }
       const uint32_t bits = acc[q] != acc[q] ? kPqNanBits : __float_as_uint(acc[q]);
       key[q] = (uint64_t)bits << 32 | id;
       if (row < r1 && (uint32_t)q < live && key[q] < limit[q]) todo |= 1u << q;
@@ -240,6 +333,26 @@ __global__ __launch_bounds__(kPqThreads) void ivfpq_scan_kernel(IvfPqGeom g, con
       part[((size_t)pid[q] * g.S + split) * k + t] = t < cnt[q] ? buf[q * cap + t] : kPqNoKey;
 }
 
+template <int QT, bool VEC>
+__global__ __launch_bounds__(kPqThreads) void ivfpq_scan_kernel(IvfPqGeom g, const float *__restrict__ queries,
+                                                                const uint32_t *__restrict__ pair_start,
+                                                                const uint32_t *__restrict__ tile_start,
+                                                                const uint32_t *__restrict__ pairs,
+                                                                uint64_t *__restrict__ part) {
+  ivfpq_scan_block<QT, VEC, false>(g, queries, nullptr, nullptr, nullptr, pair_start, tile_start, pairs, part);
+}
+
+template <int QT, bool VEC>
+__global__ __launch_bounds__(kPqThreads) void ivfpq_scan_pre_kernel(IvfPqGeom g, const float *__restrict__ terms,
+                                                                    const float *__restrict__ qterms,
+                                                                    const float *__restrict__ norms,
+                                                                    const uint32_t *__restrict__ pair_start,
+                                                                    const uint32_t *__restrict__ tile_start,
+                                                                    const uint32_t *__restrict__ pairs,
+                                                                    uint64_t *__restrict__ part) {
+  ivfpq_scan_block<QT, VEC, true>(g, nullptr, terms, qterms, norms, pair_start, tile_start, pairs, part);
+}
+
 __global__ __launch_bounds__(kPqThreads) void ivfpq_residuals_kernel(const float *__restrict__ x,
                                                                      const float *__restrict__ centroids,
                                                                      const uint32_t *__restrict__ a, uint64_t N,
@@ -251,6 +364,103 @@ __global__ __launch_bounds__(kPqThreads) void ivfpq_residuals_kernel(const float
     const uint32_t j = (uint32_t)(at - i * D), c = a[i];
     out[at] = c < K ? x[at] - centroids[(size_t)c * D + j] : NAN;
   }
+}
+
+constexpr uint32_t kIvfPqTermGroup = 64;   // clusters (ivfpq_terms) or queries (ivfpq_query_terms) of one block round
+
+// the codeword panel of sub-space m into LDS, row stride dsub | 1: no bank conflict at any dsub
+__device__ __forceinline__ void ivfpq_stage_panel(const float *__restrict__ codebooks, uint32_t m, uint32_t dsub,
+                                                  uint32_t ksub, float *panel) {
+  const float *book = codebooks + (size_t)m * ksub * dsub;
+  const uint32_t ld = dsub | 1u;
+  for (uint32_t i = threadIdx.x; i < ksub * dsub; i += kPqThreads) panel[(i / dsub) * ld + i % dsub] = book[i];
+}
+
+// sum_j fl(x_j y_j), j ascending from the j = 0 term
+__device__ __forceinline__ float ivfpq_dot(const float *x, const float *y, uint32_t dsub) {
+  float s = x[0] * y[0];
+  for (uint32_t j = 1; j < dsub; j++) s = s + x[j] * y[j];
+  return s;
+}
+
+__global__ __launch_bounds__(kPqThreads) void ivfpq_terms_kernel(const float *__restrict__ centroids,
+                                                                 const float *__restrict__ codebooks, uint32_t K,
+                                                                 uint32_t M, uint32_t dsub, uint32_t ksub,
+                                                                 float *__restrict__ terms) {
+  extern __shared__ float ivfpq_panel[];   // ksub x (dsub | 1), then kIvfPqTermGroup x dsub centroid sub-vectors
+  const uint32_t m = blockIdx.x, c = threadIdx.x, ld = dsub | 1u;
+  float *cen = ivfpq_panel + ksub * ld;
+  ivfpq_stage_panel(codebooks, m, dsub, ksub, ivfpq_panel);
+  __syncthreads();
+  const float *y = ivfpq_panel + (c < ksub ? c : 0u) * ld;
+  const float n = ivfpq_dot(y, y, dsub);
+  for (uint64_t p0 = (uint64_t)blockIdx.y * kIvfPqTermGroup; p0 < K; p0 += (uint64_t)gridDim.y * kIvfPqTermGroup) {
+    const uint32_t pn = K - p0 < kIvfPqTermGroup ? (uint32_t)(K - p0) : kIvfPqTermGroup;
+    for (uint32_t i = c; i < pn * dsub; i += kPqThreads)
+      cen[i] = centroids[(size_t)(p0 + i / dsub) * M * dsub + m * dsub + i % dsub];
+    __syncthreads();
+    if (c < ksub)
+      for (uint32_t p = 0; p < pn; p++)
+        terms[((size_t)(p0 + p) * M + m) * ksub + c] = n + 2.0f * ivfpq_dot(cen + p * dsub, y, dsub);
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kPqThreads) void ivfpq_query_terms_kernel(const float *__restrict__ queries, uint32_t Qc,
+                                                                       const float *__restrict__ codebooks, uint32_t M,
+                                                                       uint32_t dsub, uint32_t ksub,
+                                                                       float *__restrict__ qterms) {
+  extern __shared__ float ivfpq_panel[];   // ksub x (dsub | 1)
+  const uint32_t m = blockIdx.x, c = threadIdx.x;
+  ivfpq_stage_panel(codebooks, m, dsub, ksub, ivfpq_panel);
+  __syncthreads();
+  if (c >= ksub) return;
+  const float *y = ivfpq_panel + c * (dsub | 1u);
+  const uint32_t q0 = blockIdx.y * kIvfPqTermGroup;
+  for (uint32_t q = q0; q < q0 + kIvfPqTermGroup && q < Qc; q++)
+    qterms[((size_t)q * M + m) * 256 + c] = ivfpq_dot(queries + ((size_t)q * M + m) * dsub, y, dsub);
+}
+
+// norms[i] = sum_{j < D} fl(fl(x_j - g_j)^2) of live pair i = query * nprobe + rank, one chain in ascending j
+__global__ __launch_bounds__(kPqThreads) void ivfpq_pair_norms_kernel(const float *__restrict__ queries,
+                                                                      const float *__restrict__ centroids,
+                                                                      const uint32_t *__restrict__ probes, uint32_t P,
+                                                                      uint32_t nprobe, uint32_t K, uint32_t D,
+                                                                      float *__restrict__ norms) {
+  const uint64_t i = (uint64_t)blockIdx.x * kPqThreads + threadIdx.x;
+  if (i >= P) return;
+  const uint32_t c = ivfpq_pair_cluster(probes, (uint32_t)i, nprobe, K);
+  if (c >= K) return;   // a dead pair is in no tile: its norm is never read
+  const float *x = queries + (size_t)(i / nprobe) * D, *g = centroids + (size_t)c * D;
+  float acc = 0.0f;
+  if ((D & 3u) == 0 && ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(centroids)) & 15u) == 0) {
+    for (uint32_t j = 0; j < D; j += 4) {
+      const float4 xx = *reinterpret_cast<const float4 *>(x + j), gg = *reinterpret_cast<const float4 *>(g + j);
+      ivfpq_term(acc, xx.x, gg.x, j == 0);
+      ivfpq_term(acc, xx.y, gg.y, false);
+      ivfpq_term(acc, xx.z, gg.z, false);
+      ivfpq_term(acc, xx.w, gg.w, false);
+    }
+  } else {
+    for (uint32_t j = 0; j < D; j++) ivfpq_term(acc, x[j], g[j], j == 0);
+  }
+  norms[i] = acc;
+}
+
+template <int QT>
+hipError_t ivfpq_scan_pre_launch(const IvfPqGeom &g, bool vec, const float *terms, const float *qterms,
+                                 const float *norms, uint32_t tiles, const uint32_t *pair_start,
+                                 const uint32_t *tile_start, const uint32_t *pairs, uint64_t *part, hipStream_t st) {
+  const size_t lds = pq_scan_lds_bytes(g.M, g.k, QT);
+  return with_flag(vec && QT <= 4, [&](auto V16) {
+    using V = std::integral_constant<bool, decltype(V16)::value && QT <= 4>;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ivfpq_scan_pre_kernel<QT, V::value>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ivfpq_scan_pre_kernel<QT, V::value>), dim3(tiles * g.S), dim3(kPqThreads), lds, st, g, terms,
+                       qterms, norms, pair_start, tile_start, pairs, part);
+    return hipGetLastError();
+  });
 }
 
 template <int QT>
@@ -314,6 +524,54 @@ hipError_t launch_ivfpq_scan(const IvfPqGeom &g, const float *queries, uint32_t 
     case 4: return ivfpq_scan_launch<4>(g, vec, queries, tiles, pair_start, tile_start, pairs, part, st);
     case 8: return ivfpq_scan_launch<8>(g, vec, queries, tiles, pair_start, tile_start, pairs, part, st);
     case 16: return ivfpq_scan_launch<16>(g, vec, queries, tiles, pair_start, tile_start, pairs, part, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_ivfpq_terms(const float *centroids, const float *codebooks, uint32_t K, uint32_t M, uint32_t dsub,
+                              uint32_t ksub, float *terms, hipStream_t st) {
+  const size_t lds = ((size_t)ksub * (dsub | 1u) + (size_t)kIvfPqTermGroup * dsub) * sizeof(float);
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ivfpq_terms_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  const uint32_t groups = (uint32_t)(((uint64_t)K + kIvfPqTermGroup - 1) / kIvfPqTermGroup);
+  hipLaunchKernelGGL(ivfpq_terms_kernel, dim3(M, groups < 65535 ? groups : 65535), dim3(kPqThreads), lds, st,
+                     centroids, codebooks, K, M, dsub, ksub, terms);
+  return hipGetLastError();
+}
+
+hipError_t launch_ivfpq_query_terms(const float *queries, uint32_t Qc, const float *codebooks, uint32_t M,
+                                    uint32_t dsub, uint32_t ksub, float *qterms, hipStream_t st) {
+  const size_t lds = (size_t)ksub * (dsub | 1u) * sizeof(float);
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ivfpq_query_terms_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ivfpq_query_terms_kernel, dim3(M, (Qc + kIvfPqTermGroup - 1) / kIvfPqTermGroup),
+                     dim3(kPqThreads), lds, st, queries, Qc, codebooks, M, dsub, ksub, qterms);
+  return hipGetLastError();
+}
+
+hipError_t launch_ivfpq_pair_norms(const float *queries, const float *centroids, const uint32_t *probes, uint32_t P,
+                                   uint32_t nprobe, uint32_t K, uint32_t D, float *norms, hipStream_t st) {
+  const uint32_t blocks = (uint32_t)(((uint64_t)P + kPqThreads - 1) / kPqThreads);
+  hipLaunchKernelGGL(ivfpq_pair_norms_kernel, dim3(blocks), dim3(kPqThreads), 0, st, queries, centroids, probes, P,
+                     nprobe, K, D, norms);
+  return hipGetLastError();
+}
+
+hipError_t launch_ivfpq_scan_pre(const IvfPqGeom &g, const float *terms, const float *qterms, const float *norms,
+                                 uint32_t tiles, const uint32_t *pair_start, const uint32_t *tile_start,
+                                 const uint32_t *pairs, uint64_t *part, hipStream_t st) {
+  const bool vec = (g.M & 15u) == 0 && (((uintptr_t)g.codes) & 15u) == 0;
+  auto launch = [&](auto qt) {
+    return ivfpq_scan_pre_launch<decltype(qt)::value>(g, vec, terms, qterms, norms, tiles, pair_start, tile_start,
+                                                      pairs, part, st);
+  };
+  switch (g.QT) {
+    case 2: return launch(std::integral_constant<int, 2>());
+    case 4: return launch(std::integral_constant<int, 4>());
+    case 8: return launch(std::integral_constant<int, 8>());
+    case 16: return launch(std::integral_constant<int, 16>());
   }
   return hipErrorInvalidValue;
 }

@@ -457,6 +457,21 @@ hipError_t launch_ivfpq_scan(const IvfPqGeom &g, const float *queries, uint32_t 
                              const uint32_t *tile_start, const uint32_t *pairs, uint64_t *part, hipStream_t st);
 hipError_t launch_ivfpq_residuals(const float *x, const float *centroids, const uint32_t *a, uint64_t N, uint32_t D,
                                   uint32_t K, float *out, hipStream_t st);
+// The precomputed-term variant (kmamd_ivfpq_search_precomputed).  Its scan block has no staging tile:
+// LDS pq_scan_lds_bytes and the pair tile pq_query_tile (g.QT).
+// terms[cluster][m][c < ksub] = fl(sum_j fl(y_j y_j) + 2 sum_j fl(g_j y_j)): K x M x ksub floats, once per index
+hipError_t launch_ivfpq_terms(const float *centroids, const float *codebooks, uint32_t K, uint32_t M, uint32_t dsub,
+                              uint32_t ksub, float *terms, hipStream_t st);
+// qterms[query][m][c < ksub of 256] = sum_j fl(x_j y_j): Qc x M x 256 floats, at most 2^27 (the scan indexes in 32 bits)
+hipError_t launch_ivfpq_query_terms(const float *queries, uint32_t Qc, const float *codebooks, uint32_t M,
+                                    uint32_t dsub, uint32_t ksub, float *qterms, hipStream_t st);
+// norms[query * nprobe + rank] = sum_{j < D} fl(fl(x_j - g_j)^2) of the live pairs; dead pairs are left as they are
+hipError_t launch_ivfpq_pair_norms(const float *queries, const float *centroids, const uint32_t *probes, uint32_t P,
+                                   uint32_t nprobe, uint32_t K, uint32_t D, float *norms, hipStream_t st);
+// launch_ivfpq_scan's grid, part layout and selection over T = fl(terms - 2 qterms), the pair's norm added per row
+hipError_t launch_ivfpq_scan_pre(const IvfPqGeom &g, const float *terms, const float *qterms, const float *norms,
+                                 uint32_t tiles, const uint32_t *pair_start, const uint32_t *tile_start,
+                                 const uint32_t *pairs, uint64_t *part, hipStream_t st);
 
 // knn_rerank.hip -- exact re-ranking (kmamd_knn_rerank, knn_rerank_job.cpp).  For every query the k
 // smallest keys bits(d) << 32 | id over the entries id < N of its R candidates (1 <= k <= R <= 1024, k <= 256), d the

@@ -1,5 +1,6 @@
 """IVF-PQ: product-quantiser codes of residuals in cluster lists, probed by asymmetric distance computation (C ABI:
-kmamd_ivfpq_search, kmamd_ivfpq_residuals, include/kmcuda_amd.h).
+kmamd_ivfpq_search, kmamd_ivfpq_residuals, include/kmcuda_amd.h; the precomputed-term variant --
+ivfpq_terms, ivfpq_search(terms=), IvfPqIndex(precomputed=True) -- 4.24).
 
     centroids, _ = kmeans_cuda(rows, 1024)
     codebooks = ivfpq_train(rows, centroids, subspaces=32)
@@ -144,11 +145,33 @@ def ivfpq_train(rows, centroids, subspaces, ksub=256, assignments=None, *, seed=
     return books
 
 
+def ivfpq_terms(centroids, codebooks, *, metric="L2", device=0, verbosity=0):
+    """terms (K, M, ksub) float32 of an index, for ivfpq_search(terms=) (kmamd_ivfpq_terms):
+    terms[p][m][c] = fl(sum_j fl(y_j y_j) + 2 sum_j fl(g_j y_j)), y = codebooks[m][c], g the m-th sub-vector of
+    centroids[p], both sums in ascending j.  numpy or torch like its operands."""
+    if _get_metric(metric) != 0:
+        raise ValueError("IVF-PQ supports the L2 metric only")
+    device = _device(device)
+    c, on_dev = _f32(centroids, "centroids", 2, device)
+    if int(c.shape[0]) < 1:
+        raise ValueError("\"centroids\" must be (K >= 1, D)")
+    b = _check_books(codebooks, int(c.shape[1]), on_dev, device)
+    m, ksub, dsub = (int(v) for v in b.shape)
+    terms = _out((int(c.shape[0]), m, ksub), numpy.float32, on_dev, device)
+    rc = _lib.lib().kmamd_ivfpq_terms(int(c.shape[0]), m * dsub, m, dsub, ksub, device, device if on_dev else -1,
+                                      int(verbosity), _ptr(c), _ptr(b), _ptr(terms))
+    _raise_for(rc, "kmamd_ivfpq_terms")
+    return terms
+
+
 def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, *, metric="L2", device=0,
-                 verbosity=0):
+                 verbosity=0, terms=None):
     """(indices, distances), each (Q, k), over a caller's own lists (module docstring): codes (L, M) uint8 in list
     order, ids (L,), offsets (K + 1,), probes (Q, nprobe) -- entries >= K and repeated entries are ignored.  The
-    contents of codes, ids, offsets and probes are not checked and need not be: nothing in them leads out of range."""
+    contents of codes, ids, offsets and probes are not checked and need not be: nothing in them leads out of range.
+    terms: ivfpq_terms' (K, M, ksub) float32 array of this index, of the operands' kind: the precomputed-term variant
+    (kmamd_ivfpq_search_precomputed) -- T[m][c] = fl(terms[p][m][c] - 2 sum_j fl(x_j y_j)),
+    d = fl(sum_j fl(fl(x_j - g_j)^2) + sum_m T[m][code]), negative or -0 as +0: the same distance in other bits."""
     if _get_metric(metric) != 0:
         raise ValueError("IVF-PQ supports the L2 metric only")
     device = _device(device)
@@ -184,13 +207,22 @@ def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, 
         raise ValueError("\"k\" must be in [1, 256]")
     if nq > 0xFFFFFFFF:
         raise ValueError("too many queries")
+    if terms is not None:
+        a, a_dev = _f32(terms, "terms", 3, device)
+        if a_dev != on_dev:
+            raise TypeError("\"terms\" must be of the same kind as the other operands")
+        if tuple(int(v) for v in a.shape) != (clusters, m, ksub):
+            raise ValueError("\"terms\" must have the shape %r" % ((clusters, m, ksub),))
     idx = _out((nq, int(k)), numpy.uint32, on_dev, device)
     dist = _out((nq, int(k)), numpy.float32, on_dev, device)
     if nq == 0:
         return idx, dist
-    rc = _lib.lib().kmamd_ivfpq_search(nq, rows, d, clusters, m, dsub, ksub, int(k), nprobe, 0, 0, device,
-                                       device if on_dev else -1, int(verbosity), _ptr(q), _ptr(c), _ptr(b), _ptr(cd),
-                                       _ptr(i), _ptr(o), _ptr(p), _ptr(idx), _ptr(dist))
+    head = (nq, rows, d, clusters, m, dsub, ksub, int(k), nprobe, 0, 0, device, device if on_dev else -1,
+            int(verbosity), _ptr(q), _ptr(c), _ptr(b), _ptr(cd), _ptr(i), _ptr(o), _ptr(p))
+    if terms is None:
+        rc = _lib.lib().kmamd_ivfpq_search(*head, _ptr(idx), _ptr(dist))
+    else:
+        rc = _lib.lib().kmamd_ivfpq_search_precomputed(*head, _ptr(a), _ptr(idx), _ptr(dist))
     _raise_for(rc, "kmamd_ivfpq_search")
     return idx, dist
 
@@ -240,10 +272,11 @@ def knn_rerank(queries, rows, candidates, k, *, metric="L2", device=0, verbosity
 class IvfPqIndex:
     """`rows` encoded against `codebooks` (ivfpq_train's) and kept as cluster lists: .codes (L, M) uint8 in list order,
     .ids (L,) the row of every list position, .offsets (K + 1,), beside .centroids and .codebooks.  Lists come from a
-    stable sort by assignment (a list's ids ascend); rows with assignment K are left out."""
+    stable sort by assignment (a list's ids ascend); rows with assignment K are left out.  precomputed=True builds
+    .terms (ivfpq_terms) once and search() runs the precomputed-term variant (ivfpq_search's `terms`)."""
 
     def __init__(self, rows, centroids, codebooks, assignments=None, *, metric="L2", device=0, verbosity=0,
-                 keep_rows=False):
+                 keep_rows=False, precomputed=False):
         if _get_metric(metric) != 0:
             raise ValueError("IVF-PQ supports the L2 metric only")
         self.device, self.verbosity = _device(device), int(verbosity)
@@ -277,6 +310,7 @@ class IvfPqIndex:
         if len(order) == 0:
             raise ValueError("no row has a cluster")
         self.centroids, self.codebooks, self.codes = c, b, codes[order]
+        self.terms = ivfpq_terms(c, b, device=self.device, verbosity=verbosity) if precomputed else None
 
     def search(self, queries, k, nprobe=1, probes=None, refine=None):
         """(indices, distances) of the k nearest stored rows among the `nprobe` nearest clusters of every query
@@ -308,4 +342,4 @@ class IvfPqIndex:
                 probes = kmeans_predict_top(q, self.centroids, int(nprobe), device=self.device,
                                             return_distances=False, verbosity=self.verbosity)
         return ivfpq_search(queries, self.centroids, self.codebooks, self.codes, self.ids, self.offsets, probes, k,
-                            device=self.device, verbosity=self.verbosity)
+                            device=self.device, verbosity=self.verbosity, terms=getattr(self, "terms", None))

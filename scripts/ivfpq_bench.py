@@ -4,6 +4,7 @@ with recall against an exact torch brute force over the full rows, and the two f
 
     python scripts/ivfpq_bench.py                      # N=1M x 256, K=1024, M=32 x 8, Q=10000 and 100, k=10
     python scripts/ivfpq_bench.py --rows 100000 --clusters 128 --queries 1000 --repeat 3
+    python scripts/ivfpq_bench.py --precomputed --queries 10000      # both table builds, lap by lap in turn
 
 Data: a Gaussian mixture of `clusters` components (centres 2 * randn, unit noise); the mixture's centres serve as the
 coarse centroids (no K-means is run: the subject is the search); queries are fresh draws of the mixture.  Codebooks are
@@ -11,8 +12,12 @@ trained on --train-rows rows: on residuals for the index, on the raw rows for pq
 [min, max] of --repeat runs behind a warm-up, by a host clock around calls that end in a device synchronise.
 `search_ms` is IvfPqIndex.search (kmeans_predict_top + the probed scan), `scan_ms` ivfpq_search with the probes given.
 Floors: Q nprobe (N / K) M table lookups of 4 bytes against the LDS rate (256 CUs x 128 B/clk x 2.4 GHz), and the table
-build's Q nprobe 256 D 3 lane operations against 256 CUs x 64 lanes x 2.4 GHz.  There is no CPU path."""
+build's Q nprobe 256 D 3 lane operations against 256 CUs x 64 lanes x 2.4 GHz.  --precomputed adds the
+precomputed-term variant to every line: `pre_search_ms` / `pre_scan_ms` are timed in turn with the
+other two, lap by lap, `pre_recall` is against the same exact ground truth, and `pre_table_floor_ms` is the variant's
+table build, Q nprobe M KB of query terms and as many of index terms read at 6.29 TB/s.  There is no CPU path."""
 import argparse
+import copy
 import json
 import os
 import statistics
@@ -23,18 +28,26 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 LDS_BYTES_PER_S = 256 * 128 * 2.4e9
 LANE_OPS_PER_S = 256 * 64 * 2.4e9
+COPY_BYTES_PER_S = 6.29e12
+
+
+def _median_ms_in_turn(fns, repeat, sync):
+    """(median, min, max) per function: a warm-up each, then `repeat` rounds of one lap each, in turn."""
+    for fn in fns:
+        fn()
+    sync()
+    laps = [[] for _ in fns]
+    for _ in range(repeat):
+        for fn, mine in zip(fns, laps):
+            t0 = time.perf_counter()
+            fn()
+            sync()
+            mine.append((time.perf_counter() - t0) * 1e3)
+    return [(statistics.median(mine), min(mine), max(mine)) for mine in laps]
 
 
 def _median_ms(fn, repeat, sync):
-    fn()
-    sync()
-    laps = []
-    for _ in range(repeat):
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        laps.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(laps), min(laps), max(laps)
+    return _median_ms_in_turn([fn], repeat, sync)[0]
 
 
 def exact_topk(queries, rows, k, chunk=256):
@@ -63,11 +76,13 @@ def main():
     ap.add_argument("--nprobe", default="1,4,16,64")
     ap.add_argument("--train-rows", type=int, default=100000)
     ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--precomputed", action="store_true", help="time the precomputed-term variant beside the search")
     args = ap.parse_args()
     import torch
-    from kmcuda_amd import (IvfPqIndex, ivfpq_search, ivfpq_train, kmeans_batched, kmeans_predict_batched,
-                            kmeans_predict_top, pq_search)
+    from kmcuda_amd import (IvfPqIndex, ivfpq_search, ivfpq_terms, ivfpq_train, kmeans_batched,
+                            kmeans_predict_batched, kmeans_predict_top, pq_search)
     from kmcuda_amd.ivfpq import query_tile, row_split
+    from kmcuda_amd.pq import query_tile as pre_query_tile
     if not torch.cuda.is_available():
         sys.exit("ivfpq_bench needs a GPU")
     dev = torch.device("cuda", 0)
@@ -86,11 +101,20 @@ def main():
     index = IvfPqIndex(rows, centres, books)
     sync()
     build_s = time.perf_counter() - t0
+    if args.precomputed:
+        t0 = time.perf_counter()
+        terms = ivfpq_terms(centres, books)
+        sync()
+        terms_s = time.perf_counter() - t0
+        pre = copy.copy(index)            # the same lists, searched from the terms
+        pre.terms = terms
     raw_books, _, _ = kmeans_batched(train, 256, init="random", layout="columns", problems=m, max_iter=10, seed=1)
     raw_codes = kmeans_predict_batched(rows, raw_books, layout="columns", dtype="uint8")
     lens = (index.offsets[1:] - index.offsets[:-1]).long()
     print(json.dumps({"index": {"N": n, "D": d, "K": kc, "M": m, "dsub": d // m, "train_and_build_s": build_s,
-                                "list_rows": [int(lens.min()), float(lens.float().mean()), int(lens.max())]}}),
+                                "list_rows": [int(lens.min()), float(lens.float().mean()), int(lens.max())],
+                                **({"terms_s": terms_s, "terms_mb": terms.numel() * 4 / 2 ** 20}
+                                   if args.precomputed else {})}}),
           flush=True)
     for nq in (int(v) for v in args.queries.split(",")):
         queries = draw(nq)
@@ -101,18 +125,30 @@ def main():
                           "note": "[median, min, max] of %d runs" % args.repeat}), flush=True)
         for nprobe in (int(v) for v in args.nprobe.split(",")):
             probes = kmeans_predict_top(queries, centres, nprobe, return_distances=False)
-            whole = _median_ms(lambda: index.search(queries, k, nprobe=nprobe), args.repeat, sync)
-            scan = _median_ms(lambda: ivfpq_search(queries, centres, books, index.codes, index.ids, index.offsets,
-                                                   probes, k), args.repeat, sync)
+            fns = [lambda: index.search(queries, k, nprobe=nprobe),
+                   lambda: ivfpq_search(queries, centres, books, index.codes, index.ids, index.offsets, probes, k)]
+            if args.precomputed:
+                fns += [lambda: pre.search(queries, k, nprobe=nprobe),
+                        lambda: ivfpq_search(queries, centres, books, index.codes, index.ids, index.offsets, probes, k,
+                                             terms=terms)]
+            laps = _median_ms_in_turn(fns, args.repeat, sync)
+            whole, scan = laps[:2]
             found = index.search(queries, k, nprobe=nprobe)[0]
             qt = query_tile(m, k)
+            extra = {}
+            if args.precomputed:
+                pqt = pre_query_tile(m, k)
+                extra = {"pre_search_ms": laps[2], "pre_scan_ms": laps[3], "scan_over_pre_scan": scan[0] / laps[3][0],
+                         "pre_recall": recall(pre.search(queries, k, nprobe=nprobe)[0], truth), "pre_pair_tile": pqt,
+                         "pre_row_split": row_split(nq * nprobe, pqt, int(index.codes.shape[0])),
+                         "pre_table_floor_ms": 2 * nq * nprobe * m * 1024 / COPY_BYTES_PER_S * 1e3}
             print(json.dumps({
                 "ivfpq": {"Q": nq, "k": k, "nprobe": nprobe, "pair_tile": qt,
                           "row_split": row_split(nq * nprobe, qt, int(index.codes.shape[0]))},
                 "search_ms": whole, "scan_ms": scan, "scan_us_per_query": scan[0] * 1e3 / nq,
                 "recall": recall(found, truth), "pq_search_over_scan": flat[0] / scan[0],
                 "lds_floor_ms": nq * nprobe * (n / kc) * m * 4 / LDS_BYTES_PER_S * 1e3,
-                "table_build_floor_ms": nq * nprobe * 256 * d * 3 / LANE_OPS_PER_S * 1e3}), flush=True)
+                "table_build_floor_ms": nq * nprobe * 256 * d * 3 / LANE_OPS_PER_S * 1e3, **extra}), flush=True)
 
 
 if __name__ == "__main__":
