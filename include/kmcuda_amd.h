@@ -833,6 +833,35 @@ int kmamd_ivfpq_search_precomputed(uint32_t queries_size, uint64_t list_rows, ui
                                    const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
                                    const float *terms, uint32_t *indices, float *distances);
 
+/* 4-bit product-quantiser codes (beyond the reference): kmamd_pq_search and kmamd_ivfpq_search over
+ * codes of at most 16 codewords per sub-space, packed two to a byte.  The argument lists, the definitions -- T, d, key,
+ * NaN, padding, list clamping, every bit -- the refusals and the chunking are those of the byte-code entry points
+ * above; what differs:
+ *   codes      samples_size (or list_rows) x ceil(M / 2) uint8, row-major: byte j of a row holds the code of sub-space
+ *              2j in bits 0..3 and of sub-space 2j + 1 in bits 4..7.  With odd M the high nibble of a row's last byte
+ *              is ignored whatever it holds.  A nibble >= ksub names no codeword: its table entry is +inf.
+ *   Limits     1 <= M <= 128, 1 <= ksub <= 16 (dsub, N, L, k, nprobe as above); anything beyond is InvalidArguments
+ *              before any device work.
+ * For M <= 64 the outputs are, byte for byte, those of the byte-code call on the same codes unpacked one to a byte.
+ * There is no 4-bit precomputed-term search.  The flat search keeps a query chunk's tables (64 M bytes per query)
+ * within the same 512 MB and honours KMCUDA_AMD_PQ_QUERY_CHUNK.
+ * kmamd_pq4_query_tile / kmamd_ivfpq4_query_tile: the queries / (query, probe) pairs a scan block serves -- 16, 8 or 4,
+ * the largest whose tables (64 M bytes each) and candidate buffers fit a CU's LDS twice; the same rule for both, the
+ * IVF block stages its residuals where the candidates go later.  0 where M or k is out of range.  The row split of
+ * the IVF scan is kmamd_ivfpq_row_split's. */
+uint32_t kmamd_pq4_query_tile(uint32_t subspaces, uint32_t k);
+int kmamd_pq4_search(uint32_t queries_size, uint64_t samples_size, uint32_t features_size, uint32_t subspaces,
+                     uint32_t sub_features, uint32_t sub_clusters, uint32_t k, int metric, int32_t fp16x2, int device,
+                     int32_t device_ptrs, int32_t verbosity, const float *queries, const float *codebooks,
+                     const uint8_t *codes, uint32_t *indices, float *distances);
+uint32_t kmamd_ivfpq4_query_tile(uint32_t subspaces, uint32_t k);
+int kmamd_ivfpq4_search(uint32_t queries_size, uint64_t list_rows, uint32_t features_size, uint32_t clusters_size,
+                        uint32_t subspaces, uint32_t sub_features, uint32_t sub_clusters, uint32_t k, uint32_t nprobe,
+                        int metric, int32_t fp16x2, int device, int32_t device_ptrs, int32_t verbosity,
+                        const float *queries, const float *centroids, const float *codebooks, const uint8_t *codes,
+                        const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes, uint32_t *indices,
+                        float *distances);
+
 /* Exact re-ranking of per-query candidate lists, the step behind an approximate shortlist (kmamd_ivfpq_search's
  * indices, for one): queries Q x D and samples N x D float32, candidates Q x R uint32; indices and distances Q x k.
  * For query q every position j with id = candidates[q][j] < N contributes the key (bits(d) << 32) | id, where

@@ -27,6 +27,8 @@ the reference): pq_search.
 IVF-PQ (beyond the reference): codes of residuals in cluster lists, probed by the same ADC scan -- ivfpq_train,
 IvfPqIndex (search), ivfpq_search on a caller's own lists.  The precomputed-term variant of that search (its own
 bits, opt-in): ivfpq_terms, ivfpq_search(terms=), IvfPqIndex(precomputed=True).
+4-bit codes, two to a byte, for both searches (the same definition in a sixteenth of the table): pq_pack4,
+pq_search(bits=4), ivfpq_search(bits=4), IvfPqIndex(bits=4).
 Exact re-ranking of per-query candidate lists against the raw rows, the step behind such a shortlist (beyond the
 reference): knn_rerank, and IvfPqIndex(keep_rows=True).search(refine=).
 """
@@ -36,5 +38,5 @@ from .predict import kmeans_predict, kmeans_predict_top  # noqa: F401
 from .seed import kmeans_seed_parallel  # noqa: F401
 from .minibatch import MiniBatchKMeans, kmeans_minibatch  # noqa: F401
 from .batched import kmeans_batched, kmeans_predict_batched  # noqa: F401
-from .pq import pq_search  # noqa: F401
+from .pq import pq_pack4, pq_search  # noqa: F401
 from .ivfpq import IvfPqIndex, ivfpq_search, ivfpq_terms, ivfpq_train, knn_rerank  # noqa: F401

@@ -38,6 +38,7 @@ EXPORTS = [
     "kmamd_pq_search", "kmamd_pq_query_tile",
     "kmamd_ivfpq_search", "kmamd_ivfpq_residuals", "kmamd_ivfpq_query_tile", "kmamd_ivfpq_row_split",
     "kmamd_ivfpq_terms", "kmamd_ivfpq_search_precomputed",
+    "kmamd_pq4_search", "kmamd_pq4_query_tile", "kmamd_ivfpq4_search", "kmamd_ivfpq4_query_tile",
     "kmamd_knn_rerank",
     "kmamd_copy_to_device", "kmamd_profile_reset", "kmamd_profile_read", "kmamd_profile_enable", "kmamd_filter_kind", "kmamd_build_arch",
 ]
@@ -227,6 +228,11 @@ def lib():
                                      vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.kmamd_ivfpq_search_precomputed.restype = i32     # kmamd_ivfpq_search's arguments with `terms` before the outputs
     L.kmamd_ivfpq_search_precomputed.argtypes = L.kmamd_ivfpq_search.argtypes + [vp]
+    for bytewise, packed in (("kmamd_pq_query_tile", "kmamd_pq4_query_tile"), ("kmamd_pq_search", "kmamd_pq4_search"),
+                             ("kmamd_ivfpq_query_tile", "kmamd_ivfpq4_query_tile"),
+                             ("kmamd_ivfpq_search", "kmamd_ivfpq4_search")):   # 4-bit codes: the same argument lists
+        getattr(L, packed).restype = getattr(L, bytewise).restype
+        getattr(L, packed).argtypes = getattr(L, bytewise).argtypes
     L.kmamd_ivfpq_terms.restype = i32
     L.kmamd_ivfpq_terms.argtypes = [u32, u32, u32, u32, u32, i32, i32, i32, vp, vp, vp]
     L.kmamd_ivfpq_residuals.restype = i32

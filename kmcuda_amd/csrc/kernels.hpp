@@ -473,6 +473,20 @@ hipError_t launch_ivfpq_scan_pre(const IvfPqGeom &g, const float *terms, const f
                                  uint32_t tiles, const uint32_t *pair_start, const uint32_t *tile_start,
                                  const uint32_t *pairs, uint64_t *part, hipStream_t st);
 
+// pq4_scan.hip -- both scans over 4-bit codes (kmamd_pq4_search, kmamd_ivfpq4_search).  codes is
+// N (or L) x ceil(M / 2) uint8, sub-space 2j in bits 0..3 of byte j and 2j + 1 in bits 4..7; 1 <= M <= 128, ksub <= 16.
+// PqGeom and IvfPqGeom serve with M the number of sub-spaces; part layouts, grids and the merge are the byte scans'.
+// queries (or pairs) per scan block: 16, 8 or 4, the largest with two blocks in a CU's LDS; 0: M or k out of range.
+// The IVF block stages its residuals in the candidate buffers: one rule and one LDS size for both scans.
+uint32_t pq4_query_tile(uint32_t M, uint32_t k);
+size_t pq4_scan_lds_bytes(uint32_t M, uint32_t k, uint32_t QT);
+// tables[query tile][m][code < 16][q in tile, swizzled] of Qc queries, the last tile padded: ceil(Qc / QT) * QT * M * 16
+hipError_t launch_pq4_tables(const float *queries, uint32_t Qc, const float *codebooks, uint32_t M, uint32_t dsub,
+                             uint32_t ksub, uint32_t QT, float *tables, hipStream_t st);
+hipError_t launch_pq4_scan(const PqGeom &g, const float *tables, uint32_t queries, uint64_t *part, hipStream_t st);
+hipError_t launch_ivfpq4_scan(const IvfPqGeom &g, const float *queries, uint32_t tiles, const uint32_t *pair_start,
+                              const uint32_t *tile_start, const uint32_t *pairs, uint64_t *part, hipStream_t st);
+
 // knn_rerank.hip -- exact re-ranking (kmamd_knn_rerank, knn_rerank_job.cpp).  For every query the k
 // smallest keys bits(d) << 32 | id over the entries id < N of its R candidates (1 <= k <= R <= 1024, k <= 256), d the
 // L2 distance as launch_assigned_distances gives it, NaN canonical and -0 as +0; ascending, index 0xFFFFFFFF and a NaN

@@ -16,6 +16,11 @@ uint32) and distance NaN.  Limits as pq_search, 1 <= nprobe <= min(K, 64), at mo
 float32 only.  numpy in, numpy out (integers uint32); torch tensors on `device` in, torch tensors out (int32); all
 operands must be of the same kind.  Every argument is checked before the device is touched.
 
+bits=4 (kmamd_ivfpq4_search): at most 16 codewords per sub-space and the codes two to a byte, (L,
+ceil(M / 2)) as pq_pack4 lays them out, up to 128 sub-spaces; the definition and, for M <= 64, every output byte are
+those of the same codes one to a byte.  ivfpq_train(..., ksub=16) trains for it; IvfPqIndex(..., bits=4) packs.  Not with
+the precomputed-term variant.
+
 knn_rerank (kmamd_knn_rerank; DESIGN.md 4.23) re-ranks such a shortlist against the raw rows by the exact L2 distance;
 IvfPqIndex(..., keep_rows=True).search(..., refine=f) does both: a shortlist of k * f, then the exact k.
 """
@@ -25,16 +30,19 @@ from . import _lib
 from .api import _get_metric, _raise_for
 from .batched import _f32, _out, kmeans_batched, kmeans_predict_batched
 from .knn_index import _is_torch, _labels, _ptr
-from .pq import _LDS_PER_CU, _codes, _scan_lds_bytes
+from .pq import _LDS_PER_CU, _bits, _codes, _scan_lds_bytes, pq_pack4, query_tile as _pq_query_tile
 from .predict import kmeans_predict, kmeans_predict_top
 
 _BLOCKS = 512                    # kernels.hpp: kIvfPqBlocks
 _CHUNK_BYTES = 256 << 20         # the fp32 residuals of one row chunk while an index is built
 
 
-def query_tile(subspaces, k):
+def query_tile(subspaces, k, bits=8):
     """The (query, probe) pairs one scan block serves (kmamd_ivfpq_query_tile): pq.query_tile's rule with the staged
-    residual sub-vectors, 256 bytes per pair, added to the block's LDS; 0: `subspaces` or `k` out of range."""
+    residual sub-vectors, 256 bytes per pair, added to the block's LDS; 0: `subspaces` or `k` out of range.  bits=4
+    (kmamd_ivfpq4_query_tile): pq.query_tile's 4-bit rule as it is -- that block stages where its candidates go."""
+    if _bits(bits) == 4:
+        return _pq_query_tile(subspaces, k, 4)
     if not 1 <= subspaces <= 64 or not 1 <= k <= 256:
         return 0
     for budget, tiles in ((_LDS_PER_CU // 2, (16, 8, 4)), (_LDS_PER_CU, (4, 2))):
@@ -105,17 +113,18 @@ def _corpus(rows, centroids, assignments, device):
     return x, c, assignments if assignments is None else a, on_dev
 
 
-def _check_books(codebooks, width, on_dev, device):
+def _check_books(codebooks, width, on_dev, device, bits=8):
     b, b_dev = _f32(codebooks, "codebooks", 3, device)
     if b_dev != on_dev:
         raise TypeError("\"codebooks\" must be of the same kind as the other operands")
     m, ksub, dsub = (int(v) for v in b.shape)
-    if not 1 <= m <= 64:
-        raise ValueError("the number of sub-spaces must be in [1, 64]")
+    max_m, max_ksub = (128, 16) if bits == 4 else (64, 256)
+    if not 1 <= m <= max_m:
+        raise ValueError("the number of sub-spaces must be in [1, %d]" % max_m)
     if not 1 <= dsub <= 64:
         raise ValueError("the number of features per sub-space must be in [1, 64]")
-    if not 1 <= ksub <= 256:
-        raise ValueError("the number of codewords per sub-space must be in [1, 256]")
+    if not 1 <= ksub <= max_ksub:
+        raise ValueError("the number of codewords per sub-space must be in [1, %d]" % max_ksub)
     if m * dsub != width:
         raise ValueError("\"codebooks\" must cover the %d features: subspaces * sub_features" % width)
     return b
@@ -165,9 +174,10 @@ def ivfpq_terms(centroids, codebooks, *, metric="L2", device=0, verbosity=0):
 
 
 def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, *, metric="L2", device=0,
-                 verbosity=0, terms=None):
+                 verbosity=0, terms=None, bits=8):
     """(indices, distances), each (Q, k), over a caller's own lists (module docstring): codes (L, M) uint8 in list
-    order, ids (L,), offsets (K + 1,), probes (Q, nprobe) -- entries >= K and repeated entries are ignored.  The
+    order -- (L, ceil(M / 2)) packed with bits=4, which `terms` does not go with --,
+    ids (L,), offsets (K + 1,), probes (Q, nprobe) -- entries >= K and repeated entries are ignored.  The
     contents of codes, ids, offsets and probes are not checked and need not be: nothing in them leads out of range.
     terms: ivfpq_terms' (K, M, ksub) float32 array of this index, of the operands' kind: the precomputed-term variant
     (kmamd_ivfpq_search_precomputed) -- T[m][c] = fl(terms[p][m][c] - 2 sum_j fl(x_j y_j)),
@@ -175,6 +185,8 @@ def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, 
     if _get_metric(metric) != 0:
         raise ValueError("IVF-PQ supports the L2 metric only")
     device = _device(device)
+    if _bits(bits) == 4 and terms is not None:
+        raise ValueError("the precomputed-term variant has no 4-bit codes: bits=4 goes without \"terms\"")
     if isinstance(k, bool) or not isinstance(k, (int, numpy.integer)):
         raise TypeError("\"k\" must be an integer")
     q, on_dev = _f32(queries, "queries", 2, device)
@@ -185,11 +197,13 @@ def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, 
     clusters = int(c.shape[0])
     if clusters < 1 or int(c.shape[1]) != d:
         raise ValueError("\"centroids\" must be (K >= 1, %d)" % d)
-    b = _check_books(codebooks, d, on_dev, device)
+    b = _check_books(codebooks, d, on_dev, device, bits)
     m, ksub, dsub = (int(v) for v in b.shape)
     cd, cd_dev = _codes(codes, device)
     rows = int(cd.shape[0])
-    if int(cd.shape[1]) != m:
+    if bits == 4 and int(cd.shape[1]) != (m + 1) // 2:
+        raise ValueError("\"codes\" must have one column per two sub-spaces: (L, %d)" % ((m + 1) // 2))
+    if bits == 8 and int(cd.shape[1]) != m:
         raise ValueError("\"codes\" must have one column per sub-space: (L, %d)" % m)
     if not 1 <= rows <= 0xFFFFFFFE:
         raise ValueError("the number of list positions must be in [1, 2^32 - 2]")
@@ -219,7 +233,9 @@ def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, 
         return idx, dist
     head = (nq, rows, d, clusters, m, dsub, ksub, int(k), nprobe, 0, 0, device, device if on_dev else -1,
             int(verbosity), _ptr(q), _ptr(c), _ptr(b), _ptr(cd), _ptr(i), _ptr(o), _ptr(p))
-    if terms is None:
+    if bits == 4:
+        rc = _lib.lib().kmamd_ivfpq4_search(*head, _ptr(idx), _ptr(dist))
+    elif terms is None:
         rc = _lib.lib().kmamd_ivfpq_search(*head, _ptr(idx), _ptr(dist))
     else:
         rc = _lib.lib().kmamd_ivfpq_search_precomputed(*head, _ptr(a), _ptr(idx), _ptr(dist))
@@ -273,16 +289,20 @@ class IvfPqIndex:
     """`rows` encoded against `codebooks` (ivfpq_train's) and kept as cluster lists: .codes (L, M) uint8 in list order,
     .ids (L,) the row of every list position, .offsets (K + 1,), beside .centroids and .codebooks.  Lists come from a
     stable sort by assignment (a list's ids ascend); rows with assignment K are left out.  precomputed=True builds
-    .terms (ivfpq_terms) once and search() runs the precomputed-term variant (ivfpq_search's `terms`)."""
+    .terms (ivfpq_terms) once and search() runs the precomputed-term variant (ivfpq_search's `terms`).  bits=4
+    (.bits): codebooks of at most 16 codewords, .codes packed two to a byte, (L, ceil(M / 2)); not with precomputed."""
 
     def __init__(self, rows, centroids, codebooks, assignments=None, *, metric="L2", device=0, verbosity=0,
-                 keep_rows=False, precomputed=False):
+                 keep_rows=False, precomputed=False, bits=8):
         if _get_metric(metric) != 0:
             raise ValueError("IVF-PQ supports the L2 metric only")
+        self.bits = _bits(bits)
+        if self.bits == 4 and precomputed:
+            raise ValueError("the precomputed-term variant has no 4-bit codes: bits=4 goes without precomputed=True")
         self.device, self.verbosity = _device(device), int(verbosity)
         x, c, a, on_dev = _corpus(rows, centroids, assignments, self.device)
         self.rows = x if keep_rows else None       # the checked array itself, no copy: search(refine=) reads it
-        b = _check_books(codebooks, int(x.shape[1]), on_dev, self.device)
+        b = _check_books(codebooks, int(x.shape[1]), on_dev, self.device, self.bits)
         if a is None:
             a = kmeans_predict(x, c, device=self.device, verbosity=verbosity)
         n, clusters = int(x.shape[0]), int(c.shape[0])
@@ -310,6 +330,8 @@ class IvfPqIndex:
         if len(order) == 0:
             raise ValueError("no row has a cluster")
         self.centroids, self.codebooks, self.codes = c, b, codes[order]
+        if self.bits == 4:     # a row at NaN has code ksub: with 16 codewords its low nibble, as a byte keeps 256's
+            self.codes = pq_pack4(self.codes & 15)
         self.terms = ivfpq_terms(c, b, device=self.device, verbosity=verbosity) if precomputed else None
 
     def search(self, queries, k, nprobe=1, probes=None, refine=None):
@@ -342,4 +364,5 @@ class IvfPqIndex:
                 probes = kmeans_predict_top(q, self.centroids, int(nprobe), device=self.device,
                                             return_distances=False, verbosity=self.verbosity)
         return ivfpq_search(queries, self.centroids, self.codebooks, self.codes, self.ids, self.offsets, probes, k,
-                            device=self.device, verbosity=self.verbosity, terms=getattr(self, "terms", None))
+                            device=self.device, verbosity=self.verbosity, terms=getattr(self, "terms", None),
+                            bits=getattr(self, "bits", 8))

@@ -13,6 +13,11 @@ behind +inf.  1 <= M <= 64, 1 <= dsub <= 64, 1 <= ksub <= 256, 1 <= N < 2^32, 1 
 only.  numpy in, numpy out (indices uint32); torch tensors on `device` in, torch tensors out (indices int32); the three
 operands must be of the same kind.  Every argument is checked before the device is touched; what is out of range is
 refused, never routed elsewhere.
+
+bits=4 (kmamd_pq4_search): codes of at most 16 codewords per sub-space, two to a byte -- codes is
+(N, ceil(M / 2)) uint8, pq_pack4's output: sub-space 2j in bits 0..3 of byte j, sub-space 2j + 1 in bits 4..7, the last
+high nibble ignored when M is odd, a nibble >= ksub at +inf.  1 <= M <= 128, 1 <= ksub <= 16, the definition unchanged:
+for M <= 64 the result is, byte for byte, that of the same codes one to a byte.
 """
 import numpy
 
@@ -31,13 +36,25 @@ def _candidate_cap(k):
     return cap
 
 
-def _scan_lds_bytes(m, k, qt):
-    return qt * (m * 1024 + _candidate_cap(k) * 8 + 16) + 16
+def _scan_lds_bytes(m, k, qt, entries=256):
+    return qt * (m * entries * 4 + _candidate_cap(k) * 8 + 16) + 16
 
 
-def query_tile(subspaces, k):
+def _bits(bits):
+    if isinstance(bits, bool) or bits not in (4, 8):
+        raise ValueError("\"bits\" must be 8 or 4")
+    return int(bits)
+
+
+def query_tile(subspaces, k, bits=8):
     """The queries one scan block serves (kmamd_pq_query_tile): their tables share the block's LDS.  16, 8 or 4 where
-    two blocks fit a CU's LDS, else 4 or 2 with one; 0: `subspaces` or `k` out of range."""
+    two blocks fit a CU's LDS, else 4 or 2 with one; 0: `subspaces` or `k` out of range.  bits=4
+    (kmamd_pq4_query_tile, also the pair tile of the 4-bit IVF scan): tables of 16 entries, up to 128 sub-spaces, and
+    always two blocks."""
+    if _bits(bits) == 4:
+        if not 1 <= subspaces <= 128 or not 1 <= k <= 256:
+            return 0
+        return next(qt for qt in (16, 8, 4) if _scan_lds_bytes(subspaces, k, qt, 16) <= _LDS_PER_CU // 2)
     if not 1 <= subspaces <= 64 or not 1 <= k <= 256:
         return 0
     for qt in (16, 8, 4):
@@ -67,8 +84,31 @@ def _codes(x, device):
     return numpy.ascontiguousarray(x), False
 
 
-def pq_search(queries, codebooks, codes, k, *, metric="L2", device=0, verbosity=0):
+def pq_pack4(codes):
+    """(N, M) uint8 codes, every one at most 15, packed two to a byte for bits=4: (N, ceil(M / 2)) uint8, column 2j in
+    bits 0..3 of byte j and column 2j + 1 in bits 4..7 (0 behind an odd M).  numpy in, numpy out; torch in, torch out."""
+    torch_in = _is_torch(codes)
+    if torch_in:
+        import torch
+        if codes.dtype != torch.uint8:
+            raise TypeError("\"codes\" must be a uint8 tensor")
+    elif not isinstance(codes, numpy.ndarray) or codes.dtype != numpy.uint8:
+        raise TypeError("\"codes\" must be a uint8 numpy array")
+    if codes.ndim != 2:
+        raise ValueError("\"codes\" must be 2D, (N, M)")
+    if codes.shape[0] and codes.shape[1] and int(codes.max()) > 15:
+        raise ValueError("a 4-bit code is at most 15")
+    n, m = (int(v) for v in codes.shape)
+    out = codes.new_zeros((n, (m + 1) // 2)) if torch_in else numpy.zeros((n, (m + 1) // 2), numpy.uint8)
+    out[:, :m // 2] = codes[:, 1::2] << 4
+    out |= codes[:, 0::2]
+    return out
+
+
+def pq_search(queries, codebooks, codes, k, *, metric="L2", device=0, verbosity=0, bits=8):
     """(indices, distances), each (Q, k): the k rows of `codes` nearest to every query by ADC (module docstring)."""
+    bits = _bits(bits)
+    max_m, max_ksub = (128, 16) if bits == 4 else (64, 256)
     if _get_metric(metric) != 0:
         raise ValueError("pq_search supports the L2 metric only")
     if isinstance(device, bool) or not isinstance(device, (int, numpy.integer)) or device < 0:
@@ -82,13 +122,15 @@ def pq_search(queries, codebooks, codes, k, *, metric="L2", device=0, verbosity=
         raise TypeError("\"queries\", \"codebooks\" and \"codes\" must be of the same kind")
     m, ksub, dsub = (int(v) for v in b.shape)
     n = int(c.shape[0])
-    if not 1 <= m <= 64:
-        raise ValueError("the number of sub-spaces must be in [1, 64]")
+    if not 1 <= m <= max_m:
+        raise ValueError("the number of sub-spaces must be in [1, %d]" % max_m)
     if not 1 <= dsub <= 64:
         raise ValueError("the number of features per sub-space must be in [1, 64]")
-    if not 1 <= ksub <= 256:
-        raise ValueError("the number of codewords per sub-space must be in [1, 256]")
-    if int(c.shape[1]) != m:
+    if not 1 <= ksub <= max_ksub:
+        raise ValueError("the number of codewords per sub-space must be in [1, %d]" % max_ksub)
+    if bits == 4 and int(c.shape[1]) != (m + 1) // 2:
+        raise ValueError("\"codes\" must have one column per two sub-spaces: (N, %d)" % ((m + 1) // 2))
+    if bits == 8 and int(c.shape[1]) != m:
         raise ValueError("\"codes\" must have one column per sub-space: (N, %d)" % m)
     if int(q.shape[1]) != m * dsub:
         raise ValueError("\"queries\" must have %d columns" % (m * dsub))
@@ -103,8 +145,9 @@ def pq_search(queries, codebooks, codes, k, *, metric="L2", device=0, verbosity=
     dist = _out((nq, int(k)), numpy.float32, q_dev, device)
     if nq == 0:
         return idx, dist
-    rc = _lib.lib().kmamd_pq_search(nq, n, m * dsub, m, dsub, ksub, int(k), 0, 0, int(device),
-                                    int(device) if q_dev else -1, int(verbosity), _ptr(q), _ptr(b), _ptr(c),
-                                    _ptr(idx), _ptr(dist))
-    _raise_for(rc, "kmamd_pq_search")
+    name = "kmamd_pq4_search" if bits == 4 else "kmamd_pq_search"
+    rc = getattr(_lib.lib(), name)(nq, n, m * dsub, m, dsub, ksub, int(k), 0, 0, int(device),
+                                   int(device) if q_dev else -1, int(verbosity), _ptr(q), _ptr(b), _ptr(c),
+                                   _ptr(idx), _ptr(dist))
+    _raise_for(rc, name)
     return idx, dist

@@ -5,6 +5,7 @@ with recall against an exact torch brute force over the full rows, and the two f
     python scripts/ivfpq_bench.py                      # N=1M x 256, K=1024, M=32 x 8, Q=10000 and 100, k=10
     python scripts/ivfpq_bench.py --rows 100000 --clusters 128 --queries 1000 --repeat 3
     python scripts/ivfpq_bench.py --precomputed --queries 10000      # both table builds, lap by lap in turn
+    python scripts/ivfpq_bench.py --bits 4 --subspaces 64 --refine 4 --queries 10000
 
 Data: a Gaussian mixture of `clusters` components (centres 2 * randn, unit noise); the mixture's centres serve as the
 coarse centroids (no K-means is run: the subject is the search); queries are fresh draws of the mixture.  Codebooks are
@@ -15,7 +16,9 @@ Floors: Q nprobe (N / K) M table lookups of 4 bytes against the LDS rate (256 CU
 build's Q nprobe 256 D 3 lane operations against 256 CUs x 64 lanes x 2.4 GHz.  --precomputed adds the
 precomputed-term variant to every line: `pre_search_ms` / `pre_scan_ms` are timed in turn with the
 other two, lap by lap, `pre_recall` is against the same exact ground truth, and `pre_table_floor_ms` is the variant's
-table build, Q nprobe M KB of query terms and as many of index terms read at 6.29 TB/s.  There is no CPU path."""
+table build, Q nprobe M KB of query terms and as many of index terms read at 6.29 TB/s.  --bits 4:
+16 codewords per sub-space, the codes of the index and of pq_search packed two to a byte; the table-build floor then
+counts 16 codewords.  --refine F adds `refine_recall`, the recall of search(refine=F).  There is no CPU path."""
 import argparse
 import copy
 import json
@@ -76,11 +79,13 @@ def main():
     ap.add_argument("--nprobe", default="1,4,16,64")
     ap.add_argument("--train-rows", type=int, default=100000)
     ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--bits", type=int, default=8, choices=(8, 4))
+    ap.add_argument("--refine", type=int, default=0, help="also report the recall of search(refine=this)")
     ap.add_argument("--precomputed", action="store_true", help="time the precomputed-term variant beside the search")
     args = ap.parse_args()
     import torch
     from kmcuda_amd import (IvfPqIndex, ivfpq_search, ivfpq_terms, ivfpq_train, kmeans_batched,
-                            kmeans_predict_batched, kmeans_predict_top, pq_search)
+                            kmeans_predict_batched, kmeans_predict_top, pq_pack4, pq_search)
     from kmcuda_amd.ivfpq import query_tile, row_split
     from kmcuda_amd.pq import query_tile as pre_query_tile
     if not torch.cuda.is_available():
@@ -88,6 +93,9 @@ def main():
     dev = torch.device("cuda", 0)
     sync = torch.cuda.synchronize
     n, d, kc, m, k = args.rows, args.features, args.clusters, args.subspaces, args.k
+    bits, ksub = args.bits, 16 if args.bits == 4 else 256
+    if bits == 4 and args.precomputed:
+        sys.exit("the precomputed-term variant has no 4-bit codes")
     gen = torch.Generator(device=dev).manual_seed(1)
     centres = 2 * torch.randn((kc, d), generator=gen, device=dev)
 
@@ -97,8 +105,8 @@ def main():
     rows = draw(n)
     train = rows[:args.train_rows].contiguous()
     t0 = time.perf_counter()
-    books = ivfpq_train(train, centres, m, max_iter=10, seed=1)
-    index = IvfPqIndex(rows, centres, books)
+    books = ivfpq_train(train, centres, m, ksub=ksub, max_iter=10, seed=1)
+    index = IvfPqIndex(rows, centres, books, bits=bits, keep_rows=args.refine > 0)
     sync()
     build_s = time.perf_counter() - t0
     if args.precomputed:
@@ -108,10 +116,13 @@ def main():
         terms_s = time.perf_counter() - t0
         pre = copy.copy(index)            # the same lists, searched from the terms
         pre.terms = terms
-    raw_books, _, _ = kmeans_batched(train, 256, init="random", layout="columns", problems=m, max_iter=10, seed=1)
+    raw_books, _, _ = kmeans_batched(train, ksub, init="random", layout="columns", problems=m, max_iter=10, seed=1)
     raw_codes = kmeans_predict_batched(rows, raw_books, layout="columns", dtype="uint8")
+    if bits == 4:
+        raw_codes = pq_pack4(raw_codes & 15)
     lens = (index.offsets[1:] - index.offsets[:-1]).long()
-    print(json.dumps({"index": {"N": n, "D": d, "K": kc, "M": m, "dsub": d // m, "train_and_build_s": build_s,
+    print(json.dumps({"index": {"N": n, "D": d, "K": kc, "M": m, "dsub": d // m, "bits": bits,
+                                "train_and_build_s": build_s,
                                 "list_rows": [int(lens.min()), float(lens.float().mean()), int(lens.max())],
                                 **({"terms_s": terms_s, "terms_mb": terms.numel() * 4 / 2 ** 20}
                                    if args.precomputed else {})}}),
@@ -119,14 +130,16 @@ def main():
     for nq in (int(v) for v in args.queries.split(",")):
         queries = draw(nq)
         truth = exact_topk(queries, rows, k)
-        flat = _median_ms(lambda: pq_search(queries, raw_books, raw_codes, k), args.repeat, sync)
+        flat = _median_ms(lambda: pq_search(queries, raw_books, raw_codes, k, bits=bits), args.repeat, sync)
         print(json.dumps({"pq_search": {"Q": nq, "k": k, "ms": flat, "us_per_query": flat[0] * 1e3 / nq,
-                                        "recall": recall(pq_search(queries, raw_books, raw_codes, k)[0], truth)},
+                                        "recall": recall(pq_search(queries, raw_books, raw_codes, k, bits=bits)[0],
+                                                         truth)},
                           "note": "[median, min, max] of %d runs" % args.repeat}), flush=True)
         for nprobe in (int(v) for v in args.nprobe.split(",")):
             probes = kmeans_predict_top(queries, centres, nprobe, return_distances=False)
             fns = [lambda: index.search(queries, k, nprobe=nprobe),
-                   lambda: ivfpq_search(queries, centres, books, index.codes, index.ids, index.offsets, probes, k)]
+                   lambda: ivfpq_search(queries, centres, books, index.codes, index.ids, index.offsets, probes, k,
+                                        bits=bits)]
             if args.precomputed:
                 fns += [lambda: pre.search(queries, k, nprobe=nprobe),
                         lambda: ivfpq_search(queries, centres, books, index.codes, index.ids, index.offsets, probes, k,
@@ -134,11 +147,14 @@ def main():
             laps = _median_ms_in_turn(fns, args.repeat, sync)
             whole, scan = laps[:2]
             found = index.search(queries, k, nprobe=nprobe)[0]
-            qt = query_tile(m, k)
+            qt = query_tile(m, k, bits=bits)
             extra = {}
+            if args.refine:
+                extra["refine_recall"] = recall(index.search(queries, k, nprobe=nprobe, refine=args.refine)[0], truth)
             if args.precomputed:
                 pqt = pre_query_tile(m, k)
-                extra = {"pre_search_ms": laps[2], "pre_scan_ms": laps[3], "scan_over_pre_scan": scan[0] / laps[3][0],
+                extra = {**extra, "pre_search_ms": laps[2], "pre_scan_ms": laps[3],
+                         "scan_over_pre_scan": scan[0] / laps[3][0],
                          "pre_recall": recall(pre.search(queries, k, nprobe=nprobe)[0], truth), "pre_pair_tile": pqt,
                          "pre_row_split": row_split(nq * nprobe, pqt, int(index.codes.shape[0])),
                          "pre_table_floor_ms": 2 * nq * nprobe * m * 1024 / COPY_BYTES_PER_S * 1e3}
@@ -148,7 +164,7 @@ def main():
                 "search_ms": whole, "scan_ms": scan, "scan_us_per_query": scan[0] * 1e3 / nq,
                 "recall": recall(found, truth), "pq_search_over_scan": flat[0] / scan[0],
                 "lds_floor_ms": nq * nprobe * (n / kc) * m * 4 / LDS_BYTES_PER_S * 1e3,
-                "table_build_floor_ms": nq * nprobe * 256 * d * 3 / LANE_OPS_PER_S * 1e3, **extra}), flush=True)
+                "table_build_floor_ms": nq * nprobe * ksub * d * 3 / LANE_OPS_PER_S * 1e3, **extra}), flush=True)
 
 
 if __name__ == "__main__":

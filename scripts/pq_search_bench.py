@@ -5,13 +5,15 @@ over the queries to fit memory, and against the two floors of the scan.
 
     python scripts/pq_search_bench.py                  # N=1M, ksub=256, M x dsub = 32x8 and 8x32, Q=10000, k=10, 100
     python scripts/pq_search_bench.py --shapes 100000:8:4:256:1000:10 --repeat 3
+    python scripts/pq_search_bench.py --bits 4 --shapes 1000000:32:8:16:10000:10,1000000:64:4:16:10000:10
 
 Every figure is the median [min, max] of --repeat runs behind a warm-up, by a host clock around calls that end in a
 device synchronise.  The torch side runs the first --baseline-queries queries only (its time is per query all the same)
 and is the check as well: on those queries the distances agree to rounding (torch sums in another order) and the
 indices agree wherever the distances are not within rounding of a tie.  Floors: Q N M table lookups of 4 bytes against
 the LDS rate (256 CUs x 128 B/clk x 2.4 GHz), and N M ceil(Q / QT) code bytes against 8 TB/s, the HBM rate -- a floor
-only where they miss the caches, which the block order is there to avoid.  There is no CPU path."""
+only where they miss the caches, which the block order is there to avoid.  --bits 4: ksub <= 16, the
+codes packed two to a byte, half the code bytes in that floor.  There is no CPU path."""
 import argparse
 import json
 import os
@@ -61,9 +63,10 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--baseline-queries", type=int, default=512)
     ap.add_argument("--baseline-chunk", type=int, default=64)
+    ap.add_argument("--bits", type=int, default=8, choices=(8, 4))
     args = ap.parse_args()
     import torch
-    from kmcuda_amd import pq_search
+    from kmcuda_amd import pq_pack4, pq_search
     from kmcuda_amd.pq import query_tile
     if not torch.cuda.is_available():
         sys.exit("pq_search_bench needs a GPU")
@@ -75,8 +78,9 @@ def main():
         books = torch.randn((m, ksub, dsub), generator=gen, device=dev)
         codes = torch.randint(0, ksub, (n, m), generator=gen, device=dev, dtype=torch.uint8)
         queries = torch.randn((nq, m * dsub), generator=gen, device=dev)
-        ours = _median_ms(lambda: pq_search(queries, books, codes, k), args.repeat, sync)
-        idx, dist = pq_search(queries, books, codes, k)
+        stored = pq_pack4(codes) if args.bits == 4 else codes
+        ours = _median_ms(lambda: pq_search(queries, books, stored, k, bits=args.bits), args.repeat, sync)
+        idx, dist = pq_search(queries, books, stored, k, bits=args.bits)
 
         nb = min(nq, args.baseline_queries)
         codes_long = codes.long()
@@ -86,13 +90,14 @@ def main():
         # a differing index is acceptable only between rows whose distances are within rounding of each other
         differ = idx[:nb].long() != t_idx
         tied = bool(torch.allclose(dist[:nb][differ], t_dist[differ], rtol=1e-5, atol=0))
-        qt = query_tile(m, k)
+        qt = query_tile(m, k, bits=args.bits)
         print(json.dumps({
-            "shape": {"N": n, "M": m, "dsub": dsub, "ksub": ksub, "Q": nq, "k": k, "query_tile": qt},
+            "shape": {"N": n, "M": m, "dsub": dsub, "ksub": ksub, "Q": nq, "k": k, "bits": args.bits,
+                      "query_tile": qt},
             "pq_search_ms": ours, "pq_search_us_per_query": ours[0] * 1e3 / nq,
             "torch_ms": base, "torch_queries": nb, "torch_us_per_query": base[0] * 1e3 / nb,
             "lds_floor_ms": nq * n * m * 4 / LDS_BYTES_PER_S * 1e3,
-            "code_bytes_floor_ms": n * m * -(-nq // qt) / HBM_BYTES_PER_S * 1e3,
+            "code_bytes_floor_ms": n * int(stored.shape[1]) * -(-nq // qt) / HBM_BYTES_PER_S * 1e3,
             "distances_agree": close, "indices_differ": int(differ.sum()), "differing_indices_are_ties": tied,
             "note": "[median, min, max] of %d runs" % args.repeat}), flush=True)
         assert close and tied, "pq_search and the torch formulation disagree"
