@@ -862,6 +862,31 @@ int kmamd_ivfpq4_search(uint32_t queries_size, uint64_t list_rows, uint32_t feat
                         const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes, uint32_t *indices,
                         float *distances);
 
+/* fp16 lookup tables (beyond the reference): kmamd_pq_search and kmamd_ivfpq_search with every table
+ * entry rounded once to IEEE binary16 before the scan reads it -- half the LDS per query and per lookup, a distance
+ * of its own bits.  The argument lists, codes, limits, refusals, keys, NaN, padding, list clamping and chunking are
+ * those of the fp32-table entry points; what differs, with T32 the table those define (+inf for c >= ksub):
+ *   T16[m][c] = half(T32[m][c]): round to nearest even, subnormal halves kept, beyond 65504 +inf, NaN stays NaN
+ *   d         = sum_m float(T16[m][code_m]), m ascending from the m = 0 term, separate round-to-nearest fp32 additions
+ * numpy: T32.astype(float16).astype(float32), then the ascending sum.  Launch shape, tiles, chunking and arrival order
+ * reach no bit.  There is no fp16-table search over 4-bit codes or from precomputed terms.  The flat search keeps a
+ * query chunk's tables (512 M bytes per query) within the same 512 MB and honours KMCUDA_AMD_PQ_QUERY_CHUNK.
+ * kmamd_pq_f16_query_tile = kmamd_ivfpq_f16_query_tile: the queries / (query, probe) pairs a scan block serves -- the
+ * largest of 16, 8, 4 whose tables (512 M bytes each) and candidate buffers fit a CU's LDS twice, else 4 -- the IVF
+ * block stages its residuals where the candidates go later; 0 where M or k is out of range. */
+uint32_t kmamd_pq_f16_query_tile(uint32_t subspaces, uint32_t k);
+int kmamd_pq_search_f16(uint32_t queries_size, uint64_t samples_size, uint32_t features_size, uint32_t subspaces,
+                        uint32_t sub_features, uint32_t sub_clusters, uint32_t k, int metric, int32_t fp16x2, int device,
+                        int32_t device_ptrs, int32_t verbosity, const float *queries, const float *codebooks,
+                        const uint8_t *codes, uint32_t *indices, float *distances);
+uint32_t kmamd_ivfpq_f16_query_tile(uint32_t subspaces, uint32_t k);
+int kmamd_ivfpq_search_f16(uint32_t queries_size, uint64_t list_rows, uint32_t features_size, uint32_t clusters_size,
+                           uint32_t subspaces, uint32_t sub_features, uint32_t sub_clusters, uint32_t k,
+                           uint32_t nprobe, int metric, int32_t fp16x2, int device, int32_t device_ptrs,
+                           int32_t verbosity, const float *queries, const float *centroids, const float *codebooks,
+                           const uint8_t *codes, const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
+                           uint32_t *indices, float *distances);
+
 /* Exact re-ranking of per-query candidate lists, the step behind an approximate shortlist (kmamd_ivfpq_search's
  * indices, for one): queries Q x D and samples N x D float32, candidates Q x R uint32; indices and distances Q x k.
  * For query q every position j with id = candidates[q][j] < N contributes the key (bits(d) << 32) | id, where

@@ -29,6 +29,9 @@ IvfPqIndex (search), ivfpq_search on a caller's own lists.  The precomputed-term
 bits, opt-in): ivfpq_terms, ivfpq_search(terms=), IvfPqIndex(precomputed=True).
 4-bit codes, two to a byte, for both searches (the same definition in a sixteenth of the table): pq_pack4,
 pq_search(bits=4), ivfpq_search(bits=4), IvfPqIndex(bits=4).
+fp16 lookup tables for both byte-code searches (entries rounded once to binary16, summed in fp32: half the LDS, its
+own bits, opt-in): pq_search(table_dtype="float16"), ivfpq_search(table_dtype="float16"),
+IvfPqIndex(table_dtype="float16").
 Exact re-ranking of per-query candidate lists against the raw rows, the step behind such a shortlist (beyond the
 reference): knn_rerank, and IvfPqIndex(keep_rows=True).search(refine=).
 """

@@ -39,6 +39,7 @@ EXPORTS = [
     "kmamd_ivfpq_search", "kmamd_ivfpq_residuals", "kmamd_ivfpq_query_tile", "kmamd_ivfpq_row_split",
     "kmamd_ivfpq_terms", "kmamd_ivfpq_search_precomputed",
     "kmamd_pq4_search", "kmamd_pq4_query_tile", "kmamd_ivfpq4_search", "kmamd_ivfpq4_query_tile",
+    "kmamd_pq_search_f16", "kmamd_pq_f16_query_tile", "kmamd_ivfpq_search_f16", "kmamd_ivfpq_f16_query_tile",
     "kmamd_knn_rerank",
     "kmamd_copy_to_device", "kmamd_profile_reset", "kmamd_profile_read", "kmamd_profile_enable", "kmamd_filter_kind", "kmamd_build_arch",
 ]
@@ -230,7 +231,11 @@ def lib():
     L.kmamd_ivfpq_search_precomputed.argtypes = L.kmamd_ivfpq_search.argtypes + [vp]
     for bytewise, packed in (("kmamd_pq_query_tile", "kmamd_pq4_query_tile"), ("kmamd_pq_search", "kmamd_pq4_search"),
                              ("kmamd_ivfpq_query_tile", "kmamd_ivfpq4_query_tile"),
-                             ("kmamd_ivfpq_search", "kmamd_ivfpq4_search")):   # 4-bit codes: the same argument lists
+                             ("kmamd_ivfpq_search", "kmamd_ivfpq4_search"),   # 4-bit codes: the same argument lists
+                             ("kmamd_pq_query_tile", "kmamd_pq_f16_query_tile"),
+                             ("kmamd_pq_search", "kmamd_pq_search_f16"),
+                             ("kmamd_ivfpq_query_tile", "kmamd_ivfpq_f16_query_tile"),
+                             ("kmamd_ivfpq_search", "kmamd_ivfpq_search_f16")):   # fp16 tables: the same again
         getattr(L, packed).restype = getattr(L, bytewise).restype
         getattr(L, packed).argtypes = getattr(L, bytewise).argtypes
     L.kmamd_ivfpq_terms.restype = i32

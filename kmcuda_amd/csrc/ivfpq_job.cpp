@@ -1,7 +1,7 @@
-// ivfpq_job.cpp -- kmamd_ivfpq_search, kmamd_ivfpq4_search, kmamd_ivfpq_search_precomputed, kmamd_ivfpq_terms,
-// kmamd_ivfpq_residuals, the two query-tile rules and kmamd_ivfpq_row_split of include/kmcuda_amd.h: IVF-PQ search
-// (4-bit codes 4.25).  The kernels are ivfpq_scan.hip's, pq4_scan.hip's and pq_scan.hip's merge;
-// nothing here goes through an Engine.
+// ivfpq_job.cpp -- kmamd_ivfpq_search, kmamd_ivfpq4_search, kmamd_ivfpq_search_f16, kmamd_ivfpq_search_precomputed,
+// kmamd_ivfpq_terms, kmamd_ivfpq_residuals, the query-tile rules and kmamd_ivfpq_row_split of include/kmcuda_amd.h:
+// IVF-PQ search (4-bit codes 4.25; fp16 lookup tables 4.26).  The kernels are ivfpq_scan.hip's,
+// pq4_scan.hip's, pq16_scan.hip's and pq_scan.hip's merge; nothing here goes through an Engine.
 //
 // The index goes to the device whole.  The queries are cut into chunks whose partial keys stay within kIvfPqPartBytes;
 // per chunk seven launches on one stream -- the pair sort (clear, count, prefix, scatter), the fill of the partial
@@ -36,7 +36,8 @@ uint32_t ivfpq_query_chunk(uint32_t nprobe, uint32_t k, uint32_t qterm_subspaces
 
 // The searches: with `precomputed` the tables come from `terms`, else from the residuals (4.22).
 // bits 8: a code per byte, M <= 64, ksub <= 256; bits 4: two per byte, M <= 128, ksub <= 16, never precomputed (4.25).
-int ivfpq_search_job(bool precomputed, uint32_t bits, uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
+// f16: the byte codes over tables of halves built from the residuals (4.26), never precomputed and never with bits 4.
+int ivfpq_search_job(bool precomputed, uint32_t bits, bool f16, uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
                      uint32_t clusters_size, uint32_t subspaces, uint32_t sub_features, uint32_t sub_clusters,
                      uint32_t k, uint32_t nprobe, int metric, int32_t fp16x2, int device, int32_t device_ptrs,
                      int32_t verbosity, const float *queries, const float *centroids, const float *codebooks,
@@ -49,7 +50,7 @@ int ivfpq_search_job(bool precomputed, uint32_t bits, uint32_t queries_size, uin
   // everything that is refused, before any device work
   if (M == 0 || M > (nib ? 128u : 64u) || dsub == 0 || dsub > 64 || ksub == 0 || ksub > (nib ? 16u : 256u))
     return kmcudaInvalidArguments;
-  if (nib && precomputed) return kmcudaInvalidArguments;
+  if ((nib || f16) && precomputed) return kmcudaInvalidArguments;
   if (features_size != M * dsub || metric != 0 || fp16x2 != 0) return kmcudaInvalidArguments;
   if (L == 0 || L > 0xFFFFFFFEull || k == 0 || k > 256) return kmcudaInvalidArguments;
   if (K == 0 || nprobe == 0 || nprobe > std::min(K, 64u)) return kmcudaInvalidArguments;
@@ -88,8 +89,9 @@ int ivfpq_search_job(bool precomputed, uint32_t bits, uint32_t queries_size, uin
     KNN_TRY(w.alloc(&dist, (size_t)Q * k));
   }
   g.L = L; g.K = K; g.M = M; g.dsub = dsub; g.ksub = ksub; g.k = k; g.nprobe = nprobe;
-  // no staging tile in the precomputed block, none of its own in the 4-bit block
-  g.QT = nib ? pq4_query_tile(M, k) : precomputed ? pq_query_tile(M, k) : ivfpq_query_tile(M, k);
+  // no staging tile in the precomputed block, none of its own in the 4-bit block and the fp16-table block
+  g.QT = nib ? pq4_query_tile(M, k) : f16 ? pq16_query_tile(M, k) : precomputed ? pq_query_tile(M, k)
+                                                                                : ivfpq_query_tile(M, k);
   g.cap = pq_candidate_cap(k);
   const uint32_t chunk = std::min(ivfpq_query_chunk(nprobe, k, precomputed ? M : 0), Q);
   // the full chunks and the last one differ in their row split: the keys are sized for the larger of the two
@@ -116,7 +118,7 @@ int ivfpq_search_job(bool precomputed, uint32_t bits, uint32_t queries_size, uin
     const uint32_t tiles = (uint32_t)std::min<uint64_t>(P, (uint64_t)(P + g.QT - 1) / g.QT + K);
     if (verbosity > 1)
       printf("ivfpq_search%s%s: queries [%u, %u), %u pairs, tile %u, at most %u tiles x %u row splits\n",
-             precomputed ? " (precomputed)" : "", nib ? " (4-bit)" : "", q0, q0 + qc, P, g.QT, tiles, g.S);
+             precomputed ? " (precomputed)" : "", nib ? " (4-bit)" : f16 ? " (fp16 tables)" : "", q0, q0 + qc, P, g.QT, tiles, g.S);
     KMX_HIPRT(launch_ivfpq_group(prb + (size_t)q0 * nprobe, P, nprobe, K, g.QT, hist, pair_start, tile_start, cursor,
                                  pairs, st));
     KMX_HIPRT(launch_batched_fill(reinterpret_cast<uint32_t *>(part), (uint64_t)P * g.S * k * 2, ~0u, st));
@@ -128,6 +130,8 @@ int ivfpq_search_job(bool precomputed, uint32_t bits, uint32_t queries_size, uin
       KMX_HIPRT(launch_ivfpq_scan_pre(g, trm, qterms, norms, tiles, pair_start, tile_start, pairs, part, st));
     } else if (nib) {
       KMX_HIPRT(launch_ivfpq4_scan(g, qc_rows, tiles, pair_start, tile_start, pairs, part, st));
+    } else if (f16) {
+      KMX_HIPRT(launch_ivfpq16_scan(g, qc_rows, tiles, pair_start, tile_start, pairs, part, st));
     } else {
       KMX_HIPRT(launch_ivfpq_scan(g, qc_rows, tiles, pair_start, tile_start, pairs, part, st));
     }
@@ -152,6 +156,8 @@ uint32_t kmamd_ivfpq_query_tile(uint32_t subspaces, uint32_t k) { return ivfpq_q
 
 uint32_t kmamd_ivfpq4_query_tile(uint32_t subspaces, uint32_t k) { return pq4_query_tile(subspaces, k); }
 
+uint32_t kmamd_ivfpq_f16_query_tile(uint32_t subspaces, uint32_t k) { return pq16_query_tile(subspaces, k); }
+
 uint32_t kmamd_ivfpq_row_split(uint64_t pairs, uint32_t query_tile, uint64_t list_rows) {
   return ivfpq_row_split(pairs, query_tile, list_rows);
 }
@@ -162,7 +168,7 @@ int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t featu
                        const float *queries, const float *centroids, const float *codebooks, const uint8_t *codes,
                        const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes, uint32_t *indices,
                        float *distances) {
-  return ivfpq_search_job(false, 8, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
+  return ivfpq_search_job(false, 8, false, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
                           sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity, queries, centroids,
                           codebooks, codes, ids, offsets, probes, nullptr, indices, distances);
 }
@@ -173,9 +179,20 @@ int kmamd_ivfpq4_search(uint32_t queries_size, uint64_t list_rows, uint32_t feat
                         const float *queries, const float *centroids, const float *codebooks, const uint8_t *codes,
                         const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes, uint32_t *indices,
                         float *distances) {
-  return ivfpq_search_job(false, 4, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
+  return ivfpq_search_job(false, 4, false, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
                           sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity, queries, centroids,
                           codebooks, codes, ids, offsets, probes, nullptr, indices, distances);
+}
+
+int kmamd_ivfpq_search_f16(uint32_t queries_size, uint64_t list_rows, uint32_t features_size, uint32_t clusters_size,
+                           uint32_t subspaces, uint32_t sub_features, uint32_t sub_clusters, uint32_t k,
+                           uint32_t nprobe, int metric, int32_t fp16x2, int device, int32_t device_ptrs,
+                           int32_t verbosity, const float *queries, const float *centroids, const float *codebooks,
+                           const uint8_t *codes, const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
+                           uint32_t *indices, float *distances) {
+  return ivfpq_search_job(false, 8, true, queries_size, list_rows, features_size, clusters_size, subspaces,
+                          sub_features, sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity,
+                          queries, centroids, codebooks, codes, ids, offsets, probes, nullptr, indices, distances);
 }
 
 int kmamd_ivfpq_search_precomputed(uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
@@ -185,7 +202,7 @@ int kmamd_ivfpq_search_precomputed(uint32_t queries_size, uint64_t list_rows, ui
                                    const float *centroids, const float *codebooks, const uint8_t *codes,
                                    const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
                                    const float *terms, uint32_t *indices, float *distances) {
-  return ivfpq_search_job(true, 8, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
+  return ivfpq_search_job(true, 8, false, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
                           sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity, queries, centroids,
                           codebooks, codes, ids, offsets, probes, terms, indices, distances);
 }

@@ -487,6 +487,20 @@ hipError_t launch_pq4_scan(const PqGeom &g, const float *tables, uint32_t querie
 hipError_t launch_ivfpq4_scan(const IvfPqGeom &g, const float *queries, uint32_t tiles, const uint32_t *pair_start,
                               const uint32_t *tile_start, const uint32_t *pairs, uint64_t *part, hipStream_t st);
 
+// pq16_scan.hip -- both byte-code scans over fp16 lookup tables (kmamd_pq_search_f16, kmamd_ivfpq_search_f16;
+// DESIGN.md 4.26): the fp32 tables' entries rounded once to binary16, summed in fp32.  PqGeom and IvfPqGeom, part
+// layouts, grids and the merge are the byte scans'.  queries (or pairs) per scan block: 16, 8 or 4 with two blocks in a
+// CU's LDS at 512 bytes per (sub-space, query), else 4 with one; 0: M or k out of range.  The IVF block stages its
+// residuals in the candidate buffers: one rule and one LDS size for both scans.
+uint32_t pq16_query_tile(uint32_t M, uint32_t k);
+size_t pq16_scan_lds_bytes(uint32_t M, uint32_t k, uint32_t QT);
+// tables[query tile][m][code < 256][q in tile] in halves, the last tile padded: ceil(Qc / QT) * QT * M * 256 of them
+hipError_t launch_pq16_tables(const float *queries, uint32_t Qc, const float *codebooks, uint32_t M, uint32_t dsub,
+                              uint32_t ksub, uint32_t QT, uint16_t *tables, hipStream_t st);
+hipError_t launch_pq16_scan(const PqGeom &g, const uint16_t *tables, uint32_t queries, uint64_t *part, hipStream_t st);
+hipError_t launch_ivfpq16_scan(const IvfPqGeom &g, const float *queries, uint32_t tiles, const uint32_t *pair_start,
+                               const uint32_t *tile_start, const uint32_t *pairs, uint64_t *part, hipStream_t st);
+
 // knn_rerank.hip -- exact re-ranking (kmamd_knn_rerank, knn_rerank_job.cpp).  For every query the k
 // smallest keys bits(d) << 32 | id over the entries id < N of its R candidates (1 <= k <= R <= 1024, k <= 256), d the
 // L2 distance as launch_assigned_distances gives it, NaN canonical and -0 as +0; ascending, index 0xFFFFFFFF and a NaN

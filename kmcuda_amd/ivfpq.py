@@ -21,6 +21,11 @@ ceil(M / 2)) as pq_pack4 lays them out, up to 128 sub-spaces; the definition and
 those of the same codes one to a byte.  ivfpq_train(..., ksub=16) trains for it; IvfPqIndex(..., bits=4) packs.  Not with
 the precomputed-term variant.
 
+table_dtype="float16" (kmamd_ivfpq_search_f16): every entry of a pair's table is rounded once to IEEE
+binary16 and a position's distance is sum_m float(T16[m][code]) in fp32, as pq_search(table_dtype="float16"): half the
+LDS per pair and per lookup, a distance of its own bits.  Byte codes and residual tables only: not with bits=4, `terms`
+or precomputed=True.  search(refine=) re-ranks its shortlist exactly, which is what the option is meant for.
+
 knn_rerank (kmamd_knn_rerank; DESIGN.md 4.23) re-ranks such a shortlist against the raw rows by the exact L2 distance;
 IvfPqIndex(..., keep_rows=True).search(..., refine=f) does both: a shortlist of k * f, then the exact k.
 """
@@ -30,18 +35,21 @@ from . import _lib
 from .api import _get_metric, _raise_for
 from .batched import _f32, _out, kmeans_batched, kmeans_predict_batched
 from .knn_index import _is_torch, _labels, _ptr
-from .pq import _LDS_PER_CU, _bits, _codes, _scan_lds_bytes, pq_pack4, query_tile as _pq_query_tile
+from .pq import _LDS_PER_CU, _bits, _codes, _scan_lds_bytes, _table_dtype, pq_pack4, query_tile as _pq_query_tile
 from .predict import kmeans_predict, kmeans_predict_top
 
 _BLOCKS = 512                    # kernels.hpp: kIvfPqBlocks
 _CHUNK_BYTES = 256 << 20         # the fp32 residuals of one row chunk while an index is built
 
 
-def query_tile(subspaces, k, bits=8):
+def query_tile(subspaces, k, bits=8, table_dtype="float32"):
     """The (query, probe) pairs one scan block serves (kmamd_ivfpq_query_tile): pq.query_tile's rule with the staged
     residual sub-vectors, 256 bytes per pair, added to the block's LDS; 0: `subspaces` or `k` out of range.  bits=4
-    (kmamd_ivfpq4_query_tile): pq.query_tile's 4-bit rule as it is -- that block stages where its candidates go."""
-    if _bits(bits) == 4:
+    (kmamd_ivfpq4_query_tile): pq.query_tile's 4-bit rule as it is -- that block stages where its candidates go.
+    table_dtype="float16" (kmamd_ivfpq_f16_query_tile): pq.query_tile's fp16 rule as it is, for the same reason."""
+    if _table_dtype(table_dtype, _bits(bits)):
+        return _pq_query_tile(subspaces, k, 8, "float16")
+    if bits == 4:
         return _pq_query_tile(subspaces, k, 4)
     if not 1 <= subspaces <= 64 or not 1 <= k <= 256:
         return 0
@@ -174,19 +182,22 @@ def ivfpq_terms(centroids, codebooks, *, metric="L2", device=0, verbosity=0):
 
 
 def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, *, metric="L2", device=0,
-                 verbosity=0, terms=None, bits=8):
+                 verbosity=0, terms=None, bits=8, table_dtype="float32"):
     """(indices, distances), each (Q, k), over a caller's own lists (module docstring): codes (L, M) uint8 in list
     order -- (L, ceil(M / 2)) packed with bits=4, which `terms` does not go with --,
     ids (L,), offsets (K + 1,), probes (Q, nprobe) -- entries >= K and repeated entries are ignored.  The
     contents of codes, ids, offsets and probes are not checked and need not be: nothing in them leads out of range.
     terms: ivfpq_terms' (K, M, ksub) float32 array of this index, of the operands' kind: the precomputed-term variant
     (kmamd_ivfpq_search_precomputed) -- T[m][c] = fl(terms[p][m][c] - 2 sum_j fl(x_j y_j)),
-    d = fl(sum_j fl(fl(x_j - g_j)^2) + sum_m T[m][code]), negative or -0 as +0: the same distance in other bits."""
+    d = fl(sum_j fl(fl(x_j - g_j)^2) + sum_m T[m][code]), negative or -0 as +0: the same distance in other bits.
+    table_dtype="float16": the tables of halves of the module docstring (kmamd_ivfpq_search_f16); not with bits=4 or
+    `terms`."""
     if _get_metric(metric) != 0:
         raise ValueError("IVF-PQ supports the L2 metric only")
     device = _device(device)
     if _bits(bits) == 4 and terms is not None:
         raise ValueError("the precomputed-term variant has no 4-bit codes: bits=4 goes without \"terms\"")
+    half = _table_dtype(table_dtype, bits, terms is not None)
     if isinstance(k, bool) or not isinstance(k, (int, numpy.integer)):
         raise TypeError("\"k\" must be an integer")
     q, on_dev = _f32(queries, "queries", 2, device)
@@ -235,6 +246,8 @@ def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, 
             int(verbosity), _ptr(q), _ptr(c), _ptr(b), _ptr(cd), _ptr(i), _ptr(o), _ptr(p))
     if bits == 4:
         rc = _lib.lib().kmamd_ivfpq4_search(*head, _ptr(idx), _ptr(dist))
+    elif half:
+        rc = _lib.lib().kmamd_ivfpq_search_f16(*head, _ptr(idx), _ptr(dist))
     elif terms is None:
         rc = _lib.lib().kmamd_ivfpq_search(*head, _ptr(idx), _ptr(dist))
     else:
@@ -290,15 +303,19 @@ class IvfPqIndex:
     .ids (L,) the row of every list position, .offsets (K + 1,), beside .centroids and .codebooks.  Lists come from a
     stable sort by assignment (a list's ids ascend); rows with assignment K are left out.  precomputed=True builds
     .terms (ivfpq_terms) once and search() runs the precomputed-term variant (ivfpq_search's `terms`).  bits=4
-    (.bits): codebooks of at most 16 codewords, .codes packed two to a byte, (L, ceil(M / 2)); not with precomputed."""
+    (.bits): codebooks of at most 16 codewords, .codes packed two to a byte, (L, ceil(M / 2)); not with precomputed.
+    table_dtype="float16" (.table_dtype): search() scans tables of halves (ivfpq_search's `table_dtype`); the index
+    itself is the same; not with bits=4 or precomputed."""
 
     def __init__(self, rows, centroids, codebooks, assignments=None, *, metric="L2", device=0, verbosity=0,
-                 keep_rows=False, precomputed=False, bits=8):
+                 keep_rows=False, precomputed=False, bits=8, table_dtype="float32"):
         if _get_metric(metric) != 0:
             raise ValueError("IVF-PQ supports the L2 metric only")
         self.bits = _bits(bits)
         if self.bits == 4 and precomputed:
             raise ValueError("the precomputed-term variant has no 4-bit codes: bits=4 goes without precomputed=True")
+        _table_dtype(table_dtype, self.bits, bool(precomputed))
+        self.table_dtype = table_dtype
         self.device, self.verbosity = _device(device), int(verbosity)
         x, c, a, on_dev = _corpus(rows, centroids, assignments, self.device)
         self.rows = x if keep_rows else None       # the checked array itself, no copy: search(refine=) reads it
@@ -365,4 +382,4 @@ class IvfPqIndex:
                                             return_distances=False, verbosity=self.verbosity)
         return ivfpq_search(queries, self.centroids, self.codebooks, self.codes, self.ids, self.offsets, probes, k,
                             device=self.device, verbosity=self.verbosity, terms=getattr(self, "terms", None),
-                            bits=getattr(self, "bits", 8))
+                            bits=getattr(self, "bits", 8), table_dtype=getattr(self, "table_dtype", "float32"))

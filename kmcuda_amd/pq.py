@@ -18,6 +18,11 @@ bits=4 (kmamd_pq4_search): codes of at most 16 codewords per sub
 (N, ceil(M / 2)) uint8, pq_pack4's output: sub-space 2j in bits 0..3 of byte j, sub-space 2j + 1 in bits 4..7, the last
 high nibble ignored when M is odd, a nibble >= ksub at +inf.  1 <= M <= 128, 1 <= ksub <= 16, the definition unchanged:
 for M <= 64 the result is, byte for byte, that of the same codes one to a byte.
+
+table_dtype="float16" (kmamd_pq_search_f16): every table entry is rounded once to IEEE binary16 (to
+nearest even, subnormals kept, beyond 65504 +inf) and a row's distance is sum_m float(T16[m][code]) in fp32 --
+T.astype(numpy.float16).astype(numpy.float32) and the same ascending sum.  Half the LDS per query and per lookup; a
+slightly different distance with its own bits.  Byte codes only: not with bits=4.
 """
 import numpy
 
@@ -36,8 +41,8 @@ def _candidate_cap(k):
     return cap
 
 
-def _scan_lds_bytes(m, k, qt, entries=256):
-    return qt * (m * entries * 4 + _candidate_cap(k) * 8 + 16) + 16
+def _scan_lds_bytes(m, k, qt, entries=256, entry_bytes=4):
+    return qt * (m * entries * entry_bytes + _candidate_cap(k) * 8 + 16) + 16
 
 
 def _bits(bits):
@@ -46,17 +51,32 @@ def _bits(bits):
     return int(bits)
 
 
-def query_tile(subspaces, k, bits=8):
+def _table_dtype(table_dtype, bits=8, precomputed=False):
+    """True for "float16"; refuses what fp16 tables do not go with"""
+    if not isinstance(table_dtype, str) or table_dtype not in ("float32", "float16"):
+        raise ValueError("\"table_dtype\" must be \"float32\" or \"float16\"")
+    if table_dtype == "float16" and bits == 4:
+        raise ValueError("fp16 tables serve the byte codes: table_dtype=\"float16\" goes without bits=4")
+    if table_dtype == "float16" and precomputed:
+        raise ValueError("the precomputed-term variant has fp32 tables: table_dtype=\"float16\" goes without it")
+    return table_dtype == "float16"
+
+
+def query_tile(subspaces, k, bits=8, table_dtype="float32"):
     """The queries one scan block serves (kmamd_pq_query_tile): their tables share the block's LDS.  16, 8 or 4 where
     two blocks fit a CU's LDS, else 4 or 2 with one; 0: `subspaces` or `k` out of range.  bits=4
     (kmamd_pq4_query_tile, also the pair tile of the 4-bit IVF scan): tables of 16 entries, up to 128 sub-spaces, and
-    always two blocks."""
-    if _bits(bits) == 4:
+    always two blocks.  table_dtype="float16" (kmamd_pq_f16_query_tile, also the pair tile of that IVF scan): entries
+    of two bytes, 16, 8 or 4 with two blocks, else 4 with one."""
+    half = _table_dtype(table_dtype, _bits(bits))
+    if bits == 4:
         if not 1 <= subspaces <= 128 or not 1 <= k <= 256:
             return 0
         return next(qt for qt in (16, 8, 4) if _scan_lds_bytes(subspaces, k, qt, 16) <= _LDS_PER_CU // 2)
     if not 1 <= subspaces <= 64 or not 1 <= k <= 256:
         return 0
+    if half:
+        return next((qt for qt in (16, 8, 4) if _scan_lds_bytes(subspaces, k, qt, 256, 2) <= _LDS_PER_CU // 2), 4)
     for qt in (16, 8, 4):
         if _scan_lds_bytes(subspaces, k, qt) <= _LDS_PER_CU // 2:
             return qt
@@ -105,9 +125,10 @@ def pq_pack4(codes):
     return out
 
 
-def pq_search(queries, codebooks, codes, k, *, metric="L2", device=0, verbosity=0, bits=8):
+def pq_search(queries, codebooks, codes, k, *, metric="L2", device=0, verbosity=0, bits=8, table_dtype="float32"):
     """(indices, distances), each (Q, k): the k rows of `codes` nearest to every query by ADC (module docstring)."""
     bits = _bits(bits)
+    half = _table_dtype(table_dtype, bits)
     max_m, max_ksub = (128, 16) if bits == 4 else (64, 256)
     if _get_metric(metric) != 0:
         raise ValueError("pq_search supports the L2 metric only")
@@ -145,7 +166,7 @@ def pq_search(queries, codebooks, codes, k, *, metric="L2", device=0, verbosity=
     dist = _out((nq, int(k)), numpy.float32, q_dev, device)
     if nq == 0:
         return idx, dist
-    name = "kmamd_pq4_search" if bits == 4 else "kmamd_pq_search"
+    name = "kmamd_pq4_search" if bits == 4 else "kmamd_pq_search_f16" if half else "kmamd_pq_search"
     rc = getattr(_lib.lib(), name)(nq, n, m * dsub, m, dsub, ksub, int(k), 0, 0, int(device),
                                    int(device) if q_dev else -1, int(verbosity), _ptr(q), _ptr(b), _ptr(c),
                                    _ptr(idx), _ptr(dist))

@@ -18,7 +18,10 @@ precomputed-term variant to every line: `pre_search_ms` / `pre_
 other two, lap by lap, `pre_recall` is against the same exact ground truth, and `pre_table_floor_ms` is the variant's
 table build, Q nprobe M KB of query terms and as many of index terms read at 6.29 TB/s.  --bits 4:
 16 codewords per sub-space, the codes of the index and of pq_search packed two to a byte; the table-build floor then
-counts 16 codewords.  --refine F adds `refine_recall`, the recall of search(refine=F).  There is no CPU path."""
+counts 16 codewords.  --refine F adds `refine_recall`, the recall of search(refine=F).  --table-dtype float16
+ adds the search over tables of halves to every line, timed in turn with the others, lap by lap:
+`f16_ms` of pq_search, `f16_search_ms` / `f16_scan_ms`, `f16_recall` and `f16_refine_recall` against the same exact
+ground truth, `scan_over_f16_scan`.  There is no CPU path."""
 import argparse
 import copy
 import json
@@ -82,7 +85,10 @@ def main():
     ap.add_argument("--bits", type=int, default=8, choices=(8, 4))
     ap.add_argument("--refine", type=int, default=0, help="also report the recall of search(refine=this)")
     ap.add_argument("--precomputed", action="store_true", help="time the precomputed-term variant beside the search")
+    ap.add_argument("--table-dtype", default="float32", choices=("float32", "float16"),
+                    help="float16: time the search over fp16 tables beside the fp32 one")
     args = ap.parse_args()
+    half = args.table_dtype == "float16"
     import torch
     from kmcuda_amd import (IvfPqIndex, ivfpq_search, ivfpq_terms, ivfpq_train, kmeans_batched,
                             kmeans_predict_batched, kmeans_predict_top, pq_pack4, pq_search)
@@ -96,6 +102,8 @@ def main():
     bits, ksub = args.bits, 16 if args.bits == 4 else 256
     if bits == 4 and args.precomputed:
         sys.exit("the precomputed-term variant has no 4-bit codes")
+    if bits == 4 and half:
+        sys.exit("fp16 tables serve the byte codes only")
     gen = torch.Generator(device=dev).manual_seed(1)
     centres = 2 * torch.randn((kc, d), generator=gen, device=dev)
 
@@ -116,6 +124,9 @@ def main():
         terms_s = time.perf_counter() - t0
         pre = copy.copy(index)            # the same lists, searched from the terms
         pre.terms = terms
+    if half:
+        f16 = copy.copy(index)            # the same lists, scanned over tables of halves
+        f16.table_dtype = "float16"
     raw_books, _, _ = kmeans_batched(train, ksub, init="random", layout="columns", problems=m, max_iter=10, seed=1)
     raw_codes = kmeans_predict_batched(rows, raw_books, layout="columns", dtype="uint8")
     if bits == 4:
@@ -130,10 +141,15 @@ def main():
     for nq in (int(v) for v in args.queries.split(",")):
         queries = draw(nq)
         truth = exact_topk(queries, rows, k)
-        flat = _median_ms(lambda: pq_search(queries, raw_books, raw_codes, k, bits=bits), args.repeat, sync)
+        flat_fns = [lambda: pq_search(queries, raw_books, raw_codes, k, bits=bits)]
+        if half:
+            flat_fns.append(lambda: pq_search(queries, raw_books, raw_codes, k, table_dtype="float16"))
+        flat_laps = _median_ms_in_turn(flat_fns, args.repeat, sync)
+        flat = flat_laps[0]
         print(json.dumps({"pq_search": {"Q": nq, "k": k, "ms": flat, "us_per_query": flat[0] * 1e3 / nq,
-                                        "recall": recall(pq_search(queries, raw_books, raw_codes, k, bits=bits)[0],
-                                                         truth)},
+                                        "recall": recall(flat_fns[0]()[0], truth),
+                                        **({"f16_ms": flat_laps[1], "f16_recall": recall(flat_fns[1]()[0], truth),
+                                            "ms_over_f16_ms": flat[0] / flat_laps[1][0]} if half else {})},
                           "note": "[median, min, max] of %d runs" % args.repeat}), flush=True)
         for nprobe in (int(v) for v in args.nprobe.split(",")):
             probes = kmeans_predict_top(queries, centres, nprobe, return_distances=False)
@@ -144,6 +160,10 @@ def main():
                 fns += [lambda: pre.search(queries, k, nprobe=nprobe),
                         lambda: ivfpq_search(queries, centres, books, index.codes, index.ids, index.offsets, probes, k,
                                              terms=terms)]
+            if half:
+                fns += [lambda: f16.search(queries, k, nprobe=nprobe),
+                        lambda: ivfpq_search(queries, centres, books, index.codes, index.ids, index.offsets, probes, k,
+                                             table_dtype="float16")]
             laps = _median_ms_in_turn(fns, args.repeat, sync)
             whole, scan = laps[:2]
             found = index.search(queries, k, nprobe=nprobe)[0]
@@ -158,6 +178,15 @@ def main():
                          "pre_recall": recall(pre.search(queries, k, nprobe=nprobe)[0], truth), "pre_pair_tile": pqt,
                          "pre_row_split": row_split(nq * nprobe, pqt, int(index.codes.shape[0])),
                          "pre_table_floor_ms": 2 * nq * nprobe * m * 1024 / COPY_BYTES_PER_S * 1e3}
+            if half:
+                hqt = query_tile(m, k, table_dtype="float16")
+                extra = {**extra, "f16_search_ms": laps[-2], "f16_scan_ms": laps[-1],
+                         "scan_over_f16_scan": scan[0] / laps[-1][0],
+                         "f16_recall": recall(f16.search(queries, k, nprobe=nprobe)[0], truth), "f16_pair_tile": hqt,
+                         "f16_row_split": row_split(nq * nprobe, hqt, int(index.codes.shape[0]))}
+                if args.refine:
+                    extra["f16_refine_recall"] = recall(
+                        f16.search(queries, k, nprobe=nprobe, refine=args.refine)[0], truth)
             print(json.dumps({
                 "ivfpq": {"Q": nq, "k": k, "nprobe": nprobe, "pair_tile": qt,
                           "row_split": row_split(nq * nprobe, qt, int(index.codes.shape[0]))},

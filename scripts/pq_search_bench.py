@@ -13,7 +13,10 @@ and is the check as well: on those queries the distances agree to rounding (torc
 indices agree wherever the distances are not within rounding of a tie.  Floors: Q N M table lookups of 4 bytes against
 the LDS rate (256 CUs x 128 B/clk x 2.4 GHz), and N M ceil(Q / QT) code bytes against 8 TB/s, the HBM rate -- a floor
 only where they miss the caches, which the block order is there to avoid.  --bits 4: ksub <= 16, the
-codes packed two to a byte, half the code bytes in that floor.  There is no CPU path."""
+codes packed two to a byte, half the code bytes in that floor.  --table-dtype float16: the search
+over tables of halves is the subject -- its lookups are 2 bytes in the LDS floor and it agrees with torch to fp16
+rounding, 2^-11 per entry -- and the fp32-table search is timed beside it, lap by lap in turn (`fp32_tables_ms`,
+`fp32_over_fp16`).  There is no CPU path."""
 import argparse
 import json
 import os
@@ -27,16 +30,23 @@ LDS_BYTES_PER_S = 256 * 128 * 2.4e9
 HBM_BYTES_PER_S = 8e12
 
 
-def _median_ms(fn, repeat, sync):
-    fn()
-    sync()
-    laps = []
-    for _ in range(repeat):
-        t0 = time.perf_counter()
+def _median_ms_in_turn(fns, repeat, sync):
+    """(median, min, max) per function: a warm-up each, then `repeat` rounds of one lap each, in turn."""
+    for fn in fns:
         fn()
-        sync()
-        laps.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(laps), min(laps), max(laps)
+    sync()
+    laps = [[] for _ in fns]
+    for _ in range(repeat):
+        for fn, mine in zip(fns, laps):
+            t0 = time.perf_counter()
+            fn()
+            sync()
+            mine.append((time.perf_counter() - t0) * 1e3)
+    return [(statistics.median(mine), min(mine), max(mine)) for mine in laps]
+
+
+def _median_ms(fn, repeat, sync):
+    return _median_ms_in_turn([fn], repeat, sync)[0]
 
 
 def torch_adc(queries, books, codes_long, k, chunk):
@@ -64,7 +74,12 @@ def main():
     ap.add_argument("--baseline-queries", type=int, default=512)
     ap.add_argument("--baseline-chunk", type=int, default=64)
     ap.add_argument("--bits", type=int, default=8, choices=(8, 4))
+    ap.add_argument("--table-dtype", default="float32", choices=("float32", "float16"))
     args = ap.parse_args()
+    half = args.table_dtype == "float16"
+    if half and args.bits == 4:
+        sys.exit("fp16 tables serve the byte codes only")
+    rtol = 2.0 ** -10 if half else 1e-5
     import torch
     from kmcuda_amd import pq_pack4, pq_search
     from kmcuda_amd.pq import query_tile
@@ -79,24 +94,29 @@ def main():
         codes = torch.randint(0, ksub, (n, m), generator=gen, device=dev, dtype=torch.uint8)
         queries = torch.randn((nq, m * dsub), generator=gen, device=dev)
         stored = pq_pack4(codes) if args.bits == 4 else codes
-        ours = _median_ms(lambda: pq_search(queries, books, stored, k, bits=args.bits), args.repeat, sync)
-        idx, dist = pq_search(queries, books, stored, k, bits=args.bits)
+        fns = [lambda: pq_search(queries, books, stored, k, bits=args.bits, table_dtype=args.table_dtype)]
+        if half:
+            fns.append(lambda: pq_search(queries, books, stored, k))
+        laps = _median_ms_in_turn(fns, args.repeat, sync)
+        ours = laps[0]
+        idx, dist = fns[0]()
 
         nb = min(nq, args.baseline_queries)
         codes_long = codes.long()
         base = _median_ms(lambda: torch_adc(queries[:nb], books, codes_long, k, args.baseline_chunk), args.repeat, sync)
         t_idx, t_dist = torch_adc(queries[:nb], books, codes_long, k, args.baseline_chunk)
-        close = bool(torch.allclose(dist[:nb], t_dist, rtol=1e-5, atol=0))
+        close = bool(torch.allclose(dist[:nb], t_dist, rtol=rtol, atol=0))
         # a differing index is acceptable only between rows whose distances are within rounding of each other
         differ = idx[:nb].long() != t_idx
-        tied = bool(torch.allclose(dist[:nb][differ], t_dist[differ], rtol=1e-5, atol=0))
-        qt = query_tile(m, k, bits=args.bits)
+        tied = bool(torch.allclose(dist[:nb][differ], t_dist[differ], rtol=rtol, atol=0))
+        qt = query_tile(m, k, bits=args.bits, table_dtype=args.table_dtype)
         print(json.dumps({
             "shape": {"N": n, "M": m, "dsub": dsub, "ksub": ksub, "Q": nq, "k": k, "bits": args.bits,
-                      "query_tile": qt},
+                      "table_dtype": args.table_dtype, "query_tile": qt},
             "pq_search_ms": ours, "pq_search_us_per_query": ours[0] * 1e3 / nq,
             "torch_ms": base, "torch_queries": nb, "torch_us_per_query": base[0] * 1e3 / nb,
-            "lds_floor_ms": nq * n * m * 4 / LDS_BYTES_PER_S * 1e3,
+            **({"fp32_tables_ms": laps[1], "fp32_over_fp16": laps[1][0] / ours[0]} if half else {}),
+            "lds_floor_ms": nq * n * m * (2 if half else 4) / LDS_BYTES_PER_S * 1e3,
             "code_bytes_floor_ms": n * int(stored.shape[1]) * -(-nq // qt) / HBM_BYTES_PER_S * 1e3,
             "distances_agree": close, "indices_differ": int(differ.sum()), "differing_indices_are_ties": tied,
             "note": "[median, min, max] of %d runs" % args.repeat}), flush=True)
