@@ -887,6 +887,35 @@ int kmamd_ivfpq_search_f16(uint32_t queries_size, uint64_t list_rows, uint32_t f
                            const uint8_t *codes, const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
                            uint32_t *indices, float *distances);
 
+/* IVF-PQ search over NON-RESIDUAL lists (beyond the reference): the lists hold the product-quantiser
+ * codes of the rows themselves, not of their residuals (FAISS's by_residual = false), and `codebooks` is trained on
+ * rows.  The lookup table then depends on the query only -- it is kmamd_pq_search's, built once per query where the
+ * residual search builds one per (query, probe) pair -- and the answer is kmamd_pq_search's arithmetic restricted to
+ * the probed lists.  kmamd_ivfpq_search's argument list, limits, refusals, probe set, key, NaN, padding, list clamping
+ * and chunking; what differs, for query x:
+ *   T[m][c]  = sum_j fl(fl(x_{m dsub + j} - codebooks[m][c][j])^2), j ascending from the j = 0 term; +inf for c >= ksub
+ *   d(x,pos) = sum_m T[m][codes[pos][m]], m ascending from the m = 0 term, for every pos of every probed list
+ * `centroids` gives K and is checked like any other pointer; it is not read.  A query chunk also keeps its tables
+ * (M x 256 entries per query) within 2^27 entries, whatever KMCUDA_AMD_IVFPQ_QUERY_CHUNK asks for.  The pair tile is
+ * kmamd_pq_query_tile(M, k).
+ * kmamd_ivfpq_search_nonresidual_f16: the same with kmamd_pq_search_f16's tables and sum -- T16 = half(T), d =
+ * sum_m float(T16[m][code_m]) -- and the pair tile kmamd_pq_f16_query_tile(M, k).
+ * There is no non-residual search over 4-bit codes or from precomputed terms. */
+int kmamd_ivfpq_search_nonresidual(uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
+                                   uint32_t clusters_size, uint32_t subspaces, uint32_t sub_features,
+                                   uint32_t sub_clusters, uint32_t k, uint32_t nprobe, int metric, int32_t fp16x2,
+                                   int device, int32_t device_ptrs, int32_t verbosity, const float *queries,
+                                   const float *centroids, const float *codebooks, const uint8_t *codes,
+                                   const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
+                                   uint32_t *indices, float *distances);
+int kmamd_ivfpq_search_nonresidual_f16(uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
+                                       uint32_t clusters_size, uint32_t subspaces, uint32_t sub_features,
+                                       uint32_t sub_clusters, uint32_t k, uint32_t nprobe, int metric, int32_t fp16x2,
+                                       int device, int32_t device_ptrs, int32_t verbosity, const float *queries,
+                                       const float *centroids, const float *codebooks, const uint8_t *codes,
+                                       const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
+                                       uint32_t *indices, float *distances);
+
 /* Exact re-ranking of per-query candidate lists, the step behind an approximate shortlist (kmamd_ivfpq_search's
  * indices, for one): queries Q x D and samples N x D float32, candidates Q x R uint32; indices and distances Q x k.
  * For query q every position j with id = candidates[q][j] < N contributes the key (bits(d) << 32) | id, where

@@ -32,6 +32,9 @@ pq_search(bits=4), ivfpq_search(bits=4), IvfPqIndex(bits=4).
 fp16 lookup tables for both byte-code searches (entries rounded once to binary16, summed in fp32: half the LDS, its
 own bits, opt-in): pq_search(table_dtype="float16"), ivfpq_search(table_dtype="float16"),
 IvfPqIndex(table_dtype="float16").
+Non-residual IVF-PQ lists (the codes of the rows themselves: the table is pq_search's, built once per query and
+copied by the scan blocks; opt-in): ivfpq_train(residual=False), IvfPqIndex(residual=False),
+ivfpq_search(residual=False).
 Exact re-ranking of per-query candidate lists against the raw rows, the step behind such a shortlist (beyond the
 reference): knn_rerank, and IvfPqIndex(keep_rows=True).search(refine=).
 """

@@ -40,6 +40,7 @@ EXPORTS = [
     "kmamd_ivfpq_terms", "kmamd_ivfpq_search_precomputed",
     "kmamd_pq4_search", "kmamd_pq4_query_tile", "kmamd_ivfpq4_search", "kmamd_ivfpq4_query_tile",
     "kmamd_pq_search_f16", "kmamd_pq_f16_query_tile", "kmamd_ivfpq_search_f16", "kmamd_ivfpq_f16_query_tile",
+    "kmamd_ivfpq_search_nonresidual", "kmamd_ivfpq_search_nonresidual_f16",
     "kmamd_knn_rerank",
     "kmamd_copy_to_device", "kmamd_profile_reset", "kmamd_profile_read", "kmamd_profile_enable", "kmamd_filter_kind", "kmamd_build_arch",
 ]
@@ -235,7 +236,9 @@ def lib():
                              ("kmamd_pq_query_tile", "kmamd_pq_f16_query_tile"),
                              ("kmamd_pq_search", "kmamd_pq_search_f16"),
                              ("kmamd_ivfpq_query_tile", "kmamd_ivfpq_f16_query_tile"),
-                             ("kmamd_ivfpq_search", "kmamd_ivfpq_search_f16")):   # fp16 tables: the same again
+                             ("kmamd_ivfpq_search", "kmamd_ivfpq_search_f16"),    # fp16 tables: the same again
+                             ("kmamd_ivfpq_search", "kmamd_ivfpq_search_nonresidual"),   # and non-residual lists
+                             ("kmamd_ivfpq_search", "kmamd_ivfpq_search_nonresidual_f16")):
         getattr(L, packed).restype = getattr(L, bytewise).restype
         getattr(L, packed).argtypes = getattr(L, bytewise).argtypes
     L.kmamd_ivfpq_terms.restype = i32

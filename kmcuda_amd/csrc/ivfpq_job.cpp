@@ -1,12 +1,14 @@
 // ivfpq_job.cpp -- kmamd_ivfpq_search, kmamd_ivfpq4_search, kmamd_ivfpq_search_f16, kmamd_ivfpq_search_precomputed,
-// kmamd_ivfpq_terms, kmamd_ivfpq_residuals, the query-tile rules and kmamd_ivfpq_row_split of include/kmcuda_amd.h:
-// IVF-PQ search (4-bit codes 4.25; fp16 lookup tables 4.26).  The kernels are ivfpq_scan.hip's,
+// kmamd_ivfpq_search_nonresidual, kmamd_ivfpq_search_nonresidual_f16, kmamd_ivfpq_terms, kmamd_ivfpq_residuals, the
+// query-tile rules and kmamd_ivfpq_row_split of include/kmcuda_amd.h: IVF-PQ search (4-bit codes
+// 4.25; fp16 lookup tables 4.26; non-residual lists 4.27).  The kernels are ivfpq_scan.hip's,
 // pq4_scan.hip's, pq16_scan.hip's and pq_scan.hip's merge; nothing here goes through an Engine.
 //
 // The index goes to the device whole.  The queries are cut into chunks whose partial keys stay within kIvfPqPartBytes;
 // per chunk seven launches on one stream -- the pair sort (clear, count, prefix, scatter), the fill of the partial
 // keys, scan, merge -- and no host round trip before the end.  The precomputed search adds two launches per chunk, the
-// chunk's query terms and pair norms, and keeps the query terms within kIvfPqPartBytes as well.
+// chunk's query terms and pair norms, and keeps the query terms within kIvfPqPartBytes as well.  The non-residual
+// searches add one, the chunk's query tables, under the same bound.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -22,8 +24,8 @@ namespace {
 constexpr size_t kIvfPqPartBytes = (size_t)512 << 20;   // the partial keys of one query chunk at one row split
 
 // Queries per chunk; KMCUDA_AMD_IVFPQ_QUERY_CHUNK: queries per chunk (the tests force small chunks).  qterm_subspaces:
-// M where the chunk's query terms (M KB per query) are held as well -- a bound the override does not lift, because the
-// scan indexes them in 32 bits --, else 0
+// M where the chunk's query terms or query tables (M x 256 entries per query, M KB as floats) are held as well -- a
+// bound of 2^27 entries the override does not lift, because the scan indexes them in 32 bits --, else 0
 uint32_t ivfpq_query_chunk(uint32_t nprobe, uint32_t k, uint32_t qterm_subspaces) {
   size_t chunk = kIvfPqPartBytes / ((size_t)nprobe * k * sizeof(uint64_t));
   if (const char *v = getenv("KMCUDA_AMD_IVFPQ_QUERY_CHUNK")) {
@@ -37,7 +39,9 @@ uint32_t ivfpq_query_chunk(uint32_t nprobe, uint32_t k, uint32_t qterm_subspaces
 // The searches: with `precomputed` the tables come from `terms`, else from the residuals (4.22).
 // bits 8: a code per byte, M <= 64, ksub <= 256; bits 4: two per byte, M <= 128, ksub <= 16, never precomputed (4.25).
 // f16: the byte codes over tables of halves built from the residuals (4.26), never precomputed and never with bits 4.
-int ivfpq_search_job(bool precomputed, uint32_t bits, bool f16, uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
+// !residual: the lists hold the codes of the rows themselves and the tables are the queries' own (4.27), as floats or
+// with f16 as halves; never precomputed and never with bits 4; `centroids` is checked and not read.
+int ivfpq_search_job(bool precomputed, uint32_t bits, bool f16, bool residual, uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
                      uint32_t clusters_size, uint32_t subspaces, uint32_t sub_features, uint32_t sub_clusters,
                      uint32_t k, uint32_t nprobe, int metric, int32_t fp16x2, int device, int32_t device_ptrs,
                      int32_t verbosity, const float *queries, const float *centroids, const float *codebooks,
@@ -50,7 +54,8 @@ int ivfpq_search_job(bool precomputed, uint32_t bits, bool f16, uint32_t queries
   // everything that is refused, before any device work
   if (M == 0 || M > (nib ? 128u : 64u) || dsub == 0 || dsub > 64 || ksub == 0 || ksub > (nib ? 16u : 256u))
     return kmcudaInvalidArguments;
-  if ((nib || f16) && precomputed) return kmcudaInvalidArguments;
+  if ((nib || f16 || !residual) && precomputed) return kmcudaInvalidArguments;
+  if (nib && !residual) return kmcudaInvalidArguments;
   if (features_size != M * dsub || metric != 0 || fp16x2 != 0) return kmcudaInvalidArguments;
   if (L == 0 || L > 0xFFFFFFFEull || k == 0 || k > 256) return kmcudaInvalidArguments;
   if (K == 0 || nprobe == 0 || nprobe > std::min(K, 64u)) return kmcudaInvalidArguments;
@@ -75,7 +80,7 @@ int ivfpq_search_job(bool precomputed, uint32_t bits, bool f16, uint32_t queries
   IvfPqGeom g{};
   KNN_TRY(w.stage_in(queries, (size_t)Q * features_size, device_ptrs, &qry));
   KNN_TRY(w.stage_in(probes, (size_t)Q * nprobe, device_ptrs, &prb));
-  KNN_TRY(w.stage_in(centroids, (size_t)K * features_size, device_ptrs, &g.centroids));
+  if (residual) KNN_TRY(w.stage_in(centroids, (size_t)K * features_size, device_ptrs, &g.centroids));
   KNN_TRY(w.stage_in(codebooks, (size_t)M * ksub * dsub, device_ptrs, &g.codebooks));
   KNN_TRY(w.stage_in(codes, (size_t)L * width, device_ptrs, &g.codes));
   KNN_TRY(w.stage_in(ids, (size_t)L, device_ptrs, &g.ids));
@@ -90,10 +95,10 @@ int ivfpq_search_job(bool precomputed, uint32_t bits, bool f16, uint32_t queries
   }
   g.L = L; g.K = K; g.M = M; g.dsub = dsub; g.ksub = ksub; g.k = k; g.nprobe = nprobe;
   // no staging tile in the precomputed block, none of its own in the 4-bit block and the fp16-table block
-  g.QT = nib ? pq4_query_tile(M, k) : f16 ? pq16_query_tile(M, k) : precomputed ? pq_query_tile(M, k)
-                                                                                : ivfpq_query_tile(M, k);
+  g.QT = nib ? pq4_query_tile(M, k) : f16 ? pq16_query_tile(M, k) : precomputed || !residual ? pq_query_tile(M, k)
+                                                                                             : ivfpq_query_tile(M, k);
   g.cap = pq_candidate_cap(k);
-  const uint32_t chunk = std::min(ivfpq_query_chunk(nprobe, k, precomputed ? M : 0), Q);
+  const uint32_t chunk = std::min(ivfpq_query_chunk(nprobe, k, precomputed || !residual ? M : 0), Q);
   // the full chunks and the last one differ in their row split: the keys are sized for the larger of the two
   size_t part_keys = 0;
   for (uint32_t qc : {chunk, Q % chunk})
@@ -112,13 +117,17 @@ int ivfpq_search_job(bool precomputed, uint32_t bits, bool f16, uint32_t queries
     KNN_TRY(w.alloc(&qterms, (size_t)chunk * M * 256));
     KNN_TRY(w.alloc(&norms, (size_t)chunk * nprobe));
   }
+  uint16_t *qtables16 = nullptr;   // the non-residual searches' query tables: qterms as floats, these as halves
+  if (!residual && f16) KNN_TRY(w.alloc(&qtables16, (size_t)chunk * M * 256));
+  if (!residual && !f16) KNN_TRY(w.alloc(&qterms, (size_t)chunk * M * 256));
   for (uint32_t q0 = 0; q0 < Q; q0 += chunk) {
     const uint32_t qc = std::min(chunk, Q - q0), P = qc * nprobe;
     g.S = ivfpq_row_split(P, g.QT, L);
     const uint32_t tiles = (uint32_t)std::min<uint64_t>(P, (uint64_t)(P + g.QT - 1) / g.QT + K);
     if (verbosity > 1)
       printf("ivfpq_search%s%s: queries [%u, %u), %u pairs, tile %u, at most %u tiles x %u row splits\n",
-             precomputed ? " (precomputed)" : "", nib ? " (4-bit)" : f16 ? " (fp16 tables)" : "", q0, q0 + qc, P, g.QT, tiles, g.S);
+             precomputed ? " (precomputed)" : residual ? "" : " (non-residual)",
+             nib ? " (4-bit)" : f16 ? " (fp16 tables)" : "", q0, q0 + qc, P, g.QT, tiles, g.S);
     KMX_HIPRT(launch_ivfpq_group(prb + (size_t)q0 * nprobe, P, nprobe, K, g.QT, hist, pair_start, tile_start, cursor,
                                  pairs, st));
     KMX_HIPRT(launch_batched_fill(reinterpret_cast<uint32_t *>(part), (uint64_t)P * g.S * k * 2, ~0u, st));
@@ -128,6 +137,12 @@ int ivfpq_search_job(bool precomputed, uint32_t bits, bool f16, uint32_t queries
       KMX_HIPRT(launch_ivfpq_query_terms(qc_rows, qc, g.codebooks, M, dsub, ksub, qterms, st));
       KMX_HIPRT(launch_ivfpq_pair_norms(qc_rows, g.centroids, qc_probes, P, nprobe, K, features_size, norms, st));
       KMX_HIPRT(launch_ivfpq_scan_pre(g, trm, qterms, norms, tiles, pair_start, tile_start, pairs, part, st));
+    } else if (!residual && f16) {
+      KMX_HIPRT(launch_ivfpq_query_tables_f16(qc_rows, qc, g.codebooks, M, dsub, ksub, qtables16, st));
+      KMX_HIPRT(launch_ivfpq16_scan_nonres(g, qtables16, tiles, pair_start, tile_start, pairs, part, st));
+    } else if (!residual) {
+      KMX_HIPRT(launch_ivfpq_query_tables(qc_rows, qc, g.codebooks, M, dsub, ksub, qterms, st));
+      KMX_HIPRT(launch_ivfpq_scan_nonres(g, qterms, tiles, pair_start, tile_start, pairs, part, st));
     } else if (nib) {
       KMX_HIPRT(launch_ivfpq4_scan(g, qc_rows, tiles, pair_start, tile_start, pairs, part, st));
     } else if (f16) {
@@ -168,7 +183,7 @@ int kmamd_ivfpq_search(uint32_t queries_size, uint64_t list_rows, uint32_t featu
                        const float *queries, const float *centroids, const float *codebooks, const uint8_t *codes,
                        const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes, uint32_t *indices,
                        float *distances) {
-  return ivfpq_search_job(false, 8, false, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
+  return ivfpq_search_job(false, 8, false, true, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
                           sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity, queries, centroids,
                           codebooks, codes, ids, offsets, probes, nullptr, indices, distances);
 }
@@ -179,7 +194,7 @@ int kmamd_ivfpq4_search(uint32_t queries_size, uint64_t list_rows, uint32_t feat
                         const float *queries, const float *centroids, const float *codebooks, const uint8_t *codes,
                         const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes, uint32_t *indices,
                         float *distances) {
-  return ivfpq_search_job(false, 4, false, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
+  return ivfpq_search_job(false, 4, false, true, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
                           sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity, queries, centroids,
                           codebooks, codes, ids, offsets, probes, nullptr, indices, distances);
 }
@@ -190,7 +205,7 @@ int kmamd_ivfpq_search_f16(uint32_t queries_size, uint64_t list_rows, uint32_t f
                            int32_t verbosity, const float *queries, const float *centroids, const float *codebooks,
                            const uint8_t *codes, const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
                            uint32_t *indices, float *distances) {
-  return ivfpq_search_job(false, 8, true, queries_size, list_rows, features_size, clusters_size, subspaces,
+  return ivfpq_search_job(false, 8, true, true, queries_size, list_rows, features_size, clusters_size, subspaces,
                           sub_features, sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity,
                           queries, centroids, codebooks, codes, ids, offsets, probes, nullptr, indices, distances);
 }
@@ -202,9 +217,33 @@ int kmamd_ivfpq_search_precomputed(uint32_t queries_size, uint64_t list_rows, ui
                                    const float *centroids, const float *codebooks, const uint8_t *codes,
                                    const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
                                    const float *terms, uint32_t *indices, float *distances) {
-  return ivfpq_search_job(true, 8, false, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
+  return ivfpq_search_job(true, 8, false, true, queries_size, list_rows, features_size, clusters_size, subspaces, sub_features,
                           sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity, queries, centroids,
                           codebooks, codes, ids, offsets, probes, terms, indices, distances);
+}
+
+int kmamd_ivfpq_search_nonresidual(uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
+                                   uint32_t clusters_size, uint32_t subspaces, uint32_t sub_features,
+                                   uint32_t sub_clusters, uint32_t k, uint32_t nprobe, int metric, int32_t fp16x2,
+                                   int device, int32_t device_ptrs, int32_t verbosity, const float *queries,
+                                   const float *centroids, const float *codebooks, const uint8_t *codes,
+                                   const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
+                                   uint32_t *indices, float *distances) {
+  return ivfpq_search_job(false, 8, false, false, queries_size, list_rows, features_size, clusters_size, subspaces,
+                          sub_features, sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity,
+                          queries, centroids, codebooks, codes, ids, offsets, probes, nullptr, indices, distances);
+}
+
+int kmamd_ivfpq_search_nonresidual_f16(uint32_t queries_size, uint64_t list_rows, uint32_t features_size,
+                                       uint32_t clusters_size, uint32_t subspaces, uint32_t sub_features,
+                                       uint32_t sub_clusters, uint32_t k, uint32_t nprobe, int metric, int32_t fp16x2,
+                                       int device, int32_t device_ptrs, int32_t verbosity, const float *queries,
+                                       const float *centroids, const float *codebooks, const uint8_t *codes,
+                                       const uint32_t *ids, const uint32_t *offsets, const uint32_t *probes,
+                                       uint32_t *indices, float *distances) {
+  return ivfpq_search_job(false, 8, true, false, queries_size, list_rows, features_size, clusters_size, subspaces,
+                          sub_features, sub_clusters, k, nprobe, metric, fp16x2, device, device_ptrs, verbosity,
+                          queries, centroids, codebooks, codes, ids, offsets, probes, nullptr, indices, distances);
 }
 
 int kmamd_ivfpq_terms(uint32_t clusters_size, uint32_t features_size, uint32_t subspaces, uint32_t sub_features,

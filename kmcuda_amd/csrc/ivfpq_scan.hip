@@ -40,8 +40,19 @@
 //              next group's loads issued before this group's entries T = fl(A - 2 B) go to LDS with the same wide
 //              store; one barrier, then the same stream.  Behind pq_score a lane adds its slot's t1 (in registers) and
 //              turns a result that is negative or -0 into +0 before the key is formed.
+//
+// Non-residual lists (kmamd_ivfpq_search_nonresidual): the codes are those of the rows themselves, so
+// the table is pq_search's and depends on the query only.
+//   ivfpq_query_tables   once per query chunk: pq_tables' entries, bit for bit, in ivfpq_query_terms' grid and layout
+//              [query][m][256] (1 KB lines), as floats or rounded once to halves (512-byte lines, for pq16_scan.hip's
+//              scan); all 256 columns are written.
+//   ivfpq_scan_nonres      ivfpq_scan with a third prologue, pq_fill_tables (pq_select.hpp): thread c copies column c of
+//              its pairs' lines into T[m][c][q], a group of sub-spaces at a time with the next group in flight; no
+//              arithmetic, no staging tile, one barrier.  Then the same stream.
 #include <float.h>
 #include <math.h>
+
+#include <hip/hip_fp16.h>
 
 #include "kernels.hpp"
 #include "pq_select.hpp"
@@ -245,9 +256,15 @@ __device__ __forceinline__ void ivfpq_fill_tables(const IvfPqGeom &g, const floa
   __syncthreads();
 }
 
-// One scan block.  PRE: the tables come from precomputed terms (terms, qterms, norms; `queries` unused), the block has
-// no staging tile and a lane adds its slot's norm to the score; else they are built from `queries` and the centroid.
-template <int QT, bool VEC, bool PRE>
+// where a scan block's tables come from
+enum IvfPqSource {
+  kIvfPqResiduals,     // built from `queries` and the centroid through a staging tile
+  kIvfPqTerms,         // precomputed terms (terms, qterms, norms): no staging tile, a lane adds its slot's norm to the score
+  kIvfPqQueryTables,   // non-residual lists: copied from the query-level tables, which take `qterms`' place and layout
+};
+
+// One scan block; `queries` is read by kIvfPqResiduals only, `terms` and `norms` by kIvfPqTerms only.
+template <int QT, bool VEC, IvfPqSource SRC>
 __device__ __forceinline__ void ivfpq_scan_block(const IvfPqGeom &g, const float *__restrict__ queries,
                                                  const float *__restrict__ terms, const float *__restrict__ qterms,
                                                  const float *__restrict__ norms,
@@ -275,8 +292,8 @@ __device__ __forceinline__ void ivfpq_scan_block(const IvfPqGeom &g, const float
   const uint32_t live = left < (uint32_t)QT ? left : (uint32_t)QT;
 
   float *T = reinterpret_cast<float *>(ivfpq_lds4);                          // M x 256 x QT
-  float *stage = T + (size_t)QT * M * 256;                                   // QT x 64; none with PRE
-  uint64_t *buf = reinterpret_cast<uint64_t *>(stage + (PRE ? 0 : QT * kIvfPqStage));   // QT x cap
+  float *stage = T + (size_t)QT * M * 256;                                   // QT x 64, kIvfPqResiduals only
+  uint64_t *buf = reinterpret_cast<uint64_t *>(stage + (SRC == kIvfPqResiduals ? QT * kIvfPqStage : 0));   // QT x cap
   uint64_t *thr = buf + (size_t)QT * cap;                                    // QT
   uint32_t *cnt = reinterpret_cast<uint32_t *>(thr + QT);                    // QT
   uint32_t *pid = cnt + QT;                                                  // QT
@@ -288,9 +305,20 @@ __device__ __forceinline__ void ivfpq_scan_block(const IvfPqGeom &g, const float
   }
   if (t == 0) *full = 0;
   __syncthreads();
-  float t1[PRE ? QT : 1];   // the norms of the block's pairs
-  if constexpr (PRE)
+  float t1[SRC == kIvfPqTerms ? QT : 1];   // the norms of the block's pairs
+  if constexpr (SRC == kIvfPqTerms)
     ivfpq_fill_tables<QT>(g, terms + (size_t)c * M * g.ksub, qterms, norms, pid, live, T, t, t1);
+  else if constexpr (SRC == kIvfPqQueryTables)
+    pq_fill_tables<QT>(qterms, pid, live, g.nprobe, M, INFINITY, t, [&](uint32_t m, const float (&e)[QT]) {
+      float *dst = T + ((size_t)m * 256 + t) * QT;
+      if (QT == 2) {
+        *reinterpret_cast<float2 *>(dst) = make_float2(e[0], e[1]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < QT / 4; j++)
+          reinterpret_cast<float4 *>(dst)[j] = make_float4(e[j * 4], e[j * 4 + 1], e[j * 4 + 2], e[j * 4 + 3]);
+      }
+    });
   else
     ivfpq_build_tables<QT>(g, queries, g.centroids + (size_t)c * M * g.dsub, pid, stage, T, t);
 
@@ -316,7 +344,7 @@ __device__ __forceinline__ void ivfpq_scan_block(const IvfPqGeom &g, const float
     uint32_t todo = 0;
 #pragma unroll
     for (int q = 0; q < QT; q++) {
-      if constexpr (PRE) {
+      if constexpr (SRC == kIvfPqTerms) {
         const float d = t1[q] + acc[q];
         acc[q] = d <= 0.0f ? 0.0f : d;   // cancellation can leave a negative sum: the keys compare bits unsigned
       }
@@ -339,7 +367,8 @@ __global__ __launch_bounds__(kPqThreads) void ivfpq_scan_kernel(IvfPqGeom g, con
                                                                 const uint32_t *__restrict__ tile_start,
                                                                 const uint32_t *__restrict__ pairs,
                                                                 uint64_t *__restrict__ part) {
-  ivfpq_scan_block<QT, VEC, false>(g, queries, nullptr, nullptr, nullptr, pair_start, tile_start, pairs, part);
+  ivfpq_scan_block<QT, VEC, kIvfPqResiduals>(g, queries, nullptr, nullptr, nullptr, pair_start, tile_start, pairs,
+                                             part);
 }
 
 template <int QT, bool VEC>
@@ -350,7 +379,17 @@ __global__ __launch_bounds__(kPqThreads) void ivfpq_scan_pre_kernel(IvfPqGeom g,
                                                                     const uint32_t *__restrict__ tile_start,
                                                                     const uint32_t *__restrict__ pairs,
                                                                     uint64_t *__restrict__ part) {
-  ivfpq_scan_block<QT, VEC, true>(g, nullptr, terms, qterms, norms, pair_start, tile_start, pairs, part);
+  ivfpq_scan_block<QT, VEC, kIvfPqTerms>(g, nullptr, terms, qterms, norms, pair_start, tile_start, pairs, part);
+}
+
+template <int QT, bool VEC>
+__global__ __launch_bounds__(kPqThreads) void ivfpq_scan_nonres_kernel(IvfPqGeom g, const float *__restrict__ qtables,
+                                                                     const uint32_t *__restrict__ pair_start,
+                                                                     const uint32_t *__restrict__ tile_start,
+                                                                     const uint32_t *__restrict__ pairs,
+                                                                     uint64_t *__restrict__ part) {
+  ivfpq_scan_block<QT, VEC, kIvfPqQueryTables>(g, nullptr, nullptr, qtables, nullptr, pair_start, tile_start, pairs,
+                                               part);
 }
 
 __global__ __launch_bounds__(kPqThreads) void ivfpq_residuals_kernel(const float *__restrict__ x,
@@ -421,6 +460,30 @@ __global__ __launch_bounds__(kPqThreads) void ivfpq_query_terms_kernel(const flo
     qterms[((size_t)q * M + m) * 256 + c] = ivfpq_dot(queries + ((size_t)q * M + m) * dsub, y, dsub);
 }
 
+__device__ __forceinline__ void ivfpq_put_entry(float *p, float d) { *p = d; }
+__device__ __forceinline__ void ivfpq_put_entry(uint16_t *p, float d) { *p = __half_as_ushort(__float2half_rn(d)); }
+
+// pq_tables' entries in ivfpq_query_terms' grid, panel and layout: every column to 255 is written, +inf from ksub on
+template <typename E>
+__global__ __launch_bounds__(kPqThreads) void ivfpq_query_tables_kernel(const float *__restrict__ queries, uint32_t Qc,
+                                                                        const float *__restrict__ codebooks,
+                                                                        uint32_t M, uint32_t dsub, uint32_t ksub,
+                                                                        E *__restrict__ qtables) {
+  extern __shared__ float ivfpq_panel[];   // ksub x (dsub | 1)
+  const uint32_t m = blockIdx.x, c = threadIdx.x;
+  ivfpq_stage_panel(codebooks, m, dsub, ksub, ivfpq_panel);
+  __syncthreads();
+  const float *y = ivfpq_panel + (c < ksub ? c : 0u) * (dsub | 1u);
+  const uint32_t q0 = blockIdx.y * kIvfPqTermGroup;
+  for (uint32_t q = q0; q < q0 + kIvfPqTermGroup && q < Qc; q++) {
+    const float *x = queries + ((size_t)q * M + m) * dsub;
+    float d = INFINITY;
+    if (c < ksub)
+      for (uint32_t j = 0; j < dsub; j++) ivfpq_term(d, x[j], y[j], j == 0);
+    ivfpq_put_entry(qtables + ((size_t)q * M + m) * 256 + c, d);
+  }
+}
+
 // norms[i] = sum_{j < D} fl(fl(x_j - g_j)^2) of live pair i = query * nprobe + rank, one chain in ascending j
 __global__ __launch_bounds__(kPqThreads) void ivfpq_pair_norms_kernel(const float *__restrict__ queries,
                                                                       const float *__restrict__ centroids,
@@ -459,6 +522,22 @@ hipError_t ivfpq_scan_pre_launch(const IvfPqGeom &g, bool vec, const float *term
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((ivfpq_scan_pre_kernel<QT, V::value>), dim3(tiles * g.S), dim3(kPqThreads), lds, st, g, terms,
                        qterms, norms, pair_start, tile_start, pairs, part);
+    return hipGetLastError();
+  });
+}
+
+template <int QT>
+hipError_t ivfpq_scan_nonres_launch(const IvfPqGeom &g, bool vec, const float *qtables, uint32_t tiles,
+                                  const uint32_t *pair_start, const uint32_t *tile_start, const uint32_t *pairs,
+                                  uint64_t *part, hipStream_t st) {
+  const size_t lds = pq_scan_lds_bytes(g.M, g.k, QT);
+  return with_flag(vec && QT <= 4, [&](auto V16) {
+    using V = std::integral_constant<bool, decltype(V16)::value && QT <= 4>;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ivfpq_scan_nonres_kernel<QT, V::value>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ivfpq_scan_nonres_kernel<QT, V::value>), dim3(tiles * g.S), dim3(kPqThreads), lds, st, g, qtables,
+                       pair_start, tile_start, pairs, part);
     return hipGetLastError();
   });
 }
@@ -566,6 +645,43 @@ hipError_t launch_ivfpq_scan_pre(const IvfPqGeom &g, const float *terms, const f
   auto launch = [&](auto qt) {
     return ivfpq_scan_pre_launch<decltype(qt)::value>(g, vec, terms, qterms, norms, tiles, pair_start, tile_start,
                                                       pairs, part, st);
+  };
+  switch (g.QT) {
+    case 2: return launch(std::integral_constant<int, 2>());
+    case 4: return launch(std::integral_constant<int, 4>());
+    case 8: return launch(std::integral_constant<int, 8>());
+    case 16: return launch(std::integral_constant<int, 16>());
+  }
+  return hipErrorInvalidValue;
+}
+
+template <typename E>
+hipError_t ivfpq_query_tables_launch(const float *queries, uint32_t Qc, const float *codebooks, uint32_t M,
+                                     uint32_t dsub, uint32_t ksub, E *qtables, hipStream_t st) {
+  const size_t lds = (size_t)ksub * (dsub | 1u) * sizeof(float);
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ivfpq_query_tables_kernel<E>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ivfpq_query_tables_kernel<E>, dim3(M, (Qc + kIvfPqTermGroup - 1) / kIvfPqTermGroup),
+                     dim3(kPqThreads), lds, st, queries, Qc, codebooks, M, dsub, ksub, qtables);
+  return hipGetLastError();
+}
+
+hipError_t launch_ivfpq_query_tables(const float *queries, uint32_t Qc, const float *codebooks, uint32_t M,
+                                     uint32_t dsub, uint32_t ksub, float *qtables, hipStream_t st) {
+  return ivfpq_query_tables_launch(queries, Qc, codebooks, M, dsub, ksub, qtables, st);
+}
+
+hipError_t launch_ivfpq_query_tables_f16(const float *queries, uint32_t Qc, const float *codebooks, uint32_t M,
+                                         uint32_t dsub, uint32_t ksub, uint16_t *qtables, hipStream_t st) {
+  return ivfpq_query_tables_launch(queries, Qc, codebooks, M, dsub, ksub, qtables, st);
+}
+
+hipError_t launch_ivfpq_scan_nonres(const IvfPqGeom &g, const float *qtables, uint32_t tiles, const uint32_t *pair_start,
+                                  const uint32_t *tile_start, const uint32_t *pairs, uint64_t *part, hipStream_t st) {
+  const bool vec = (g.M & 15u) == 0 && (((uintptr_t)g.codes) & 15u) == 0;
+  auto launch = [&](auto qt) {
+    return ivfpq_scan_nonres_launch<decltype(qt)::value>(g, vec, qtables, tiles, pair_start, tile_start, pairs, part, st);
   };
   switch (g.QT) {
     case 2: return launch(std::integral_constant<int, 2>());

@@ -472,6 +472,22 @@ hipError_t launch_ivfpq_pair_norms(const float *queries, const float *centroids,
 hipError_t launch_ivfpq_scan_pre(const IvfPqGeom &g, const float *terms, const float *qterms, const float *norms,
                                  uint32_t tiles, const uint32_t *pair_start, const uint32_t *tile_start,
                                  const uint32_t *pairs, uint64_t *part, hipStream_t st);
+// Non-residual lists (kmamd_ivfpq_search_nonresidual, _f16): the codes are the rows' own, the table is
+// pq_search's and depends on the query only.  No staging tile: LDS and pair tile (g.QT) are pq_scan_lds_bytes /
+// pq_query_tile, with halves pq16_scan_lds_bytes / pq16_query_tile.  g.centroids is not read.
+// qtables[query][m][c < 256] = sum_j fl(fl(x_j - y_j)^2), +inf for c >= ksub: Qc x M x 256 floats, or the same rounded
+// to halves; at most 2^27 entries (the scans index them in 32 bits)
+hipError_t launch_ivfpq_query_tables(const float *queries, uint32_t Qc, const float *codebooks, uint32_t M,
+                                     uint32_t dsub, uint32_t ksub, float *qtables, hipStream_t st);
+hipError_t launch_ivfpq_query_tables_f16(const float *queries, uint32_t Qc, const float *codebooks, uint32_t M,
+                                         uint32_t dsub, uint32_t ksub, uint16_t *qtables, hipStream_t st);
+// launch_ivfpq_scan's grid, part layout and selection over the pairs' lines of qtables; the second is pq16_scan.hip's
+hipError_t launch_ivfpq_scan_nonres(const IvfPqGeom &g, const float *qtables, uint32_t tiles,
+                                    const uint32_t *pair_start, const uint32_t *tile_start, const uint32_t *pairs,
+                                    uint64_t *part, hipStream_t st);
+hipError_t launch_ivfpq16_scan_nonres(const IvfPqGeom &g, const uint16_t *qtables, uint32_t tiles,
+                                      const uint32_t *pair_start, const uint32_t *tile_start, const uint32_t *pairs,
+                                      uint64_t *part, hipStream_t st);
 
 // pq4_scan.hip -- both scans over 4-bit codes (kmamd_pq4_search, kmamd_ivfpq4_search).  codes is
 // N (or L) x ceil(M / 2) uint8, sub-space 2j in bits 0..3 of byte j and 2j + 1 in bits 4..7; 1 <= M <= 128, ksub <= 16.

@@ -28,6 +28,9 @@
 //              as halves with one wide LDS write.  The residuals are staged in the candidate buffers (QT x 256 of their
 //              QT x cap x 8 >= QT x 512 bytes), which nothing uses before the stream starts: one LDS size and one tile
 //              rule for both scans.
+//   ivfpq16_scan_nonres  the same block over non-residual lists (kmamd_ivfpq_search_nonresidual_f16):
+//              the tables are pq_fill_tables' copy (pq_select.hpp) of the pairs' query-level lines of halves
+//              (ivfpq_query_tables, 512 bytes per sub-space), QT halves packed into one wide LDS write; no arithmetic.
 #include <float.h>
 #include <math.h>
 
@@ -262,10 +265,29 @@ __device__ __forceinline__ void ivfpq16_build_tables(const IvfPqGeom &g, const f
   }
 }
 
-template <int QT, bool VEC>
-__global__ __launch_bounds__(kPqThreads, kPq16Waves) void ivfpq16_scan_kernel(
-    IvfPqGeom g, const float *__restrict__ queries, const uint32_t *__restrict__ pair_start,
-    const uint32_t *__restrict__ tile_start, const uint32_t *__restrict__ pairs, uint64_t *__restrict__ part) {
+// QT halves, as they lie in a query's table line, into an entry: one wide write (two at QT = 16)
+template <int QT>
+__device__ __forceinline__ void pq16_store_halves(uint32_t *e, const uint16_t (&h)[QT]) {
+  uint32_t p[QT / 2];
+#pragma unroll
+  for (int i = 0; i < QT / 2; i++) p[i] = (uint32_t)h[2 * i] | (uint32_t)h[2 * i + 1] << 16;
+  if (QT == 4) {
+    *reinterpret_cast<uint2 *>(e) = make_uint2(p[0], p[1]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < QT / 8; j++)
+      reinterpret_cast<uint4 *>(e)[j] = make_uint4(p[j * 4], p[j * 4 + 1], p[j * 4 + 2], p[j * 4 + 3]);
+  }
+}
+
+// One IVF scan block.  LINES: non-residual lists -- the tables are copied from `qtables`, the query-level lines of
+// halves (`queries` unused); else they are built from `queries` and the centroid.
+template <int QT, bool VEC, bool LINES>
+__device__ __forceinline__ void ivfpq16_scan_block(const IvfPqGeom &g, const float *__restrict__ queries,
+                                                   const uint16_t *__restrict__ qtables,
+                                                   const uint32_t *__restrict__ pair_start,
+                                                   const uint32_t *__restrict__ tile_start,
+                                                   const uint32_t *__restrict__ pairs, uint64_t *__restrict__ part) {
   extern __shared__ uint4 ivfpq16_lds4[];
   const uint32_t M = g.M, k = g.k, cap = g.cap, K = g.K, t = threadIdx.x;
   const uint32_t split = blockIdx.x % g.S, tile = blockIdx.x / g.S;
@@ -299,8 +321,13 @@ __global__ __launch_bounds__(kPqThreads, kPq16Waves) void ivfpq16_scan_kernel(
   }
   if (t == 0) *full = 0;
   __syncthreads();
-  // cap >= 64 keys: QT x 512 bytes, twice the staged sub-vectors
-  ivfpq16_build_tables<QT>(g, queries, g.centroids + (size_t)c * M * g.dsub, pid, reinterpret_cast<float *>(buf), T, t);
+  if constexpr (LINES)
+    pq_fill_tables<QT>(qtables, pid, live, g.nprobe, M, (uint16_t)0x7C00u, t, [&](uint32_t m, const uint16_t (&h)[QT]) {
+      pq16_store_halves<QT>(T + ((size_t)m * 256 + t) * (QT / 2), h);
+    });
+  else   // cap >= 64 keys: QT x 512 bytes, twice the staged sub-vectors
+    ivfpq16_build_tables<QT>(g, queries, g.centroids + (size_t)c * M * g.dsub, pid, reinterpret_cast<float *>(buf), T,
+                             t);
 
   const bool dwords = (M & 3u) == 0 && (reinterpret_cast<uintptr_t>(g.codes) & 3u) == 0;
   uint64_t limit[QT];   // every lane's copy of thr[]
@@ -337,6 +364,20 @@ __global__ __launch_bounds__(kPqThreads, kPq16Waves) void ivfpq16_scan_kernel(
       part[((size_t)pid[q] * g.S + split) * k + t] = t < cnt[q] ? buf[q * cap + t] : kPqNoKey;
 }
 
+template <int QT, bool VEC>
+__global__ __launch_bounds__(kPqThreads, kPq16Waves) void ivfpq16_scan_kernel(
+    IvfPqGeom g, const float *__restrict__ queries, const uint32_t *__restrict__ pair_start,
+    const uint32_t *__restrict__ tile_start, const uint32_t *__restrict__ pairs, uint64_t *__restrict__ part) {
+  ivfpq16_scan_block<QT, VEC, false>(g, queries, nullptr, pair_start, tile_start, pairs, part);
+}
+
+template <int QT, bool VEC>
+__global__ __launch_bounds__(kPqThreads, kPq16Waves) void ivfpq16_scan_nonres_kernel(
+    IvfPqGeom g, const uint16_t *__restrict__ qtables, const uint32_t *__restrict__ pair_start,
+    const uint32_t *__restrict__ tile_start, const uint32_t *__restrict__ pairs, uint64_t *__restrict__ part) {
+  ivfpq16_scan_block<QT, VEC, true>(g, nullptr, qtables, pair_start, tile_start, pairs, part);
+}
+
 // a code row is read 16 bytes at a time where M is a multiple of 16 and the matrix is 16-byte aligned; a tile of 16
 // never meets such a row (M <= 8 there)
 bool pq16_vec(const uint8_t *codes, uint32_t M) {
@@ -369,6 +410,22 @@ hipError_t ivfpq16_scan_launch(const IvfPqGeom &g, const float *queries, uint32_
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((ivfpq16_scan_kernel<QT, V>), dim3(tiles * g.S), dim3(kPqThreads), lds, st, g, queries,
+                       pair_start, tile_start, pairs, part);
+    return hipGetLastError();
+  });
+}
+
+template <int QT>
+hipError_t ivfpq16_scan_nonres_launch(const IvfPqGeom &g, const uint16_t *qtables, uint32_t tiles,
+                                      const uint32_t *pair_start, const uint32_t *tile_start, const uint32_t *pairs,
+                                      uint64_t *part, hipStream_t st) {
+  const size_t lds = pq16_scan_lds_bytes(g.M, g.k, QT);
+  return with_flag(QT <= 8 && pq16_vec(g.codes, g.M), [&](auto V16) {
+    constexpr bool V = decltype(V16)::value && QT <= 8;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ivfpq16_scan_nonres_kernel<QT, V>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ivfpq16_scan_nonres_kernel<QT, V>), dim3(tiles * g.S), dim3(kPqThreads), lds, st, g, qtables,
                        pair_start, tile_start, pairs, part);
     return hipGetLastError();
   });
@@ -417,6 +474,17 @@ hipError_t launch_ivfpq16_scan(const IvfPqGeom &g, const float *queries, uint32_
     case 4: return ivfpq16_scan_launch<4>(g, queries, tiles, pair_start, tile_start, pairs, part, st);
     case 8: return ivfpq16_scan_launch<8>(g, queries, tiles, pair_start, tile_start, pairs, part, st);
     case 16: return ivfpq16_scan_launch<16>(g, queries, tiles, pair_start, tile_start, pairs, part, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_ivfpq16_scan_nonres(const IvfPqGeom &g, const uint16_t *qtables, uint32_t tiles,
+                                      const uint32_t *pair_start, const uint32_t *tile_start, const uint32_t *pairs,
+                                      uint64_t *part, hipStream_t st) {
+  switch (g.QT) {
+    case 4: return ivfpq16_scan_nonres_launch<4>(g, qtables, tiles, pair_start, tile_start, pairs, part, st);
+    case 8: return ivfpq16_scan_nonres_launch<8>(g, qtables, tiles, pair_start, tile_start, pairs, part, st);
+    case 16: return ivfpq16_scan_nonres_launch<16>(g, qtables, tiles, pair_start, tile_start, pairs, part, st);
   }
   return hipErrorInvalidValue;
 }

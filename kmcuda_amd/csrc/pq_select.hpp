@@ -78,6 +78,44 @@ __device__ __forceinline__ void pq_score(const float *__restrict__ T, const uint
     }
 }
 
+constexpr int kPqFillLoads = 16;   // table entries a thread keeps in flight per group of pq_fill_tables
+
+// The tables of a block's pairs out of per-query lines in global memory (the non-residual IVF scans):
+// lines[query][m][256] of E -- a float, or a uint16_t that holds a half -- complete to column 255.  pid[q]: the pair of
+// slot q < live, its query pid[q] / nprobe; a slot without a pair gets `inf`.  Thread t owns column t: it loads the QT
+// entries of 16 / QT sub-spaces, issues the next group's loads, and hands this group's to put(m, e) -- which stores the
+// QT adjacent entries T[m][t][0..QT) with one wide LDS write.  The lines are indexed in 32 bits: the host keeps a
+// chunk's within 2^27 entries.  One barrier, at the end.
+template <int QT, typename E, typename Put>
+__device__ __forceinline__ void pq_fill_tables(const E *__restrict__ lines, const uint32_t *pid, uint32_t live,
+                                               uint32_t nprobe, uint32_t M, E inf, uint32_t t, Put put) {
+  constexpr int G = kPqFillLoads / QT;
+  uint32_t at[QT];   // the index of (query of slot q, m = 0, column t)
+#pragma unroll
+  for (int q = 0; q < QT; q++) at[q] = (uint32_t)q < live ? (pid[q] / nprobe * M) * 256u + t : 0u;
+  E e[G][QT], en[G][QT];
+  auto load = [&](uint32_t m0, E (&v)[G][QT]) {
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+      const uint32_t m = m0 + i;
+#pragma unroll
+      for (int q = 0; q < QT; q++) v[i][q] = m < M && (uint32_t)q < live ? lines[at[q] + m * 256u] : inf;
+    }
+  };
+  load(0, en);
+  for (uint32_t m0 = 0; m0 < M; m0 += G) {
+#pragma unroll
+    for (int i = 0; i < G; i++)
+#pragma unroll
+      for (int q = 0; q < QT; q++) e[i][q] = en[i][q];
+    load(m0 + G, en);   // in flight over this group's stores
+#pragma unroll
+    for (int i = 0; i < G; i++)
+      if (m0 + i < M) put(m0 + i, e[i]);
+  }
+  __syncthreads();
+}
+
 // The block sorts the buffers named in `need` (cnt[q] keys each, the rest padded) and keeps their k smallest keys.
 template <int QT>
 __device__ __forceinline__ void pq_reduce(uint64_t *buf, uint64_t *thr, uint32_t *cnt, uint32_t cap, uint32_t k,

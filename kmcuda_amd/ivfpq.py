@@ -1,6 +1,6 @@
 """IVF-PQ: product-quantiser codes of residuals in cluster lists, probed by asymmetric distance computation (C ABI:
 kmamd_ivfpq_search, kmamd_ivfpq_residuals, include/kmcuda_amd.h; the precomputed-term variant --
-ivfpq_terms, ivfpq_search(terms=), IvfPqIndex(precomputed=True) -- 4.24).
+ivfpq_terms, ivfpq_search(terms=), IvfPqIndex(precomputed=True) -- 4.24; non-residual lists, residual=False, 4.27).
 
     centroids, _ = kmeans_cuda(rows, 1024)
     codebooks = ivfpq_train(rows, centroids, subspaces=32)
@@ -26,6 +26,13 @@ binary16 and a position's distance is sum_m float(T16[m][code]) in fp32, as pq_s
 LDS per pair and per lookup, a distance of its own bits.  Byte codes and residual tables only: not with bits=4, `terms`
 or precomputed=True.  search(refine=) re-ranks its shortlist exactly, which is what the option is meant for.
 
+residual=False (kmamd_ivfpq_search_nonresidual, _f16): the lists hold the codes of the rows themselves
+(FAISS's by_residual = false) and the codebooks are trained on rows.  The table is then pq_search's, T[m][c] =
+sum_j fl(fl(x_j - y_j)^2) of the query's own sub-vectors, built once per query and copied by the scan blocks; the result
+is pq_search's arithmetic -- with table_dtype="float16" that of pq_search(table_dtype="float16") -- over the probed
+lists.  `centroids` only gives K.  Coarser codes than residuals': search(refine=) is there to buy accuracy back.  Byte
+codes only: not with bits=4, `terms` or precomputed=True.
+
 knn_rerank (kmamd_knn_rerank; DESIGN.md 4.23) re-ranks such a shortlist against the raw rows by the exact L2 distance;
 IvfPqIndex(..., keep_rows=True).search(..., refine=f) does both: a shortlist of k * f, then the exact k.
 """
@@ -42,12 +49,27 @@ _BLOCKS = 512                    # kernels.hpp: kIvfPqBlocks
 _CHUNK_BYTES = 256 << 20         # the fp32 residuals of one row chunk while an index is built
 
 
-def query_tile(subspaces, k, bits=8, table_dtype="float32"):
+def _residual(residual, bits=8, precomputed=False):
+    """False for non-residual lists; refuses what they do not go with"""
+    if not isinstance(residual, (bool, numpy.bool_)):
+        raise ValueError("\"residual\" must be a bool")
+    if not residual and precomputed:
+        raise ValueError("the precomputed terms cheapen residual tables: residual=False goes without them")
+    if not residual and bits == 4:
+        raise ValueError("non-residual lists hold byte codes: residual=False goes without bits=4")
+    return bool(residual)
+
+
+def query_tile(subspaces, k, bits=8, table_dtype="float32", residual=True):
     """The (query, probe) pairs one scan block serves (kmamd_ivfpq_query_tile): pq.query_tile's rule with the staged
     residual sub-vectors, 256 bytes per pair, added to the block's LDS; 0: `subspaces` or `k` out of range.  bits=4
     (kmamd_ivfpq4_query_tile): pq.query_tile's 4-bit rule as it is -- that block stages where its candidates go.
-    table_dtype="float16" (kmamd_ivfpq_f16_query_tile): pq.query_tile's fp16 rule as it is, for the same reason."""
-    if _table_dtype(table_dtype, _bits(bits)):
+    table_dtype="float16" (kmamd_ivfpq_f16_query_tile): pq.query_tile's fp16 rule as it is, for the same reason.
+    residual=False: pq.query_tile's rule as it is for either table type -- that block stages nothing."""
+    half = _table_dtype(table_dtype, _bits(bits))
+    if not _residual(residual, bits):
+        return _pq_query_tile(subspaces, k, 8, table_dtype)
+    if half:
         return _pq_query_tile(subspaces, k, 8, "float16")
     if bits == 4:
         return _pq_query_tile(subspaces, k, 4)
@@ -139,11 +161,13 @@ def _check_books(codebooks, width, on_dev, device, bits=8):
 
 
 def ivfpq_train(rows, centroids, subspaces, ksub=256, assignments=None, *, seed=0, max_iter=25, tolerance=0.0,
-                metric="L2", device=0, verbosity=0):
+                metric="L2", device=0, verbosity=0, residual=True):
     """codebooks (subspaces, ksub, D / subspaces): one kmeans_batched call (layout="columns", init="random") over the
-    residuals of `rows` against `centroids`; rows without a cluster (assignment K) are left out."""
+    residuals of `rows` against `centroids` -- with residual=False over the rows themselves; rows without a cluster
+    (assignment K) are left out."""
     if _get_metric(metric) != 0:
         raise ValueError("IVF-PQ supports the L2 metric only")
+    residual = _residual(residual)
     device = _device(device)
     if isinstance(subspaces, bool) or not isinstance(subspaces, (int, numpy.integer)) or not 1 <= subspaces <= 64:
         raise ValueError("\"subspaces\" must be an integer in [1, 64]")
@@ -155,7 +179,7 @@ def ivfpq_train(rows, centroids, subspaces, ksub=256, assignments=None, *, seed=
         raise ValueError("the features must split into `subspaces` blocks of at most 64")
     if a is None:
         a = kmeans_predict(x, c, device=device, verbosity=verbosity)
-    res = _residuals(x, c, a, on_dev, device, verbosity)
+    res = _residuals(x, c, a, on_dev, device, verbosity) if residual else x
     res = res[(a.long() if on_dev else a) < int(c.shape[0])]
     books, _, _ = kmeans_batched(res, int(ksub), init="random", max_iter=max_iter, tolerance=tolerance, seed=seed,
                                  layout="columns", problems=int(subspaces), device=device, verbosity=verbosity)
@@ -182,7 +206,7 @@ def ivfpq_terms(centroids, codebooks, *, metric="L2", device=0, verbosity=0):
 
 
 def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, *, metric="L2", device=0,
-                 verbosity=0, terms=None, bits=8, table_dtype="float32"):
+                 verbosity=0, terms=None, bits=8, table_dtype="float32", residual=True):
     """(indices, distances), each (Q, k), over a caller's own lists (module docstring): codes (L, M) uint8 in list
     order -- (L, ceil(M / 2)) packed with bits=4, which `terms` does not go with --,
     ids (L,), offsets (K + 1,), probes (Q, nprobe) -- entries >= K and repeated entries are ignored.  The
@@ -191,6 +215,9 @@ def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, 
     (kmamd_ivfpq_search_precomputed) -- T[m][c] = fl(terms[p][m][c] - 2 sum_j fl(x_j y_j)),
     d = fl(sum_j fl(fl(x_j - g_j)^2) + sum_m T[m][code]), negative or -0 as +0: the same distance in other bits.
     table_dtype="float16": the tables of halves of the module docstring (kmamd_ivfpq_search_f16); not with bits=4 or
+    `terms`.
+    residual=False: `codes` are those of the rows themselves and `codebooks` their quantiser (module docstring;
+    kmamd_ivfpq_search_nonresidual, with table_dtype="float16" kmamd_ivfpq_search_nonresidual_f16); not with bits=4 or
     `terms`."""
     if _get_metric(metric) != 0:
         raise ValueError("IVF-PQ supports the L2 metric only")
@@ -198,6 +225,7 @@ def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, 
     if _bits(bits) == 4 and terms is not None:
         raise ValueError("the precomputed-term variant has no 4-bit codes: bits=4 goes without \"terms\"")
     half = _table_dtype(table_dtype, bits, terms is not None)
+    residual = _residual(residual, bits, terms is not None)
     if isinstance(k, bool) or not isinstance(k, (int, numpy.integer)):
         raise TypeError("\"k\" must be an integer")
     q, on_dev = _f32(queries, "queries", 2, device)
@@ -244,7 +272,10 @@ def ivfpq_search(queries, centroids, codebooks, codes, ids, offsets, probes, k, 
         return idx, dist
     head = (nq, rows, d, clusters, m, dsub, ksub, int(k), nprobe, 0, 0, device, device if on_dev else -1,
             int(verbosity), _ptr(q), _ptr(c), _ptr(b), _ptr(cd), _ptr(i), _ptr(o), _ptr(p))
-    if bits == 4:
+    if not residual:
+        name = "kmamd_ivfpq_search_nonresidual_f16" if half else "kmamd_ivfpq_search_nonresidual"
+        rc = getattr(_lib.lib(), name)(*head, _ptr(idx), _ptr(dist))
+    elif bits == 4:
         rc = _lib.lib().kmamd_ivfpq4_search(*head, _ptr(idx), _ptr(dist))
     elif half:
         rc = _lib.lib().kmamd_ivfpq_search_f16(*head, _ptr(idx), _ptr(dist))
@@ -305,10 +336,12 @@ class IvfPqIndex:
     .terms (ivfpq_terms) once and search() runs the precomputed-term variant (ivfpq_search's `terms`).  bits=4
     (.bits): codebooks of at most 16 codewords, .codes packed two to a byte, (L, ceil(M / 2)); not with precomputed.
     table_dtype="float16" (.table_dtype): search() scans tables of halves (ivfpq_search's `table_dtype`); the index
-    itself is the same; not with bits=4 or precomputed."""
+    itself is the same; not with bits=4 or precomputed.  residual=False (.residual): .codes are those of the rows
+    themselves against `codebooks` (ivfpq_train(residual=False)'s) and search() scans query-level tables
+    (ivfpq_search's `residual`); not with bits=4 or precomputed."""
 
     def __init__(self, rows, centroids, codebooks, assignments=None, *, metric="L2", device=0, verbosity=0,
-                 keep_rows=False, precomputed=False, bits=8, table_dtype="float32"):
+                 keep_rows=False, precomputed=False, bits=8, table_dtype="float32", residual=True):
         if _get_metric(metric) != 0:
             raise ValueError("IVF-PQ supports the L2 metric only")
         self.bits = _bits(bits)
@@ -316,6 +349,7 @@ class IvfPqIndex:
             raise ValueError("the precomputed-term variant has no 4-bit codes: bits=4 goes without precomputed=True")
         _table_dtype(table_dtype, self.bits, bool(precomputed))
         self.table_dtype = table_dtype
+        self.residual = _residual(residual, self.bits, bool(precomputed))
         self.device, self.verbosity = _device(device), int(verbosity)
         x, c, a, on_dev = _corpus(rows, centroids, assignments, self.device)
         self.rows = x if keep_rows else None       # the checked array itself, no copy: search(refine=) reads it
@@ -326,7 +360,9 @@ class IvfPqIndex:
         codes = _out((n, int(b.shape[0])), numpy.uint8, on_dev, self.device)
         step = max(1, _CHUNK_BYTES // (4 * int(x.shape[1])))
         for r0 in range(0, n, step):
-            res = _residuals(x[r0:r0 + step], c, a[r0:r0 + step], on_dev, self.device, verbosity)
+            res = x[r0:r0 + step]
+            if self.residual:
+                res = _residuals(res, c, a[r0:r0 + step], on_dev, self.device, verbosity)
             codes[r0:r0 + step] = kmeans_predict_batched(res, b, layout="columns", dtype=numpy.uint8,
                                                          device=self.device, verbosity=verbosity)
         if on_dev:
@@ -382,4 +418,5 @@ class IvfPqIndex:
                                             return_distances=False, verbosity=self.verbosity)
         return ivfpq_search(queries, self.centroids, self.codebooks, self.codes, self.ids, self.offsets, probes, k,
                             device=self.device, verbosity=self.verbosity, terms=getattr(self, "terms", None),
-                            bits=getattr(self, "bits", 8), table_dtype=getattr(self, "table_dtype", "float32"))
+                            bits=getattr(self, "bits", 8), table_dtype=getattr(self, "table_dtype", "float32"),
+                            residual=getattr(self, "residual", True))

@@ -6,6 +6,7 @@ with recall against an exact torch brute force over the full rows, and the two f
     python scripts/ivfpq_bench.py --rows 100000 --clusters 128 --queries 1000 --repeat 3
     python scripts/ivfpq_bench.py --precomputed --queries 10000      # both table builds, lap by lap in turn
     python scripts/ivfpq_bench.py --bits 4 --subspaces 64 --refine 4 --queries 10000
+    python scripts/ivfpq_bench.py --no-residual --table-dtype float16 --refine 4,16 --queries 10000
 
 Data: a Gaussian mixture of `clusters` components (centres 2 * randn, unit noise); the mixture's centres serve as the
 coarse centroids (no K-means is run: the subject is the search); queries are fresh draws of the mixture.  Codebooks are
@@ -18,10 +19,15 @@ precomputed-term variant to every line: `pre_search_ms` / `pre_
 other two, lap by lap, `pre_recall` is against the same exact ground truth, and `pre_table_floor_ms` is the variant's
 table build, Q nprobe M KB of query terms and as many of index terms read at 6.29 TB/s.  --bits 4:
 16 codewords per sub-space, the codes of the index and of pq_search packed two to a byte; the table-build floor then
-counts 16 codewords.  --refine F adds `refine_recall`, the recall of search(refine=F).  --table-dtype float16
+counts 16 codewords.  --refine F adds `refine_recall`, the recall of search(refine=F); with several factors, F1,F2, a
+recall per factor.  --table-dtype float16
  adds the search over tables of halves to every line, timed in turn with the others, lap by lap:
 `f16_ms` of pq_search, `f16_search_ms` / `f16_scan_ms`, `f16_recall` and `f16_refine_recall` against the same exact
-ground truth, `scan_over_f16_scan`.  There is no CPU path."""
+ground truth, `scan_over_f16_scan`.  --no-residual adds a second index over the same rows and coarse
+centroids with non-residual lists (codebooks from ivfpq_train(residual=False)), timed in turn with the others:
+`nr_search_ms` / `nr_scan_ms`, `nr_recall`, `nr_refine_recall`, `scan_over_nr_scan`, with --table-dtype float16 also
+`nr_f16_*` (against `f16_scan_ms`: `f16_scan_over_nr_f16_scan`), and `nr_table_copy_floor_ms`, the Q nprobe M KB of
+table lines (half that in halves) a scan's blocks copy, against 6.29 TB/s.  There is no CPU path."""
 import argparse
 import copy
 import json
@@ -83,12 +89,14 @@ def main():
     ap.add_argument("--train-rows", type=int, default=100000)
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--bits", type=int, default=8, choices=(8, 4))
-    ap.add_argument("--refine", type=int, default=0, help="also report the recall of search(refine=this)")
+    ap.add_argument("--refine", default="", help="also report the recall of search(refine=this); F or F1,F2,...")
+    ap.add_argument("--no-residual", action="store_true", help="time an index of non-residual lists beside the search")
     ap.add_argument("--precomputed", action="store_true", help="time the precomputed-term variant beside the search")
     ap.add_argument("--table-dtype", default="float32", choices=("float32", "float16"),
                     help="float16: time the search over fp16 tables beside the fp32 one")
     args = ap.parse_args()
     half = args.table_dtype == "float16"
+    refines = [int(v) for v in args.refine.split(",") if v]
     import torch
     from kmcuda_amd import (IvfPqIndex, ivfpq_search, ivfpq_terms, ivfpq_train, kmeans_batched,
                             kmeans_predict_batched, kmeans_predict_top, pq_pack4, pq_search)
@@ -104,6 +112,8 @@ def main():
         sys.exit("the precomputed-term variant has no 4-bit codes")
     if bits == 4 and half:
         sys.exit("fp16 tables serve the byte codes only")
+    if bits == 4 and args.no_residual:
+        sys.exit("non-residual lists hold byte codes only")
     gen = torch.Generator(device=dev).manual_seed(1)
     centres = 2 * torch.randn((kc, d), generator=gen, device=dev)
 
@@ -114,9 +124,17 @@ def main():
     train = rows[:args.train_rows].contiguous()
     t0 = time.perf_counter()
     books = ivfpq_train(train, centres, m, ksub=ksub, max_iter=10, seed=1)
-    index = IvfPqIndex(rows, centres, books, bits=bits, keep_rows=args.refine > 0)
+    index = IvfPqIndex(rows, centres, books, bits=bits, keep_rows=bool(refines))
     sync()
     build_s = time.perf_counter() - t0
+    if args.no_residual:
+        t0 = time.perf_counter()
+        nr_books = ivfpq_train(train, centres, m, ksub=ksub, max_iter=10, seed=1, residual=False)
+        nr = IvfPqIndex(rows, centres, nr_books, keep_rows=bool(refines), residual=False)
+        sync()
+        nr_build_s = time.perf_counter() - t0
+        nr16 = copy.copy(nr)
+        nr16.table_dtype = "float16"
     if args.precomputed:
         t0 = time.perf_counter()
         terms = ivfpq_terms(centres, books)
@@ -135,6 +153,7 @@ def main():
     print(json.dumps({"index": {"N": n, "D": d, "K": kc, "M": m, "dsub": d // m, "bits": bits,
                                 "train_and_build_s": build_s,
                                 "list_rows": [int(lens.min()), float(lens.float().mean()), int(lens.max())],
+                                **({"nr_train_and_build_s": nr_build_s} if args.no_residual else {}),
                                 **({"terms_s": terms_s, "terms_mb": terms.numel() * 4 / 2 ** 20}
                                    if args.precomputed else {})}}),
           flush=True)
@@ -164,13 +183,22 @@ def main():
                 fns += [lambda: f16.search(queries, k, nprobe=nprobe),
                         lambda: ivfpq_search(queries, centres, books, index.codes, index.ids, index.offsets, probes, k,
                                              table_dtype="float16")]
+            if args.no_residual:      # behind everything else: laps[-2:] with fp32 tables, laps[-4:] with both
+                for ix in (nr, nr16) if half else (nr,):
+                    fns += [lambda ix=ix: ix.search(queries, k, nprobe=nprobe),
+                            lambda ix=ix: ivfpq_search(queries, centres, ix.codebooks, ix.codes, ix.ids, ix.offsets,
+                                                       probes, k, table_dtype=ix.table_dtype, residual=False)]
             laps = _median_ms_in_turn(fns, args.repeat, sync)
             whole, scan = laps[:2]
+
+            def refined(ix):
+                found = {f: recall(ix.search(queries, k, nprobe=nprobe, refine=f)[0], truth) for f in refines}
+                return found[refines[0]] if len(refines) == 1 else found
             found = index.search(queries, k, nprobe=nprobe)[0]
             qt = query_tile(m, k, bits=bits)
             extra = {}
-            if args.refine:
-                extra["refine_recall"] = recall(index.search(queries, k, nprobe=nprobe, refine=args.refine)[0], truth)
+            if refines:
+                extra["refine_recall"] = refined(index)
             if args.precomputed:
                 pqt = pre_query_tile(m, k)
                 extra = {**extra, "pre_search_ms": laps[2], "pre_scan_ms": laps[3],
@@ -180,13 +208,26 @@ def main():
                          "pre_table_floor_ms": 2 * nq * nprobe * m * 1024 / COPY_BYTES_PER_S * 1e3}
             if half:
                 hqt = query_tile(m, k, table_dtype="float16")
-                extra = {**extra, "f16_search_ms": laps[-2], "f16_scan_ms": laps[-1],
-                         "scan_over_f16_scan": scan[0] / laps[-1][0],
+                f16_laps = laps[-6:-4] if args.no_residual else laps[-2:]
+                extra = {**extra, "f16_search_ms": f16_laps[0], "f16_scan_ms": f16_laps[1],
+                         "scan_over_f16_scan": scan[0] / f16_laps[1][0],
                          "f16_recall": recall(f16.search(queries, k, nprobe=nprobe)[0], truth), "f16_pair_tile": hqt,
                          "f16_row_split": row_split(nq * nprobe, hqt, int(index.codes.shape[0]))}
-                if args.refine:
-                    extra["f16_refine_recall"] = recall(
-                        f16.search(queries, k, nprobe=nprobe, refine=args.refine)[0], truth)
+                if refines:
+                    extra["f16_refine_recall"] = refined(f16)
+            if args.no_residual:
+                rows_l = int(nr.codes.shape[0])
+                for ix, tag, mine, base in ((nr, "nr_", laps[-4:-2] if half else laps[-2:], scan),) + (
+                        ((nr16, "nr_f16_", laps[-2:], extra["f16_scan_ms"]),) if half else ()):
+                    tile = query_tile(m, k, table_dtype=ix.table_dtype, residual=False)
+                    extra = {**extra, tag + "search_ms": mine[0], tag + "scan_ms": mine[1],
+                             ("scan_over_" if ix is nr else "f16_scan_over_") + tag + "scan": base[0] / mine[1][0],
+                             tag + "recall": recall(ix.search(queries, k, nprobe=nprobe)[0], truth),
+                             tag + "pair_tile": tile, tag + "row_split": row_split(nq * nprobe, tile, rows_l),
+                             tag + "table_copy_floor_ms": nq * nprobe * m * (512 if ix is nr16 else 1024)
+                             / COPY_BYTES_PER_S * 1e3}
+                    if refines:
+                        extra[tag + "refine_recall"] = refined(ix)
             print(json.dumps({
                 "ivfpq": {"Q": nq, "k": k, "nprobe": nprobe, "pair_tile": qt,
                           "row_split": row_split(nq * nprobe, qt, int(index.codes.shape[0]))},
